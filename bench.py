@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the QGTC bit-GEMM hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE bitMM2Bit launch over the workload BASELINE.json's north star and BASELINE.md §1's bold row name: a 1-bit
@@ -12,8 +12,13 @@ the reference's way (QGTC_device.cu:407-418: launches back to back on one stream
 With N > 1 ranks every GPU runs its own copy (cluster batches are independent: no data-path collective) - weak scaling,
 value = all ranks' ops / max time; RCCL only takes the max time and gathers per-rank checksums / per-batch outputs.
 
-Rank 0 prints ONE short JSON line LAST on stdout: the contract's fields, `roofline` (dominant kernel + both epochs of
-BASELINE.json's metric as flat epoch_gcn_* / epoch_gin_* scalars), `cpu_baseline`. Tables, notes and every other leg go to
+A plain run sets up, warms up, times the K steps, writes the last step's output with --dump-outputs DIR (DIR/bitMM2Bit_out.npy:
+the packed int32 words the caller receives, as float64) and prints the contract's fields. Everything else runs with --full:
+the engines' agreement, HIP-event windows behind the timed region, the other issue and engine, parity with the C oracle,
+`cpu_baseline`, the 32768^2 launches, the reference's tables, the epoch legs and RCCL at world size 1.
+
+Rank 0 prints ONE short JSON line LAST on stdout. With --full it also holds `roofline` (dominant kernel + both epochs of
+BASELINE.json's metric as flat epoch_gcn_* / epoch_gin_* scalars) and `cpu_baseline`; tables, notes and every other leg go to
 the file the line names (`extras_file`). The legs live in benchmarks/ (headline, cpu, epochs, tables, launcher)."""
 from __future__ import annotations
 
@@ -41,7 +46,12 @@ def parse():
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--bits", type=int, default=1, help="feature bit width w of the headline workload")
-    p.add_argument("--no-extras", action="store_true", help="headline only: skip the epoch / table / CPU legs")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: engine agreement, roofline windows, the other issue and engine, oracle parity, CPU "
+                        "baselines, tables, epoch legs, RCCL at world size 1 (off by default: a plain run times the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip the epoch / table / CPU legs")
     p.add_argument("--no-tables", action="store_true", help="skip the reference's benchmark tables (extras file only)")
     p.add_argument("--streams", type=int, default=1,
                    help="issue the steps round-robin on this many HIP streams (default 1 = the reference's metric)")
@@ -60,8 +70,9 @@ def parse():
 
 
 def compose_line(args, world, ranks_seen, M, K, N, w, value, wall_max, fp4_kernel, roofline):
-    """The contract's fields. Strings are short on purpose: the line is machine-read."""
-    return {"metric": "effective bit-GEMM TOPS (2*M*K*N/t), 1-bit A x %d-bit X, M=K=4096, N=64" % w,
+    """The contract's fields (and `roofline` unless it is None: a run without --full measures none). Strings are short on
+    purpose: the line is machine-read."""
+    line = {"metric": "effective bit-GEMM TOPS (2*M*K*N/t), 1-bit A x %d-bit X, M=K=4096, N=64" % w,
             "value": round(value, 3), "unit": "TOPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(wall_max * 1e3 / args.steps, 6), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": round(value / REF_TFLOPS_4096_64[w], 3) if w in REF_TFLOPS_4096_64 else None,
@@ -71,7 +82,18 @@ def compose_line(args, world, ranks_seen, M, K, N, w, value, wall_max, fp4_kerne
                        "inputs": "seeded Bernoulli(0.5) adjacency, uniform w-bit features, packed, resident in HBM",
                        "parallelism": f"replica-per-GPU x{world}, no data-path collective", "engine": args.engine,
                        "issue": args.issue if args.streams <= 1 else f"eager on {args.streams} streams"},
-            "ranks_seen": ranks_seen, "roofline": roofline}
+            "ranks_seen": ranks_seen}
+    if roofline is not None:
+        line["roofline"] = roofline
+    return line
+
+
+def dump_outputs(folder, rank, out):
+    """What the timed path computed in its last step: the packed int32 words bitMM2Bit hands its caller, as float64 (exact), in
+    DIR/bitMM2Bit_out.npy (rank r > 0: bitMM2Bit_out_rank<r>.npy). The inputs are seeded, so two builds compare word for word."""
+    os.makedirs(folder, exist_ok=True)
+    name = "bitMM2Bit_out.npy" if rank == 0 else f"bitMM2Bit_out_rank{rank}.npy"
+    np.save(os.path.join(folder, name), out.cpu().numpy().astype(np.float64))
 
 
 def write_extras(path, extras):
@@ -116,7 +138,7 @@ def main():
     from qgtc_ppopp22_amd import dist as D
 
     rank, world, local = D.init_from_env(backend=args.backend)
-    solo = rank == 0 and world == 1 and not args.no_extras
+    solo = args.full and rank == 0 and world == 1 and not args.no_extras
     host_kernarg_ms = rccl = None
     if solo and torch.cuda.device_count() > 0:
         # two child processes, started before THIS process touches the GPU: a process-wide HIP runtime knob, and RCCL at world 1
@@ -134,6 +156,24 @@ def main():
     M = K = 4096
     N, w = 64, args.bits
     A, X, bit_A, bit_X = make_workload(Q, M, K, N, w, device, seed=3 + rank)
+    # which kernel runs at this shape: the FP4 matrix-core kernel when the float32 sums stay exact (K (2^a - 1)(2^w - 1) < 2^24)
+    fp4_kernel = args.engine != "popcount" and w <= 8 and K * (2 ** w - 1) < 2 ** 24
+    if not args.full:
+        with engine(Q, args.engine):
+            out_e = Q.bitMM2Bit(bit_A, bit_X, M, K, N, 1, w, w)
+            # ================= the timed region (benchmarks/headline.py::time_steps) =================
+            wall, _ = headline.time_steps(Q, out_e, bit_A, bit_X, M, K, N, w, args.steps, args.warmup, D.barrier, args.streams, args.issue,
+                                          live_windows=False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, out_e)
+        wall_max = D.max_over_ranks(wall, device)
+        value = world * args.steps * 2.0 * M * K * N / wall_max / 1e12
+        line = compose_line(args, world, D.world_size(), M, K, N, w, value, wall_max, fp4_kernel, None)
+        if rank == 0:
+            flush_c_stdio()
+            print(json.dumps(line), flush=True)
+        D.shutdown()
+        return
     with engine(Q, "popcount"):
         out = Q.bitMM2Bit(bit_A, bit_X, M, K, N, 1, w, w)   # AND + popcount kernels: the words every engine must produce
     extras, pop_block = {}, None
@@ -142,6 +182,8 @@ def main():
         assert torch.equal(out_e, out), "engines disagree"
         # ================= the timed region (benchmarks/headline.py::time_steps) =================
         wall, kern = headline.time_steps(Q, out_e, bit_A, bit_X, M, K, N, w, args.steps, args.warmup, D.barrier, args.streams, args.issue)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, out_e)
         assert torch.equal(out_e, out), "the timed launches changed the result"
         if solo and args.streams <= 1:   # the same K steps issued the other way, and on the other engine (identical words)
             other = "graph" if args.issue == "eager" else "eager"
@@ -153,8 +195,6 @@ def main():
             o_wall, o_kern = headline.time_steps(Q, torch.empty_like(out), bit_A, bit_X, M, K, N, w, args.steps, args.warmup, D.barrier, args.streams, args.issue)
         extras["headline_on_engine_" + other_engine] = headline.other_engine_block(M, K, N, w, o_wall, o_kern, args.steps, other_engine == "popcount")
         pop_block = extras["headline_on_engine_" + other_engine] if other_engine == "popcount" else None
-    # which kernel runs at this shape: the FP4 matrix-core kernel when the float32 sums stay exact (K (2^a - 1)(2^w - 1) < 2^24)
-    fp4_kernel = args.engine != "popcount" and w <= 8 and K * (2 ** w - 1) < 2 ** 24
     wall_max = D.max_over_ranks(wall, device)
     value = world * args.steps * 2.0 * M * K * N / wall_max / 1e12
     csum = torch.tensor([[float(out.to(torch.int64).sum().item())]], dtype=torch.float64, device=device)

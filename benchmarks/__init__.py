@@ -7,5 +7,6 @@
   tables.py    the reference's benchmark tables (2_7c, 5_9, Fig. 8a int8 comparison, width sweep) - extras file only
   launcher.py  `--gpus N` without a launcher, and the GPU-free dry run of the collectives
 
-bench.py prints ONE short JSON line; everything a table needs goes to the extras file the line names.
+bench.py prints ONE short JSON line; with --full every leg but the headline runs too, and everything a table needs goes to the
+extras file the line names.
 """

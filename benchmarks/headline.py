@@ -12,12 +12,12 @@ from .common import (CLOCK_WARMUP_S, EVENT_MIN_LAUNCHES, FP4_PEAK_TFLOPS, HBM_PE
                      VALU_PEAK_BITOPS_SURVEY, profile_summary)
 
 
-def time_steps(Q, out, bit_A, bit_X, M, K, N, w, steps, warmup, barrier, streams=1, issue="eager"):
+def time_steps(Q, out, bit_A, bit_X, M, K, N, w, steps, warmup, barrier, streams=1, issue="eager", live_windows=True):
     """`warmup` untimed launches, then EXACTLY `steps` launches between barrier + synchronize pairs (wall seconds), then
-    max(3, steps // 200) windows of 200 of the same launches, each between its own pair of HIP events on the launch
-    stream (their MEDIAN = the kernel's average launch duration: kernel + dependent-launch gap) - issued like the timed region
-    and, for the eager issue, once more replayed from a graph captured behind it. The events stay OUT of the timed region:
-    recording two of them costs 11-12 us of a 72 us region.
+    (unless `live_windows` is False: bench.py without --full) max(3, steps // 200) windows of 200 of the same launches, each between
+    its own pair of HIP events on the launch stream (their MEDIAN = the kernel's average launch duration: kernel + dependent-launch
+    gap) - issued like the timed region and, for the eager issue, once more replayed from a graph captured behind it. The events
+    stay OUT of the timed region: recording two of them costs 11-12 us of a 72 us region.
     issue: "eager" (default, the reference's loop) = K hipLaunchKernel calls inside the region; "graph" = the K launches
     captured once AHEAD of the region and replayed by one hipGraphLaunch inside it (same kernels in stream order).
     Returns (wall seconds, {how the window was issued: seconds per launch})."""
@@ -55,6 +55,8 @@ def time_steps(Q, out, bit_A, bit_X, M, K, N, w, steps, warmup, barrier, streams
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
+    if not live_windows:
+        return t1 - t0, {}
     # ---- the roofline's live launch duration: event-bracketed windows right behind it ----
     def windows(run):
         per_window = []

@@ -345,6 +345,26 @@ def test_bench_default_issue_is_the_references_loop():
     assert out.stdout.split() == ["eager", "1", "auto"], out.stderr[-500:]
 
 
+def test_plain_bench_run_is_the_headline_only():
+    """Without --full bench.py measures the headline alone: every other leg is off, nothing is dumped unless asked, and its line
+    carries the contract's fields without a `roofline` block."""
+    import argparse
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.argv=['bench.py']; import bench; a = bench.parse(); print(a.full, a.dump_outputs)\n"
+            "sys.argv=['bench.py', '--full', '--dump-outputs', 'd']; a = bench.parse(); print(a.full, a.dump_outputs)")
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    assert out.stdout.split() == ["False", "None", "True", "d"], out.stderr[-500:]
+    args = argparse.Namespace(steps=20, warmup=5, engine="auto", issue="eager", streams=1)
+    line = bench.compose_line(args, 1, 1, 4096, 4096, 64, 1, 600.0, 20 * 3.6e-6, True, None)
+    assert "roofline" not in line and line["ms_per_step"] == pytest.approx(0.0036)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+
+
 def test_quiet_fd1_keeps_c_printf_off_stdout():
     """The counter operators print with C printf (qgtc_torch.cpp, as kernel.h:19,27 do); a pipe-buffered printf surfaces at exit,
     BEHIND the JSON line, unless file descriptor 1 itself is parked and C stdio flushed - what benchmarks.common.quiet_fd1 does."""
