@@ -7,3 +7,6 @@ from qgtc_ppopp22_amd import load_ext as _load_ext
 _ext = _load_ext()
 globals().update({k: getattr(_ext, k) for k in dir(_ext) if not k.startswith("_") and k != "torch"})
 __doc__ = _ext.__doc__
+
+# the tile-compressed whole-graph adjacency (Python objects over the extension's _tiled_* entries)
+from qgtc_ppopp22_amd.tiled import TiledAdjacency, pack_edges_tiled, tiledMM2Bit, tiledMM2Int  # noqa: E402,F401

@@ -407,6 +407,38 @@ int qgtc_load_batches(const qgtc_loader_batch *batches, int count, int max_n, ui
                       uint64_t *stats, int *bad_index, unsigned formats, uint32_t *work, size_t work_words, void *stream);
 size_t qgtc_load_work_words(int count, int max_n, uint64_t total_edges);
 
+/* ---- Tile-compressed adjacency: a whole graph's 1-bit adjacency as its occupied tiles ------------------------------------------
+ * The dense route (qgtc_pack_edge_list + qgtc_bitmm2bit) stores and streams all n^2 / 8 bytes of the adjacency and stops at
+ * n = 185 363 (4 GiB per packed operand). This format keeps only the 32-row x 128-column tiles with a set bit, block-sparse like BSR:
+ *   row_ptr  int64 [S32(n) + 1]       the tiles of 32-row block rb are row_ptr[rb] .. row_ptr[rb + 1] - 1; row_ptr[S32(n)] = T
+ *   kquad    int32 [T]                the k-quad (128-column group) of each tile, strictly ascending within a row block
+ *   tiles    32-bit words [T][32][4]  the 512-byte adjacency tile of qgtc_adj_tiles_words: row r of the block, the tile's 4 words of
+ *                                     that row, element i at word i>>5, bit 31-(i&31); rows and columns past n are zero
+ * S32(n) = (n + 31) / 32. Domain 1 <= n <= 2^23. The bits are exactly the words qgtc_pack_edge_list gives for the same raw edge list
+ * (duplicates allowed: multiplicities 1, 2, >= 3 quantise to 1, 0, 1; self loops kept); only tiles with a set bit are stored, so the
+ * format is canonical.
+ *
+ * Packing takes two calls, because T is known only after the first:
+ *   qgtc_tiled_count   sorts the edges' cell keys in `work` (qgtc_tiled_work_words(n_edges) 32-bit words, 256-byte aligned) and
+ *                      writes row_ptr; the caller reads row_ptr[S32(n)] = T and allocates kquad and tiles;
+ *   qgtc_tiled_fill    writes kquad and every word of tiles from the same `work`, untouched in between.
+ * Out-of-range or negative indices are skipped and, if `bad_index` (device int, cleared by the call) is given, reported there (1).
+ *
+ * Product (qgtc_tiledmm2bit / qgtc_tiledmm2int): requant(A_tiled . X), word for word what qgtc_bitmm2bit / qgtc_bitmm2int
+ * (pad_128 = 1) give for the dense rows-layout A of the same edge list: X in the cols layout [bit2][PAD128(N)][S128(n)*4]
+ * (bit2 1 .. 8, any N >= 1); out = rows layout [output_bit][PAD8(n)][S128(N)*4] (every word written; a row block without tiles
+ * gives zeros) or float32 [n, N]. The int32 sums are exact for every row (deg (2^bit2 - 1) < 2^31). One kernel family whatever
+ * the engine flags of the dense entries say; no work buffer. */
+size_t qgtc_tiled_work_words(size_t n_edges);
+int qgtc_tiled_count(const int64_t *src, const int64_t *dst, size_t n_edges, int n, int64_t *row_ptr, uint32_t *work,
+                     size_t work_words, int *bad_index, void *stream);
+int qgtc_tiled_fill(size_t n_edges, int n, int64_t n_tiles, int32_t *kquad, uint32_t *tiles, const uint32_t *work,
+                    size_t work_words, void *stream);
+int qgtc_tiledmm2bit(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+                     size_t x_words, int N, int bit2, int output_bit, uint32_t *out, size_t out_words, void *stream);
+int qgtc_tiledmm2int(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+                     size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,17 +72,31 @@ class GCNConv_Qnt(torch.nn.Module):
         return QGTC.val2bit(X.contiguous(), self.act_bit, False, False)
 
     def forward(self, A, X):
-        """X: node embeddings [n_nodes, n_dim]; A: the subgraph's adjacency (dense or edge list)."""
+        """X: node embeddings [n_nodes, n_dim]; A: the subgraph's adjacency (dense or edge list), or a whole graph's
+        QGTC.TiledAdjacency (QGTC.pack_edges_tiled)."""
         if self.bit_W_in is None or self._packed_from != self._weights_key():
             self.weight_Qnt()
         assert X.device == self.W_in.device, "inputs and weights must be on the same device"
         n = X.size(0)
+        if isinstance(A, QGTC.TiledAdjacency):
+            return self._forward_tiled(A, X)
         bit_A = self.A_Qnt(A)
         bit_X = self.X_Qnt(X)
         bit_h = Aggregation_Qnt.apply(bit_A, bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim,
                                       self.act_bit, self.w_bit, False)
         return Aggregation_Qnt.apply(bit_A, bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim,
                                      self.act_bit, self.w_bit, True)
+
+    def _forward_tiled(self, A, X):
+        """The same two layers with the tile-compressed aggregate: per layer X.W re-packed in the cols layout
+        (bitMM2Bit_col), then tiledMM2Bit / tiledMM2Int - the words gcn_layer gives on the dense adjacency."""
+        n = X.size(0)
+        assert A.n == n, "the adjacency and X must have the same number of nodes"
+        bit_X = self.X_Qnt(X)
+        t = QGTC.bitMM2Bit_col(bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim, self.act_bit, self.w_bit, self.act_bit)
+        bit_h = QGTC.tiledMM2Bit(A, t, self.hidden_dim, self.act_bit, self.act_bit)
+        t = QGTC.bitMM2Bit_col(bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim, self.act_bit, self.w_bit, self.act_bit)
+        return QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit)
 
 
 class GCNConv(torch.nn.Module):

@@ -1,0 +1,152 @@
+// qgtc_tiled.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the tile-compressed adjacency of a
+// whole graph (tiled_kernels.hip.h) - the two-phase packer from a raw edge list and the product requant(A_tiled . X) - and their
+// launchers. The packer's sort and scans are rocPRIM's.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "qgtc.h"
+
+#include "common.hip.h"
+#include "bitmm_popcount.hip.h"   // requant (templates only: nothing is instantiated here)
+#include "tiled_kernels.hip.h"
+
+namespace {
+
+constexpr int TILED_MAX_N = 1 << 23;
+
+int tiled_grid(uint64_t items) {
+    const uint64_t b = (items + 255) / 256;
+    return static_cast<int>(b < 8192 ? (b ? b : 1) : 8192);
+}
+
+// bytes of rocPRIM temporary storage for n_edges keys: the larger of the sort's and the scan's (the queries look at the current
+// device; false when they fail)
+bool tiled_temp_bytes(size_t e, size_t &bytes) {
+    size_t sort_bytes = 0, scan_bytes = 0;
+    if (rocprim::radix_sort_keys(nullptr, sort_bytes, static_cast<const uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), e, 0,
+                                 TILED_KEY_BITS) != hipSuccess ||
+        rocprim::exclusive_scan(nullptr, scan_bytes, static_cast<const uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+                                static_cast<uint64_t>(0), e, rocprim::plus<uint64_t>()) != hipSuccess)
+        return false;
+    bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
+    return true;
+}
+
+// work buffer: [keys A | keys B | keys C] (n_edges 64-bit words each) then the temporary storage at a 256-byte boundary
+size_t tiled_temp_offset_bytes(size_t e) { return (3 * e * sizeof(uint64_t) + 255) & ~static_cast<size_t>(255); }
+
+}  // namespace
+
+size_t qgtc_tiled_work_words(size_t n_edges) {
+    size_t temp = 0;
+    if (n_edges == 0 || !tiled_temp_bytes(n_edges, temp)) return 0;
+    return (tiled_temp_offset_bytes(n_edges) + temp + 3) / 4;
+}
+
+int qgtc_tiled_count(const int64_t *src, const int64_t *dst, size_t n_edges, int n, int64_t *row_ptr, uint32_t *work,
+                     size_t work_words, int *bad_index, void *stream) {
+    if (!row_ptr || n < 1 || n > TILED_MAX_N || (n_edges && (!src || !dst || !work))) return QGTC_EINVAL;
+    if (n_edges && work_words < qgtc_tiled_work_words(n_edges)) return QGTC_ESIZE;
+    if (reinterpret_cast<uintptr_t>(work) & 255u) return QGTC_EALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nq = step128(n), nrb = (n + 31) / 32;
+    HIP_TRY(hipMemsetAsync(row_ptr, 0, (nrb + 1) * sizeof(int64_t), st));
+    if (bad_index) HIP_TRY(hipMemsetAsync(bad_index, 0, sizeof(int), st));
+    if (!n_edges) return QGTC_OK;
+    const uint64_t e = n_edges;
+    uint64_t *A = reinterpret_cast<uint64_t *>(work), *B = A + e, *C = B + e;
+    void *temp = reinterpret_cast<char *>(work) + tiled_temp_offset_bytes(e);
+    size_t temp_bytes = 0;
+    if (!tiled_temp_bytes(e, temp_bytes)) return QGTC_ENODEVICE;
+    const int g = tiled_grid(e);
+    hipLaunchKernelGGL(k_tiled_keys, dim3(g), dim3(256), 0, st, src, dst, e, n, nq, A, bad_index);
+    HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, e, 0, TILED_KEY_BITS, st));
+    hipLaunchKernelGGL(k_tiled_flags, dim3(g), dim3(256), 0, st, B, e, C);
+    HIP_TRY(rocprim::exclusive_scan(temp, temp_bytes, C, A, static_cast<uint64_t>(0), e, rocprim::plus<uint64_t>(), st));
+    HIP_TRY(hipMemsetAsync(C, 0xFF, e * sizeof(uint64_t), st));
+    hipLaunchKernelGGL(k_tiled_compact, dim3(g), dim3(256), 0, st, B, A, e, C);
+    hipLaunchKernelGGL(k_tiled_starts, dim3(g), dim3(256), 0, st, C, e, A);
+    HIP_TRY(rocprim::exclusive_scan(temp, temp_bytes, A, B, static_cast<uint64_t>(0), e, rocprim::plus<uint64_t>(), st));
+    hipLaunchKernelGGL(k_tiled_row_ptr, dim3(g), dim3(256), 0, st, C, A, B, e, nq, nrb, row_ptr);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+int qgtc_tiled_fill(size_t n_edges, int n, int64_t n_tiles, int32_t *kquad, uint32_t *tiles, const uint32_t *work,
+                    size_t work_words, void *stream) {
+    if (n < 1 || n > TILED_MAX_N || n_tiles < 0 || (n_tiles && (!kquad || !tiles || !work)) ||
+        static_cast<uint64_t>(n_tiles) > n_edges)
+        return QGTC_EINVAL;
+    if (n_tiles == 0) return QGTC_OK;
+    if (work_words < qgtc_tiled_work_words(n_edges)) return QGTC_ESIZE;
+    if (reinterpret_cast<uintptr_t>(work) & 255u) return QGTC_EALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t e = n_edges;
+    const uint64_t *A = reinterpret_cast<const uint64_t *>(work), *B = A + e, *C = B + e;
+    HIP_TRY(hipMemsetAsync(tiles, 0, static_cast<size_t>(n_tiles) * 512, st));
+    hipLaunchKernelGGL(k_tiled_fill, dim3(tiled_grid(e)), dim3(256), 0, st, C, A, B, e, step128(n), static_cast<uint64_t>(n_tiles),
+                       kquad, tiles);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+namespace {
+
+template <int MODE>
+int tiled_mm(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+             size_t x_words, int N, int bit2, int ob, void *out, hipStream_t st) {
+    const int nrb = (n + 31) / 32;
+    const float maxv = std::ldexp(1.0f, ob), maxm1 = maxv - 1.0f;
+    const dim3 block(256);
+    // rows a thread owns: the narrowest layout whose columns cover min(N, 128)
+    const int R = N <= 16 ? 2 : (N <= 32 ? 4 : (N <= 64 ? 8 : 16));
+    const dim3 grid(nrb, R == 16 ? step128(N) : 1);
+    const uint64_t nt = static_cast<uint64_t>(n_tiles);
+#define QGTC_TILED_LAUNCH(RR)                                                                                                   \
+    hipLaunchKernelGGL((k_tiled_mm<RR, MODE>), grid, block, 0, st, row_ptr, kquad, tiles, nt, n, X, static_cast<uint64_t>(x_words), \
+                       N, bit2, ob, maxv, maxm1, out)
+    switch (R) {
+        case 2: QGTC_TILED_LAUNCH(2); break;
+        case 4: QGTC_TILED_LAUNCH(4); break;
+        case 8: QGTC_TILED_LAUNCH(8); break;
+        default: QGTC_TILED_LAUNCH(16); break;
+    }
+#undef QGTC_TILED_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+int tiled_mm_args_ok(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+                     int N, int bit2, const void *out) {
+    if (!row_ptr || !X || !out || n < 1 || n > TILED_MAX_N || N < 1 || bit2 < 1 || bit2 > 8 || n_tiles < 0 ||
+        (n_tiles && (!kquad || !tiles)))
+        return QGTC_EINVAL;
+    if (!aligned16(X) || !aligned16(out) || (tiles && !aligned16(tiles))) return QGTC_EALIGN;
+    return QGTC_OK;
+}
+
+}  // namespace
+
+int qgtc_tiledmm2bit(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+                     size_t x_words, int N, int bit2, int output_bit, uint32_t *out, size_t out_words, void *stream) {
+    const int rc = tiled_mm_args_ok(row_ptr, kquad, tiles, n_tiles, n, X, N, bit2, out);
+    if (rc != QGTC_OK) return rc;
+    if (!bits_ok(output_bit)) return QGTC_EINVAL;
+    if (out_words < qgtc_rows_words(n, N, output_bit)) return QGTC_ESIZE;
+    return tiled_mm<0>(row_ptr, kquad, tiles, n_tiles, n, X, x_words, N, bit2, output_bit, out, static_cast<hipStream_t>(stream));
+}
+
+int qgtc_tiledmm2int(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
+                     size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream) {
+    const int rc = tiled_mm_args_ok(row_ptr, kquad, tiles, n_tiles, n, X, N, bit2, out);
+    if (rc != QGTC_OK) return rc;
+    if (out_elems < static_cast<size_t>(n) * N) return QGTC_ESIZE;
+    return tiled_mm<2>(row_ptr, kquad, tiles, n_tiles, n, X, x_words, N, bit2, 1, out, static_cast<hipStream_t>(stream));
+}

@@ -365,6 +365,76 @@ torch::Tensor pack_edges(torch::Tensor src, torch::Tensor dst, const int height,
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Tile-compressed adjacency (qgtc_tiled_*; the Python object is qgtc_ppopp22_amd.tiled.TiledAdjacency). Packing returns
+// [row_ptr int64 [S32(n)+1], kquad int32 [T], tiles int32 [T, 32, 4]]; the count phase ends in the one host read of T.
+std::vector<torch::Tensor> tiled_pack(torch::Tensor src, torch::Tensor dst, const int64_t n, const bool validate) {
+    CHECK_INPUT(src);
+    CHECK_INPUT(dst);
+    TORCH_CHECK(src.scalar_type() == torch::kInt64 && dst.scalar_type() == torch::kInt64, "src and dst must be int64 index tensors");
+    TORCH_CHECK(src.dim() == 1 && src.sizes() == dst.sizes(), "src and dst must be 1-D and equally long");
+    TORCH_CHECK(src.device() == dst.device(), "src and dst must be on the same device");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    c10::DeviceGuard guard(src.device());
+    const auto dev = src.device();
+    const size_t e = static_cast<size_t>(src.numel());
+    const int nrb = static_cast<int>((n + 31) / 32);
+    auto row_ptr = torch::empty({nrb + 1}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    const size_t work_words = qgtc_tiled_work_words(e);
+    torch::Tensor work;
+    if (work_words) work = torch::empty({static_cast<int64_t>(work_words)}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    torch::Tensor bad;
+    if (validate) bad = torch::empty({1}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    void *st = current_stream(src);
+    uint32_t *w = work.defined() ? words_mut(work) : nullptr;
+    check_rc(qgtc_tiled_count(e ? src.data_ptr<int64_t>() : nullptr, e ? dst.data_ptr<int64_t>() : nullptr, e, static_cast<int>(n),
+                              row_ptr.data_ptr<int64_t>(), w, work_words, validate ? bad.data_ptr<int>() : nullptr, st),
+             "pack_edges_tiled");
+    const int64_t T = row_ptr[nrb].item<int64_t>();
+    if (validate) TORCH_CHECK(bad.item<int>() == 0, "edge index out of range");
+    auto kquad = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    auto tiles = torch::empty({T, 32, 4}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    check_rc(qgtc_tiled_fill(e, static_cast<int>(n), T, T ? kquad.data_ptr<int32_t>() : nullptr, T ? words_mut(tiles) : nullptr, w,
+                             work_words, st),
+             "pack_edges_tiled");
+    return {row_ptr, kquad, tiles};
+}
+
+torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor bit_X,
+                       const int N, const int bit2, const int output_bit, const bool to_float) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    CHECK_INPUT(tiles);
+    CHECK_INPUT(bit_X);
+    check_bits_tensor(bit_X, "bit_X");
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
+    TORCH_CHECK(row_ptr.device() == bit_X.device() && kquad.device() == bit_X.device() && tiles.device() == bit_X.device(),
+                "the adjacency and bit_X must be on the same device");
+    TORCH_CHECK(N > 0, "bad dimensions");
+    c10::DeviceGuard guard(bit_X.device());
+    const int nn = static_cast<int>(n);
+    const int64_t T = kquad.numel();
+    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    if (to_float) {
+        auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
+        check_rc(qgtc_tiledmm2int(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, out.data_ptr<float>(),
+                                  out.numel(), current_stream(bit_X)),
+                 "tiledMM2Int");
+        return out;
+    }
+    auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
+                            torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
+    check_rc(qgtc_tiledmm2bit(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
+                              words_mut(out), out.numel(), current_stream(bit_X)),
+             "tiledMM2Bit");
+    return out;
+}
+
 // int8 MFMA GEMM (comparison path, cuBLASGemmEX analogue): float32 [M,N] = A[M,K] x Bt[N,K]^T
 torch::Tensor i8gemm(torch::Tensor A, torch::Tensor Bt) {
     CHECK_INPUT(A);
@@ -1363,6 +1433,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pack_edges", &pack_edges, "rows-layout bit planes of the [height, width] adjacency of an edge list "
           "(= val2bit of the dense matrix, without materialising it)", py::arg("src"), py::arg("dst"),
           py::arg("height"), py::arg("width"), py::arg("nbits") = 1, py::arg("validate") = true);
+    m.def("_tiled_pack", &tiled_pack, "[row_ptr, kquad, tiles] of the tile-compressed 1-bit adjacency of an edge list "
+          "(QGTC.pack_edges_tiled wraps it)", py::arg("src"), py::arg("dst"), py::arg("n"), py::arg("validate") = true);
+    m.def("_tiled_mm", &tiled_mm, "requant(A_tiled . X): rows-layout bits, or float32 [n, N] with to_float "
+          "(QGTC.tiledMM2Bit / tiledMM2Int wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"),
+          py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"), py::arg("to_float"));
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");
     m.def("i8gemm_profile", &i8gemm_profile, "time `reps` i8gemm launches; returns milliseconds",
           py::arg("A"), py::arg("Bt"), py::arg("reps") = 200, py::arg("print") = true);

@@ -1,0 +1,60 @@
+"""C-ABI of the tile-compressed adjacency (include/qgtc.h, qgtc_tiled_*): exported, and bad arguments are refused before any device
+work (no GPU needed). The test keeps its own ctypes mirrors of the entry points."""
+import ctypes
+
+import pytest
+
+EINVAL, ESIZE = 1, 2
+P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import qgtc_ppopp22_amd
+
+    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
+    L.qgtc_tiled_work_words.restype = SZ
+    L.qgtc_tiled_work_words.argtypes = [SZ]
+    L.qgtc_tiled_count.argtypes = [P, P, SZ, I, P, P, SZ, P, P]
+    L.qgtc_tiled_fill.argtypes = [SZ, I, I64, P, P, P, SZ, P]
+    L.qgtc_tiledmm2bit.argtypes = [P, P, P, I64, I, P, SZ, I, I, I, P, SZ, P]
+    L.qgtc_tiledmm2int.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P]
+    return L
+
+
+def _buf(words):
+    b = (ctypes.c_uint32 * (words + 64))()
+    addr = ctypes.addressof(b)
+    return b, (addr + 255) & ~255   # keep the buffer alive; 256-byte aligned address inside it
+
+
+def test_entries_are_exported(lib):
+    for name in ("qgtc_tiled_work_words", "qgtc_tiled_count", "qgtc_tiled_fill", "qgtc_tiledmm2bit", "qgtc_tiledmm2int"):
+        assert hasattr(lib, name)
+    assert lib.qgtc_tiled_work_words(0) == 0
+
+
+def test_count_and_fill_refuse_bad_arguments(lib):
+    keep, p = _buf(1024)
+    assert lib.qgtc_tiled_count(p, p, 10, 0, p, p, 1024, None, None) == EINVAL            # n < 1
+    assert lib.qgtc_tiled_count(p, p, 10, (1 << 23) + 1, p, p, 1024, None, None) == EINVAL  # n > 2^23
+    assert lib.qgtc_tiled_count(None, p, 10, 100, p, p, 1024, None, None) == EINVAL       # edges without src
+    assert lib.qgtc_tiled_count(p, p, 10, 100, None, p, 1024, None, None) == EINVAL       # no row_ptr
+    assert lib.qgtc_tiled_count(p, p, 10, 100, p, None, 0, None, None) == EINVAL          # edges without a work buffer
+    assert lib.qgtc_tiled_fill(10, 100, -1, p, p, p, 1024, None) == EINVAL                # negative tile count
+    assert lib.qgtc_tiled_fill(10, 100, 11, p, p, p, 1024, None) == EINVAL                # more tiles than edges
+    assert lib.qgtc_tiled_fill(10, 100, 3, None, p, p, 1024, None) == EINVAL              # no kquad
+
+
+def test_products_refuse_bad_arguments(lib):
+    keep, p = _buf(1 << 16)
+    for fn, tail in ((lib.qgtc_tiledmm2bit, lambda w, ob: (w, ob, p, 1 << 16, None)), (lib.qgtc_tiledmm2int, lambda w, ob: (w, p, 1 << 16, None))):
+        assert fn(p, p, p, 1, 0, p, 1 << 16, 8, *tail(2, 2)) == EINVAL       # n < 1
+        assert fn(p, p, p, 1, 100, p, 1 << 16, 0, *tail(2, 2)) == EINVAL     # N < 1
+        assert fn(p, p, p, 1, 100, p, 1 << 16, 8, *tail(9, 2)) == EINVAL     # bit2 > 8
+        assert fn(p, p, p, 1, 100, p, 1 << 16, 8, *tail(0, 2)) == EINVAL     # bit2 < 1
+        assert fn(p, None, p, 1, 100, p, 1 << 16, 8, *tail(2, 2)) == EINVAL  # tiles without kquad
+        assert fn(None, p, p, 1, 100, p, 1 << 16, 8, *tail(2, 2)) == EINVAL  # no row_ptr
+    assert lib.qgtc_tiledmm2bit(p, p, p, 1, 100, p, 1 << 16, 8, 2, 33, p, 1 << 16, None) == EINVAL   # output_bit > 32
+    assert lib.qgtc_tiledmm2bit(p, p, p, 1, 100, p, 1 << 16, 8, 2, 4, p, 10, None) == ESIZE          # out too small
+    assert lib.qgtc_tiledmm2int(p, p, p, 1, 100, p, 1 << 16, 8, 2, p, 799, None) == ESIZE            # out too small

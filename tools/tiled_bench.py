@@ -1,0 +1,107 @@
+"""Measure the tile-compressed whole-graph adjacency (QGTC.pack_edges_tiled + tiledMM2Bit) on SBM graphs of public-dataset size.
+
+Per graph, as generated (block-local numbering) and under a random node permutation: pack time, occupied tiles T, tile bytes, and
+the aggregate requant(A . X) (rows-layout output, ob = w) at N in {16, 64, 256} and w in {1, 2, 4}, with the HBM fraction of the
+algorithmic bytes (512 T + 12 T + X + out) against 8 TB/s. At the arxiv size also the dense route (pack_edges + bitMM2Bit).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+GRAPHS = {  # name -> (nodes, average out-degree)
+    "arxiv": (169343, 7.0),
+    "reddit": (232965, 20.0),
+    "products": (2449029, 25.0),
+}
+HBM_BPS = 8e12
+
+
+def timed(torch, fn, reps, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return float(np.median([a.elapsed_time(b) for a, b in ev]))   # ms
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--graphs", default="arxiv,reddit,products")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+
+    import torch
+
+    import QGTC
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in args.graphs.split(","):
+        n, deg = GRAPHS[name]
+        t0 = time.time()
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        gen_s = time.time() - t0
+        perm = np.random.default_rng(7).permutation(n)
+        for order in ("block-local", "permuted"):
+            src, dst = (g.src, g.dst) if order == "block-local" else (perm[g.src], perm[g.dst])
+            dsrc, ddst = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda()
+            pack_ms = timed(torch, lambda: QGTC.pack_edges_tiled(dsrc, ddst, n, False), max(3, args.reps // 3), warmup=1)
+            adj = QGTC.pack_edges_tiled(dsrc, ddst, n)
+            T = adj.n_tiles
+            rec = {"graph": name, "order": order, "n": n, "edges": int(src.size), "gen_s": round(gen_s, 1), "pack_ms": round(pack_ms, 3),
+                   "tiles": T, "tile_bytes": 512 * T, "max_block_tiles": adj.max_block_tiles, "agg": []}
+            rng = np.random.default_rng(1)
+            for N in (16, 64, 256):
+                for w in (1, 2, 4):
+                    X = QGTC.val2bit(torch.from_numpy(rng.integers(0, 2 ** w, size=(n, N)).astype(np.float32)).cuda(), w, True, False)
+                    out = QGTC.tiledMM2Bit(adj, X, N, w, w)
+                    ms = timed(torch, lambda: QGTC.tiledMM2Bit(adj, X, N, w, w), args.reps)
+                    algo = 524 * T + X.numel() * 4 + out.numel() * 4
+                    rec["agg"].append({"N": N, "w": w, "ms": round(ms, 4), "hbm_frac": round(algo / (ms * 1e-3) / HBM_BPS, 4)})
+                    print(f"{name:9s} {order:11s} T={T:>10d} N={N:<4d} w={w} agg {ms:9.4f} ms  hbm {rec['agg'][-1]['hbm_frac']:.3f}",
+                          flush=True)
+                    del X, out
+            if name == "arxiv":
+                # the dense route of the same edge list: pack_edges + bitMM2Bit (n^2 / 8 bytes of adjacency)
+                A = QGTC.pack_edges(dsrc, ddst, n, n, 1, False)
+                dense = {"pack_ms": round(timed(torch, lambda: QGTC.pack_edges(dsrc, ddst, n, n, 1, False), 3, warmup=1), 3),
+                         "adj_bytes": A.numel() * 4, "agg": []}
+                for N, w in ((16, 1), (64, 2), (256, 4)):
+                    X = QGTC.val2bit(torch.from_numpy(rng.integers(0, 2 ** w, size=(n, N)).astype(np.float32)).cuda(), w, True, False)
+                    ms = timed(torch, lambda: QGTC.bitMM2Bit(A, X, n, n, N, 1, w, w), max(3, args.reps // 2))
+                    assert torch.equal(QGTC.bitMM2Bit(A, X, n, n, N, 1, w, w), QGTC.tiledMM2Bit(adj, X, N, w, w))
+                    dense["agg"].append({"N": N, "w": w, "ms": round(ms, 4)})
+                    print(f"{name:9s} {order:11s} dense route N={N:<4d} w={w} agg {ms:9.4f} ms (pack {dense['pack_ms']} ms)", flush=True)
+                    del X
+                rec["dense"] = dense
+                del A
+            print(f"{name:9s} {order:11s} pack {pack_ms:.3f} ms  T={T}  tiles {512 * T / 2**20:.1f} MiB  edges {src.size}", flush=True)
+            rows.append(rec)
+            del adj, dsrc, ddst
+            torch.cuda.empty_cache()
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+    print(json.dumps({"tiled_bench": [{k: v for k, v in r.items() if k != "agg"} for r in rows]}))
+
+
+if __name__ == "__main__":
+    main()
