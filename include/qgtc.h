@@ -439,6 +439,29 @@ int qgtc_tiledmm2bit(const int64_t *row_ptr, const int32_t *kquad, const uint32_
 int qgtc_tiledmm2int(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
                      size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream);
 
+/* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
+ * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
+ * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:
+ *   neighbour entries  every valid edge s -> d with s != d adds the entries (s, d) and (d, s); duplicates count once each; self loops
+ *                      and out-of-range edges add nothing (the latter are reported through `bad_index`, as in qgtc_tiled_count);
+ *   sweeps             label[x] = x, then sweeps t = 0 .. sweeps - 1 (all on the labels before the sweep): a node x with entries and
+ *                      (x + t) even proposes the label l most of its entries' other ends carry, ties to the smallest
+ *                      mix32(l ^ (0x9E3779B9 (t + 1) mod 2^32)) (lowbias32); every other node proposes its own label. A proposal
+ *                      is taken when it is the current label or at most `cap` nodes propose it (a soft cap). The sweeps stop after
+ *                      two in a row that change no label;
+ *   output             perm (int64 [n]) = the nodes sorted by (label, id), perm[new] = old; rank (int64 [n], may be NULL) its
+ *                      inverse, rank[old] = new. With no edges or sweeps = 0 both are the identity.
+ * The result is deterministic (integer counts; it does not depend on the order in which atomics land) and equals the NumPy model in
+ * tests/reorder_model.py element for element. Relabelled edges (rank[src], rank[dst]) packed with qgtc_tiled_count / _fill give the
+ * adjacency in the new numbering; the products then read X and give their output in that numbering.
+ * Domain: 1 <= n <= 2^23, 0 <= sweeps <= 64, cap >= 1. `work`: qgtc_reorder_work_words(n, n_edges) 32-bit words, 256-byte aligned
+ * (unused and may be NULL without edges; the size query needs the device: 0 when it fails or n is outside the domain). QGTC_EINVAL
+ * for a domain violation, a missing perm, or edges without src, dst or work; QGTC_ESIZE for a work buffer that is too small. The host
+ * queues every launch without reading anything back. */
+size_t qgtc_reorder_work_words(int n, size_t n_edges);
+int qgtc_reorder_nodes(const int64_t *src, const int64_t *dst, size_t n_edges, int n, int sweeps, int cap, int64_t *perm,
+                       int64_t *rank, uint32_t *work, size_t work_words, int *bad_index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

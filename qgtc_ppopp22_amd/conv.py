@@ -89,14 +89,17 @@ class GCNConv_Qnt(torch.nn.Module):
 
     def _forward_tiled(self, A, X):
         """The same two layers with the tile-compressed aggregate: per layer X.W re-packed in the cols layout
-        (bitMM2Bit_col), then tiledMM2Bit / tiledMM2Int - the words gcn_layer gives on the dense adjacency."""
+        (bitMM2Bit_col), then tiledMM2Bit / tiledMM2Int - the words gcn_layer gives on the dense adjacency. A reordered
+        adjacency (A.perm set) gets X in its numbering and gives the output back in X's: every term moves with its node and the
+        quantisers work element by element, so the result is bit-identical to the unreordered one."""
         n = X.size(0)
         assert A.n == n, "the adjacency and X must have the same number of nodes"
+        X = A.to_new(X)
         bit_X = self.X_Qnt(X)
         t = QGTC.bitMM2Bit_col(bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim, self.act_bit, self.w_bit, self.act_bit)
         bit_h = QGTC.tiledMM2Bit(A, t, self.hidden_dim, self.act_bit, self.act_bit)
         t = QGTC.bitMM2Bit_col(bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim, self.act_bit, self.w_bit, self.act_bit)
-        return QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit)
+        return A.to_old(QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit))
 
 
 class GCNConv(torch.nn.Module):

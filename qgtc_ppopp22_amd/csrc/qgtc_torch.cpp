@@ -400,6 +400,36 @@ std::vector<torch::Tensor> tiled_pack(torch::Tensor src, torch::Tensor dst, cons
     return {row_ptr, kquad, tiles};
 }
 
+// Node reordering (qgtc_reorder_*): [perm, rank] int64 [n] on the edges' device; validate ends in one host read of bad_index.
+std::vector<torch::Tensor> reorder_nodes(torch::Tensor src, torch::Tensor dst, const int64_t n, const int64_t sweeps, const int64_t cap,
+                                         const bool validate) {
+    CHECK_INPUT(src);
+    CHECK_INPUT(dst);
+    TORCH_CHECK(src.scalar_type() == torch::kInt64 && dst.scalar_type() == torch::kInt64, "src and dst must be int64 index tensors");
+    TORCH_CHECK(src.dim() == 1 && src.sizes() == dst.sizes(), "src and dst must be 1-D and equally long");
+    TORCH_CHECK(src.device() == dst.device(), "src and dst must be on the same device");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(sweeps >= 0 && sweeps <= 64, "sweeps must lie in [0, 64]");
+    TORCH_CHECK(cap >= 1 && cap <= INT32_MAX, "cap must be at least 1");
+    c10::DeviceGuard guard(src.device());
+    const auto opts = torch::TensorOptions().dtype(torch::kInt64).device(src.device());
+    const size_t e = static_cast<size_t>(src.numel());
+    auto perm = torch::empty({n}, opts), rank = torch::empty({n}, opts);
+    const size_t work_words = e ? qgtc_reorder_work_words(static_cast<int>(n), e) : 0;
+    TORCH_CHECK(!e || work_words, "reorder_nodes: no usable device");
+    torch::Tensor work;
+    if (work_words) work = torch::empty({static_cast<int64_t>(work_words)}, torch::TensorOptions().dtype(torch::kInt32).device(src.device()));
+    torch::Tensor bad;
+    if (validate) bad = torch::empty({1}, torch::TensorOptions().dtype(torch::kInt32).device(src.device()));
+    check_rc(qgtc_reorder_nodes(e ? src.data_ptr<int64_t>() : nullptr, e ? dst.data_ptr<int64_t>() : nullptr, e, static_cast<int>(n),
+                                static_cast<int>(sweeps), static_cast<int>(cap), perm.data_ptr<int64_t>(), rank.data_ptr<int64_t>(),
+                                work.defined() ? words_mut(work) : nullptr, work_words, validate ? bad.data_ptr<int>() : nullptr,
+                                current_stream(src)),
+             "reorder_nodes");
+    if (validate) TORCH_CHECK(bad.item<int>() == 0, "edge index out of range");
+    return {perm, rank};
+}
+
 torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor bit_X,
                        const int N, const int bit2, const int output_bit, const bool to_float) {
     CHECK_INPUT(row_ptr);
@@ -1435,6 +1465,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("height"), py::arg("width"), py::arg("nbits") = 1, py::arg("validate") = true);
     m.def("_tiled_pack", &tiled_pack, "[row_ptr, kquad, tiles] of the tile-compressed 1-bit adjacency of an edge list "
           "(QGTC.pack_edges_tiled wraps it)", py::arg("src"), py::arg("dst"), py::arg("n"), py::arg("validate") = true);
+    m.def("_reorder_nodes", &reorder_nodes, "[perm, rank] of the node reordering for the tiled adjacency (QGTC.reorder_nodes and "
+          "pack_edges_tiled(reorder=True) wrap it)", py::arg("src"), py::arg("dst"), py::arg("n"), py::arg("sweeps") = 20,
+          py::arg("cap") = 128, py::arg("validate") = true);
     m.def("_tiled_mm", &tiled_mm, "requant(A_tiled . X): rows-layout bits, or float32 [n, N] with to_float "
           "(QGTC.tiledMM2Bit / tiledMM2Int wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"),
           py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"), py::arg("to_float"));

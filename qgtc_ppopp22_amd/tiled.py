@@ -3,7 +3,11 @@
 The dense route packs an n x n adjacency into n^2/8 bytes and stops at n = 185 363 (4 GiB per packed operand). A
 :class:`TiledAdjacency` keeps only the occupied 32-row x 128-column tiles, block-sparse like BSR, and
 :func:`tiledMM2Bit` / :func:`tiledMM2Int` multiply from that storage: word for word what ``bitMM2Bit`` / ``bitMM2Int`` give
-on ``pack_edges(src, dst, n, n, 1)`` of the same edge list. ``QGTC`` re-exports the three functions and the class.
+on ``pack_edges(src, dst, n, n, 1)`` of the same edge list. ``QGTC`` re-exports the functions and the class.
+
+The format is compact only when a node's neighbours have nearby ids. :func:`reorder_nodes` renumbers the nodes of an edge list with
+any ids on the device (include/qgtc.h, "Node reordering"), and ``pack_edges_tiled(..., reorder=True)`` packs the graph in that
+numbering; the adjacency then carries ``perm`` / ``rank`` and moves tensors between the two numberings.
 """
 from __future__ import annotations
 
@@ -13,7 +17,7 @@ from . import load_ext
 
 _ext = load_ext()
 
-__all__ = ["TiledAdjacency", "pack_edges_tiled", "tiledMM2Bit", "tiledMM2Int"]
+__all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int"]
 
 
 class TiledAdjacency:
@@ -22,11 +26,18 @@ class TiledAdjacency:
     ``row_ptr`` int64 [S32(n) + 1]: the tiles of 32-row block rb are ``row_ptr[rb] .. row_ptr[rb+1] - 1``;
     ``kquad`` int32 [T]: the 128-column group of each tile, strictly ascending within a row block;
     ``tiles`` int32 words [T, 32, 4]: row r of the block, the tile's 4 words of that row (element i at word i>>5, bit 31-(i&31)).
+
+    From ``pack_edges_tiled(..., reorder=True)`` the adjacency is that of the renumbered graph: ``perm`` int64 [n] (perm[new] = old)
+    and ``rank`` int64 [n] (rank[old] = new) are set, and tiledMM2Bit / tiledMM2Int read X and give their output in the new
+    numbering (:meth:`to_new`, :meth:`to_old`, :meth:`to_old_packed` move tensors across). Otherwise both are None and the node ids
+    are the edge list's.
     """
 
-    def __init__(self, n: int, row_ptr: torch.Tensor, kquad: torch.Tensor, tiles: torch.Tensor):
+    def __init__(self, n: int, row_ptr: torch.Tensor, kquad: torch.Tensor, tiles: torch.Tensor, perm: torch.Tensor | None = None,
+                 rank: torch.Tensor | None = None):
         self.n = int(n)
         self.row_ptr, self.kquad, self.tiles = row_ptr, kquad, tiles
+        self.perm, self.rank = perm, rank
         self._max_block_tiles = None
 
     @property
@@ -60,16 +71,61 @@ class TiledAdjacency:
             dense[rows, self.kquad.long()[:, None].expand(-1, 32)] = self.tiles
         return dense[: (n + 7) // 8 * 8].reshape((n + 7) // 8 * 8, nq * 4).contiguous()
 
+    def to_new(self, x: torch.Tensor) -> torch.Tensor:
+        """Rows of x [n, ...] in the edge list's numbering -> the adjacency's (x[perm]); x itself when not reordered."""
+        if self.perm is None:
+            return x
+        assert x.size(0) == self.n, "x must have one row per node"
+        return x.index_select(0, self.perm)
+
+    def to_old(self, y: torch.Tensor) -> torch.Tensor:
+        """Rows of y [n, ...] in the adjacency's numbering (a tiledMM2Int output) -> the edge list's (y[rank]); y itself when not
+        reordered."""
+        if self.rank is None:
+            return y
+        assert y.size(0) == self.n, "y must have one row per node"
+        return y.index_select(0, self.rank)
+
+    def to_old_packed(self, words: torch.Tensor, planes: int) -> torch.Tensor:
+        """A rows-layout bit output [planes * PAD8(n), W] in the adjacency's numbering (tiledMM2Bit with output_bit = planes) ->
+        the edge list's: rows 0 .. n-1 of every plane gathered by rank, the pad rows kept. ``words`` itself when not reordered."""
+        if self.rank is None:
+            return words
+        p8 = (self.n + 7) // 8 * 8
+        assert words.dim() == 2 and words.size(0) == planes * p8, "words must be [planes * PAD8(n), W]"
+        v = words.view(planes, p8, words.size(1))
+        out = v.clone()
+        out[:, : self.n] = v.index_select(1, self.rank)
+        return out.view_as(words)
+
     def __repr__(self) -> str:
-        return f"TiledAdjacency(n={self.n}, n_tiles={self.n_tiles}, nbytes={self.nbytes})"
+        return f"TiledAdjacency(n={self.n}, n_tiles={self.n_tiles}, nbytes={self.nbytes}, reordered={self.perm is not None})"
 
 
-def pack_edges_tiled(src: torch.Tensor, dst: torch.Tensor, n: int, validate: bool = True) -> TiledAdjacency:
+def reorder_nodes(src: torch.Tensor, dst: torch.Tensor, n: int, sweeps: int = 20, cap: int = 128, validate: bool = True) -> torch.Tensor:
+    """perm (int64 [n] on the edges' device, perm[new] = old): a numbering under which neighbours have nearby ids, from size-capped
+    label propagation on the symmetrised graph (``sweeps`` 0 .. 64, communities of about ``cap`` nodes; include/qgtc.h,
+    "Node reordering"). Deterministic. ``validate`` raises on an out-of-range or negative index; without it such edges are skipped."""
+    perm, _ = _ext._reorder_nodes(src, dst, int(n), int(sweeps), int(cap), bool(validate))
+    return perm
+
+
+def pack_edges_tiled(src: torch.Tensor, dst: torch.Tensor, n: int, validate: bool = True, reorder: bool = False) -> TiledAdjacency:
     """Tile-compressed adjacency of the raw edge list (src[i] -> row, dst[i] -> column; duplicates allowed: multiplicities
     1, 2, >= 3 quantise to 1, 0, 1 as in ``pack_edges``). ``validate`` raises on an out-of-range or negative index;
-    without it such edges are skipped."""
-    row_ptr, kquad, tiles = _ext._tiled_pack(src, dst, int(n), bool(validate))
-    return TiledAdjacency(n, row_ptr, kquad, tiles)
+    without it such edges are skipped. ``reorder`` renumbers the nodes first (:func:`reorder_nodes` with its defaults) and packs
+    the edges (rank[src], rank[dst]): the result carries ``perm`` / ``rank`` and works in the new numbering."""
+    if not reorder:
+        row_ptr, kquad, tiles = _ext._tiled_pack(src, dst, int(n), bool(validate))
+        return TiledAdjacency(n, row_ptr, kquad, tiles)
+    perm, rank = _ext._reorder_nodes(src, dst, int(n), 20, 128, bool(validate))
+    if src.numel():
+        # out-of-range indices stay out of range (the packer skips them); the others move to their new ids
+        ok_s, ok_d = (src >= 0) & (src < n), (dst >= 0) & (dst < n)
+        src = torch.where(ok_s, rank.index_select(0, src.clamp(0, n - 1)), src)
+        dst = torch.where(ok_d, rank.index_select(0, dst.clamp(0, n - 1)), dst)
+    row_ptr, kquad, tiles = _ext._tiled_pack(src.contiguous(), dst.contiguous(), int(n), False)
+    return TiledAdjacency(n, row_ptr, kquad, tiles, perm, rank)
 
 
 def _check(adj) -> None:

@@ -1,8 +1,9 @@
 """Measure the tile-compressed whole-graph adjacency (QGTC.pack_edges_tiled + tiledMM2Bit) on SBM graphs of public-dataset size.
 
-Per graph, as generated (block-local numbering) and under a random node permutation: pack time, occupied tiles T, tile bytes, and
-the aggregate requant(A . X) (rows-layout output, ob = w) at N in {16, 64, 256} and w in {1, 2, 4}, with the HBM fraction of the
-algorithmic bytes (512 T + 12 T + X + out) against 8 TB/s. At the arxiv size also the dense route (pack_edges + bitMM2Bit).
+Per graph, as generated (block-local numbering), under a random node permutation, and that permutation renumbered on the device
+(`reordered`: QGTC.reorder_nodes with its defaults, then pack_edges_tiled(..., reorder=True); reorder_ms is the reordering alone):
+pack time, occupied tiles T, tile bytes, and the aggregate requant(A . X) (rows-layout output, ob = w) at N in {16, 64, 256} and
+w in {1, 2, 4}, with the HBM fraction of the algorithmic bytes (512 T + 12 T + X + out) against 8 TB/s. At the arxiv size also the dense route (pack_edges + bitMM2Bit).
 
     python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT]
 """
@@ -59,14 +60,19 @@ def main() -> None:
         g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
         gen_s = time.time() - t0
         perm = np.random.default_rng(7).permutation(n)
-        for order in ("block-local", "permuted"):
+        for order in ("block-local", "permuted", "reordered"):
             src, dst = (g.src, g.dst) if order == "block-local" else (perm[g.src], perm[g.dst])
             dsrc, ddst = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda()
-            pack_ms = timed(torch, lambda: QGTC.pack_edges_tiled(dsrc, ddst, n, False), max(3, args.reps // 3), warmup=1)
-            adj = QGTC.pack_edges_tiled(dsrc, ddst, n)
+            reorder = order == "reordered"
+            pack_ms = timed(torch, lambda: QGTC.pack_edges_tiled(dsrc, ddst, n, False, reorder), max(3, args.reps // 3), warmup=1)
+            adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=reorder)
             T = adj.n_tiles
             rec = {"graph": name, "order": order, "n": n, "edges": int(src.size), "gen_s": round(gen_s, 1), "pack_ms": round(pack_ms, 3),
                    "tiles": T, "tile_bytes": 512 * T, "max_block_tiles": adj.max_block_tiles, "agg": []}
+            if reorder:
+                rec["reorder_ms"] = round(timed(torch, lambda: QGTC.reorder_nodes(dsrc, ddst, n, validate=False), max(3, args.reps // 3),
+                                                warmup=1), 3)
+                print(f"{name:9s} {order:11s} reorder_nodes {rec['reorder_ms']:.3f} ms", flush=True)
             rng = np.random.default_rng(1)
             for N in (16, 64, 256):
                 for w in (1, 2, 4):
@@ -78,7 +84,7 @@ def main() -> None:
                     print(f"{name:9s} {order:11s} T={T:>10d} N={N:<4d} w={w} agg {ms:9.4f} ms  hbm {rec['agg'][-1]['hbm_frac']:.3f}",
                           flush=True)
                     del X, out
-            if name == "arxiv":
+            if name == "arxiv" and not reorder:
                 # the dense route of the same edge list: pack_edges + bitMM2Bit (n^2 / 8 bytes of adjacency)
                 A = QGTC.pack_edges(dsrc, ddst, n, n, 1, False)
                 dense = {"pack_ms": round(timed(torch, lambda: QGTC.pack_edges(dsrc, ddst, n, n, 1, False), 3, warmup=1), 3),
