@@ -439,6 +439,33 @@ int qgtc_tiledmm2bit(const int64_t *row_ptr, const int32_t *kquad, const uint32_
 int qgtc_tiledmm2int(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
                      size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream);
 
+/* ---- Transposed tiled adjacency: A^T . X from the same tiles ----------------------------------------------------------------------
+ * The format above lists the tiles by row block (row = source: the product sums over out-neighbours). The in-neighbour sum A^T . X
+ * reads the same tiles listed by k-quad, through a column index:
+ *   col_ptr   int64 [S128(n) + 1]  the tiles of k-quad q are entries col_ptr[q] .. col_ptr[q + 1] - 1; col_ptr[S128(n)] = T
+ *   col_tile  int64 [T]            the tile ids, ascending within a k-quad (so also in row-block order)
+ *   col_rb    int32 [T]            the row block of each listed tile
+ * The index is canonical: a function of row_ptr and kquad alone. qgtc_tiled_colindex builds it with one radix sort of the
+ * (kquad, tile id) keys in `work` (qgtc_tiled_colindex_work_words(n_tiles) 32-bit words, 256-byte aligned) and one kernel; nothing is
+ * read back to the host. Refusals: QGTC_EINVAL for n outside 1 .. 2^23, a negative n_tiles or a missing pointer (row_ptr, kquad,
+ * col_tile, col_rb and work may be NULL when n_tiles is 0); QGTC_ESIZE for a short work buffer. The size query gives 0 for
+ * n_tiles <= 0 (no buffer needed at 0) and when it cannot ask the device.
+ *
+ * Product (qgtc_tiledmm2bit_t / qgtc_tiledmm2int_t): requant(A_tiled^T . X), word for word what qgtc_tiledmm2bit / qgtc_tiledmm2int
+ * give on the adjacency packed from the reversed edge list (qgtc_tiled_count / _fill(dst, src, n)), and so what qgtc_bitmm2bit /
+ * qgtc_bitmm2int give on qgtc_pack_edge_list(dst, src, n, n, 1): multiplicities quantise per cell and survive the reversal. X, the
+ * outputs, the domain (bit2 1 .. 8, output_bit 1 .. 32, any N >= 1) and the refusals are those of the forward entries; every output
+ * word is written (a k-quad without tiles gives zero rows); the int32 sums are exact (in-degree (2^bit2 - 1) < 2^31). List bounds are
+ * clamped to n_tiles and out-of-range row blocks skipped. The tiles are bit-transposed on the fly: no second copy is kept. */
+size_t qgtc_tiled_colindex_work_words(int64_t n_tiles);
+int qgtc_tiled_colindex(const int64_t *row_ptr, const int32_t *kquad, int64_t n_tiles, int n, int64_t *col_ptr, int64_t *col_tile,
+                        int32_t *col_rb, uint32_t *work, size_t work_words, void *stream);
+int qgtc_tiledmm2bit_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                       int n, const uint32_t *X, size_t x_words, int N, int bit2, int output_bit, uint32_t *out, size_t out_words,
+                       void *stream);
+int qgtc_tiledmm2int_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                       int n, const uint32_t *X, size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

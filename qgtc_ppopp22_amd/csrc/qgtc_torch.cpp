@@ -465,6 +465,75 @@ torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor
     return out;
 }
 
+// Transposed tiled adjacency (qgtc_tiled_colindex, qgtc_tiledmm2*_t): [col_ptr int64 [S128(n)+1], col_tile int64 [T], col_rb int32 [T]]
+// from row_ptr and kquad, with no host read; and requant(A_tiled^T . X) from the index and the same tiles.
+std::vector<torch::Tensor> tiled_colindex(torch::Tensor row_ptr, torch::Tensor kquad, const int64_t n) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(row_ptr.device() == kquad.device(), "row_ptr and kquad must be on the same device");
+    c10::DeviceGuard guard(row_ptr.device());
+    const auto dev = row_ptr.device();
+    const int64_t T = kquad.numel();
+    auto col_ptr = torch::empty({(n + 127) / 128 + 1}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    auto col_tile = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
+    auto col_rb = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    const size_t work_words = qgtc_tiled_colindex_work_words(T);
+    TORCH_CHECK(!T || work_words, "tiled colindex: no usable device");
+    torch::Tensor work;
+    if (work_words) work = torch::empty({static_cast<int64_t>(work_words)}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    check_rc(qgtc_tiled_colindex(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T, static_cast<int>(n),
+                                 col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
+                                 T ? col_rb.data_ptr<int32_t>() : nullptr, work.defined() ? words_mut(work) : nullptr, work_words,
+                                 current_stream(row_ptr)),
+             "tiled colindex");
+    return {col_ptr, col_tile, col_rb};
+}
+
+torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                         torch::Tensor bit_X, const int N, const int bit2, const int output_bit, const bool to_float) {
+    CHECK_INPUT(col_ptr);
+    CHECK_INPUT(col_tile);
+    CHECK_INPUT(col_rb);
+    CHECK_INPUT(tiles);
+    CHECK_INPUT(bit_X);
+    check_bits_tensor(bit_X, "bit_X");
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
+                "col_ptr and col_tile must be int64, col_rb int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
+    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
+                "col_tile, col_rb and tiles must list the same tiles");
+    TORCH_CHECK(col_ptr.device() == bit_X.device() && col_tile.device() == bit_X.device() && col_rb.device() == bit_X.device() &&
+                    tiles.device() == bit_X.device(),
+                "the adjacency and bit_X must be on the same device");
+    TORCH_CHECK(N > 0 && bit2 >= 1 && bit2 <= 8, "bad dimensions");
+    TORCH_CHECK(bit_X.numel() >= static_cast<int64_t>(bit2) * P128(N) * S128(static_cast<int>(n)) * 4,
+                "bit_X must hold bit2 x PAD128(N) x S128(n)*4 words (val2bit(X, bit2, True, False))");
+    c10::DeviceGuard guard(bit_X.device());
+    const int nn = static_cast<int>(n);
+    const int64_t T = col_tile.numel();
+    const int64_t *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
+    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    if (to_float) {
+        auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
+        check_rc(qgtc_tiledmm2int_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
+                                    out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
+                 "tiledMM2Int (transposed)");
+        return out;
+    }
+    auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
+                            torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
+    check_rc(qgtc_tiledmm2bit_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
+                                words_mut(out), out.numel(), current_stream(bit_X)),
+             "tiledMM2Bit (transposed)");
+    return out;
+}
+
 // int8 MFMA GEMM (comparison path, cuBLASGemmEX analogue): float32 [M,N] = A[M,K] x Bt[N,K]^T
 torch::Tensor i8gemm(torch::Tensor A, torch::Tensor Bt) {
     CHECK_INPUT(A);
@@ -1471,6 +1540,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("_tiled_mm", &tiled_mm, "requant(A_tiled . X): rows-layout bits, or float32 [n, N] with to_float "
           "(QGTC.tiledMM2Bit / tiledMM2Int wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"),
           py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"), py::arg("to_float"));
+    m.def("_tiled_colindex", &tiled_colindex, "[col_ptr, col_tile, col_rb]: the tiles of a tiled adjacency listed by k-quad "
+          "(TiledAdjacency.T builds it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("n"));
+    m.def("_tiled_mm_t", &tiled_mm_t, "requant(A_tiled^T . X) from the column index and the same tiles: rows-layout bits, or float32 "
+          "[n, N] with to_float (QGTC.tiledMM2Bit / tiledMM2Int on adj.T wrap it)", py::arg("col_ptr"), py::arg("col_tile"),
+          py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"),
+          py::arg("to_float"));
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");
     m.def("i8gemm_profile", &i8gemm_profile, "time `reps` i8gemm launches; returns milliseconds",
           py::arg("A"), py::arg("Bt"), py::arg("reps") = 200, py::arg("print") = true);

@@ -8,6 +8,11 @@ on ``pack_edges(src, dst, n, n, 1)`` of the same edge list. ``QGTC`` re-exports 
 The format is compact only when a node's neighbours have nearby ids. :func:`reorder_nodes` renumbers the nodes of an edge list with
 any ids on the device (include/qgtc.h, "Node reordering"), and ``pack_edges_tiled(..., reorder=True)`` packs the graph in that
 numbering; the adjacency then carries ``perm`` / ``rank`` and moves tensors between the two numberings.
+
+The rows are sources, so ``tiledMM2Int(adj, X)[s]`` sums X over the out-neighbours of s. ``adj.T`` is the transposed adjacency
+(include/qgtc.h, "Transposed tiled adjacency"): the same tiles, listed by k-quad through a small column index built on the device on
+first use, and the same functions on it give A^T . X, the in-neighbour sum of message passing (``copy_u`` + ``sum``), word for word
+what they give on ``pack_edges_tiled(dst, src, n)``.
 """
 from __future__ import annotations
 
@@ -31,6 +36,11 @@ class TiledAdjacency:
     and ``rank`` int64 [n] (rank[old] = new) are set, and tiledMM2Bit / tiledMM2Int read X and give their output in the new
     numbering (:meth:`to_new`, :meth:`to_old`, :meth:`to_old_packed` move tensors across). Otherwise both are None and the node ids
     are the edge list's.
+
+    :attr:`T` is the transposed adjacency (``transposed`` True): it shares the four tensors above, so nothing is copied, and adds
+    the column index ``col_ptr`` int64 [S128(n) + 1] (the tiles of k-quad q are entries ``col_ptr[q] .. col_ptr[q+1] - 1``),
+    ``col_tile`` int64 [T] (tile ids, ascending within a k-quad) and ``col_rb`` int32 [T] (each listed tile's row block), built by
+    one device call on first use and cached on this object. ``adj.T.T is adj``; both share one numbering.
     """
 
     def __init__(self, n: int, row_ptr: torch.Tensor, kquad: torch.Tensor, tiles: torch.Tensor, perm: torch.Tensor | None = None,
@@ -38,7 +48,20 @@ class TiledAdjacency:
         self.n = int(n)
         self.row_ptr, self.kquad, self.tiles = row_ptr, kquad, tiles
         self.perm, self.rank = perm, rank
+        self.transposed = False
         self._max_block_tiles = None
+        self._other = None   # the transposed view (built on first use), or, on that view, the adjacency it transposes
+
+    @property
+    def T(self) -> "TiledAdjacency":
+        """The transposed adjacency A^T: tiledMM2Bit / tiledMM2Int on it sum over in-neighbours. Cached; ``adj.T.T is adj``."""
+        if self._other is None:
+            col_ptr, col_tile, col_rb = _ext._tiled_colindex(self.row_ptr, self.kquad, self.n)
+            t = TiledAdjacency(self.n, self.row_ptr, self.kquad, self.tiles, self.perm, self.rank)
+            t.transposed = True
+            t.col_ptr, t.col_tile, t.col_rb = col_ptr, col_tile, col_rb
+            t._other, self._other = self, t
+        return self._other
 
     @property
     def n_tiles(self) -> int:
@@ -50,18 +73,29 @@ class TiledAdjacency:
 
     @property
     def nbytes(self) -> int:
-        """Bytes of the three tensors (512 a tile, 4 a k-quad index, 8 a row block)."""
-        return sum(t.numel() * t.element_size() for t in (self.row_ptr, self.kquad, self.tiles))
+        """Bytes of the three tensors (512 a tile, 4 a k-quad index, 8 a row block); transposed, also of the column index (8 a
+        k-quad, 12 a tile)."""
+        parts = (self.row_ptr, self.kquad, self.tiles) + ((self.col_ptr, self.col_tile, self.col_rb) if self.transposed else ())
+        return sum(t.numel() * t.element_size() for t in parts)
 
     @property
     def max_block_tiles(self) -> int:
-        """Most tiles in one 32-row block (one host read, on first use)."""
+        """Most tiles in one 32-row block; transposed, in one k-quad's list (one host read, on first use)."""
         if self._max_block_tiles is None:
-            self._max_block_tiles = int((self.row_ptr[1:] - self.row_ptr[:-1]).max().item()) if self.row_ptr.numel() > 1 else 0
+            ptr = self.col_ptr if self.transposed else self.row_ptr
+            self._max_block_tiles = int((ptr[1:] - ptr[:-1]).max().item()) if ptr.numel() > 1 else 0
         return self._max_block_tiles
 
     def to_rows(self) -> torch.Tensor:
-        """The dense rows-layout words [PAD8(n), S128(n)*4] (what ``pack_edges(src, dst, n, n, 1)`` returns). A test aid for small n."""
+        """The dense rows-layout words [PAD8(n), S128(n)*4] (what ``pack_edges(src, dst, n, n, 1)`` returns; transposed, what
+        ``pack_edges(dst, src, n, n, 1)`` returns). A test aid for small n."""
+        if self.transposed:
+            n, p8, w = self.n, (self.n + 7) // 8 * 8, (self.n + 127) // 128 * 4
+            shifts = 31 - torch.arange(32, device=self.device, dtype=torch.int64)
+            bits = (self._other.to_rows().to(torch.int64)[:, :, None] >> shifts) & 1            # [P8, W, 32]
+            dense = torch.zeros((p8, w * 32), dtype=torch.int64, device=self.device)
+            dense[:n, :n] = bits.reshape(p8, w * 32)[:n, :n].t()
+            return (dense.view(p8, w, 32) << shifts).sum(-1).to(torch.int32).contiguous()
         n = self.n
         nrb, nq = (n + 31) // 32, (n + 127) // 128
         dense = torch.zeros((nrb * 32, nq, 4), dtype=torch.int32, device=self.device)
@@ -99,7 +133,8 @@ class TiledAdjacency:
         return out.view_as(words)
 
     def __repr__(self) -> str:
-        return f"TiledAdjacency(n={self.n}, n_tiles={self.n_tiles}, nbytes={self.nbytes}, reordered={self.perm is not None})"
+        return (f"TiledAdjacency(n={self.n}, n_tiles={self.n_tiles}, nbytes={self.nbytes}, reordered={self.perm is not None}, "
+                f"transposed={self.transposed})")
 
 
 def reorder_nodes(src: torch.Tensor, dst: torch.Tensor, n: int, sweeps: int = 20, cap: int = 128, validate: bool = True) -> torch.Tensor:
@@ -135,12 +170,18 @@ def _check(adj) -> None:
 
 def tiledMM2Bit(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int) -> torch.Tensor:
     """requant(A . X) in the rows layout [output_bit * PAD8(n), S128(N)*4]: ``bitMM2Bit(A_rows, bit_X, n, n, N, 1, bit2,
-    output_bit)``. bit_X: cols layout [bit2][PAD128(N)][S128(n)*4] (``val2bit(X, bit2, True, False)`` / ``bitMM2Bit_col``)."""
+    output_bit)``. bit_X: cols layout [bit2][PAD128(N)][S128(n)*4] (``val2bit(X, bit2, True, False)`` / ``bitMM2Bit_col``).
+    On ``adj.T`` it is requant(A^T . X), from the same tiles, bit-transposed in the kernel."""
     _check(adj)
+    if adj.transposed:
+        return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit),
+                                False)
     return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), False)
 
 
 def tiledMM2Int(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int) -> torch.Tensor:
-    """float32 [n, N] = A . X: ``bitMM2Int(A_rows, bit_X, n, n, N, 1, bit2, True)``."""
+    """float32 [n, N] = A . X: ``bitMM2Int(A_rows, bit_X, n, n, N, 1, bit2, True)``; on ``adj.T``, A^T . X."""
     _check(adj)
+    if adj.transposed:
+        return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), 1, True)
     return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), 1, True)

@@ -5,7 +5,12 @@ Per graph, as generated (block-local numbering), under a random node permutation
 pack time, occupied tiles T, tile bytes, and the aggregate requant(A . X) (rows-layout output, ob = w) at N in {16, 64, 256} and
 w in {1, 2, 4}, with the HBM fraction of the algorithmic bytes (512 T + 12 T + X + out) against 8 TB/s. At the arxiv size also the dense route (pack_edges + bitMM2Bit).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT]
+`--leg transposed` measures A^T . X instead, on the reordered graphs and on an arxiv-sized graph whose in-degree
+follows a power law (`arxiv-skew`: half the edges point at Zipf-drawn nodes): the column index build (`adj.T`) and its bytes, the
+reversed pack a user would do without it (`pack_edges_tiled(rank[dst], rank[src], n)`), and tiledMM2Bit at N in {16, 64, 256} and
+w in {1, 2} (ob = w) on adj.T, on that reverse-packed adjacency and forward on adj (the first two checked equal).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed]
 """
 from __future__ import annotations
 
@@ -41,11 +46,59 @@ def timed(torch, fn, reps, warmup=2):
     return float(np.median([a.elapsed_time(b) for a, b in ev]))   # ms
 
 
+def transposed_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        base = name.split("-")[0]
+        n, deg = GRAPHS[base]
+        g = make_sbm_graph(base, n, max(1, n // 128), deg, 1, seed=3)
+        rng = np.random.default_rng(7)
+        perm = rng.permutation(n)
+        src, dst = g.src, g.dst
+        if name.endswith("-skew"):
+            hubs = rng.permutation(n)
+            zipf = hubs[(rng.zipf(1.6, size=dst.size) - 1) % n]
+            dst = np.where(rng.random(dst.size) < 0.5, zipf, dst)
+        dsrc, ddst = torch.from_numpy(perm[src]).cuda(), torch.from_numpy(perm[dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        rs, rd = adj.rank.index_select(0, dsrc), adj.rank.index_select(0, ddst)
+        index_ms = timed(torch, lambda: tiled._ext._tiled_colindex(adj.row_ptr, adj.kquad, n), reps, warmup=2)
+        rev_pack_ms = timed(torch, lambda: QGTC.pack_edges_tiled(rd, rs, n, False), reps, warmup=2)
+        t = adj.T
+        rev = QGTC.pack_edges_tiled(rd, rs, n)
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(src.size), "tiles": adj.n_tiles, "rev_tiles": rev.n_tiles,
+               "index_ms": round(index_ms, 4), "index_bytes": t.nbytes - adj.nbytes, "rev_pack_ms": round(rev_pack_ms, 4),
+               "rev_bytes": rev.nbytes, "max_block_tiles": adj.max_block_tiles, "max_col_tiles": t.max_block_tiles, "agg": []}
+        print(f"{name:12s} T={adj.n_tiles} index {index_ms:.4f} ms ({rec['index_bytes']} B), reversed pack {rev_pack_ms:.4f} ms "
+              f"({rev.nbytes} B), longest row list {adj.max_block_tiles}, longest column list {t.max_block_tiles}", flush=True)
+        xr = np.random.default_rng(1)
+        for N in (16, 64, 256):
+            for w in (1, 2):
+                X = QGTC.val2bit(torch.from_numpy(xr.integers(0, 2 ** w, size=(n, N)).astype(np.float32)).cuda(), w, True, False)
+                assert torch.equal(QGTC.tiledMM2Bit(t, X, N, w, w), QGTC.tiledMM2Bit(rev, X, N, w, w))
+                ms_t = timed(torch, lambda: QGTC.tiledMM2Bit(t, X, N, w, w), reps)
+                ms_r = timed(torch, lambda: QGTC.tiledMM2Bit(rev, X, N, w, w), reps)
+                ms_f = timed(torch, lambda: QGTC.tiledMM2Bit(adj, X, N, w, w), reps)
+                rec["agg"].append({"N": N, "w": w, "transposed_ms": round(ms_t, 4), "reverse_packed_ms": round(ms_r, 4),
+                                   "forward_ms": round(ms_f, 4), "t_over_rev": round(ms_t / ms_r, 3)})
+                print(f"{name:12s} N={N:<4d} w={w} A^T.X {ms_t:8.4f} ms  reverse-packed {ms_r:8.4f} ms  forward {ms_f:8.4f} ms  "
+                      f"ratio {ms_t / ms_r:.2f}", flush=True)
+                del X
+        rows.append(rec)
+        del adj, t, rev, dsrc, ddst, rs, rd
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed"))
     args = ap.parse_args()
 
     import torch
@@ -53,6 +106,14 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
+    if args.leg == "transposed":
+        rows = transposed_leg(torch, QGTC, args.graphs.split(","), args.reps)
+        if args.json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+            with open(args.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        print(json.dumps({"tiled_bench_transposed": [{k: v for k, v in r.items() if k != "agg"} for r in rows]}))
+        return
     rows = []
     for name in args.graphs.split(","):
         n, deg = GRAPHS[name]
