@@ -103,7 +103,7 @@ def test_32768_squared_times_1024_sampled_rows_and_row_checksums(qgtc, oracle, k
 def test_long_k_kernel_on_ragged_shapes(qgtc, oracle):
     """k_bitmm_fp4_stream's edges against the oracle (engine "mfma": the kernel wherever it applies; "auto" keeps small M on
     k_bitmm_fp4_skinny): K one bit past / short of its 128-byte blocks and 256- / 512-byte groups, rows and columns off every tile size,
-    one to four column tiles, float output with N % 4 != 0."""
+    one to four column tiles, float output with N % 4 != 0, and output_bit up to 32 (both requant branches)."""
     import torch
     rng = np.random.default_rng(3)
     qgtc.set_engine("mfma")
@@ -117,7 +117,7 @@ def test_long_k_kernel_on_ragged_shapes(qgtc, oracle):
             dX = torch.from_numpy(X.view(np.int32).reshape(P8(M), S128(K) * 4)).cuda()
             dW = torch.from_numpy(Wt.view(np.int32).reshape(S128(K) * 4, P128(N))).cuda()
             np.testing.assert_array_equal(qgtc.bitMM2Int(dX, dW, M, K, N, 1, 1, True).cpu().numpy(), oracle.bitmm2int(X, Wt, M, K, N, 1, 1, True))
-            for ob in (1, 2, 13, 24):
+            for ob in (1, 2, 13, 24, 31, 32):   # from ob 24 up the epilogue takes requant's float compare
                 np.testing.assert_array_equal(to_np_u32(qgtc.bitMM2Bit(dX, dW, M, K, N, 1, 1, ob)), oracle.bitmm2bit(X, Wt, M, K, N, 1, 1, ob))
                 np.testing.assert_array_equal(to_np_u32(qgtc.bitMM2Bit_col(dX, dW, M, K, N, 1, 1, ob)),
                                               oracle.bitmm2bit(X, Wt, M, K, N, 1, 1, ob, col=True))

@@ -6,25 +6,9 @@ import pytest
 
 from helpers import ENGINES, to_np_u32, use_engine
 from qgtc_ppopp22_amd.shapes import P8, S128
+from tiled_model import np_tiled
 
 pytestmark = pytest.mark.gpu
-
-
-def np_tiled(src, dst, n):
-    """NumPy model of the format: (row_ptr int64, kquad int32, tiles uint32 [T, 32, 4])."""
-    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
-    ok = (src >= 0) & (src < n) & (dst >= 0) & (dst < n)
-    cells, counts = np.unique(src[ok] * n + dst[ok], return_counts=True)
-    cells = cells[(counts == 1) | (counts >= 3)]          # the 1-bit quantiser of the summed matrix
-    r, c = cells // n, cells % n
-    nrb, nq = (n + 31) // 32, (n + 127) // 128
-    tile = (r // 32) * nq + c // 128
-    uniq, inv = np.unique(tile, return_inverse=True)
-    tiles = np.zeros((uniq.size, 32, 4), dtype=np.uint32)
-    np.bitwise_or.at(tiles, (inv, r % 32, (c % 128) // 32), (np.uint32(1) << (31 - (c % 32)).astype(np.uint32)))
-    row_ptr = np.zeros(nrb + 1, dtype=np.int64)
-    row_ptr[1:] = np.cumsum(np.bincount(uniq // nq, minlength=nrb))
-    return row_ptr, (uniq % nq).astype(np.int32), tiles
 
 
 def random_edges(rng, n, e, dup=True, self_loops=True, empty_block=True):
@@ -114,7 +98,8 @@ def test_bad_indices_raise_or_are_skipped(qgtc):
     assert torch.equal(adj.to_rows(), qgtc.pack_edges(_dev(torch, src), _dev(torch, dst), n, n, 1, False))
 
 
-# (n, N, w, ob): every N of {1, 10, 16, 33, 64, 128, 256, 602, 1024}, every w of {1, 2, 3, 4, 8}, every ob of {1, 2, 4, 8, 16, 32}
+# (n, N, w, ob): every N of {1, 10, 16, 24, 33, 64, 128, 256, 602, 1024} (every kernel variant), every w of {1, 2, 3, 4, 5, 8}, every ob
+# of {1, 2, 3, 4, 8, 16, 32}
 PRODUCTS = [
     (1, 1, 1, 1),
     (33, 10, 2, 2),
@@ -128,6 +113,7 @@ PRODUCTS = [
     (20000, 16, 4, 4),
     (777, 1024, 1, 32),
     (9000, 602, 3, 16),
+    (300, 24, 5, 3),
 ]
 
 

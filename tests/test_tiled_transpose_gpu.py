@@ -7,42 +7,11 @@ import pytest
 
 from helpers import ENGINES, to_np_u32, use_engine
 from qgtc_ppopp22_amd.shapes import P8, S128
+from tiled_model import np_colindex, random_edges
 
 pytestmark = pytest.mark.gpu
 
 NS = [1, 31, 129, 1000, 4097, 70000]
-
-
-def np_colindex(row_ptr, kquad, n):
-    """NumPy model of the column index: (col_ptr int64 [S128(n)+1], col_tile int64 [T], col_rb int32 [T])."""
-    row_ptr, kquad = np.asarray(row_ptr, np.int64), np.asarray(kquad, np.int64)
-    nq, T = (n + 127) // 128, kquad.size
-    rb = np.repeat(np.arange(row_ptr.size - 1), np.diff(row_ptr))
-    order = np.lexsort((np.arange(T), kquad))          # by k-quad, then tile id
-    col_ptr = np.zeros(nq + 1, np.int64)
-    col_ptr[1:] = np.cumsum(np.bincount(kquad, minlength=nq))
-    return col_ptr, order.astype(np.int64), rb[order].astype(np.int32)
-
-
-def random_edges(rng, n, e):
-    """Random edges with duplicates of multiplicity 2, 3 and 4, self loops, a hub row and a hub column; for n >= 96 row block 1
-    (rows 32 .. 63) stays empty, and for n >= 384 k-quad 1 (columns 128 .. 255) too."""
-    src = rng.integers(0, n, size=e, dtype=np.int64)
-    dst = rng.integers(0, n, size=e, dtype=np.int64)
-    if n > 2:
-        src[: e // 8] = n // 2                     # a hub row
-        dst[e // 8: e // 4] = n // 3               # a hub column
-    if n >= 96:
-        src = np.where((src >= 32) & (src < 64), src + 32, src)
-    if n >= 384:
-        dst = np.where((dst >= 128) & (dst < 256), dst + 128, dst)
-    k = min(e, 16)
-    dst[:k] = src[:k]                              # self loops
-    if e:
-        idx = rng.integers(0, e, size=max(1, e // 10))
-        src = np.concatenate([src, src[idx], src[idx[::2]], src[idx[::4]]])
-        dst = np.concatenate([dst, dst[idx], dst[idx[::2]], dst[idx[::4]]])
-    return src, dst
 
 
 def _dev(torch, a):
@@ -93,7 +62,7 @@ def test_index_of_an_empty_adjacency(qgtc):
     assert not qgtc.tiledMM2Int(t, X, 20, 2).any()
 
 
-# (n, N, w, ob): n over NS, N over {1, 7, 64, 128, 129, 300}, w over 1 .. 8, ob over {1, 2, 3, 8, 32}
+# (n, N, w, ob): n over NS, N over {1, 7, 17, 64, 128, 129, 300} (every kernel variant), w over 1 .. 8, ob over {1, 2, 3, 8, 16, 32}
 PRODUCTS = [
     (1, 1, 1, 1),
     (31, 7, 2, 2),
@@ -107,6 +76,7 @@ PRODUCTS = [
     (70000, 64, 1, 2),
     (31, 129, 2, 32),
     (4097, 128, 1, 1),
+    (4097, 17, 4, 16),
 ]
 
 
