@@ -466,6 +466,51 @@ int qgtc_tiledmm2bit_t(const int64_t *col_ptr, const int64_t *col_tile, const in
 int qgtc_tiledmm2int_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
                        int n, const uint32_t *X, size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream);
 
+/* ---- Scaled tiled products and degrees: a per-row float scale in the products' epilogue (mean aggregation) ---------------------------
+ * The products above requantise the plain sum over neighbours, and requant clamps every sum above 2^output_bit: right inside a
+ * Cluster-GCN batch, nearly constant on a whole graph. The scaled entries multiply each output row by a caller-given float before
+ * the output is formed; with row_scale = 1 / degree that is the mean over neighbours, which stays in 0 .. 2^bit2 - 1.
+ *
+ * Semantics. For output row r (the adjacency's numbering), column c, the exact integer sum s = (A . X)[r, c] (A^T . X for the _t
+ * entries) and row_scale float32 [n]:
+ *     y[r, c] = fl32( fl32(s) * row_scale[r] )
+ * fl32(s) is the int32 -> float32 conversion, round to nearest even; the product is one IEEE single multiply, round to nearest even,
+ * fused with nothing. Nothing is special-cased: a row without tiles has s = 0, so a scale of inf or NaN gives NaN there. row_scale
+ * may hold any float; products that are subnormal are outside the tested domain.
+ *   qgtc_tiledmm2int_scaled / _t_scaled   out = y, float32 [n, N].
+ *   qgtc_tiledmm2bit_scaled / _t_scaled   out = rows layout [output_bit][PAD8(n)][S128(N)*4], every word written as by the unscaled
+ *                                         entries, holding the VALUE QUANTISER of y at output_bit bits - what qgtc_val2bit gives on
+ *                                         y (above 2^output_bit -> 2^output_bit - 1, negative -> 1, round half to even, NaN -> 0):
+ *                                         word for word qgtc_val2bit(rows layout) of the float entry's output. It is the value
+ *                                         quantiser and not requant, because requant truncates and a mean must round. For
+ *                                         output_bit <= 30 a scale of all ones gives the words of the unscaled entry (the quantiser
+ *                                         of fl32(s) equals requant(s) there); at 31 / 32 the quantiser alone defines the output.
+ * Domain, X, the variant choice by N and the refusals are those of the unscaled entries (1 <= n <= 2^23, bit2 1 .. 8, any N >= 1,
+ * output_bit 1 .. 32; QGTC_ESIZE for a short out, QGTC_EALIGN as there), plus QGTC_EINVAL for a NULL row_scale. The unscaled entries
+ * launch the kernels they always launched.
+ *
+ * Degrees (qgtc_tiled_degrees): out_deg[u] = set cells in row u, in_deg[v] = set cells in column v of the quantised adjacency
+ * (multiplicities 1, 2, >= 3 count 1, 0, 1; self loops count) - the number of terms of the forward and of the transposed sum -, int32
+ * [n], every element written; out_inv / in_inv float32 [n] = 1.0f / (float)deg correctly rounded, 0.0f where the degree is 0. Each of
+ * the four may be NULL, not all four; a reciprocal needs its degree array (the reciprocal pass reads it: no work buffer). The
+ * in-degrees are summed with integer atomics, so the result does not depend on the order in which they land; no column index needed.
+ * QGTC_EINVAL for n outside 1 .. 2^23, a negative n_tiles, tiles without row_ptr / kquad / tiles, all four outputs NULL, or a
+ * reciprocal without its degrees; QGTC_EALIGN for tiles off a 16-byte boundary. */
+int qgtc_tiled_degrees(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, int32_t *out_deg,
+                       int32_t *in_deg, float *out_inv, float *in_inv, void *stream);
+int qgtc_tiledmm2bit_scaled(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                            const uint32_t *X, size_t x_words, int N, int bit2, int output_bit, const float *row_scale, uint32_t *out,
+                            size_t out_words, void *stream);
+int qgtc_tiledmm2int_scaled(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                            const uint32_t *X, size_t x_words, int N, int bit2, const float *row_scale, float *out, size_t out_elems,
+                            void *stream);
+int qgtc_tiledmm2bit_t_scaled(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                              int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N, int bit2, int output_bit,
+                              const float *row_scale, uint32_t *out, size_t out_words, void *stream);
+int qgtc_tiledmm2int_t_scaled(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                              int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N, int bit2, const float *row_scale,
+                              float *out, size_t out_elems, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -35,10 +35,17 @@ class Aggregation_Qnt(torch.autograd.Function):
 
 
 class GCNConv_Qnt(torch.nn.Module):
-    """Two-layer quantised GCN (QGTC_conv.py:38-78): out = A · q(q(A · q(X·W_in)) · W_out)."""
+    """Two-layer quantised GCN (QGTC_conv.py:38-78): out = A · q(q(A · q(X·W_in)) · W_out).
 
-    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, w_bit=2, act_bit=3):
+    ``aggr="sum"`` is the reference's aggregate. ``aggr="mean"`` divides each aggregate by the row's degree (the rows of the view it
+    is given: out-neighbours on ``adj``, in-neighbours on ``adj.T``), in the product kernel's epilogue; it needs a whole graph's
+    QGTC.TiledAdjacency, where the plain sum runs into requant's clamp."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, w_bit=2, act_bit=3, aggr="sum"):
         super().__init__()
+        if aggr not in ("sum", "mean"):
+            raise ValueError(f'aggr must be "sum" or "mean", not {aggr!r}')
+        self.aggr = aggr
         self.input_dim, self.hidden_dim, self.output_dim = input_dim, hidden_dim, output_dim
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
@@ -80,6 +87,8 @@ class GCNConv_Qnt(torch.nn.Module):
         n = X.size(0)
         if isinstance(A, QGTC.TiledAdjacency):
             return self._forward_tiled(A, X)
+        if self.aggr == "mean":
+            raise NotImplementedError('aggr="mean" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A')
         bit_A = self.A_Qnt(A)
         bit_X = self.X_Qnt(X)
         bit_h = Aggregation_Qnt.apply(bit_A, bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim,
@@ -91,15 +100,17 @@ class GCNConv_Qnt(torch.nn.Module):
         """The same two layers with the tile-compressed aggregate: per layer X.W re-packed in the cols layout
         (bitMM2Bit_col), then tiledMM2Bit / tiledMM2Int - the words gcn_layer gives on the dense adjacency. A reordered
         adjacency (A.perm set) gets X in its numbering and gives the output back in X's: every term moves with its node and the
-        quantisers work element by element, so the result is bit-identical to the unreordered one."""
+        quantisers work element by element, so the result is bit-identical to the unreordered one. With aggr="mean" both aggregates
+        take A.mean_scale() as their row scale (it lives in A's numbering and follows the view)."""
         n = X.size(0)
         assert A.n == n, "the adjacency and X must have the same number of nodes"
         X = A.to_new(X)
         bit_X = self.X_Qnt(X)
         t = QGTC.bitMM2Bit_col(bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim, self.act_bit, self.w_bit, self.act_bit)
-        bit_h = QGTC.tiledMM2Bit(A, t, self.hidden_dim, self.act_bit, self.act_bit)
+        scale = A.mean_scale() if self.aggr == "mean" else None
+        bit_h = QGTC.tiledMM2Bit(A, t, self.hidden_dim, self.act_bit, self.act_bit, scale)
         t = QGTC.bitMM2Bit_col(bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim, self.act_bit, self.w_bit, self.act_bit)
-        return A.to_old(QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit))
+        return A.to_old(QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit, scale))
 
 
 class GCNConv(torch.nn.Module):

@@ -16,10 +16,9 @@
 #include "common.hip.h"
 #include "bitmm_popcount.hip.h"   // requant (templates only: nothing is instantiated here)
 #include "tiled_kernels.hip.h"
+#include "tiled_args.hip.h"
 
 namespace {
-
-constexpr int TILED_MAX_N = 1 << 23;
 
 int tiled_grid(uint64_t items) {
     const uint64_t b = (items + 255) / 256;
@@ -120,15 +119,6 @@ int tiled_mm(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles
     }
 #undef QGTC_TILED_LAUNCH
     HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-int tiled_mm_args_ok(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
-                     int N, int bit2, const void *out) {
-    if (!row_ptr || !X || !out || n < 1 || n > TILED_MAX_N || N < 1 || bit2 < 1 || bit2 > 8 || n_tiles < 0 ||
-        (n_tiles && (!kquad || !tiles)))
-        return QGTC_EINVAL;
-    if (!aligned16(X) || !aligned16(out) || (tiles && !aligned16(tiles))) return QGTC_EALIGN;
     return QGTC_OK;
 }
 

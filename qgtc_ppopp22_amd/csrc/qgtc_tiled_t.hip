@@ -15,10 +15,10 @@
 #include "common.hip.h"
 #include "bitmm_popcount.hip.h"   // requant (templates only: nothing is instantiated here)
 #include "tiled_t_kernels.hip.h"
+#include "tiled_args.hip.h"
 
 namespace {
 
-constexpr int TILED_T_MAX_N = 1 << 23;
 constexpr int64_t TILED_T_MAX_TILES = int64_t{1} << 40;   // tile ids fit 40 bits, k-quads 17: a sort key fits 57
 
 int tiled_t_grid(uint64_t items) {
@@ -51,7 +51,7 @@ size_t qgtc_tiled_colindex_work_words(int64_t n_tiles) {
 
 int qgtc_tiled_colindex(const int64_t *row_ptr, const int32_t *kquad, int64_t n_tiles, int n, int64_t *col_ptr, int64_t *col_tile,
                         int32_t *col_rb, uint32_t *work, size_t work_words, void *stream) {
-    if (!col_ptr || n < 1 || n > TILED_T_MAX_N || n_tiles < 0 || n_tiles > TILED_T_MAX_TILES ||
+    if (!col_ptr || n < 1 || n > TILED_MAX_N || n_tiles < 0 || n_tiles > TILED_T_MAX_TILES ||
         (n_tiles && (!row_ptr || !kquad || !col_tile || !col_rb || !work)))
         return QGTC_EINVAL;
     if (n_tiles) {
@@ -100,15 +100,6 @@ int tiled_mm_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *c
     }
 #undef QGTC_TILED_T_LAUNCH
     HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-int tiled_mm_t_args_ok(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
-                       int n, const uint32_t *X, int N, int bit2, const void *out) {
-    if (!col_ptr || !X || !out || n < 1 || n > TILED_T_MAX_N || N < 1 || bit2 < 1 || bit2 > 8 || n_tiles < 0 ||
-        (n_tiles && (!col_tile || !col_rb || !tiles)))
-        return QGTC_EINVAL;
-    if (!aligned16(X) || !aligned16(out) || (tiles && !aligned16(tiles))) return QGTC_EALIGN;
     return QGTC_OK;
 }
 

@@ -430,8 +430,20 @@ std::vector<torch::Tensor> reorder_nodes(torch::Tensor src, torch::Tensor dst, c
     return {perm, rank};
 }
 
+// row_scale of the scaled tiled products: float32 [n], contiguous, on bit_X's device (the Python wrappers check the same before they
+// get here, with the exception types their callers expect)
+const float *tiled_row_scale(const c10::optional<torch::Tensor> &row_scale, const int64_t n, const torch::Tensor &bit_X) {
+    if (!row_scale.has_value()) return nullptr;
+    const torch::Tensor &s = *row_scale;
+    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
+                "row_scale must be a contiguous float32 tensor of n elements");
+    TORCH_CHECK(s.device() == bit_X.device(), "row_scale must be on the adjacency's device");
+    return s.data_ptr<float>();
+}
+
 torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor bit_X,
-                       const int N, const int bit2, const int output_bit, const bool to_float) {
+                       const int N, const int bit2, const int output_bit, const bool to_float,
+                       const c10::optional<torch::Tensor> &row_scale) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -450,19 +462,54 @@ torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor
     const int64_t T = kquad.numel();
     const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
+    const float *sc = tiled_row_scale(row_scale, n, bit_X);
     if (to_float) {
         auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
-        check_rc(qgtc_tiledmm2int(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, out.data_ptr<float>(),
-                                  out.numel(), current_stream(bit_X)),
-                 "tiledMM2Int");
+        if (sc)
+            check_rc(qgtc_tiledmm2int_scaled(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, sc,
+                                             out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
+                     "tiledMM2Int (scaled)");
+        else
+            check_rc(qgtc_tiledmm2int(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
+                                      out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
+                     "tiledMM2Int");
         return out;
     }
     auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
                             torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
-    check_rc(qgtc_tiledmm2bit(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
-                              words_mut(out), out.numel(), current_stream(bit_X)),
-             "tiledMM2Bit");
+    if (sc)
+        check_rc(qgtc_tiledmm2bit_scaled(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit, sc,
+                                         words_mut(out), out.numel(), current_stream(bit_X)),
+                 "tiledMM2Bit (scaled)");
+    else
+        check_rc(qgtc_tiledmm2bit(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
+                                  words_mut(out), out.numel(), current_stream(bit_X)),
+                 "tiledMM2Bit");
     return out;
+}
+
+// Degrees of a tiled adjacency in both directions and their reciprocals (qgtc_tiled_degrees):
+// [out_deg int32 [n], in_deg int32 [n], out_inv float32 [n], in_inv float32 [n]], one device call, no host read.
+std::vector<torch::Tensor> tiled_degrees(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
+    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    c10::DeviceGuard guard(row_ptr.device());
+    const auto dev = row_ptr.device();
+    const int64_t T = kquad.numel();
+    auto out_deg = torch::empty({n}, torch::TensorOptions().dtype(torch::kInt32).device(dev)), in_deg = torch::empty_like(out_deg);
+    auto out_inv = torch::empty({n}, torch::TensorOptions().dtype(torch::kFloat32).device(dev)), in_inv = torch::empty_like(out_inv);
+    check_rc(qgtc_tiled_degrees(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T,
+                                static_cast<int>(n), out_deg.data_ptr<int32_t>(), in_deg.data_ptr<int32_t>(), out_inv.data_ptr<float>(),
+                                in_inv.data_ptr<float>(), current_stream(row_ptr)),
+             "tiled degrees");
+    return {out_deg, in_deg, out_inv, in_inv};
 }
 
 // Transposed tiled adjacency (qgtc_tiled_colindex, qgtc_tiledmm2*_t): [col_ptr int64 [S128(n)+1], col_tile int64 [T], col_rb int32 [T]]
@@ -493,7 +540,8 @@ std::vector<torch::Tensor> tiled_colindex(torch::Tensor row_ptr, torch::Tensor k
 }
 
 torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                         torch::Tensor bit_X, const int N, const int bit2, const int output_bit, const bool to_float) {
+                         torch::Tensor bit_X, const int N, const int bit2, const int output_bit, const bool to_float,
+                         const c10::optional<torch::Tensor> &row_scale) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -519,18 +567,29 @@ torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::T
     const int64_t *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
     const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
+    const float *sc = tiled_row_scale(row_scale, n, bit_X);
     if (to_float) {
         auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
-        check_rc(qgtc_tiledmm2int_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
-                                    out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
-                 "tiledMM2Int (transposed)");
+        if (sc)
+            check_rc(qgtc_tiledmm2int_t_scaled(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, sc,
+                                               out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
+                     "tiledMM2Int (transposed, scaled)");
+        else
+            check_rc(qgtc_tiledmm2int_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
+                                        out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
+                     "tiledMM2Int (transposed)");
         return out;
     }
     auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
                             torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
-    check_rc(qgtc_tiledmm2bit_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
-                                words_mut(out), out.numel(), current_stream(bit_X)),
-             "tiledMM2Bit (transposed)");
+    if (sc)
+        check_rc(qgtc_tiledmm2bit_t_scaled(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
+                                           output_bit, sc, words_mut(out), out.numel(), current_stream(bit_X)),
+                 "tiledMM2Bit (transposed, scaled)");
+    else
+        check_rc(qgtc_tiledmm2bit_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
+                                    words_mut(out), out.numel(), current_stream(bit_X)),
+                 "tiledMM2Bit (transposed)");
     return out;
 }
 
@@ -1539,13 +1598,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("cap") = 128, py::arg("validate") = true);
     m.def("_tiled_mm", &tiled_mm, "requant(A_tiled . X): rows-layout bits, or float32 [n, N] with to_float "
           "(QGTC.tiledMM2Bit / tiledMM2Int wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"),
-          py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"), py::arg("to_float"));
+          py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"), py::arg("to_float"), py::arg("row_scale") = py::none());
+    m.def("_tiled_degrees", &tiled_degrees, "[out_deg, in_deg, out_inv, in_inv] of a tiled adjacency: the set cells of every row and "
+          "column and their reciprocals (TiledAdjacency.degrees / mean_scale wrap it)", py::arg("row_ptr"), py::arg("kquad"),
+          py::arg("tiles"), py::arg("n"));
     m.def("_tiled_colindex", &tiled_colindex, "[col_ptr, col_tile, col_rb]: the tiles of a tiled adjacency listed by k-quad "
           "(TiledAdjacency.T builds it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("n"));
     m.def("_tiled_mm_t", &tiled_mm_t, "requant(A_tiled^T . X) from the column index and the same tiles: rows-layout bits, or float32 "
           "[n, N] with to_float (QGTC.tiledMM2Bit / tiledMM2Int on adj.T wrap it)", py::arg("col_ptr"), py::arg("col_tile"),
           py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"),
-          py::arg("to_float"));
+          py::arg("to_float"), py::arg("row_scale") = py::none());
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");
     m.def("i8gemm_profile", &i8gemm_profile, "time `reps` i8gemm launches; returns milliseconds",
           py::arg("A"), py::arg("Bt"), py::arg("reps") = 200, py::arg("print") = true);

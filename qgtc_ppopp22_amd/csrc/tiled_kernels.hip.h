@@ -100,11 +100,21 @@ __global__ void k_tiled_fill(const uint64_t *__restrict__ cells, const uint64_t 
 // up a wave's rows are the same for all its lanes, so the tile rows arrive by scalar loads and empty rows are skipped by a scalar
 // branch. MODE 0: the requantised sums are ORed bit by bit into an LDS staging of the block's output words and stored as whole
 // 16-byte granules (rows past n, columns past N: zeros); MODE 2: float32 [n, N].
-template <int R, int MODE>
+//
+// SCALED (include/qgtc.h, "Scaled tiled products and degrees"): the epilogue loads row_scale[row] for the
+// thread's R rows (row < n only) and forms y = float(sum) * row_scale[row], one IEEE single multiply; MODE 2 stores y, MODE 0 runs
+// the value quantiser quant1 on y in place of requant. `Scale` is empty - the unscaled kernel, with the arguments and the code it
+// always had - or one `const float *`, row_scale, behind `out`.
+__device__ __forceinline__ const float *tiled_scale_ptr() { return nullptr; }
+__device__ __forceinline__ const float *tiled_scale_ptr(const float *p) { return p; }
+
+template <int R, int MODE, typename... Scale>
 __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                   const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                   const uint32_t *__restrict__ X, uint64_t x_words, int N, int bit2, int ob,
-                                                  float maxv, float maxm1, void *__restrict__ out) {
+                                                  float maxv, float maxm1, void *__restrict__ out, Scale... scale) {
+    constexpr bool SCALED = sizeof...(Scale) > 0;
+    [[maybe_unused]] const float *__restrict__ row_scale = tiled_scale_ptr(scale...);
     constexpr int RS = 32 / R, CW = 256 / RS;   // row groups per block, columns per workgroup
     const int rb = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
     const int rs = CW >= 64 ? __builtin_amdgcn_readfirstlane(tid / CW) : tid / CW;
@@ -147,7 +157,10 @@ __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ ro
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const int row = rb * 32 + rs * R + i;
-                if (row < n) o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]);
+                if (row < n) {
+                    if constexpr (SCALED) o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]) * row_scale[row];
+                    else o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]);
+                }
             }
         }
     } else {
@@ -162,7 +175,9 @@ __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ ro
             for (int i = 0; i < R; ++i) {
                 const int row = rs * R + i;
                 if (rb * 32 + row >= n) continue;
-                uint32_t m = static_cast<uint32_t>(requant(acc[i], maxv, maxm1)) & keep;
+                uint32_t m;
+                if constexpr (SCALED) m = quant1(static_cast<float>(acc[i]) * row_scale[rb * 32 + row], maxv, maxm1) & keep;
+                else m = static_cast<uint32_t>(requant(acc[i], maxv, maxm1)) & keep;
                 while (m) {
                     const int b = __builtin_ctz(m);
                     m &= m - 1;

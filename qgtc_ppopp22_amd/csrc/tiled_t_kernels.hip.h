@@ -77,11 +77,18 @@ __device__ __forceinline__ void tiled_t_transpose(uint32_t (&v)[4], int lane) {
             v[k] = tiled_t_stage(v[k], static_cast<uint32_t>(__shfl_xor(static_cast<int>(v[k]), J[st])), lane, J[st], M[st]);
 }
 
-template <int R, int MODE>
+// SCALED: as in k_tiled_mm - y = float(sum) * row_scale[row] in the epilogue (row < n only), stored (MODE 2) or quantised by quant1
+// in place of requant (MODE 0). `Scale` is empty (the unscaled kernel, arguments and code as they always were) or one `const float *`.
+__device__ __forceinline__ const float *tiled_t_scale_ptr() { return nullptr; }
+__device__ __forceinline__ const float *tiled_t_scale_ptr(const float *p) { return p; }
+
+template <int R, int MODE, typename... Scale>
 __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                     const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                     uint64_t n_tiles, int n, const uint32_t *__restrict__ X, uint64_t x_words, int N,
-                                                    int bit2, int ob, float maxv, float maxm1, void *__restrict__ out) {
+                                                    int bit2, int ob, float maxv, float maxm1, void *__restrict__ out, Scale... scale) {
+    constexpr bool SCALED = sizeof...(Scale) > 0;
+    [[maybe_unused]] const float *__restrict__ row_scale = tiled_t_scale_ptr(scale...);
     constexpr int RS = 128 / R, CW = 256 / RS;   // row groups per k-quad, columns per workgroup
     constexpr int TS = TILED_T_TS;
     const int q = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
@@ -152,14 +159,24 @@ __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ 
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const int row = q * 128 + rs * R + i;
-                if (row < n) o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]);
+                if (row < n) {
+                    if constexpr (SCALED) o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]) * row_scale[row];
+                    else o[static_cast<uint64_t>(row) * N + c] = static_cast<float>(acc[i]);
+                }
             }
         }
     } else {
         __shared__ uint32_t st[8 * 128 * 4];   // [plane of the group][row of the k-quad][word of the chunk]
         const uint32_t keep = ob >= 32 ? ~0u : ((1u << ob) - 1u);
 #pragma unroll
-        for (int i = 0; i < R; ++i) acc[i] = static_cast<int>(static_cast<uint32_t>(requant(acc[i], maxv, maxm1)) & keep);
+        for (int i = 0; i < R; ++i) {
+            if constexpr (SCALED) {
+                const int row = q * 128 + rs * R + i;
+                acc[i] = row < n ? static_cast<int>(quant1(static_cast<float>(acc[i]) * row_scale[row], maxv, maxm1) & keep) : 0;
+            } else {
+                acc[i] = static_cast<int>(static_cast<uint32_t>(requant(acc[i], maxv, maxm1)) & keep);
+            }
+        }
         const uint32_t bit = 1u << (31 - (c & 31));
         const int word = (c & 127) >> 5;
         const int rows_out = pad8(n);

@@ -13,6 +13,10 @@ The rows are sources, so ``tiledMM2Int(adj, X)[s]`` sums X over the out-neighbou
 (include/qgtc.h, "Transposed tiled adjacency"): the same tiles, listed by k-quad through a small column index built on the device on
 first use, and the same functions on it give A^T . X, the in-neighbour sum of message passing (``copy_u`` + ``sum``), word for word
 what they give on ``pack_edges_tiled(dst, src, n)``.
+
+Both take ``row_scale`` (include/qgtc.h, "Scaled tiled products and degrees"): a float32 [n] the kernel multiplies every output row by
+before the output is formed. With ``adj.mean_scale()``, the reciprocal of ``adj.degrees()``, that is the MEAN over neighbours, which
+stays in 0 .. 2^bit2 - 1 where the plain sum of a whole graph runs into requant's clamp.
 """
 from __future__ import annotations
 
@@ -51,6 +55,7 @@ class TiledAdjacency:
         self.transposed = False
         self._max_block_tiles = None
         self._other = None   # the transposed view (built on first use), or, on that view, the adjacency it transposes
+        self._degrees = None  # [out_deg, in_deg, out_inv, in_inv], kept on the untransposed adjacency for both views
 
     @property
     def T(self) -> "TiledAdjacency":
@@ -85,6 +90,24 @@ class TiledAdjacency:
             ptr = self.col_ptr if self.transposed else self.row_ptr
             self._max_block_tiles = int((ptr[1:] - ptr[:-1]).max().item()) if ptr.numel() > 1 else 0
         return self._max_block_tiles
+
+    def _degree_tensors(self):
+        base = self._other if self.transposed else self
+        if base._degrees is None:
+            base._degrees = _ext._tiled_degrees(base.row_ptr, base.kquad, base.tiles, base.n)
+        return base._degrees
+
+    def degrees(self) -> torch.Tensor:
+        """int32 [n]: the set cells in every row of this view - the out-degree on ``adj``, the in-degree on ``adj.T`` -, which is the
+        number of terms tiledMM2Int sums for that row (cells of multiplicity 2 are unset and do not count; self loops do). In the
+        adjacency's numbering (:meth:`to_old` moves it). One device call computes both directions on first use; ``adj`` and
+        ``adj.T`` share the result."""
+        return self._degree_tensors()[1 if self.transposed else 0]
+
+    def mean_scale(self) -> torch.Tensor:
+        """float32 [n]: 1 / degrees(), correctly rounded, 0 where the degree is 0 - the ``row_scale`` that turns tiledMM2Bit /
+        tiledMM2Int on this view into the mean over neighbours."""
+        return self._degree_tensors()[3 if self.transposed else 2]
 
     def to_rows(self) -> torch.Tensor:
         """The dense rows-layout words [PAD8(n), S128(n)*4] (what ``pack_edges(src, dst, n, n, 1)`` returns; transposed, what
@@ -168,20 +191,47 @@ def _check(adj) -> None:
         raise TypeError("adj must be a TiledAdjacency (QGTC.pack_edges_tiled)")
 
 
-def tiledMM2Bit(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int) -> torch.Tensor:
-    """requant(A . X) in the rows layout [output_bit * PAD8(n), S128(N)*4]: ``bitMM2Bit(A_rows, bit_X, n, n, N, 1, bit2,
-    output_bit)``. bit_X: cols layout [bit2][PAD128(N)][S128(n)*4] (``val2bit(X, bit2, True, False)`` / ``bitMM2Bit_col``).
-    On ``adj.T`` it is requant(A^T . X), from the same tiles, bit-transposed in the kernel."""
+def _check_scale(adj: TiledAdjacency, row_scale) -> None:
+    if not isinstance(row_scale, torch.Tensor):
+        raise TypeError("row_scale must be a torch.Tensor (float32 [n]) or None")
+    if row_scale.dtype != torch.float32:
+        raise TypeError(f"row_scale must be float32, not {row_scale.dtype}")
+    if row_scale.dim() != 1 or row_scale.numel() != adj.n:
+        raise ValueError(f"row_scale must have shape [{adj.n}], not {list(row_scale.shape)}")
+    if row_scale.device != adj.device:
+        raise ValueError(f"row_scale must be on the adjacency's device {adj.device}, not {row_scale.device}")
+    if not row_scale.is_contiguous():
+        raise ValueError("row_scale must be contiguous")
+
+
+def _tiled(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int, to_float: bool, row_scale) -> torch.Tensor:
     _check(adj)
+    if row_scale is None:
+        # exactly the unscaled call
+        if adj.transposed:
+            return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit),
+                                    to_float)
+        return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), to_float)
+    _check_scale(adj, row_scale)
     if adj.transposed:
         return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit),
-                                False)
-    return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), False)
+                                to_float, row_scale)
+    return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), to_float, row_scale)
 
 
-def tiledMM2Int(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int) -> torch.Tensor:
-    """float32 [n, N] = A . X: ``bitMM2Int(A_rows, bit_X, n, n, N, 1, bit2, True)``; on ``adj.T``, A^T . X."""
-    _check(adj)
-    if adj.transposed:
-        return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), 1, True)
-    return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), 1, True)
+def tiledMM2Bit(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int,
+                row_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """requant(A . X) in the rows layout [output_bit * PAD8(n), S128(N)*4]: ``bitMM2Bit(A_rows, bit_X, n, n, N, 1, bit2,
+    output_bit)``. bit_X: cols layout [bit2][PAD128(N)][S128(n)*4] (``val2bit(X, bit2, True, False)`` / ``bitMM2Bit_col``).
+    On ``adj.T`` it is requant(A^T . X), from the same tiles, bit-transposed in the kernel.
+
+    With ``row_scale`` (float32 [n], contiguous, on the adjacency's device, in the adjacency's numbering like bit_X) the words hold
+    the value quantiser of y = float(A . X) * row_scale[:, None] instead: ``val2bit(tiledMM2Int(adj, bit_X, N, bit2, row_scale),
+    output_bit, False, False)``, word for word, in one kernel."""
+    return _tiled(adj, bit_X, N, bit2, output_bit, False, row_scale)
+
+
+def tiledMM2Int(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, row_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """float32 [n, N] = A . X: ``bitMM2Int(A_rows, bit_X, n, n, N, 1, bit2, True)``; on ``adj.T``, A^T . X. With ``row_scale`` every
+    row r is multiplied by row_scale[r] (one float32 multiply of the exact sum's float32 conversion)."""
+    return _tiled(adj, bit_X, N, bit2, 1, True, row_scale)

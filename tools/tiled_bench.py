@@ -10,7 +10,14 @@ follows a power law (`arxiv-skew`: half the edges point at Zipf-drawn nodes): th
 reversed pack a user would do without it (`pack_edges_tiled(rank[dst], rank[src], n)`), and tiledMM2Bit at N in {16, 64, 256} and
 w in {1, 2} (ob = w) on adj.T, on that reverse-packed adjacency and forward on adj (the first two checked equal).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed]
+`--leg scaled` measures the scaled products and the degrees on the reordered graphs, both directions, N in
+{16, 64, 256}, w in {1, 2}, ob = w, with the mean scale: (a) tiledMM2Bit with and without row_scale, the two launched alternately in
+one timed loop, and with a scale of ones (the unscaled words through the scaled kernels); (b) the degrees call (both directions and both reciprocals: the first `degrees()` / `mean_scale()`); (c) the route
+without the feature - tiledMM2Int, a float multiply by the scale, val2bit - checked equal to (a). Each figure is the median of the
+per-launch event times with their 10th and 90th percentiles. It also counts, on the device, the share of in-neighbour outputs at
+the clamp value 2^b - 1 for the plain sum and for the mean at 2 / 3 / 4 bits (N = 64, random features over the full range).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled]
 """
 from __future__ import annotations
 
@@ -93,12 +100,95 @@ def transposed_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def timed_alternating(torch, fns, reps, warmup=3):
+    """Several callables launched in turn inside one loop, so that drift of the clocks or of a shared machine hits them alike; the
+    order changes from round to round through every permutation, so that each follows each other equally often (a launch inherits
+    the caches its predecessor leaves). Per callable (median, 10th percentile, 90th percentile) of the per-launch event times, ms."""
+    import itertools
+
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    orders = list(itertools.permutations(range(len(fns))))
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in fns] for _ in range(reps)]
+    for r, row in enumerate(ev):
+        for k in orders[r % len(orders)]:
+            a, b = row[k]
+            a.record()
+            fns[k]()
+            b.record()
+    torch.cuda.synchronize()
+    out = []
+    for k in range(len(fns)):
+        t = np.array([row[k][0].elapsed_time(row[k][1]) for row in ev])
+        out.append(tuple(round(float(v), 4) for v in (np.median(t), np.percentile(t, 10), np.percentile(t, 90))))
+    return out
+
+
+def scaled_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        (deg_ms,) = timed_alternating(torch, [lambda: tiled._ext._tiled_degrees(adj.row_ptr, adj.kquad, adj.tiles, n)], reps)
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "tiles": adj.n_tiles,
+               "degrees_ms": deg_ms, "zero_out_degree": int((adj.degrees() == 0).sum()), "zero_in_degree": int((t.degrees() == 0).sum()),
+               "agg": [], "saturation": []}
+        print(f"{name:9s} T={adj.n_tiles} degrees + reciprocals, both directions {deg_ms[0]:.4f} ms [{deg_ms[1]:.4f}, {deg_ms[2]:.4f}]", flush=True)
+        xr = np.random.default_rng(1)
+        ones = torch.ones(n, dtype=torch.float32, device="cuda")
+        for N in (16, 64, 256):
+            for w in (1, 2):
+                X = QGTC.val2bit(torch.from_numpy(xr.integers(0, 2 ** w, size=(n, N)).astype(np.float32)).cuda(), w, True, False)
+                for a, direction in ((adj, "forward"), (t, "transposed")):
+                    scale = a.mean_scale()
+                    manual = lambda: QGTC.val2bit(QGTC.tiledMM2Int(a, X, N, w) * scale[:, None], w, False, False)  # noqa: E731
+                    assert torch.equal(QGTC.tiledMM2Bit(a, X, N, w, w, scale), manual())
+                    # a scale of ones gives the words of the unscaled call: the same data-dependent epilogue, plus the scale's cost
+                    assert torch.equal(QGTC.tiledMM2Bit(a, X, N, w, w, ones), QGTC.tiledMM2Bit(a, X, N, w, w))
+                    un, sc, one, man = timed_alternating(torch, [lambda: QGTC.tiledMM2Bit(a, X, N, w, w),
+                                                                 lambda: QGTC.tiledMM2Bit(a, X, N, w, w, scale),
+                                                                 lambda: QGTC.tiledMM2Bit(a, X, N, w, w, ones), manual], reps)
+                    rec["agg"].append({"N": N, "w": w, "direction": direction, "unscaled_ms": un, "scaled_ms": sc, "scaled_ones_ms": one,
+                                       "manual_ms": man, "scaled_over_unscaled": round(sc[0] / un[0], 3),
+                                       "ones_over_unscaled": round(one[0] / un[0], 3), "manual_over_scaled": round(man[0] / sc[0], 3)})
+                    print(f"{name:9s} N={N:<4d} w={w} {direction:10s} unscaled {un[0]:8.4f} [{un[1]:.4f}, {un[2]:.4f}]  mean scale {sc[0]:8.4f} "
+                          f"[{sc[1]:.4f}, {sc[2]:.4f}] ({sc[0] / un[0]:.3f}x)  ones {one[0]:8.4f} ({one[0] / un[0]:.3f}x)  "
+                          f"Int * scale, val2bit {man[0]:8.4f} ({man[0] / sc[0]:.2f}x)", flush=True)
+                del X
+        # what requant's clamp leaves of an in-neighbour aggregate: outputs at 2^b - 1, decoded from the kernels' own words
+        for b in (2, 3, 4):
+            N = 64
+            X = QGTC.val2bit(torch.from_numpy(xr.integers(0, 2 ** b, size=(n, N)).astype(np.float32)).cuda(), b, True, False)
+            v_sum = QGTC.bit2val(QGTC.tiledMM2Bit(t, X, N, b, b), b, n, N)
+            v_mean = QGTC.bit2val(QGTC.tiledMM2Bit(t, X, N, b, b, t.mean_scale()), b, n, N)
+            sat = {"bits": b, "sum_at_clamp": round(float((v_sum == 2 ** b - 1).float().mean()), 4),
+                   "mean_at_clamp": round(float((v_mean == 2 ** b - 1).float().mean()), 4), "mean_distinct": int(torch.unique(v_mean).numel()),
+                   "sum_distinct": int(torch.unique(v_sum).numel())}
+            rec["saturation"].append(sat)
+            print(f"{name:9s} in-neighbour aggregate at {b} bits, N = 64: at 2^b - 1 sum {sat['sum_at_clamp']:.4f} mean {sat['mean_at_clamp']:.4f}; "
+                  f"distinct values sum {sat['sum_distinct']} mean {sat['mean_distinct']}", flush=True)
+            del X, v_sum, v_mean
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled"))
     args = ap.parse_args()
 
     import torch
@@ -106,13 +196,14 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg == "transposed":
-        rows = transposed_leg(torch, QGTC, args.graphs.split(","), args.reps)
+    if args.leg in ("transposed", "scaled"):
+        leg = transposed_leg if args.leg == "transposed" else scaled_leg
+        rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
             with open(args.json, "w") as f:
                 json.dump(rows, f, indent=1)
-        print(json.dumps({"tiled_bench_transposed": [{k: v for k, v in r.items() if k != "agg"} for r in rows]}))
+        print(json.dumps({"tiled_bench_" + args.leg: [{k: v for k, v in r.items() if k != "agg"} for r in rows]}))
         return
     rows = []
     for name in args.graphs.split(","):
