@@ -511,6 +511,39 @@ int qgtc_tiledmm2int_t_scaled(const int64_t *col_ptr, const int64_t *col_tile, c
                               int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N, int bit2, const float *row_scale,
                               float *out, size_t out_elems, void *stream);
 
+/* ---- Float tiled products: the tiled adjacency times a float32 matrix, forwards and transposed -------------------------------------
+ * Every product above takes its right operand as packed bit planes of at most 8 bits. These two entries aggregate a FLOAT32 matrix
+ * over the same tiles: a full-precision output layer, raw input features, the A^T . dY of a backward pass.
+ *
+ * Semantics. X is float32 [n, N], row-major and contiguous, rows in the adjacency's numbering; out is float32 [n, N]; N >= 1, any
+ * value; 1 <= n <= 2^23. For output row r let v_1 < v_2 < ... < v_d be the ids of its neighbours in ASCENDING order (qgtc_tiledmm_f32:
+ * the set cells of row r; qgtc_tiledmm_f32_t: the set cells of column r; cells as the packer quantised them, self loops included).
+ * Then for every column c
+ *     s = +0.0f;  for k = 1 .. d:  s = fl32(s + X[v_k, c])          (IEEE single add, round to nearest even)
+ *     out[r, c] = s                                  row_scale NULL
+ *     out[r, c] = fl32(s * row_scale[r])             otherwise (one IEEE single multiply, fused with nothing)
+ * The order is part of the contract: the result is a function of the inputs alone, identical on every launch and every kernel variant,
+ * and equals the NumPy model of tests/tiled_float_model.py bit for bit. It follows that
+ *   - out[r] depends on the rows of X that are neighbours of r and on no others: a NaN or an infinity in X[v] reaches exactly the rows
+ *     adjacent to v (no tile is expanded to a dense 0/1 matrix, where 0 * NaN would spread it);
+ *   - a row without neighbours gives +0.0f (times the scale, if any: nothing is special-cased, so 0 * inf is NaN);
+ *   - when X holds integers and every partial sum stays below 2^24 in magnitude all adds are exact, and the result equals
+ *     qgtc_tiledmm2int (_scaled) on the packed planes of the same integers bit for bit.
+ * No float atomics are used. NaN payloads and signs are not specified. Inputs, partial sums or products that are subnormal are outside
+ * the tested domain. A long row or column list (a hub) is summed serially by one row group: splitting it would change the order.
+ *
+ * Pointer types and the meaning of the index arrays are those of qgtc_tiledmm2int / qgtc_tiledmm2int_t. X and out must not overlap.
+ * Every element of out[0 .. n*N) is written and nothing past it; list bounds are clamped to n_tiles, out-of-range k-quads / row blocks
+ * and neighbour ids from n up are skipped. Refusals, before any device work: QGTC_EINVAL for n outside 1 .. 2^23, N < 1, a negative
+ * n_tiles or a missing pointer (the index arrays and tiles may be NULL only when n_tiles is 0; row_scale may always be NULL);
+ * QGTC_EALIGN for tiles off a 16-byte boundary or X / out / row_scale off a 4-byte boundary (rows of X are not 16-byte aligned when
+ * N % 4 != 0: the kernels read and write single dwords); QGTC_ESIZE for x_elems < n * N or out_elems < n * N. */
+int qgtc_tiledmm_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                     size_t x_elems, int N, const float *row_scale, float *out, size_t out_elems, void *stream);
+int qgtc_tiledmm_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                       int n, const float *X, size_t x_elems, int N, const float *row_scale, float *out, size_t out_elems,
+                       void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

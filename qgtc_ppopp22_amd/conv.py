@@ -39,13 +39,18 @@ class GCNConv_Qnt(torch.nn.Module):
 
     ``aggr="sum"`` is the reference's aggregate. ``aggr="mean"`` divides each aggregate by the row's degree (the rows of the view it
     is given: out-neighbours on ``adj``, in-neighbours on ``adj.T``), in the product kernel's epilogue; it needs a whole graph's
-    QGTC.TiledAdjacency, where the plain sum runs into requant's clamp."""
+    QGTC.TiledAdjacency, where the plain sum runs into requant's clamp.
 
-    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, w_bit=2, act_bit=3, aggr="sum"):
+    ``float_out=True`` keeps the last layer in full precision: the class scores h . W_out stay the float32 product (bitMM2Int) and
+    are aggregated as floats (QGTC.tiledMMFloat) instead of being requantised to ``act_bit`` bits before the neighbours are summed.
+    It needs a QGTC.TiledAdjacency too; the first layer is unchanged."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, w_bit=2, act_bit=3, aggr="sum", float_out=False):
         super().__init__()
         if aggr not in ("sum", "mean"):
             raise ValueError(f'aggr must be "sum" or "mean", not {aggr!r}')
         self.aggr = aggr
+        self.float_out = bool(float_out)
         self.input_dim, self.hidden_dim, self.output_dim = input_dim, hidden_dim, output_dim
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
@@ -89,6 +94,8 @@ class GCNConv_Qnt(torch.nn.Module):
             return self._forward_tiled(A, X)
         if self.aggr == "mean":
             raise NotImplementedError('aggr="mean" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A')
+        if self.float_out:
+            raise NotImplementedError("float_out=True needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
         bit_A = self.A_Qnt(A)
         bit_X = self.X_Qnt(X)
         bit_h = Aggregation_Qnt.apply(bit_A, bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim,
@@ -101,7 +108,9 @@ class GCNConv_Qnt(torch.nn.Module):
         (bitMM2Bit_col), then tiledMM2Bit / tiledMM2Int - the words gcn_layer gives on the dense adjacency. A reordered
         adjacency (A.perm set) gets X in its numbering and gives the output back in X's: every term moves with its node and the
         quantisers work element by element, so the result is bit-identical to the unreordered one. With aggr="mean" both aggregates
-        take A.mean_scale() as their row scale (it lives in A's numbering and follows the view)."""
+        take A.mean_scale() as their row scale (it lives in A's numbering and follows the view). With float_out the last layer is
+        tiledMMFloat on the float32 product h . W_out (bitMM2Int). Its adds follow A's numbering; the class scores are integers, so
+        as long as the sums stay below 2^24 every add is exact and a reordered adjacency still gives the unreordered bits."""
         n = X.size(0)
         assert A.n == n, "the adjacency and X must have the same number of nodes"
         X = A.to_new(X)
@@ -109,6 +118,9 @@ class GCNConv_Qnt(torch.nn.Module):
         t = QGTC.bitMM2Bit_col(bit_X, self.bit_W_in, n, self.input_dim, self.hidden_dim, self.act_bit, self.w_bit, self.act_bit)
         scale = A.mean_scale() if self.aggr == "mean" else None
         bit_h = QGTC.tiledMM2Bit(A, t, self.hidden_dim, self.act_bit, self.act_bit, scale)
+        if self.float_out:
+            hw = QGTC.bitMM2Int(bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim, self.act_bit, self.w_bit)
+            return A.to_old(QGTC.tiledMMFloat(A, hw, scale))
         t = QGTC.bitMM2Bit_col(bit_h, self.bit_W_out, n, self.hidden_dim, self.output_dim, self.act_bit, self.w_bit, self.act_bit)
         return A.to_old(QGTC.tiledMM2Int(A, t, self.output_dim, self.act_bit, scale))
 

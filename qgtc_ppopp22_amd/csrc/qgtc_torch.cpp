@@ -593,6 +593,69 @@ torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::T
     return out;
 }
 
+// Float tiled products (qgtc_tiledmm_f32 / _t): float32 [n, N] = A_tiled . X (A_tiled^T . X) for a float32 X [n, N], the neighbours'
+// rows added in ascending id order; with row_scale every row is multiplied by row_scale[row] (QGTC.tiledMMFloat checks the same
+// conditions first, with the exception types its callers expect).
+void check_float_operand(const torch::Tensor &X, const int64_t n, const torch::Tensor &index) {
+    CHECK_INPUT(X);
+    TORCH_CHECK(X.scalar_type() == torch::kFloat32 && X.dim() == 2 && X.size(0) == n && X.size(1) >= 1,
+                "X must be a contiguous float32 tensor [n, N] with N >= 1");
+    TORCH_CHECK(X.device() == index.device(), "the adjacency and X must be on the same device");
+}
+
+torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                           const c10::optional<torch::Tensor> &row_scale) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
+    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    check_float_operand(X, n, row_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    c10::DeviceGuard guard(X.device());
+    const int64_t T = kquad.numel();
+    const float *sc = tiled_row_scale(row_scale, n, X);
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    check_rc(qgtc_tiledmm_f32(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T,
+                              static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
+                              out.data_ptr<float>(), out.numel(), current_stream(X)),
+             "tiledMMFloat");
+    return out;
+}
+
+torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale) {
+    CHECK_INPUT(col_ptr);
+    CHECK_INPUT(col_tile);
+    CHECK_INPUT(col_rb);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
+                "col_ptr and col_tile must be int64, col_rb int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
+    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
+                "col_tile, col_rb and tiles must list the same tiles");
+    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
+                "the adjacency must be on one device");
+    check_float_operand(X, n, col_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    c10::DeviceGuard guard(X.device());
+    const int64_t T = col_tile.numel();
+    const float *sc = tiled_row_scale(row_scale, n, X);
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    check_rc(qgtc_tiledmm_f32_t(col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
+                                T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, static_cast<int>(n),
+                                X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc, out.data_ptr<float>(), out.numel(),
+                                current_stream(X)),
+             "tiledMMFloat (transposed)");
+    return out;
+}
+
 // int8 MFMA GEMM (comparison path, cuBLASGemmEX analogue): float32 [M,N] = A[M,K] x Bt[N,K]^T
 torch::Tensor i8gemm(torch::Tensor A, torch::Tensor Bt) {
     CHECK_INPUT(A);
@@ -1608,6 +1671,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[n, N] with to_float (QGTC.tiledMM2Bit / tiledMM2Int on adj.T wrap it)", py::arg("col_ptr"), py::arg("col_tile"),
           py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("bit_X"), py::arg("N"), py::arg("bit2"), py::arg("output_bit"),
           py::arg("to_float"), py::arg("row_scale") = py::none());
+    m.def("_tiled_mm_f32", &tiled_mm_f32, "float32 [n, N] = A_tiled . X for a float32 X [n, N], neighbours added in ascending id order "
+          "(QGTC.tiledMMFloat wraps it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
+          py::arg("row_scale") = py::none());
+    m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
+          "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
+          py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none());
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");
     m.def("i8gemm_profile", &i8gemm_profile, "time `reps` i8gemm launches; returns milliseconds",
           py::arg("A"), py::arg("Bt"), py::arg("reps") = 200, py::arg("print") = true);

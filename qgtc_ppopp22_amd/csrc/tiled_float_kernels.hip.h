@@ -1,0 +1,155 @@
+// tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float.hip and qgtc_tiled_float_t.hip): the product of the
+// tile-compressed 1-bit adjacency with a FLOAT32 right operand, out = A_tiled . X (include/qgtc.h, "Float tiled products"; DESIGN.md
+// section 6.14) - the in-order row adder both directions share, the forward kernel and the argument checks of the two entries.
+//
+// The bit products AND + popcount whole 128-bit tile rows because their operand is bit planes. Here the operand is floats and the
+// tiles of real graphs are nearly empty (about 9 of 4096 cells), so a tile is read as a compressed neighbour list: the set bits of a
+// tile row are decoded MSB first (count leading zeros = ascending column = ascending neighbour id) and the addressed rows of X are
+// added. The contract fixes the order of the adds (ascending neighbour id, one IEEE single add each), so a lane keeps the running sum
+// of its own column(s) in registers and adds the neighbours' values strictly in the order they were decoded; only the LOADS run ahead.
+#pragma once
+
+namespace {
+
+constexpr int TILED_F32_CAP = 32;   // decoded neighbour ids a row group queues in LDS before it adds their rows
+constexpr int TILED_F32_AHEAD = 4;  // rows of X whose loads are in flight before the first of them is added
+
+// s[cc] += X[list[j], c0 + cc * LPR] for j = 0 .. cnt-1, IN THAT ORDER. The loads of TILED_F32_AHEAD neighbours are issued together
+// (past the end of the list the last entry is loaded again and not added); the adds of one column are a dependent chain by contract.
+// A column past N reads nothing and keeps +0. `list` lives in LDS and every lane of the row group wrote every entry itself (the same
+// value to the same address), so no lane reads a word another lane produced.
+template <int LPR, int CPL>
+__device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *list, int cnt, const float *__restrict__ X, int N, int c0) {
+    for (int j = 0; j < cnt; j += TILED_F32_AHEAD) {
+        float x[TILED_F32_AHEAD][CPL];
+#pragma unroll
+        for (int u = 0; u < TILED_F32_AHEAD; ++u) {
+            const int v = list[j + u < cnt ? j + u : cnt - 1];
+            const float *__restrict__ row = X + static_cast<uint64_t>(v) * N;
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) x[u][cc] = c0 + cc * LPR < N ? row[c0 + cc * LPR] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < TILED_F32_AHEAD; ++u)
+            if (j + u < cnt) {
+#pragma unroll
+                for (int cc = 0; cc < CPL; ++cc) s[cc] += x[u][cc];
+            }
+    }
+}
+
+// the set bits of `m`, MSB first, as neighbour ids base + (leading zeros), queued in `list`; ids from n up are dropped (the format keeps
+// such cells zero; a foreign tile must not make the kernel read past X). A full queue is added at once.
+template <int LPR, int CPL>
+__device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, float (&s)[CPL], int *list, int &cnt,
+                                                 const float *__restrict__ X, int N, int c0) {
+    while (m) {
+        const int b = __builtin_clz(m);
+        m &= ~(0x80000000u >> b);
+        const int v = base + b;
+        if (v < n) {
+            list[cnt++] = v;
+            if (cnt == TILED_F32_CAP) {
+                tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0);
+                cnt = 0;
+            }
+        }
+    }
+}
+
+// ---- forward: out = A_tiled . X -------------------------------------------------------------------------------------------------------
+// One workgroup (256 threads) per 32-row block and chunk of LPR * CPL output columns. A ROW GROUP of LPR lanes (16, 32 or a whole wave)
+// owns RPG = 32 / (256 / LPR) output rows of the block, with lane l on the columns chunk + l + cc * LPR, cc < CPL: a neighbour's row of
+// X is one coalesced read per cc. The group walks the block's tiles once, in k-quad order: lanes 0 .. RPG-1 load the 16-byte tile rows
+// of the group's rows (the next tile's while this one is decoded), every row's 4 words are broadcast and decoded into that row's own
+// queue, and a full queue is added to the row's running sums s[row][cc]; what is left is added after the walk. A row's adds are
+// thereby in tile order = ascending neighbour id. Narrow outputs take narrow groups, so that a wave keeps the loads of up to 4 rows
+// in flight at once. With LPR = 64 the tile words are wave-uniform (v_readlane) and the decode loop is scalar.
+// The rows are stored once; SCALED multiplies by row_scale[row] first (one IEEE single multiply).
+template <int LPR>
+__device__ __forceinline__ uint32_t tiled_f32_bcast(uint32_t v, int src) {
+    if constexpr (LPR == 64) return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), src));
+    else return static_cast<uint32_t>(__shfl(static_cast<int>(v), src, LPR));
+}
+
+template <int LPR, int CPL, bool SCALED>
+__global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
+                                                      const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
+                                                      const float *__restrict__ X, int N, const float *__restrict__ row_scale,
+                                                      float *__restrict__ out) {
+    constexpr int G = 256 / LPR, RPG = 32 / G;   // row groups per workgroup, rows per group
+    __shared__ int lists[G][RPG][TILED_F32_CAP];
+    const int rb = blockIdx.x, tid = threadIdx.x;
+    const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
+    const int l = tid % LPR, c0 = blockIdx.y * (LPR * CPL) + l;
+    const int nq = step128(n);
+
+    uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
+    if (n_tiles) {
+        t0 = static_cast<uint64_t>(row_ptr[rb]);
+        t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
+        t1 = t1 < n_tiles ? t1 : n_tiles;
+    }
+    float s[RPG][CPL];
+    int cnt[RPG];
+#pragma unroll
+    for (int ri = 0; ri < RPG; ++ri) {
+        cnt[ri] = 0;
+#pragma unroll
+        for (int cc = 0; cc < CPL; ++cc) s[ri][cc] = 0.0f;
+    }
+    const uint32_t *mine = tiles + (g * RPG + (l < RPG ? l : 0)) * 4;   // lane l < RPG: row g * RPG + l of every tile
+    uint4 a = make_uint4(0, 0, 0, 0);
+    int q = -1;
+    if (t0 < t1) {
+        q = kquad[t0];
+        if (l < RPG) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+    }
+    for (uint64_t t = t0; t < t1; ++t) {
+        uint4 an = make_uint4(0, 0, 0, 0);
+        int qn = -1;
+        if (t + 1 < t1) {
+            qn = kquad[t + 1];
+            if (l < RPG) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+        }
+        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) {
+            const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int ri = 0; ri < RPG; ++ri)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0);
+        }
+        a = an;
+        q = qn;
+    }
+#pragma unroll
+    for (int ri = 0; ri < RPG; ++ri) {
+        tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0);
+        const int row = rb * 32 + g * RPG + ri;
+        if (row < n) {
+            float sc = 1.0f;
+            if constexpr (SCALED) sc = row_scale[row];
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) {
+                const int c = c0 + cc * LPR;
+                if (c < N) out[static_cast<uint64_t>(row) * N + c] = SCALED ? s[ri][cc] * sc : s[ri][cc];
+            }
+        }
+    }
+}
+
+// ---- the argument checks of qgtc_tiledmm_f32 / qgtc_tiledmm_f32_t, made before any device work -----------------------------------------
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// `index_ok`: every index array of the direction is there (they and `tiles` may be NULL only when n_tiles is 0)
+inline int tiled_f32_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, size_t x_elems, int N,
+                             const float *row_scale, const float *out, size_t out_elems) {
+    if (!X || !out || n < 1 || n > (1 << 23) || N < 1 || n_tiles < 0 || (n_tiles && (!index_ok || !tiles))) return QGTC_EINVAL;
+    if ((tiles && !aligned16(tiles)) || !aligned4(X) || !aligned4(out) || !aligned4(row_scale)) return QGTC_EALIGN;
+    const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);
+    if (x_elems < need || out_elems < need) return QGTC_ESIZE;
+    return QGTC_OK;
+}
+
+}  // namespace

@@ -1,0 +1,119 @@
+// tiled_float_t_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float_t.hip, after tiled_t_kernels.hip.h and
+// tiled_float_kernels.hip.h): the transposed float product of the tile-compressed adjacency, out = A_tiled^T . X (include/qgtc.h,
+// "Float tiled products").
+//
+// One workgroup (256 threads) per k-quad q (output rows 128 q .. 128 q + 127) and chunk of LPR * CPL output columns. The k-quad's column
+// list is walked in ascending tile order - ascending row block, so ascending neighbour id - TS = 8 tiles a round:
+//   transpose  as in k_tiled_mm_t: each half-wave takes one tile (its list entry was loaded two rounds, its words one round ahead,
+//              so that a round does not wait for them) and runs the 32 x 32 bit transpose on its 4 words; the masks (tile
+//              column j over the tile's 32 rows, row i at bit 31 - i) go to LDS as [tile column][staged tile], so an output row
+//              reads the round's 8 masks as two 16-byte words;
+//   add        a ROW GROUP of LPR = 16 lanes owns the output rows j = g, g + 16, ...; lane l owns the columns chunk + l + cc * LPR,
+//              cc < CPL (a wave thereby keeps the loads of 4 rows in flight). A row with a mask in this round takes its running sums
+//              from LDS, decodes the staged tiles in order, each MSB first (ascending source row), adds the addressed rows of X in
+//              that order and puts the sums back. The sums of the 128 x LPR * CPL outputs live in LDS between rounds because a row
+//              is touched in few rounds and the row index is a loop variable; each word is read and written by one lane only.
+// The rows are stored once at the end; SCALED multiplies by row_scale[row] first (one IEEE single multiply).
+#pragma once
+
+namespace {
+
+template <int LPR, int CPL, bool SCALED>
+__global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
+                                                        const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
+                                                        uint64_t n_tiles, int n, const float *__restrict__ X, int N,
+                                                        const float *__restrict__ row_scale, float *__restrict__ out) {
+    constexpr int G = 256 / LPR, TS = TILED_T_TS;
+    static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
+    __shared__ __attribute__((aligned(16))) uint32_t mk[128 * TS];   // [tile column][staged tile]
+    __shared__ int srb[TS];
+    constexpr int W = LPR * CPL;   // output columns per workgroup
+    __shared__ float acc[128 * W];
+    __shared__ int lists[G][TILED_F32_CAP];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
+    const int l = tid % LPR, c0 = blockIdx.y * W + l;
+    const int nrb = (n + 31) / 32;
+    int *list = lists[g];
+    for (int j = g; j < 128; j += G)
+#pragma unroll
+        for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = 0.0f;
+
+    const int lane = tid & 31, s_own = tid >> 5;   // transposer role: half-wave s of the workgroup stages tile base + s
+    uint64_t b0 = 0, t1 = 0;                       // an adjacency without tiles may come without col_ptr
+    if (n_tiles) {
+        b0 = static_cast<uint64_t>(col_ptr[q]);
+        t1 = static_cast<uint64_t>(col_ptr[q + 1]);
+        t1 = t1 < n_tiles ? t1 : n_tiles;
+    }
+    uint4 w = make_uint4(0, 0, 0, 0);
+    // the loads of the transposer role run ahead of the rounds: the list entry two rounds ahead, the tile words one round ahead
+    // (an entry is checked when it is used, not when it is loaded: a skipped tile or row block leaves zero masks)
+    auto entry = [&](uint64_t i, uint64_t &t, int &rb) {
+        t = n_tiles;
+        rb = -1;
+        if (i < t1) {
+            t = static_cast<uint64_t>(col_tile[i]);
+            rb = col_rb[i];
+        }
+    };
+    auto words = [&](uint64_t t, int &rb) {
+        if (t < n_tiles && static_cast<unsigned>(rb) < static_cast<unsigned>(nrb))
+            return *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+        rb = -1;
+        return make_uint4(0, 0, 0, 0);
+    };
+    uint64_t tn;
+    int rb, rbn;
+    {
+        uint64_t tc;
+        entry(b0 + s_own, tc, rb);
+        entry(b0 + TS + s_own, tn, rbn);
+        w = words(tc, rb);
+    }
+    for (uint64_t base = b0; base < t1; base += TS) {
+        {
+            uint32_t v[4] = {w.x, w.y, w.z, w.w};
+            tiled_t_transpose(v, lane);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mk[(k * 32 + 31 - lane) * TS + s_own] = v[k];
+            if (lane == 0) srb[s_own] = rb;
+            rb = rbn;
+            w = words(tn, rb);
+            entry(base + 2 * TS + s_own, tn, rbn);
+        }
+        __syncthreads();
+        for (int j = g; j < 128; j += G) {
+            if (q * 128 + j >= n) break;
+            const uint4 ma = *reinterpret_cast<const uint4 *>(mk + j * TS), mb = *reinterpret_cast<const uint4 *>(mk + j * TS + 4);
+            const uint32_t m[TS] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+            if (!(ma.x | ma.y | ma.z | ma.w | mb.x | mb.y | mb.z | mb.w)) continue;
+            float s[CPL];
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) s[cc] = acc[j * W + cc * LPR + l];
+            int cnt = 0;
+#pragma unroll
+            for (int st = 0; st < TS; ++st)
+                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0);
+            tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0);
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = s[cc];
+        }
+        __syncthreads();
+    }
+
+    for (int j = g; j < 128; j += G) {
+        const int row = q * 128 + j;
+        if (row >= n) break;
+        float sc = 1.0f;
+        if constexpr (SCALED) sc = row_scale[row];
+#pragma unroll
+        for (int cc = 0; cc < CPL; ++cc) {
+            const int c = c0 + cc * LPR;
+            const float s = acc[j * W + cc * LPR + l];
+            if (c < N) out[static_cast<uint64_t>(row) * N + c] = SCALED ? s * sc : s;
+        }
+    }
+}
+
+}  // namespace

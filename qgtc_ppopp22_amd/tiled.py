@@ -17,6 +17,10 @@ what they give on ``pack_edges_tiled(dst, src, n)``.
 Both take ``row_scale`` (include/qgtc.h, "Scaled tiled products and degrees"): a float32 [n] the kernel multiplies every output row by
 before the output is formed. With ``adj.mean_scale()``, the reciprocal of ``adj.degrees()``, that is the MEAN over neighbours, which
 stays in 0 .. 2^bit2 - 1 where the plain sum of a whole graph runs into requant's clamp.
+
+:func:`tiledMMFloat` aggregates a float32 matrix over the same tiles, on ``adj`` and ``adj.T`` (include/qgtc.h, "Float tiled
+products"): each output row adds its neighbours' rows in ascending id order, one float32 add each, so the result is a function of the
+inputs alone.
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ from . import load_ext
 
 _ext = load_ext()
 
-__all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int"]
+__all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat"]
 
 
 class TiledAdjacency:
@@ -235,3 +239,33 @@ def tiledMM2Int(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, row
     """float32 [n, N] = A . X: ``bitMM2Int(A_rows, bit_X, n, n, N, 1, bit2, True)``; on ``adj.T``, A^T . X. With ``row_scale`` every
     row r is multiplied by row_scale[r] (one float32 multiply of the exact sum's float32 conversion)."""
     return _tiled(adj, bit_X, N, bit2, 1, True, row_scale)
+
+
+def _check_float_operand(adj: TiledAdjacency, X) -> None:
+    if not isinstance(X, torch.Tensor):
+        raise TypeError(f"X must be a torch.Tensor (float32 [{adj.n}, N]), not {type(X).__name__}")
+    if X.dtype != torch.float32:
+        raise TypeError(f"X must be float32, not {X.dtype}")
+    if X.dim() != 2 or X.size(0) != adj.n or X.size(1) < 1:
+        raise ValueError(f"X must have shape [{adj.n}, N] with N >= 1, not {list(X.shape)}")
+    if X.device != adj.device:
+        raise ValueError(f"X must be on the adjacency's device {adj.device}, not {X.device}")
+    if not X.is_contiguous():
+        raise ValueError(f"X must be contiguous; its strides are {list(X.stride())}")
+
+
+def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
+    on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
+    add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
+    result is the same bits on every launch; a NaN or an infinity in X[v] reaches exactly the rows adjacent to v; for integer X with
+    sums below 2^24 it equals ``tiledMM2Int`` on the packed planes of X. Nothing is converted or copied: another dtype is a
+    TypeError, another shape, device or a non-contiguous X a ValueError. On a reordered adjacency ``to_new`` / ``to_old`` move X and
+    the result (the adds then follow the new ids)."""
+    _check(adj)
+    _check_float_operand(adj, X)
+    if row_scale is not None:
+        _check_scale(adj, row_scale)
+    if adj.transposed:
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale)
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale)

@@ -17,7 +17,13 @@ without the feature - tiledMM2Int, a float multiply by the scale, val2bit - chec
 per-launch event times with their 10th and 90th percentiles. It also counts, on the device, the share of in-neighbour outputs at
 the clamp value 2^b - 1 for the plain sum and for the mean at 2 / 3 / 4 bits (N = 64, random features over the full range).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled]
+`--leg float` measures the float products (QGTC.tiledMMFloat) on the reordered graphs, both directions, N in
+{16, 64, 256}, launched alternately in one timed loop with (a) tiledMMFloat with the mean scale, (b) the only comparable route without
+the feature, tiledMM2Int on the 8 bit planes of the same matrix (integers 0 .. 255, so the two agree bit for bit: checked), and (c)
+that route with its val2bit inside the clock. Reported with the traffic floor of the float product - (set cells x N x 4 bytes of X
+rows + n x N x 4 bytes written + 524 bytes a tile) / 8 TB/s - as a fraction of the measured time.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float]
 """
 from __future__ import annotations
 
@@ -183,12 +189,53 @@ def scaled_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def float_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        cells = int(adj.degrees().sum())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles,
+               "max_out_degree": int(adj.degrees().max()), "max_in_degree": int(t.degrees().max()),
+               "max_block_tiles": adj.max_block_tiles, "max_col_tiles": t.max_block_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells} ({cells / max(1, adj.n_tiles):.1f} a tile)", flush=True)
+        xr = np.random.default_rng(1)
+        for N in (16, 64, 256):
+            X = torch.from_numpy(xr.integers(0, 256, size=(n, N)).astype(np.float32)).cuda()
+            bits = QGTC.val2bit(X, 8, True, False)
+            floor_ms = (cells * N * 4 + n * N * 4 + 524 * adj.n_tiles) / HBM_BPS * 1e3
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                scale = a.mean_scale()
+                for s, kind in ((None, "sum"), (scale, "mean")):   # integers below 2^24: the float and the bit route agree to the bit
+                    assert torch.equal(QGTC.tiledMMFloat(a, X, s).view(torch.int32), QGTC.tiledMM2Int(a, bits, N, 8, s).view(torch.int32)), (N, direction, kind)
+                fl, fs, bi, bv = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X), lambda: QGTC.tiledMMFloat(a, X, scale),
+                                                           lambda: QGTC.tiledMM2Int(a, bits, N, 8),
+                                                           lambda: QGTC.tiledMM2Int(a, QGTC.val2bit(X, 8, True, False), N, 8)], reps)
+                rec["agg"].append({"N": N, "direction": direction, "float_ms": fl, "float_mean_ms": fs, "bit8_ms": bi, "bit8_with_val2bit_ms": bv,
+                                   "float_over_bit8": round(fl[0] / bi[0], 3), "mean_over_sum": round(fs[0] / fl[0], 3),
+                                   "floor_ms": round(floor_ms, 5), "floor_frac": round(floor_ms / fl[0], 4)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} float {fl[0]:8.4f} [{fl[1]:.4f}, {fl[2]:.4f}]  mean {fs[0]:8.4f} [{fs[1]:.4f}, {fs[2]:.4f}] "
+                      f"({fs[0] / fl[0]:.3f}x)  8 planes {bi[0]:8.4f} [{bi[1]:.4f}, {bi[2]:.4f}] (float / planes {fl[0] / bi[0]:.3f})  "
+                      f"with val2bit {bv[0]:8.4f}  floor {floor_ms:.4f} ms = {floor_ms / fl[0]:.3f} of the time", flush=True)
+            del X, bits
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float"))
     args = ap.parse_args()
 
     import torch
@@ -196,8 +243,8 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled"):
-        leg = transposed_leg if args.leg == "transposed" else scaled_leg
+    if args.leg in ("transposed", "scaled", "float"):
+        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
