@@ -9,4 +9,4 @@ globals().update({k: getattr(_ext, k) for k in dir(_ext) if not k.startswith("_"
 __doc__ = _ext.__doc__
 
 # the tile-compressed whole-graph adjacency (Python objects over the extension's _tiled_* entries)
-from qgtc_ppopp22_amd.tiled import TiledAdjacency, pack_edges_tiled, reorder_nodes, tiledMM2Bit, tiledMM2Int, tiledMMFloat  # noqa: E402,F401
+from qgtc_ppopp22_amd.tiled import TiledAdjacency, pack_edges_tiled, reorder_nodes, tiledMM2Bit, tiledMM2Int, tiledMMFloat, tiledAggregate, add_self_loops  # noqa: E402,F401

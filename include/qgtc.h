@@ -544,6 +544,33 @@ int qgtc_tiledmm_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const in
                        int n, const float *X, size_t x_elems, int N, const float *row_scale, float *out, size_t out_elems,
                        void *stream);
 
+/* Source scale (qgtc_tiledmm_f32_src / qgtc_tiledmm_f32_t_src): the arguments of the two entries above plus src_scale, float32 [n] in the
+ * adjacency's numbering, a factor on the NEIGHBOUR being added:
+ *     s = +0.0f;  for k = 1 .. d:  s = fl32( s + fl32( src_scale[v_k] * X[v_k, c] ) )
+ *     out[r, c] = s   or   fl32(s * row_scale[r])                                       as above
+ * One IEEE single multiply, then one IEEE single add, both round to nearest even and NOT fused: the two roundings per term are part of
+ * the contract, so the result is bit for bit qgtc_tiledmm_f32 (_t) on the matrix fl32(src_scale[v] * X[v, c]), without that matrix
+ * being formed (tests/tiled_sym_model.py). The order of the adds is unchanged. out = diag(row_scale) . A . diag(src_scale) . X; its
+ * gradient with respect to X is the same product on the other direction with the two scales swapped, diag(src_scale) . A^T .
+ * diag(row_scale) . dY, so a backward pass is one call of the twin entry and is specified to the bit as well. With row_scale the
+ * inverse square roots of the out-degrees and src_scale those of the in-degrees (qgtc_tiled_inv_sqrt_degree) it is the GCN
+ * normalisation D_out^-1/2 . A . D_in^-1/2. Nothing is special-cased: a NaN in src_scale[v] reaches exactly the rows adjacent to v,
+ * 0 * inf is NaN. src_scale NULL: the call IS qgtc_tiledmm_f32 (_t), the same kernels and the same refusals. Otherwise the refusals
+ * and the rules for what is written are those entries' (every element of out[0 .. n*N) and nothing past it), plus QGTC_EALIGN for
+ * src_scale off a 4-byte boundary.
+ *
+ * qgtc_tiled_inv_sqrt_degree: out[i] = fl32( 1 / fl32( sqrt( fl32(deg[i]) ) ) ) for i < n, the square root and the division each
+ * correctly rounded (np.float32(1) / np.sqrt(np.float32(deg))); 0.0f where deg[i] is 0 (or negative). deg is what qgtc_tiled_degrees
+ * wrote, int32 [n]; every element of out is written with plain stores. QGTC_EINVAL for a missing pointer or n outside 1 .. 2^23,
+ * QGTC_EALIGN for a pointer off a 4-byte boundary. */
+int qgtc_tiledmm_f32_src(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                         size_t x_elems, int N, const float *row_scale, const float *src_scale, float *out, size_t out_elems,
+                         void *stream);
+int qgtc_tiledmm_f32_t_src(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                           int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *row_scale,
+                           const float *src_scale, float *out, size_t out_elems, void *stream);
+int qgtc_tiled_inv_sqrt_degree(const int32_t *deg, int n, float *out, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -6,7 +6,8 @@ aggregation (QGTC_conv.py:14-22: X·W, then A·(XW)), with the operand layouts t
 need: X·W is re-packed in the cols layout by `bitMM2Bit_col` so that it can be the right operand of
 A·(XW) (what unitest.py:100-109 does).
 
-Inference only, like the reference (its backward is `pass`, QGTC_conv.py:24-27).
+The quantised layers are inference only, like the reference (its backward is `pass`, QGTC_conv.py:24-27); the float `GCNConv` on a
+tile-compressed adjacency is trainable (QGTC.tiledAggregate).
 """
 from __future__ import annotations
 
@@ -126,12 +127,36 @@ class GCNConv_Qnt(torch.nn.Module):
 
 
 class GCNConv(torch.nn.Module):
-    """The float reference layer pair of QGTC_conv.py:101-121 (A · ((A · (X·W_in)) · W_out))."""
+    """The float reference layer pair of QGTC_conv.py:101-121 (A · ((A · (X·W_in)) · W_out)).
 
-    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2):
+    Given a whole graph's QGTC.TiledAdjacency the two aggregates are QGTC.tiledAggregate (float32, differentiable: the layer pair is
+    trainable), under ``norm``: None the plain sum, "mean" D^-1 . A (``A.mean_scale()`` on the output row), "sym" the GCN
+    normalisation D_out^-1/2 . A . D_in^-1/2 (``A.sym_scale()`` on the output row, ``A.T.sym_scale()`` on the neighbour being added;
+    on a symmetric edge list, D^-1/2 . A . D^-1/2 - QGTC.add_self_loops gives the A + I of Kipf and Welling). A dense ``A`` takes
+    ``norm=None`` only."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None):
         super().__init__()
+        if norm not in (None, "mean", "sym"):
+            raise ValueError(f'norm must be None, "mean" or "sym", not {norm!r}')
+        self.norm = norm
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
     def forward(self, A, X):
+        if isinstance(A, QGTC.TiledAdjacency):
+            return self._forward_tiled(A, X)
+        if self.norm is not None:
+            raise NotImplementedError(f'norm="{self.norm}" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A')
         return torch.mm(A, torch.mm(torch.mm(A, torch.mm(X, self.W_in)), self.W_out))
+
+    def _forward_tiled(self, A, X):
+        """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm``; X moves to A's numbering and the result back."""
+        assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        row = src = None
+        if self.norm == "mean":
+            row = A.mean_scale()
+        elif self.norm == "sym":
+            row, src = A.sym_scale(), A.T.sym_scale()
+        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src)
+        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src))

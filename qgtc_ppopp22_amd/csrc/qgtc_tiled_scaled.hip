@@ -1,6 +1,6 @@
 // qgtc_tiled_scaled.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the scaled product of the
 // tile-compressed adjacency, quantise(fl32(A_tiled . X) * row_scale) (the SCALED instantiations of tiled_kernels.hip.h), and the
-// degrees of a tiled adjacency with their reciprocals (tiled_degree_kernels.hip.h), with their launchers.
+// degrees of a tiled adjacency with their reciprocals and inverse square roots (tiled_degree_kernels.hip.h), with their launchers.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -90,6 +90,15 @@ int qgtc_tiled_degrees(const int64_t *row_ptr, const int32_t *kquad, const uint3
     if (out_inv || in_inv)
         hipLaunchKernelGGL(k_tiled_inv_degree, dim3(degree_grid(static_cast<uint64_t>(n))), dim3(256), 0, st, out_deg, out_inv, in_deg,
                            in_inv, n);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+int qgtc_tiled_inv_sqrt_degree(const int32_t *deg, int n, float *out, void *stream) {
+    if (!deg || !out || n < 1 || n > TILED_MAX_N) return QGTC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(deg) | reinterpret_cast<uintptr_t>(out)) & 3u) return QGTC_EALIGN;
+    hipLaunchKernelGGL(k_tiled_inv_sqrt_degree, dim3(degree_grid(static_cast<uint64_t>(n))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       deg, out, n);
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }

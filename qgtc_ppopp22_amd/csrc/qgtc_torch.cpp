@@ -603,8 +603,19 @@ void check_float_operand(const torch::Tensor &X, const int64_t n, const torch::T
     TORCH_CHECK(X.device() == index.device(), "the adjacency and X must be on the same device");
 }
 
-torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                           const c10::optional<torch::Tensor> &row_scale) {
+// src_scale (qgtc_tiledmm_f32_src / _t_src): every neighbour's row is multiplied by src_scale[neighbour] as it is added (one multiply, one
+// add, not fused). Without it the entries and arguments are the ones the bindings always used.
+const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, const int64_t n, const torch::Tensor &X) {
+    if (!src_scale.has_value()) return nullptr;
+    const torch::Tensor &s = *src_scale;
+    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
+                "src_scale must be a contiguous float32 tensor of n elements");
+    TORCH_CHECK(s.device() == X.device(), "src_scale must be on the adjacency's device");
+    return s.data_ptr<float>();
+}
+
+torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -618,17 +629,31 @@ torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Te
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     c10::DeviceGuard guard(X.device());
     const int64_t T = kquad.numel();
-    const float *sc = tiled_row_scale(row_scale, n, X);
+    const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    check_rc(qgtc_tiledmm_f32(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T,
-                              static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
-                              out.data_ptr<float>(), out.numel(), current_stream(X)),
-             "tiledMMFloat");
+    const int64_t *rp = row_ptr.data_ptr<int64_t>();
+    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    const int N = static_cast<int>(X.size(1));
+    if (src)
+        check_rc(qgtc_tiledmm_f32_src(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
+                                      out.numel(), current_stream(X)),
+                 "tiledMMFloat (source scale)");
+    else
+        check_rc(qgtc_tiledmm_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, out.data_ptr<float>(),
+                                  out.numel(), current_stream(X)),
+                 "tiledMMFloat");
     return out;
 }
 
-torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale) {
+torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                           const c10::optional<torch::Tensor> &row_scale) {
+    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt);
+}
+
+torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                                 torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
+                                 const c10::optional<torch::Tensor> &src_scale) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -646,13 +671,37 @@ torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torc
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     c10::DeviceGuard guard(X.device());
     const int64_t T = col_tile.numel();
-    const float *sc = tiled_row_scale(row_scale, n, X);
+    const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    check_rc(qgtc_tiledmm_f32_t(col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
-                                T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, static_cast<int>(n),
-                                X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc, out.data_ptr<float>(), out.numel(),
-                                current_stream(X)),
-             "tiledMMFloat (transposed)");
+    const int64_t *cp = col_ptr.data_ptr<int64_t>(), *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
+    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    const int N = static_cast<int>(X.size(1));
+    if (src)
+        check_rc(qgtc_tiledmm_f32_t_src(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
+                                        out.data_ptr<float>(), out.numel(), current_stream(X)),
+                 "tiledMMFloat (transposed, source scale)");
+    else
+        check_rc(qgtc_tiledmm_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, out.data_ptr<float>(),
+                                    out.numel(), current_stream(X)),
+                 "tiledMMFloat (transposed)");
+    return out;
+}
+
+torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale) {
+    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt);
+}
+
+// float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)
+torch::Tensor tiled_inv_sqrt_degree(torch::Tensor deg) {
+    CHECK_INPUT(deg);
+    TORCH_CHECK(deg.scalar_type() == torch::kInt32 && deg.dim() == 1 && deg.numel() >= 1 && deg.numel() <= (int64_t{1} << 23),
+                "deg must be an int32 tensor of 1 .. 2^23 elements");
+    c10::DeviceGuard guard(deg.device());
+    auto out = torch::empty({deg.numel()}, torch::TensorOptions().dtype(torch::kFloat32).device(deg.device()));
+    check_rc(qgtc_tiled_inv_sqrt_degree(deg.data_ptr<int32_t>(), static_cast<int>(deg.numel()), out.data_ptr<float>(), current_stream(deg)),
+             "tiled inverse square root of the degrees");
     return out;
 }
 
@@ -1677,6 +1726,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
           "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
           py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none());
+    m.def("_tiled_mm_f32_src", &tiled_mm_f32_src, "float32 [n, N] = A_tiled . diag(src_scale) . X: every neighbour's row times "
+          "src_scale[neighbour] as it is added (QGTC.tiledMMFloat with src_scale wraps it)", py::arg("row_ptr"), py::arg("kquad"),
+          py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"));
+    m.def("_tiled_mm_f32_t_src", &tiled_mm_f32_t_src, "float32 [n, N] = A_tiled^T . diag(src_scale) . X (QGTC.tiledMMFloat on adj.T with "
+          "src_scale wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"),
+          py::arg("row_scale"), py::arg("src_scale"));
+    m.def("_tiled_inv_sqrt_degree", &tiled_inv_sqrt_degree, "float32 [n] = 1 / sqrt(deg), correctly rounded, 0 where deg is 0 "
+          "(TiledAdjacency.sym_scale wraps it)", py::arg("deg"));
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");
     m.def("i8gemm_profile", &i8gemm_profile, "time `reps` i8gemm launches; returns milliseconds",
           py::arg("A"), py::arg("Bt"), py::arg("reps") = 200, py::arg("print") = true);

@@ -1,5 +1,6 @@
 // tiled_degree_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_scaled.hip): the degrees of a tile-compressed adjacency
-// in both directions and their reciprocals (include/qgtc.h, "Scaled tiled products and degrees"). A degree is
+// in both directions, their reciprocals and their inverse square roots (include/qgtc.h, "Scaled tiled products and degrees" and "Float
+// tiled products"; DESIGN.md sections 6.13, 6.15). A degree is
 // the number of set cells of a row (out) or a column (in) of the quantised adjacency: the number of terms of the product's sum.
 #pragma once
 
@@ -65,6 +66,16 @@ __global__ void k_tiled_inv_degree(const int32_t *__restrict__ deg_a, float *__r
             const int d = deg_b[i];
             inv_b[i] = d ? __fdiv_rn(1.0f, static_cast<float>(d)) : 0.0f;
         }
+    }
+}
+
+// out[i] = fl32(1 / fl32(sqrt(fl32(deg[i])))): the conversion is exact (degrees are at most 2^23), the square root and the division are
+// each correctly rounded (sqrtf and `/` are under hipcc's default; __fsqrt_rn is the approximate v_sqrt_f32 alone); 0 where the degree
+// is 0. Plain stores.
+__global__ void k_tiled_inv_sqrt_degree(const int32_t *__restrict__ deg, float *__restrict__ out, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int d = deg[i];
+        out[i] = d > 0 ? __fdiv_rn(1.0f, sqrtf(static_cast<float>(d))) : 0.0f;
     }
 }
 

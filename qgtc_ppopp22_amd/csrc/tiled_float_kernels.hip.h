@@ -1,12 +1,17 @@
-// tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float.hip and qgtc_tiled_float_t.hip): the product of the
-// tile-compressed 1-bit adjacency with a FLOAT32 right operand, out = A_tiled . X (include/qgtc.h, "Float tiled products"; DESIGN.md
-// section 6.14) - the in-order row adder both directions share, the forward kernel and the argument checks of the two entries.
+// tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float.hip, qgtc_tiled_float_t.hip and their _src twins): the
+// product of the tile-compressed 1-bit adjacency with a FLOAT32 right operand, out = A_tiled . X (include/qgtc.h, "Float tiled
+// products"; DESIGN.md sections 6.14, 6.15) - the in-order row adder both directions share, the forward kernel and the argument checks
+// of the entries.
 //
 // The bit products AND + popcount whole 128-bit tile rows because their operand is bit planes. Here the operand is floats and the
 // tiles of real graphs are nearly empty (about 9 of 4096 cells), so a tile is read as a compressed neighbour list: the set bits of a
 // tile row are decoded MSB first (count leading zeros = ascending column = ascending neighbour id) and the addressed rows of X are
 // added. The contract fixes the order of the adds (ascending neighbour id, one IEEE single add each), so a lane keeps the running sum
 // of its own column(s) in registers and adds the neighbours' values strictly in the order they were decoded; only the LOADS run ahead.
+//
+// Every template below ends in a pack `Src...`: empty, it is the code that existed before the source scale (same arguments, the same
+// instructions); with one `const float *` (src_scale, n floats) a neighbour's value is multiplied by src_scale[neighbour] before it is
+// added - one IEEE multiply, then one IEEE add, never fused.
 #pragma once
 
 namespace {
@@ -14,35 +19,53 @@ namespace {
 constexpr int TILED_F32_CAP = 32;   // decoded neighbour ids a row group queues in LDS before it adds their rows
 constexpr int TILED_F32_AHEAD = 4;  // rows of X whose loads are in flight before the first of them is added
 
+inline __device__ const float *tiled_f32_src(const float *src_scale) { return src_scale; }
+
+// fl32(s + fl32(w * x)): two roundings. hipcc contracts a * b + c into one fma by default (and __fmul_rn is a plain `*` here), so the
+// pair is written under `fp contract(off)`.
+__device__ __forceinline__ float tiled_f32_mul_add(float s, float w, float x) {
+#pragma clang fp contract(off)
+    const float p = w * x;
+    return s + p;
+}
+
 // s[cc] += X[list[j], c0 + cc * LPR] for j = 0 .. cnt-1, IN THAT ORDER. The loads of TILED_F32_AHEAD neighbours are issued together
 // (past the end of the list the last entry is loaded again and not added); the adds of one column are a dependent chain by contract.
 // A column past N reads nothing and keeps +0. `list` lives in LDS and every lane of the row group wrote every entry itself (the same
-// value to the same address), so no lane reads a word another lane produced.
-template <int LPR, int CPL>
-__device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *list, int cnt, const float *__restrict__ X, int N, int c0) {
+// value to the same address), so no lane reads a word another lane produced. With a source scale the neighbour's factor - one dword at
+// the same address for all lanes of the group - is loaded together with its row, so it is in flight with them and adds no dependent
+// latency; the term is then fl32(src_scale[v] * x), added with a separate add.
+template <int LPR, int CPL, class... Src>
+__device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *list, int cnt, const float *__restrict__ X, int N, int c0,
+                                                   Src... src) {
     for (int j = 0; j < cnt; j += TILED_F32_AHEAD) {
         float x[TILED_F32_AHEAD][CPL];
+        [[maybe_unused]] float w[TILED_F32_AHEAD];
 #pragma unroll
         for (int u = 0; u < TILED_F32_AHEAD; ++u) {
             const int v = list[j + u < cnt ? j + u : cnt - 1];
             const float *__restrict__ row = X + static_cast<uint64_t>(v) * N;
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) x[u][cc] = c0 + cc * LPR < N ? row[c0 + cc * LPR] : 0.0f;
+            if constexpr (sizeof...(Src) != 0) w[u] = tiled_f32_src(src...)[v];
         }
 #pragma unroll
         for (int u = 0; u < TILED_F32_AHEAD; ++u)
             if (j + u < cnt) {
 #pragma unroll
-                for (int cc = 0; cc < CPL; ++cc) s[cc] += x[u][cc];
+                for (int cc = 0; cc < CPL; ++cc) {
+                    if constexpr (sizeof...(Src) != 0) s[cc] = tiled_f32_mul_add(s[cc], w[u], x[u][cc]);
+                    else s[cc] += x[u][cc];
+                }
             }
     }
 }
 
 // the set bits of `m`, MSB first, as neighbour ids base + (leading zeros), queued in `list`; ids from n up are dropped (the format keeps
 // such cells zero; a foreign tile must not make the kernel read past X). A full queue is added at once.
-template <int LPR, int CPL>
+template <int LPR, int CPL, class... Src>
 __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, float (&s)[CPL], int *list, int &cnt,
-                                                 const float *__restrict__ X, int N, int c0) {
+                                                 const float *__restrict__ X, int N, int c0, Src... src) {
     while (m) {
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
@@ -50,7 +73,7 @@ __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, fl
         if (v < n) {
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
-                tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0);
+                tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
                 cnt = 0;
             }
         }
@@ -72,11 +95,11 @@ __device__ __forceinline__ uint32_t tiled_f32_bcast(uint32_t v, int src) {
     else return static_cast<uint32_t>(__shfl(static_cast<int>(v), src, LPR));
 }
 
-template <int LPR, int CPL, bool SCALED>
+template <int LPR, int CPL, bool SCALED, class... Src>
 __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                       const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                       const float *__restrict__ X, int N, const float *__restrict__ row_scale,
-                                                      float *__restrict__ out) {
+                                                      float *__restrict__ out, Src... src) {
     constexpr int G = 256 / LPR, RPG = 32 / G;   // row groups per workgroup, rows per group
     __shared__ int lists[G][RPG][TILED_F32_CAP];
     const int rb = blockIdx.x, tid = threadIdx.x;
@@ -118,14 +141,15 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
             for (int ri = 0; ri < RPG; ++ri)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0);
+                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
+                                               src...);
         }
         a = an;
         q = qn;
     }
 #pragma unroll
     for (int ri = 0; ri < RPG; ++ri) {
-        tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0);
+        tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0, src...);
         const int row = rb * 32 + g * RPG + ri;
         if (row < n) {
             float sc = 1.0f;
@@ -139,14 +163,15 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
     }
 }
 
-// ---- the argument checks of qgtc_tiledmm_f32 / qgtc_tiledmm_f32_t, made before any device work -----------------------------------------
+// ---- the argument checks of qgtc_tiledmm_f32 / _t and qgtc_tiledmm_f32_src / _t_src, made before any device work -----------------------------------------
 inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // `index_ok`: every index array of the direction is there (they and `tiles` may be NULL only when n_tiles is 0)
 inline int tiled_f32_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, size_t x_elems, int N,
-                             const float *row_scale, const float *out, size_t out_elems) {
+                             const float *row_scale, const float *out, size_t out_elems, const float *src_scale = nullptr) {
     if (!X || !out || n < 1 || n > (1 << 23) || N < 1 || n_tiles < 0 || (n_tiles && (!index_ok || !tiles))) return QGTC_EINVAL;
-    if ((tiles && !aligned16(tiles)) || !aligned4(X) || !aligned4(out) || !aligned4(row_scale)) return QGTC_EALIGN;
+    if ((tiles && !aligned16(tiles)) || !aligned4(X) || !aligned4(out) || !aligned4(row_scale) || !aligned4(src_scale))
+        return QGTC_EALIGN;
     const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);
     if (x_elems < need || out_elems < need) return QGTC_ESIZE;
     return QGTC_OK;

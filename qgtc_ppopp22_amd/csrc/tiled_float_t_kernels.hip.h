@@ -1,6 +1,6 @@
-// tiled_float_t_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float_t.hip, after tiled_t_kernels.hip.h and
-// tiled_float_kernels.hip.h): the transposed float product of the tile-compressed adjacency, out = A_tiled^T . X (include/qgtc.h,
-// "Float tiled products").
+// tiled_float_t_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float_t.hip and qgtc_tiled_float_t_src.hip, after
+// tiled_t_kernels.hip.h and tiled_float_kernels.hip.h): the transposed float product of the tile-compressed adjacency,
+// out = A_tiled^T . X (include/qgtc.h, "Float tiled products"; DESIGN.md sections 6.14, 6.15).
 //
 // One workgroup (256 threads) per k-quad q (output rows 128 q .. 128 q + 127) and chunk of LPR * CPL output columns. The k-quad's column
 // list is walked in ascending tile order - ascending row block, so ascending neighbour id - TS = 8 tiles a round:
@@ -13,16 +13,17 @@
 //              from LDS, decodes the staged tiles in order, each MSB first (ascending source row), adds the addressed rows of X in
 //              that order and puts the sums back. The sums of the 128 x LPR * CPL outputs live in LDS between rounds because a row
 //              is touched in few rounds and the row index is a loop variable; each word is read and written by one lane only.
-// The rows are stored once at the end; SCALED multiplies by row_scale[row] first (one IEEE single multiply).
+// The rows are stored once at the end; SCALED multiplies by row_scale[row] first (one IEEE single multiply). The trailing pack `Src...`
+// is tiled_float_kernels.hip.h's: empty, the kernel that existed; with src_scale, the shared adder scales every term by its source row.
 #pragma once
 
 namespace {
 
-template <int LPR, int CPL, bool SCALED>
+template <int LPR, int CPL, bool SCALED, class... Src>
 __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                         const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                         uint64_t n_tiles, int n, const float *__restrict__ X, int N,
-                                                        const float *__restrict__ row_scale, float *__restrict__ out) {
+                                                        const float *__restrict__ row_scale, float *__restrict__ out, Src... src) {
     constexpr int G = 256 / LPR, TS = TILED_T_TS;
     static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
     __shared__ __attribute__((aligned(16))) uint32_t mk[128 * TS];   // [tile column][staged tile]
@@ -94,8 +95,8 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
             int cnt = 0;
 #pragma unroll
             for (int st = 0; st < TS; ++st)
-                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0);
-            tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0);
+                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0, src...);
+            tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = s[cc];
         }

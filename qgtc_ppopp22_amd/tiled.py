@@ -20,7 +20,10 @@ stays in 0 .. 2^bit2 - 1 where the plain sum of a whole graph runs into requant'
 
 :func:`tiledMMFloat` aggregates a float32 matrix over the same tiles, on ``adj`` and ``adj.T`` (include/qgtc.h, "Float tiled
 products"): each output row adds its neighbours' rows in ascending id order, one float32 add each, so the result is a function of the
-inputs alone.
+inputs alone. With ``src_scale`` every neighbour's row is multiplied by its own factor as it is added (include/qgtc.h, "Source scale"):
+``row_scale=adj.sym_scale(), src_scale=adj.T.sym_scale()`` is the GCN normalisation D^-1/2 . A . D^-1/2 in one launch.
+:func:`tiledAggregate` is the same product under ``torch.autograd``: its backward is the product on the other view with the two scales
+swapped, one launch too. :func:`add_self_loops` prepares an edge list for it.
 """
 from __future__ import annotations
 
@@ -30,7 +33,8 @@ from . import load_ext
 
 _ext = load_ext()
 
-__all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat"]
+__all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat", "tiledAggregate",
+           "add_self_loops"]
 
 
 class TiledAdjacency:
@@ -60,6 +64,7 @@ class TiledAdjacency:
         self._max_block_tiles = None
         self._other = None   # the transposed view (built on first use), or, on that view, the adjacency it transposes
         self._degrees = None  # [out_deg, in_deg, out_inv, in_inv], kept on the untransposed adjacency for both views
+        self._sym = None      # [out, in] inverse square roots of the degrees, beside them
 
     @property
     def T(self) -> "TiledAdjacency":
@@ -112,6 +117,17 @@ class TiledAdjacency:
         """float32 [n]: 1 / degrees(), correctly rounded, 0 where the degree is 0 - the ``row_scale`` that turns tiledMM2Bit /
         tiledMM2Int on this view into the mean over neighbours."""
         return self._degree_tensors()[3 if self.transposed else 2]
+
+    def sym_scale(self) -> torch.Tensor:
+        """float32 [n]: 1 / sqrt(degrees()) of this view, both operations correctly rounded, 0 where the degree is 0. With
+        ``row_scale=adj.sym_scale(), src_scale=adj.T.sym_scale()`` tiledMMFloat / tiledAggregate on ``adj`` give
+        D_out^-1/2 . A . D_in^-1/2 (on ``adj.T`` swap the two views): on a symmetric edge list the GCN normalisation
+        D^-1/2 . A . D^-1/2. Computed for both directions on first use; ``adj`` and ``adj.T`` share the result."""
+        base = self._other if self.transposed else self
+        if base._sym is None:
+            deg = self._degree_tensors()
+            base._sym = [_ext._tiled_inv_sqrt_degree(deg[0]), _ext._tiled_inv_sqrt_degree(deg[1])]
+        return base._sym[1 if self.transposed else 0]
 
     def to_rows(self) -> torch.Tensor:
         """The dense rows-layout words [PAD8(n), S128(n)*4] (what ``pack_edges(src, dst, n, n, 1)`` returns; transposed, what
@@ -195,17 +211,17 @@ def _check(adj) -> None:
         raise TypeError("adj must be a TiledAdjacency (QGTC.pack_edges_tiled)")
 
 
-def _check_scale(adj: TiledAdjacency, row_scale) -> None:
+def _check_scale(adj: TiledAdjacency, row_scale, name: str = "row_scale") -> None:
     if not isinstance(row_scale, torch.Tensor):
-        raise TypeError("row_scale must be a torch.Tensor (float32 [n]) or None")
+        raise TypeError(f"{name} must be a torch.Tensor (float32 [n]) or None")
     if row_scale.dtype != torch.float32:
-        raise TypeError(f"row_scale must be float32, not {row_scale.dtype}")
+        raise TypeError(f"{name} must be float32, not {row_scale.dtype}")
     if row_scale.dim() != 1 or row_scale.numel() != adj.n:
-        raise ValueError(f"row_scale must have shape [{adj.n}], not {list(row_scale.shape)}")
+        raise ValueError(f"{name} must have shape [{adj.n}], not {list(row_scale.shape)}")
     if row_scale.device != adj.device:
-        raise ValueError(f"row_scale must be on the adjacency's device {adj.device}, not {row_scale.device}")
+        raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {row_scale.device}")
     if not row_scale.is_contiguous():
-        raise ValueError("row_scale must be contiguous")
+        raise ValueError(f"{name} must be contiguous")
 
 
 def _tiled(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int, to_float: bool, row_scale) -> torch.Tensor:
@@ -254,18 +270,65 @@ def _check_float_operand(adj: TiledAdjacency, X) -> None:
         raise ValueError(f"X must be contiguous; its strides are {list(X.stride())}")
 
 
-def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None) -> torch.Tensor:
+def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
+                 src_scale: torch.Tensor | None = None) -> torch.Tensor:
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
     result is the same bits on every launch; a NaN or an infinity in X[v] reaches exactly the rows adjacent to v; for integer X with
     sums below 2^24 it equals ``tiledMM2Int`` on the packed planes of X. Nothing is converted or copied: another dtype is a
     TypeError, another shape, device or a non-contiguous X a ValueError. On a reordered adjacency ``to_new`` / ``to_old`` move X and
-    the result (the adds then follow the new ids)."""
+    the result (the adds then follow the new ids).
+
+    With ``src_scale`` (float32 [n], like ``row_scale``) neighbour v's row is multiplied by src_scale[v] as it is added - one float32
+    multiply, then the add, not fused -, so the result is diag(row_scale) . A . diag(src_scale) . X, bit for bit
+    ``tiledMMFloat(adj, src_scale[:, None] * X, row_scale)`` without the elementwise pass. Without it the call is the one it was."""
     _check(adj)
     _check_float_operand(adj, X)
     if row_scale is not None:
         _check_scale(adj, row_scale)
+    if src_scale is not None:
+        _check_scale(adj, src_scale, "src_scale")
+        if adj.transposed:
+            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale)
+        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale)
     if adj.transposed:
         return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale)
     return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale)
+
+
+class _TiledAggregate(torch.autograd.Function):
+    """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped."""
+
+    @staticmethod
+    def forward(ctx, adj, X, row_scale, src_scale):
+        ctx.adj, ctx.row_scale, ctx.src_scale = adj, row_scale, src_scale
+        return tiledMMFloat(adj, X, row_scale, src_scale)
+
+    @staticmethod
+    def backward(ctx, dY):
+        dX = None
+        if ctx.needs_input_grad[1]:
+            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale)
+        return None, dX, None, None
+
+
+def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
+                   src_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
+    for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
+    The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
+    (``to_new`` / ``to_old`` are ``index_select`` and differentiate by themselves)."""
+    for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
+        if isinstance(sc, torch.Tensor) and sc.requires_grad:
+            raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to X only")
+    return _TiledAggregate.apply(adj, X, row_scale, src_scale)
+
+
+def add_self_loops(src: torch.Tensor, dst: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(src, dst) with every existing (i, i) edge removed and exactly one appended for each node 0 .. n-1. The packer quantises
+    multiplicity 2 to 0, so loops appended to a list that already holds some would erase those; this keeps one of each. Torch
+    operations only, on the edges' device; the other edges keep their order."""
+    keep = src != dst
+    loops = torch.arange(int(n), dtype=src.dtype, device=src.device)
+    return torch.cat([src[keep], loops]), torch.cat([dst[keep], loops.to(dst.dtype)])

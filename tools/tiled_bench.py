@@ -23,7 +23,14 @@ the feature, tiledMM2Int on the 8 bit planes of the same matrix (integers 0 .. 2
 that route with its val2bit inside the clock. Reported with the traffic floor of the float product - (set cells x N x 4 bytes of X
 rows + n x N x 4 bytes written + 524 bytes a tile) / 8 TB/s - as a fraction of the measured time.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float]
+`--leg sym` measures the source scale and the differentiable aggregate (QGTC.tiledMMFloat(src_scale=), QGTC.tiledAggregate; DESIGN.md
+6.15) on the reordered graphs, both directions, N in {16, 64, 256}, standard-normal X, with the symmetric normalisation
+(row_scale = sym_scale() of the view, src_scale = that of the other view), launched alternately in one timed loop: (a) tiledMMFloat with
+the row scale only, (b) with both scales in one launch, (c) the route without the feature, tiledMMFloat(adj, X * c[:, None], r)
+(checked bit-equal to (b) before timing), (d) forward plus backward of one tiledAggregate. Medians with their 10th and 90th
+percentiles, and the ratios (b) / (a), (b) / (c), (d) / (b).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym]
 """
 from __future__ import annotations
 
@@ -230,12 +237,55 @@ def float_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def sym_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        cells = int(adj.degrees().sum())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells} ({cells / max(1, adj.n_tiles):.1f} a tile)", flush=True)
+        xr = np.random.default_rng(1)
+        for N in (16, 64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                r, c = a.sym_scale(), a.T.sym_scale()
+                manual = lambda: QGTC.tiledMMFloat(a, X * c[:, None], r)  # noqa: E731
+                assert torch.equal(QGTC.tiledMMFloat(a, X, r, c).view(torch.int32), manual().view(torch.int32)), (N, direction)
+
+                def both_ways():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, r, c), Xg, dY)
+
+                assert torch.equal(both_ways()[0].view(torch.int32), QGTC.tiledMMFloat(a.T, dY, c, r).view(torch.int32)), (N, direction)
+                ta, tb, tc, td = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X, r), lambda: QGTC.tiledMMFloat(a, X, r, c),
+                                                           manual, both_ways], reps)
+                rec["agg"].append({"N": N, "direction": direction, "row_scale_ms": ta, "both_scales_ms": tb, "premultiplied_ms": tc,
+                                   "forward_backward_ms": td, "both_over_row": round(tb[0] / ta[0], 3),
+                                   "both_over_premultiplied": round(tb[0] / tc[0], 3), "fwd_bwd_over_both": round(td[0] / tb[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} row scale {ta[0]:8.4f} [{ta[1]:.4f}, {ta[2]:.4f}]  both scales {tb[0]:8.4f} "
+                      f"[{tb[1]:.4f}, {tb[2]:.4f}] ({tb[0] / ta[0]:.3f}x)  X * c, then row scale {tc[0]:8.4f} [{tc[1]:.4f}, {tc[2]:.4f}] "
+                      f"(both / it {tb[0] / tc[0]:.3f})  forward + backward {td[0]:8.4f} [{td[1]:.4f}, {td[2]:.4f}]", flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym"))
     args = ap.parse_args()
 
     import torch
@@ -243,8 +293,8 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float"):
-        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg}[args.leg]
+    if args.leg in ("transposed", "scaled", "float", "sym"):
+        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
