@@ -46,6 +46,46 @@ int hip_fail(hipError_t e, const char *where) {
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool bits_ok(int b) { return b >= 1 && b <= 32; }
 
+// ------------------------------------------------------------------------------------------
+// Clearing a buffer ahead of an atomic-OR / atomic-add kernel: a kernel of the library's own, not hipMemsetAsync. Captured into a
+// graph, the runtime's memset node clears the buffer on the first launch of the graph only (ROCm 7.0: every later replay writes
+// other values - tests/test_stream_abi_gpu.py replays each of these entries three times); a kernel node replays like every other
+// kernel. `words` 32-bit words of `value`: scalar stores up to the first 16-byte boundary and behind the last, 16-byte stores between.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_fill_words(uint32_t *__restrict__ p, uint32_t value, unsigned long long head,
+                                                    unsigned long long quads, unsigned long long words) {
+    const unsigned long long t = blockIdx.x * 256ull + threadIdx.x, stride = gridDim.x * 256ull;
+    if (t < head) p[t] = value;
+    uint4 *body = reinterpret_cast<uint4 *>(p + head);
+    for (unsigned long long i = t; i < quads; i += stride) body[i] = make_uint4(value, value, value, value);
+    const unsigned long long tail = head + 4ull * quads;
+    if (tail + t < words) p[tail + t] = value;      // at most three words
+}
+
+// `bytes` bytes of `byte` at p on `st`. Word-sized regions (every one the library clears) take the kernel; anything else the runtime.
+int fill_bytes(void *p, int byte, size_t bytes, hipStream_t st) {
+    if (!bytes) return QGTC_OK;
+    if ((reinterpret_cast<uintptr_t>(p) | bytes) & 3u) {
+        const hipError_t e = hipMemsetAsync(p, byte, bytes, st);
+        return e == hipSuccess ? QGTC_OK : hip_fail(e, "hipMemsetAsync");
+    }
+    const unsigned long long words = bytes / 4u;
+    unsigned long long head = ((16u - (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / 4u;
+    if (head > words) head = words;
+    const unsigned long long quads = (words - head) / 4u;
+    const uint32_t value = 0x01010101u * static_cast<uint32_t>(byte & 0xFF);
+    const unsigned long long blocks = (quads + 255u) / 256u;
+    hipLaunchKernelGGL(k_fill_words, dim3(static_cast<unsigned>(blocks < 1u ? 1u : (blocks > 4096u ? 4096u : blocks))), dim3(256), 0, st,
+                       static_cast<uint32_t *>(p), value, head, quads, words);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? QGTC_OK : hip_fail(e, "k_fill_words");
+}
+#define FILL_TRY(p, byte, bytes, st)                                  \
+    do {                                                              \
+        const int rc_ = fill_bytes((p), (byte), (bytes), (st));       \
+        if (rc_ != QGTC_OK) return rc_;                               \
+    } while (0)
+
 // bounds-safe word / granule loads: indices past the buffer read as zero
 __device__ __forceinline__ uint32_t ldw(const uint32_t *__restrict__ p, unsigned long long n,
                                         unsigned long long i) {

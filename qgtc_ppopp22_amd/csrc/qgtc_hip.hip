@@ -276,7 +276,7 @@ int qgtc_tile_counters(const uint32_t *X, size_t x_words, int M, int K, int N, i
     if (!X || !counters || M <= 0 || K <= 0 || N <= 0 || !bits_ok(bit1) || !bits_ok(bit2))
         return QGTC_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(uint64_t), st));
+    FILL_TRY(counters, 0, 2 * sizeof(uint64_t), st);
     const unsigned long long gdx = step8(M), gdy = step8(N), gdk = step128(K);
     const unsigned long long total = gdx * gdy * gdk * bit1 * bit2;
     const size_t items = static_cast<size_t>(bit1) * gdx * gdk;
@@ -508,7 +508,7 @@ int qgtc_pack_edges(const int64_t *cells, const int32_t *counts, size_t n_cells,
     if (!out || H <= 0 || W <= 0 || !bits_ok(nbits) || (n_cells && !cells)) return QGTC_EINVAL;
     if (out_words < qgtc_rows_words(H, W, nbits)) return QGTC_ESIZE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(out, 0, qgtc_rows_words(H, W, nbits) * sizeof(uint32_t), st));
+    FILL_TRY(out, 0, qgtc_rows_words(H, W, nbits) * sizeof(uint32_t), st);
     if (n_cells) {
         const float ub = std::ldexp(1.0f, nbits), ubm1 = ub - 1.0f;
         hipLaunchKernelGGL(k_pack_edges, dim3(grid_for(n_cells, 256)), dim3(256), 0, st, cells, counts,
@@ -525,12 +525,12 @@ int qgtc_pack_edge_list(const int64_t *src, const int64_t *dst, size_t n_edges, 
     if (out_words < words || scratch_words < 2 * words) return QGTC_ESIZE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (scratch == out + words) {   // one allocation [out | scratch] (the PyTorch binding's): one memset
-        HIP_TRY(hipMemsetAsync(out, 0, 3 * words * sizeof(uint32_t), st));
+        FILL_TRY(out, 0, 3 * words * sizeof(uint32_t), st);
     } else {
-        HIP_TRY(hipMemsetAsync(out, 0, words * sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(scratch, 0, 2 * words * sizeof(uint32_t), st));
+        FILL_TRY(out, 0, words * sizeof(uint32_t), st);
+        FILL_TRY(scratch, 0, 2 * words * sizeof(uint32_t), st);
     }
-    if (bad_index) HIP_TRY(hipMemsetAsync(bad_index, 0, sizeof(int), st));
+    if (bad_index) FILL_TRY(bad_index, 0, sizeof(int), st);
     if (n_edges) {
         hipLaunchKernelGGL(k_edge_list_count, dim3(grid_for(n_edges, 256)), dim3(256), 0, st, src, dst, n_edges, H, W,
                            out, scratch, scratch + words, step128(W) * 4, bad_index);
@@ -564,8 +564,8 @@ int qgtc_load_batches(const qgtc_loader_batch *batches, int count, int max_n, ui
     if (feats && (F <= 0 || !bits_ok(x_bits))) return QGTC_EINVAL;
     if (max_edges >= (1ull << 40)) return QGTC_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(zero, 0, zero_bytes, st));
-    if (bad_index) HIP_TRY(hipMemsetAsync(bad_index, 0, sizeof(int), st));
+    FILL_TRY(zero, 0, zero_bytes, st);
+    if (bad_index) FILL_TRY(bad_index, 0, sizeof(int), st);
     const int rb_max = (max_n + TM - 1) / TM;
     const size_t work_fixed = load_work_offsets(count, max_n) + load_work_counts(count, max_n);
     if (work) {   // a work buffer that cannot serve is an error, not a reason to take the route whose `zero` region the caller did not supply

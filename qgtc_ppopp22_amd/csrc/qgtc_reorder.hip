@@ -73,7 +73,7 @@ int qgtc_reorder_nodes(const int64_t *src, const int64_t *dst, size_t n_edges, i
         if (reinterpret_cast<uintptr_t>(work) & 255u) return QGTC_EALIGN;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (bad_index) HIP_TRY(hipMemsetAsync(bad_index, 0, sizeof(int), st));
+    if (bad_index) FILL_TRY(bad_index, 0, sizeof(int), st);
     if (!n_edges || !sweeps) {   // no neighbour entries or no sweep: every label stays the node's own id
         if (n_edges && bad_index)
             hipLaunchKernelGGL(k_reorder_check, dim3(reorder_grid(n_edges)), dim3(256), 0, st, src, dst, static_cast<uint64_t>(n_edges), n,
@@ -94,8 +94,8 @@ int qgtc_reorder_nodes(const int64_t *src, const int64_t *dst, size_t n_edges, i
     size_t temp_bytes = L.temp_bytes;
     const uint64_t e = n_edges, m = 2 * e;
 
-    HIP_TRY(hipMemsetAsync(size, 0, static_cast<size_t>(n) * 8, st));
-    HIP_TRY(hipMemsetAsync(changed, 0, REORDER_MAX_SWEEPS * 4, st));
+    FILL_TRY(size, 0, static_cast<size_t>(n) * 8, st);
+    FILL_TRY(changed, 0, REORDER_MAX_SWEEPS * 4, st);
     // symmetrised neighbour lists
     hipLaunchKernelGGL(k_reorder_entry_keys, dim3(reorder_grid(e)), dim3(256), 0, st, src, dst, e, n, A, bad_index);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, m, 0, REORDER_KEY_BITS, st));

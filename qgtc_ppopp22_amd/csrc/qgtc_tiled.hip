@@ -56,8 +56,8 @@ int qgtc_tiled_count(const int64_t *src, const int64_t *dst, size_t n_edges, int
     if (reinterpret_cast<uintptr_t>(work) & 255u) return QGTC_EALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nq = step128(n), nrb = (n + 31) / 32;
-    HIP_TRY(hipMemsetAsync(row_ptr, 0, (nrb + 1) * sizeof(int64_t), st));
-    if (bad_index) HIP_TRY(hipMemsetAsync(bad_index, 0, sizeof(int), st));
+    FILL_TRY(row_ptr, 0, (nrb + 1) * sizeof(int64_t), st);
+    if (bad_index) FILL_TRY(bad_index, 0, sizeof(int), st);
     if (!n_edges) return QGTC_OK;
     const uint64_t e = n_edges;
     uint64_t *A = reinterpret_cast<uint64_t *>(work), *B = A + e, *C = B + e;
@@ -69,7 +69,7 @@ int qgtc_tiled_count(const int64_t *src, const int64_t *dst, size_t n_edges, int
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, e, 0, TILED_KEY_BITS, st));
     hipLaunchKernelGGL(k_tiled_flags, dim3(g), dim3(256), 0, st, B, e, C);
     HIP_TRY(rocprim::exclusive_scan(temp, temp_bytes, C, A, static_cast<uint64_t>(0), e, rocprim::plus<uint64_t>(), st));
-    HIP_TRY(hipMemsetAsync(C, 0xFF, e * sizeof(uint64_t), st));
+    FILL_TRY(C, 0xFF, e * sizeof(uint64_t), st);
     hipLaunchKernelGGL(k_tiled_compact, dim3(g), dim3(256), 0, st, B, A, e, C);
     hipLaunchKernelGGL(k_tiled_starts, dim3(g), dim3(256), 0, st, C, e, A);
     HIP_TRY(rocprim::exclusive_scan(temp, temp_bytes, A, B, static_cast<uint64_t>(0), e, rocprim::plus<uint64_t>(), st));
@@ -89,7 +89,7 @@ int qgtc_tiled_fill(size_t n_edges, int n, int64_t n_tiles, int32_t *kquad, uint
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t e = n_edges;
     const uint64_t *A = reinterpret_cast<const uint64_t *>(work), *B = A + e, *C = B + e;
-    HIP_TRY(hipMemsetAsync(tiles, 0, static_cast<size_t>(n_tiles) * 512, st));
+    FILL_TRY(tiles, 0, static_cast<size_t>(n_tiles) * 512, st);
     hipLaunchKernelGGL(k_tiled_fill, dim3(tiled_grid(e)), dim3(256), 0, st, C, A, B, e, step128(n), static_cast<uint64_t>(n_tiles),
                        kquad, tiles);
     HIP_TRY(hipGetLastError());

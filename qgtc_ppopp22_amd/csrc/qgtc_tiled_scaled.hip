@@ -84,7 +84,7 @@ int qgtc_tiled_degrees(const int64_t *row_ptr, const int32_t *kquad, const uint3
         hipLaunchKernelGGL(k_tiled_out_degree, dim3(degree_grid((static_cast<uint64_t>(n) + 31) / 32 * 32)), dim3(256), 0, st, row_ptr,
                            kquad, tiles, nt, n, out_deg);
     if (in_deg) {
-        HIP_TRY(hipMemsetAsync(in_deg, 0, static_cast<size_t>(n) * sizeof(int32_t), st));
+        FILL_TRY(in_deg, 0, static_cast<size_t>(n) * sizeof(int32_t), st);
         if (nt) hipLaunchKernelGGL(k_tiled_in_degree, dim3(degree_grid(nt * 32)), dim3(256), 0, st, kquad, tiles, nt, n, in_deg);
     }
     if (out_inv || in_inv)

@@ -62,7 +62,7 @@ int qgtc_tiled_colindex(const int64_t *row_ptr, const int32_t *kquad, int64_t n_
     if (reinterpret_cast<uintptr_t>(work) & 255u) return QGTC_EALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nq = step128(n), nrb = (n + 31) / 32;
-    HIP_TRY(hipMemsetAsync(col_ptr, 0, (static_cast<size_t>(nq) + 1) * sizeof(int64_t), st));
+    FILL_TRY(col_ptr, 0, (static_cast<size_t>(nq) + 1) * sizeof(int64_t), st);
     if (!n_tiles) return QGTC_OK;
     const uint64_t t = static_cast<uint64_t>(n_tiles);
     const unsigned tile_bits = bit_width(t - 1) ? bit_width(t - 1) : 1, end_bit = tile_bits + bit_width(static_cast<uint64_t>(nq));

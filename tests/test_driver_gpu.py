@@ -46,6 +46,47 @@ def test_epoch_outputs_match_oracle(qgtc, oracle, chain, gin, bits, batched):
             np.testing.assert_array_equal(expect, integer_gcn_reference(bi["A"], bi["X"], 64, 10, bits, oracle))
 
 
+def _epoch_equals_the_oracle(res, oracle, chain, gin, bits):
+    """Every batch of a run on the 'tiny' graph against the oracle's chain, as test_epoch_outputs_match_oracle checks it."""
+    from qgtc_ppopp22_amd import graph as G
+
+    graph = G.make_graph("tiny", PSIZE)
+    random.seed(2)                     # the driver's seed: same partition shuffle
+    par = G.partition_list(graph, PSIZE)
+    random.shuffle(par)
+    W = oracle_weights(oracle, graph.feat.shape[1], 64, 10, bits)
+    assert len(res["outs"]) == PSIZE // BS
+    for cid in range(PSIZE // BS):
+        bi = oracle_batch_inputs(oracle, graph, par, cid, PSIZE, BS, bits)
+        expect = oracle_chain(oracle, bi, W, bits, chain, gin)[-1]
+        np.testing.assert_array_equal(res["outs"][cid].cpu().numpy(), expect, err_msg=f"batch {cid}")
+
+
+@pytest.mark.parametrize("chain", ["reference", "correct"])
+@pytest.mark.parametrize("gin", [False, True])
+@pytest.mark.parametrize("bits", [1, 2, 4, 8, 16])
+def test_graph_mode_outputs_match_oracle(qgtc, oracle, chain, gin, bits):
+    """--graph: the six calls per batch warmed up on a side stream, captured once and replayed per epoch (two epochs: the second replay
+    runs on the outputs the first left behind)."""
+    from qgtc_ppopp22_amd import driver
+
+    res = driver.run(_args(["--chain", chain, "--bit_width", str(bits), "--graph"] + (["--run_GIN"] if gin else [])), Q=qgtc)
+    _epoch_equals_the_oracle(res, oracle, chain, gin, bits)
+
+
+@pytest.mark.parametrize("chain", ["reference", "correct"])
+@pytest.mark.parametrize("gin", [False, True])
+@pytest.mark.parametrize("bits", [2, 4])
+@pytest.mark.parametrize("streams", [1, 3, 4])
+def test_streams_mode_outputs_match_oracle(qgtc, oracle, chain, gin, bits, streams):
+    """--streams N: one launch per batch and operator, batch i on pool stream i % N, every stage forked from and joined to the current
+    stream (BatchedGemm.run_per_problem); two epochs."""
+    from qgtc_ppopp22_amd import driver
+
+    res = driver.run(_args(["--chain", chain, "--bit_width", str(bits), "--streams", str(streams)] + (["--run_GIN"] if gin else [])), Q=qgtc)
+    _epoch_equals_the_oracle(res, oracle, chain, gin, bits)
+
+
 @pytest.mark.parametrize("engine", ["mfma", "popcount"])
 @pytest.mark.parametrize("gin", [False, True])
 @pytest.mark.parametrize("batched", [False, True])
@@ -196,6 +237,27 @@ def test_full_size_epoch_matches_oracle_on_every_batch(qgtc, oracle, dataset, bi
         if chain == "correct":
             assert grouped["outs"][cid].abs().sum().item() > 0
     assert min(sizes) > (1100 if dataset == "ogbn-arxiv" else 500)
+
+
+@pytest.mark.parametrize("mode", [["--graph"], ["--streams", "4"]], ids=["graph", "streams4"])
+def test_full_size_epoch_under_graph_and_streams(qgtc, oracle, mode):
+    """The arxiv-sized graph (75 batches of ~1213 nodes, 2-bit Cluster-GCN, layout-correct chain) under --graph (450 captured launches,
+    replayed twice) and --streams 4: every batch equals the per-batch run, which test_full_size_epoch_matches_oracle_on_every_batch pins
+    to the oracle, and three batches the oracle's chain directly."""
+    import torch
+
+    driver, base, graph, par = _full_size("ogbn-arxiv", 2, 128, False, "correct")
+    base[base.index("--n-epochs") + 1] = "2"
+    per_batch = driver.run(driver.build_parser().parse_args(base), Q=qgtc, graph=graph)
+    got = driver.run(driver.build_parser().parse_args(base + mode), Q=qgtc, graph=graph)
+    assert len(got["outs"]) == len(per_batch["outs"]) == 75
+    for cid in range(75):
+        assert torch.equal(got["outs"][cid], per_batch["outs"][cid]), f"batch {cid}"
+    W = oracle_weights(oracle, graph.feat.shape[1], 128, 10, 2)
+    for cid in (0, 37, 74):
+        bi = oracle_batch_inputs(oracle, graph, par, cid, 1500, 20, 2)
+        np.testing.assert_array_equal(got["outs"][cid].cpu().numpy(), oracle_chain(oracle, bi, W, 2, "correct", False)[-1], err_msg=f"batch {cid}")
+        assert got["outs"][cid].abs().sum().item() > 0
 
 
 @pytest.mark.parametrize("dataset,nodes_per_batch", [("ogbn-products", 2500), ("Proteins", 500)])
