@@ -571,6 +571,48 @@ int qgtc_tiledmm_f32_t_src(const int64_t *col_ptr, const int64_t *col_tile, cons
                            const float *src_scale, float *out, size_t out_elems, void *stream);
 int qgtc_tiled_inv_sqrt_degree(const int32_t *deg, int n, float *out, void *stream);
 
+/* ---- Extremum tiled products: the element-wise maximum / minimum over neighbours, and its gradient -----------------------------------
+ * The third reducer of message passing next to sum and mean (GraphSAGE-pool, PointNet-style layers, PNA). No scale turns a sum into a
+ * maximum, so these are entries of their own. Operands, numbering, alignment and limits are those of "Float tiled products": X (dY) is
+ * float32 [n, N], row-major and contiguous, rows in the adjacency's numbering; 1 <= n <= 2^23; N >= 1. `op` is 0 for max, 1 for min.
+ *
+ * Forward (qgtc_tiledmax_f32: the set cells of row r; qgtc_tiledmax_f32_t: the set cells of column r). For output row r let
+ * v_1 < v_2 < ... < v_d be its neighbours in ascending order. For every column c
+ *     d == 0:  out[r, c] = +0.0f, arg[r, c] = -1
+ *     else:    a = v_1, s = X[v_1, c]
+ *              for k = 2 .. d:  x = X[v_k, c];  if s is not NaN and (x is NaN or x > s  [min: x < s]):  s = x, a = v_k
+ *              out[r, c] = s, arg[r, c] = a
+ * out[r, c] is the word X[arg[r, c], c] bit for bit (a NaN may be any NaN): nothing is added, so nothing is rounded. The first NaN in
+ * id order wins and stays; otherwise the lowest id among those attaining the extremum wins; -0 and +0 compare equal, so the lower id
+ * wins and keeps its sign; infinities are ordinary values. arg is int32 [n, N] in the adjacency's numbering; it may be NULL, in which
+ * case it is not written. A value in X[v] reaches only the rows adjacent to v.
+ *
+ * Select, the gradient (qgtc_tiledsel_f32: the set cells of row v; qgtc_tiledsel_f32_t: the set cells of column v). For output row v
+ * let r_1 < r_2 < ... < r_d be its neighbours in ascending order. For every column c
+ *     s = +0.0f;  for k = 1 .. d:  if arg[r_k, c] == v:  s = fl32(s + dY[r_k, c])
+ *     out[v, c] = s
+ * An unselected term contributes nothing, even if it is NaN or infinite (a sum that starts at +0 is never -0, so adding +0 for it
+ * gives the same bits as skipping it). arg is data: any int32 is compared and never used as an address. The gradient of the forward
+ * on one view with respect to X is the select on the OTHER view with that forward's arg, one launch; under ties the whole gradient
+ * goes to the winner arg names. The order of the adds is the contract, as for the float products.
+ *
+ * Both are functions of their inputs alone - no atomics, the same bits on every launch and every kernel variant - and equal the NumPy
+ * model of tests/tiled_max_model.py bit for bit. Every element of out[0 .. n*N) (and of arg[0 .. n*N) in the forward, when given) is
+ * written and nothing past them; n_tiles == 0 with NULL index pointers gives +0 and -1 in the forward and +0 in the select. One launch
+ * on `stream`, no host read. Refusals, before any device work, are those of qgtc_tiledmm_f32 (_t) without a row scale, and: QGTC_EINVAL
+ * for op outside {0, 1} and for a NULL arg in the select entries; QGTC_EALIGN for arg off a 4-byte boundary; QGTC_ESIZE for
+ * arg_elems < n * N when arg is given. */
+int qgtc_tiledmax_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                      size_t x_elems, int N, int op, float *out, size_t out_elems, int32_t *arg, size_t arg_elems, void *stream);
+int qgtc_tiledmax_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                        int n, const float *X, size_t x_elems, int N, int op, float *out, size_t out_elems, int32_t *arg,
+                        size_t arg_elems, void *stream);
+int qgtc_tiledsel_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *dY,
+                      size_t dy_elems, int N, const int32_t *arg, size_t arg_elems, float *out, size_t out_elems, void *stream);
+int qgtc_tiledsel_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                        int n, const float *dY, size_t dy_elems, int N, const int32_t *arg, size_t arg_elems, float *out,
+                        size_t out_elems, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -133,13 +133,22 @@ class GCNConv(torch.nn.Module):
     trainable), under ``norm``: None the plain sum, "mean" D^-1 . A (``A.mean_scale()`` on the output row), "sym" the GCN
     normalisation D_out^-1/2 . A . D_in^-1/2 (``A.sym_scale()`` on the output row, ``A.T.sym_scale()`` on the neighbour being added;
     on a symmetric edge list, D^-1/2 . A . D^-1/2 - QGTC.add_self_loops gives the A + I of Kipf and Welling). A dense ``A`` takes
-    ``norm=None`` only."""
+    ``norm=None`` only.
 
-    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None):
+    ``aggr`` is the reducer of both aggregates: "sum" (the default, under ``norm``), or "max" / "min", the element-wise extremum over
+    the neighbours (``tiledAggregate(reduce=)``; the gradient goes to the neighbour that won). An extremum has no normalisation, so
+    "max" / "min" with a ``norm`` is a ValueError, and it needs a QGTC.TiledAdjacency."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum"):
         super().__init__()
         if norm not in (None, "mean", "sym"):
             raise ValueError(f'norm must be None, "mean" or "sym", not {norm!r}')
+        if aggr not in ("sum", "max", "min"):
+            raise ValueError(f'aggr must be "sum", "max" or "min", not {aggr!r}')
+        if aggr != "sum" and norm is not None:
+            raise ValueError(f'aggr="{aggr}" takes no norm (norm={norm!r}): an extremum is not scaled')
         self.norm = norm
+        self.aggr = aggr
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
@@ -148,11 +157,17 @@ class GCNConv(torch.nn.Module):
             return self._forward_tiled(A, X)
         if self.norm is not None:
             raise NotImplementedError(f'norm="{self.norm}" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A')
+        if self.aggr != "sum":
+            raise NotImplementedError(f'aggr="{self.aggr}" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A')
         return torch.mm(A, torch.mm(torch.mm(A, torch.mm(X, self.W_in)), self.W_out))
 
     def _forward_tiled(self, A, X):
-        """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm``; X moves to A's numbering and the result back."""
+        """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm`` / ``aggr``; X moves to A's numbering and the result
+        back."""
         assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        if self.aggr != "sum":
+            h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), reduce=self.aggr)
+            return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), reduce=self.aggr))
         row = src = None
         if self.norm == "mean":
             row = A.mean_scale()

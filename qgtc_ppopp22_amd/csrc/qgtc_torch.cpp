@@ -693,6 +693,104 @@ torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torc
     return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt);
 }
 
+// Extremum tiled products (qgtc_tiledmax_f32 / _t, qgtc_tiledsel_f32 / _t), the keyword overloads of _tiled_mm_f32 / _tiled_mm_f32_t:
+// reduce "max" / "min" gives [out] or, with return_arg, [out, arg] (int32 [n, N], the winning neighbour, -1 for a row without any);
+// reduce "select" takes that arg and X = dY and gives [the gradient]. One kernel on current_stream(X) either way.
+int tiled_reduce_code(const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg, const torch::Tensor &X) {
+    TORCH_CHECK(reduce == "max" || reduce == "min" || reduce == "select", "reduce must be \"max\", \"min\" or \"select\", not \"", reduce,
+                "\"");
+    if (reduce != "select") {
+        TORCH_CHECK(!arg.has_value(), "arg is the operand of reduce=\"select\" only");
+        return reduce == "min" ? 1 : 0;
+    }
+    TORCH_CHECK(arg.has_value(), "reduce=\"select\" needs arg");
+    TORCH_CHECK(!return_arg, "return_arg belongs to reduce=\"max\" / \"min\": the select has no winners to return");
+    const torch::Tensor &a = *arg;
+    TORCH_CHECK(a.scalar_type() == torch::kInt32 && a.sizes() == X.sizes() && a.is_contiguous(),
+                "arg must be a contiguous int32 tensor of X's shape");
+    TORCH_CHECK(a.device() == X.device(), "arg must be on the adjacency's device");
+    return 2;
+}
+
+std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                                         const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
+    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    check_float_operand(X, n, row_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    const int code = tiled_reduce_code(reduce, arg, return_arg, X);
+    c10::DeviceGuard guard(X.device());
+    const int64_t T = kquad.numel();
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    const int64_t *rp = row_ptr.data_ptr<int64_t>();
+    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    const int N = static_cast<int>(X.size(1));
+    if (code == 2) {
+        check_rc(qgtc_tiledsel_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
+                                   arg->numel(), out.data_ptr<float>(), out.numel(), current_stream(X)),
+                 "tiledMMFloat (select)");
+        return {out};
+    }
+    torch::Tensor win;
+    if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
+    check_rc(qgtc_tiledmax_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                               out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                               current_stream(X)),
+             "tiledMMFloat (max / min)");
+    if (return_arg) return {out, win};
+    return {out};
+}
+
+std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
+                                           const int64_t n, torch::Tensor X, const std::string &reduce,
+                                           const c10::optional<torch::Tensor> &arg, const bool return_arg) {
+    CHECK_INPUT(col_ptr);
+    CHECK_INPUT(col_tile);
+    CHECK_INPUT(col_rb);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
+                "col_ptr and col_tile must be int64, col_rb int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
+    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
+                "col_tile, col_rb and tiles must list the same tiles");
+    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
+                "the adjacency must be on one device");
+    check_float_operand(X, n, col_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    const int code = tiled_reduce_code(reduce, arg, return_arg, X);
+    c10::DeviceGuard guard(X.device());
+    const int64_t T = col_tile.numel();
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    const int64_t *cp = col_ptr.data_ptr<int64_t>(), *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
+    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
+    const uint32_t *tw = T ? words(tiles) : nullptr;
+    const int N = static_cast<int>(X.size(1));
+    if (code == 2) {
+        check_rc(qgtc_tiledsel_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
+                                     arg->numel(), out.data_ptr<float>(), out.numel(), current_stream(X)),
+                 "tiledMMFloat (transposed, select)");
+        return {out};
+    }
+    torch::Tensor win;
+    if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
+    check_rc(qgtc_tiledmax_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                                 out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                                 current_stream(X)),
+             "tiledMMFloat (transposed, max / min)");
+    if (return_arg) return {out, win};
+    return {out};
+}
+
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)
 torch::Tensor tiled_inv_sqrt_degree(torch::Tensor deg) {
     CHECK_INPUT(deg);
@@ -1726,6 +1824,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
           "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
           py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none());
+    // the keyword overloads: a call that names `reduce` takes them, every other call is the entry above
+    m.def("_tiled_mm_f32", &tiled_red_f32, "reduce \"max\" / \"min\": [out] or [out, arg], the element-wise extremum of X over every "
+          "row's neighbours and the neighbour that won; reduce \"select\": [the gradient], X = dY routed by arg (QGTC.tiledMMFloat(reduce=) "
+          "and QGTC.tiledAggregate's backward wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
+          py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false);
+    m.def("_tiled_mm_f32_t", &tiled_red_f32_t, "the keyword overload of _tiled_mm_f32 on the column index: the extremum over every "
+          "column's neighbours, or its select", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"),
+          py::arg("X"), py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false);
     m.def("_tiled_mm_f32_src", &tiled_mm_f32_src, "float32 [n, N] = A_tiled . diag(src_scale) . X: every neighbour's row times "
           "src_scale[neighbour] as it is added (QGTC.tiledMMFloat with src_scale wraps it)", py::arg("row_ptr"), py::arg("kquad"),
           py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"));

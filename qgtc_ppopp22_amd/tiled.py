@@ -24,6 +24,12 @@ inputs alone. With ``src_scale`` every neighbour's row is multiplied by its own 
 ``row_scale=adj.sym_scale(), src_scale=adj.T.sym_scale()`` is the GCN normalisation D^-1/2 . A . D^-1/2 in one launch.
 :func:`tiledAggregate` is the same product under ``torch.autograd``: its backward is the product on the other view with the two scales
 swapped, one launch too. :func:`add_self_loops` prepares an edge list for it.
+
+``reduce="max"`` / ``"min"`` on both functions replace the sum by the element-wise extremum over the neighbours (include/qgtc.h,
+"Extremum tiled products"): the value is a neighbour's own word, the lowest id wins a tie and the first NaN wins outright, a row
+without neighbours gives +0. ``return_arg=True`` also returns the winning neighbour of every element (int32, -1 for none), and
+:func:`tiledAggregate` routes the gradient to exactly that neighbour with one gather on the other view - no atomics, the same bits on
+every launch.
 """
 from __future__ import annotations
 
@@ -271,7 +277,7 @@ def _check_float_operand(adj: TiledAdjacency, X) -> None:
 
 
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
-                 src_scale: torch.Tensor | None = None) -> torch.Tensor:
+                 src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -282,9 +288,30 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
 
     With ``src_scale`` (float32 [n], like ``row_scale``) neighbour v's row is multiplied by src_scale[v] as it is added - one float32
     multiply, then the add, not fused -, so the result is diag(row_scale) . A . diag(src_scale) . X, bit for bit
-    ``tiledMMFloat(adj, src_scale[:, None] * X, row_scale)`` without the elementwise pass. Without it the call is the one it was."""
+    ``tiledMMFloat(adj, src_scale[:, None] * X, row_scale)`` without the elementwise pass. Without it the call is the one it was.
+
+    ``reduce="max"`` / ``"min"`` give the element-wise extremum over each row's neighbours instead of their sum (include/qgtc.h,
+    "Extremum tiled products"): out[r, c] is the word X[v, c] of the winning neighbour v, bit for bit - the first NaN in id order,
+    otherwise the lowest id among those attaining the extremum (-0 and +0 compare equal) -, and +0 for a row without neighbours.
+    ``return_arg=True`` returns ``(out, arg)`` with arg int32 [n, N], the winner in the adjacency's numbering, -1 for a row without
+    neighbours. A scale with "max" / "min", ``return_arg`` with "sum" and any other ``reduce`` are a ValueError."""
     _check(adj)
+    if reduce not in ("sum", "max", "min"):
+        raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+    if reduce == "sum":
+        if return_arg:
+            raise ValueError('return_arg needs reduce="max" or "min": a sum has no winning neighbour')
+    else:
+        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
+            if sc is not None:
+                raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
     _check_float_operand(adj, X)
+    if reduce != "sum":
+        if adj.transposed:
+            res = _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg))
+        else:
+            res = _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg))
+        return (res[0], res[1]) if return_arg else res[0]
     if row_scale is not None:
         _check_scale(adj, row_scale)
     if src_scale is not None:
@@ -295,6 +322,14 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     if adj.transposed:
         return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale)
     return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale)
+
+
+def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
+    """float32 [n, N]: row v adds, in ascending id order, dY[r] of its neighbours r where arg[r] names v (include/qgtc.h, "Extremum
+    tiled products", the select). On the other view of a max / min forward with that forward's arg it is the gradient for X."""
+    if adj.transposed:
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, dY, reduce="select", arg=arg)[0]
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, dY, reduce="select", arg=arg)[0]
 
 
 class _TiledAggregate(torch.autograd.Function):
@@ -313,15 +348,44 @@ class _TiledAggregate(torch.autograd.Function):
         return None, dX, None, None
 
 
+class _TiledExtremum(torch.autograd.Function):
+    """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
+
+    @staticmethod
+    def forward(ctx, adj, X, reduce):
+        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True)
+        ctx.adj, ctx.arg = adj, arg
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dY):
+        dX = None
+        if ctx.needs_input_grad[1]:
+            dX = _tiled_select(ctx.adj.T, dY.contiguous(), ctx.arg)
+        return None, dX, None
+
+
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
-                   src_scale: torch.Tensor | None = None) -> torch.Tensor:
+                   src_scale: torch.Tensor | None = None, reduce: str = "sum") -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
-    (``to_new`` / ``to_old`` are ``index_select`` and differentiate by themselves)."""
+    (``to_new`` / ``to_old`` are ``index_select`` and differentiate by themselves).
+
+    With ``reduce="max"`` / ``"min"`` the forward is ``tiledMMFloat(adj, X, reduce=reduce)``; it keeps the winners, and the backward
+    gives each element of dY to the neighbour that won it (under ties, all of it to the one ``arg`` names): one gather on the other
+    view, its adds in ascending id order. There is no second derivative: differentiating the backward raises. A scale with them is a
+    ValueError."""
+    if reduce not in ("sum", "max", "min"):
+        raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
+        if reduce != "sum" and sc is not None:
+            raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
             raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to X only")
+    if reduce != "sum":
+        return _TiledExtremum.apply(adj, X, reduce)
     return _TiledAggregate.apply(adj, X, row_scale, src_scale)
 
 

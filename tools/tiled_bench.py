@@ -30,12 +30,19 @@ the row scale only, (b) with both scales in one launch, (c) the route without th
 (checked bit-equal to (b) before timing), (d) forward plus backward of one tiledAggregate. Medians with their 10th and 90th
 percentiles, and the ratios (b) / (a), (b) / (c), (d) / (b).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym]
+`--leg max` measures the extremum products (QGTC.tiledMMFloat(reduce="max"), QGTC.tiledAggregate(reduce="max")) on the
+reordered graphs, both directions, N in {64, 256}, standard-normal X, launched alternately in one timed loop: (a) the float sum launch
+tiledMMFloat(a, X), the comparison at the same shape, (b) the forward max without and (c) with the winners written, (d) the select alone
+on the other view, (e) forward plus backward of one tiledAggregate(reduce="max"). Medians with their 10th and 90th percentiles, and the
+ratios (b) / (a), (c) / (a), (d) / (a), (e) / (c). The winners are checked against a gather of X before timing.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max]
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -115,8 +122,9 @@ def transposed_leg(torch, QGTC, graphs, reps):
 
 def timed_alternating(torch, fns, reps, warmup=3):
     """Several callables launched in turn inside one loop, so that drift of the clocks or of a shared machine hits them alike; the
-    order changes from round to round through every permutation, so that each follows each other equally often (a launch inherits
-    the caches its predecessor leaves). Per callable (median, 10th percentile, 90th percentile) of the per-launch event times, ms."""
+    order changes from round to round through every permutation (strided, so that few rounds still spread over all of them), so that
+    each follows each other equally often (a launch inherits the caches its predecessor leaves). Per callable (median, 10th percentile,
+    90th percentile) of the per-launch event times, ms."""
     import itertools
 
     for _ in range(warmup):
@@ -124,9 +132,12 @@ def timed_alternating(torch, fns, reps, warmup=3):
             fn()
     torch.cuda.synchronize()
     orders = list(itertools.permutations(range(len(fns))))
+    # itertools lists the permutations in lexicographic order: taken as they come, ten rounds of five callables would all start with
+    # the same two. A stride coprime to their number spreads any count of rounds over the whole list and still visits every order.
+    stride = next(k for k in range(max(1, round(len(orders) * 0.382)), 2 * len(orders) + 2) if math.gcd(k, len(orders)) == 1)
     ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in fns] for _ in range(reps)]
     for r, row in enumerate(ev):
-        for k in orders[r % len(orders)]:
+        for k in orders[r * stride % len(orders)]:
             a, b = row[k]
             a.record()
             fns[k]()
@@ -280,12 +291,61 @@ def sym_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def max_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        cells = int(adj.degrees().sum())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells} ({cells / max(1, adj.n_tiles):.1f} a tile)", flush=True)
+        xr = np.random.default_rng(1)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                out, arg = QGTC.tiledMMFloat(a, X, reduce="max", return_arg=True)
+                has = arg >= 0                     # the value is the winner's own word; rows without neighbours give +0
+                assert torch.equal(torch.where(has, X.gather(0, arg.clamp(min=0).long()), torch.zeros_like(X)).view(torch.int32),
+                                   out.view(torch.int32)), (N, direction)
+                assert torch.equal(has[:, 0], a.degrees() > 0)
+
+                def both_ways():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, reduce="max"), Xg, dY)
+
+                assert torch.equal(both_ways()[0].view(torch.int32), tiled._tiled_select(a.T, dY, arg).view(torch.int32)), (N, direction)
+                ts, tm, ta, tsel, tb = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X), lambda: QGTC.tiledMMFloat(a, X, reduce="max"),
+                                                                 lambda: QGTC.tiledMMFloat(a, X, reduce="max", return_arg=True),
+                                                                 lambda: tiled._tiled_select(a.T, dY, arg), both_ways], reps)
+                rec["agg"].append({"N": N, "direction": direction, "sum_ms": ts, "max_ms": tm, "max_arg_ms": ta, "select_ms": tsel,
+                                   "forward_backward_ms": tb, "max_over_sum": round(tm[0] / ts[0], 3),
+                                   "max_arg_over_sum": round(ta[0] / ts[0], 3), "select_over_sum": round(tsel[0] / ts[0], 3),
+                                   "fwd_bwd_over_max_arg": round(tb[0] / ta[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} sum {ts[0]:8.4f} [{ts[1]:.4f}, {ts[2]:.4f}]  max {tm[0]:8.4f} [{tm[1]:.4f}, {tm[2]:.4f}] "
+                      f"({tm[0] / ts[0]:.3f}x)  max + arg {ta[0]:8.4f} [{ta[1]:.4f}, {ta[2]:.4f}] ({ta[0] / ts[0]:.3f}x)  select on the other "
+                      f"view {tsel[0]:8.4f} [{tsel[1]:.4f}, {tsel[2]:.4f}] ({tsel[0] / ts[0]:.3f}x)  forward + backward {tb[0]:8.4f} "
+                      f"[{tb[1]:.4f}, {tb[2]:.4f}]", flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max"))
     args = ap.parse_args()
 
     import torch
@@ -293,8 +353,8 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym"):
-        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg}[args.leg]
+    if args.leg in ("transposed", "scaled", "float", "sym", "max"):
+        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
