@@ -613,6 +613,78 @@ int qgtc_tiledsel_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const i
                         int n, const float *dY, size_t dy_elems, int N, const int32_t *arg, size_t arg_elems, float *out,
                         size_t out_elems, void *stream);
 
+/* ---- Attention tiled products: the softmax-weighted sum over neighbours, and its gradients ------------------------------------------
+ * The reducer of GAT: out[o] = sum_k alpha[o, k] . X[k] with alpha the softmax, over o's neighbours, of the edge logits
+ * leaky_relu(p[o] + q[k]). A logit is a function of two per-node scalars, so no per-edge storage exists: the weight of an edge is
+ * rebuilt inside the tile walk. Operands, numbering, alignment and limits are those of "Float tiled products".
+ *
+ * Notation. A view is the row view (entries without _t: the neighbours of o are the set cells of row o) or the column view (_t: the
+ * set cells of column o); out node o has the neighbours k_1 < k_2 < ... < k_d, ascending. p and q are float32 [n], a = negative_slope
+ * is a float32 in [0, 1], X is float32 [n, N]. fl is one IEEE single operation, round to nearest even, never fused: the kernels
+ * contain no fma. L(e) = e if e > 0, else fl(a * e).
+ *
+ * Scores. p and q must be finite, except that q[k] = -inf is allowed when a > 0 and masks neighbour k (its weight is exactly 0); a row
+ * with neighbours needs one that is not masked. Outside that (NaN, +inf, a masked score with a = 0, a row whose neighbours are all
+ * masked) the values are unspecified; nothing faults and nothing is read or written out of bounds. Subnormal inputs, sums and
+ * products are outside the tested domain, as for the float products.
+ *
+ * EXP(z) for z <= 0, a fixed sequence of float32 operations (the hardware's transcendental is not used):
+ *     z < -87:  0
+ *     else      k = rint(fl(z * 1.44269504088896341f))                               (round half to even)
+ *               r = fl( fl(z - fl(k * 0.693359375f)) - fl(k * -2.12194440e-4f) )
+ *               y = 1.9875691500e-4f;  then for c in 1.3981999507e-3f, 8.3334519073e-3f, 4.1665795894e-2f, 1.6666665459e-1f,
+ *                   5.0000001201e-1f:  y = fl(fl(y * r) + c)                          (the Cephes expf polynomial, Horner)
+ *               y = fl( fl( fl(y * fl(r * r)) + r ) + 1 )
+ *               EXP = ldexp(y, k)
+ * The result is a normal number in [FLT_MIN, 1] (so ldexp is exact and adds k to the exponent field), EXP(+-0) = 1, EXP(-inf) = 0;
+ * against the real exponential the error stays below 1 ulp on [-87, 0]. No subnormal is produced or relied on.
+ *
+ * DOT(x, y) for rows of length N, the same at every N: for j = 0 .. 63: t_j = +0, then for c = j, j + 64, ... < N:
+ * t_j = fl(t_j + fl(x[c] * y[c])); then for h = 32, 16, 8, 4, 2, 1: every t_j = fl(t_j + t_(j xor h)); DOT = t_0 (all 64 are equal).
+ *
+ * Forward (qgtc_tiledatt_f32 / _t with backward = 0; att_own = p, att_nbr = q, shift = M). For each out node o
+ *     M[o]   = element [o, 0] of qgtc_tiledmax_f32 (_t) on q as an [n, 1] matrix, op 0: the caller runs that launch first. L and the
+ *              rounded add are monotone, so the largest logit of o is L(fl(p[o] + M[o])) exactly; +0 when d = 0.
+ *     m[o]   = L(fl(p[o] + M[o]))
+ *     den = +0, s[c] = +0;  for k = k_1 .. k_d:  e = fl(p[o] + q[k]);  z = fl(L(e) - m[o]) (<= 0);  w = EXP(z);
+ *                                                den = fl(den + w);  s[c] = fl(s[c] + fl(w * X[k, c]))
+ *     inv[o] = fl(1 / den) if d > 0 (the maximal neighbour has w = 1, so den >= 1), else 0
+ *     out[o, c] = fl(s[c] * inv[o])
+ * A row without neighbours gives out = +0, m = L(p[o]), inv = 0. m and inv (float32 [n]) are outputs and feed the backward.
+ *
+ * Backward. With dY, the forward's Y, m and inv, D[o] = DOT(dY[o], Y[o]) (qgtc_rowdot_f32), and per edge, recomputed with the same
+ * bits, e = fl(p[o] + q[k]), w = EXP(fl(L(e) - m[o])), alpha = fl(w * inv[o]):
+ *     dX[k, c]  on the OTHER view, over the neighbours o of k ascending: s = fl(s + fl(alpha * dY[o, c]))
+ *               (qgtc_tiledatt_f32 / _t with backward = 1: X = dY, att_own = q, att_nbr = p, shift = m, inv read, m unused)
+ *     u         = fl(alpha * fl(DOT(dY[o], X[k]) - D[o]));  if not e > 0:  u = fl(a * u)
+ *     dp[o]     the fold of u over k ascending on the forward's view
+ *               (qgtc_tiledatt_grad_f32 / _t, nbr_owns = 0: A = dY, B = X, att_own = p, att_nbr = q)
+ *     dq[k]     the fold of u over o ascending on the other view
+ *               (qgtc_tiledatt_grad_f32 / _t, nbr_owns = 1: A = X, B = dY, att_own = q, att_nbr = p; m, inv, D are the neighbour's)
+ * Every fold starts from +0 and adds one term at a time. No atomics: all results are functions of the inputs alone, the same bits on
+ * every launch and every kernel variant, and equal the NumPy model of tests/tiled_attn_model.py bit for bit.
+ *
+ * Every element of out (forward / backward: [n, N]; gradient and row dot: [n]), and of m and inv in the forward, is written and
+ * nothing past them; n_tiles == 0 with NULL index pointers is an adjacency without edges. One launch on `stream` each, no host read.
+ * Refusals, before any device work, in the order of qgtc_tiledmm_f32: QGTC_EINVAL for its cases, a missing vector (att_own, att_nbr,
+ * shift, inv, m where it is written; B, m, inv, D in the gradient), backward / nbr_owns outside {0, 1} and a slope outside [0, 1] or
+ * NaN; QGTC_EALIGN for a pointer off its boundary (4 bytes for all floats); QGTC_ESIZE for x_elems (ab_elems: A and B each) < n * N,
+ * out_elems < n * N (gradient and row dot: < n). */
+int qgtc_tiledatt_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                      size_t x_elems, int N, const float *att_own, const float *att_nbr, float negative_slope, int backward,
+                      const float *shift, float *m, float *inv, float *out, size_t out_elems, void *stream);
+int qgtc_tiledatt_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
+                        int n, const float *X, size_t x_elems, int N, const float *att_own, const float *att_nbr, float negative_slope,
+                        int backward, const float *shift, float *m, float *inv, float *out, size_t out_elems, void *stream);
+int qgtc_tiledatt_grad_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *A,
+                           const float *B, size_t ab_elems, int N, const float *att_own, const float *att_nbr, float negative_slope,
+                           int nbr_owns, const float *m, const float *inv, const float *D, float *out, size_t out_elems, void *stream);
+int qgtc_tiledatt_grad_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                             int64_t n_tiles, int n, const float *A, const float *B, size_t ab_elems, int N, const float *att_own,
+                             const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv, const float *D,
+                             float *out, size_t out_elems, void *stream);
+int qgtc_rowdot_f32(const float *A, const float *B, size_t ab_elems, int n, int N, float *out, size_t out_elems, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

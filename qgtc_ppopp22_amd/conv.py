@@ -175,3 +175,41 @@ class GCNConv(torch.nn.Module):
             row, src = A.sym_scale(), A.T.sym_scale()
         h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src)
         return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src))
+
+
+class GATConv(torch.nn.Module):
+    """One graph attention layer (Velickovic et al., 2018) on a whole graph's QGTC.TiledAdjacency: h = X . W, and per head the
+    softmax-weighted sum of the neighbours' h with the edge logits leaky_relu(a_dst . h_i + a_src . h_j)
+    (``QGTC.tiledAggregate(A, h_head, attn=(p, q))`` with p = h_head . a_dst, q = h_head . a_src: no per-edge tensor exists). The
+    heads are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged ([n, output_dim]). Trainable in W, a_dst and
+    a_src. ``A`` is the view whose rows are the receiving nodes: ``adj`` aggregates over out-neighbours, ``adj.T`` over in-neighbours;
+    on a reordered adjacency X moves to its numbering and the result back. Self loops are the edge list's business
+    (QGTC.add_self_loops). One head is one launch sequence; all heads in one launch are not built."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True):
+        super().__init__()
+        if int(heads) < 1:
+            raise ValueError(f"heads must be at least 1, not {heads!r}")
+        if not 0.0 <= float(negative_slope) <= 1.0:
+            raise ValueError(f"negative_slope must lie in [0, 1], not {negative_slope!r}")
+        self.input_dim, self.output_dim, self.heads = int(input_dim), int(output_dim), int(heads)
+        self.negative_slope, self.concat = float(negative_slope), bool(concat)
+        self.W = torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
+        self.a_dst = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
+        self.a_src = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
+
+    def forward(self, A, X):
+        if not isinstance(A, QGTC.TiledAdjacency):
+            raise NotImplementedError("GATConv needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
+        assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        h = torch.mm(A.to_new(X), self.W)
+        outs = []
+        for i in range(self.heads):
+            hi = h[:, i * self.output_dim:(i + 1) * self.output_dim].contiguous()
+            p, q = torch.mv(hi, self.a_dst[i]), torch.mv(hi, self.a_src[i])
+            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope))
+        if self.concat:
+            out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
+        else:
+            out = outs[0] if self.heads == 1 else torch.stack(outs).mean(dim=0)
+        return A.to_old(out)

@@ -791,6 +791,146 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     return {out};
 }
 
+// Attention tiled products (qgtc_tiledatt_f32 / _t, qgtc_tiledatt_grad_f32 / _t, qgtc_rowdot_f32), the `att_mode` keyword overloads of
+// _tiled_mm_f32 / _tiled_mm_f32_t: "forward" gives [out, m, inv] from shift = M (the maximum of att_nbr over the neighbours);
+// "backward" gives [dX] from X = dY, shift = m and inv; "grad_own" / "grad_nbr" give [dp] / [dq] (float32 [n]) from X = the out node's
+// rows, other = the neighbours' rows, shift = m, inv and D; "rowdot" gives [D] = DOT(X[o], other[o]). One kernel on current_stream(X).
+const float *tiled_att_vector(const c10::optional<torch::Tensor> &v, const char *name, const int64_t n, const torch::Tensor &X) {
+    TORCH_CHECK(v.has_value(), name, " is needed by this att_mode");
+    TORCH_CHECK(v->scalar_type() == torch::kFloat32 && v->numel() == n && v->is_contiguous(), name,
+                " must be a contiguous float32 tensor of n elements");
+    TORCH_CHECK(v->device() == X.device(), name, " must be on the adjacency's device");
+    return v->data_ptr<float>();
+}
+
+const float *tiled_att_other(const c10::optional<torch::Tensor> &other, const torch::Tensor &X) {
+    TORCH_CHECK(other.has_value(), "other is needed by this att_mode");
+    TORCH_CHECK(other->scalar_type() == torch::kFloat32 && other->sizes() == X.sizes() && other->is_contiguous(),
+                "other must be a contiguous float32 tensor of X's shape");
+    TORCH_CHECK(other->device() == X.device(), "other must be on the adjacency's device");
+    return other->data_ptr<float>();
+}
+
+int tiled_att_mode(const std::string &mode) {
+    const char *names[] = {"forward", "backward", "grad_own", "grad_nbr", "rowdot"};
+    for (int i = 0; i < 5; ++i)
+        if (mode == names[i]) return i;
+    TORCH_CHECK(false, "att_mode must be \"forward\", \"backward\", \"grad_own\", \"grad_nbr\" or \"rowdot\", not \"", mode, "\"");
+    return -1;
+}
+
+// idx: the index pointers of the view (row view: row_ptr, kquad, NULL; column view: col_ptr, col_tile, col_rb)
+std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, const void *i1, const void *i2, const uint32_t *tw,
+                                         const int64_t T, const int64_t n, const torch::Tensor &X, const std::string &att_mode,
+                                         const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
+                                         const double negative_slope, const c10::optional<torch::Tensor> &shift,
+                                         const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
+                                         const c10::optional<torch::Tensor> &D) {
+    const int mode = tiled_att_mode(att_mode);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    c10::DeviceGuard guard(X.device());
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(X.device());
+    const int N = static_cast<int>(X.size(1)), nn = static_cast<int>(n);
+    const float *x = X.data_ptr<float>();
+    void *st = current_stream(X);
+    if (mode == 4) {
+        auto out = torch::empty({n}, f32);
+        check_rc(qgtc_rowdot_f32(x, tiled_att_other(other, X), X.numel(), nn, N, out.data_ptr<float>(), out.numel(), st),
+                 "tiledMMFloat (row dot)");
+        return {out};
+    }
+    const float slope = static_cast<float>(negative_slope);
+    TORCH_CHECK(slope >= 0.0f && slope <= 1.0f, "negative_slope must lie in [0, 1]");
+    const float *own = tiled_att_vector(att_own, "att_own", n, X), *nbr = tiled_att_vector(att_nbr, "att_nbr", n, X);
+    const float *sh = tiled_att_vector(shift, "shift", n, X);
+    const int64_t *p0 = static_cast<const int64_t *>(i0);
+    if (mode == 0) {
+        TORCH_CHECK(!inv.has_value() && !other.has_value() && !D.has_value(), "att_mode=\"forward\" takes no inv, other or D");
+        auto out = torch::empty({n, X.size(1)}, f32), m = torch::empty({n}, f32), iv = torch::empty({n}, f32);
+        if (transposed)
+            check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
+                                         own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
+                                         out.numel(), st),
+                     "tiledMMFloat (transposed, attention)");
+        else
+            check_rc(qgtc_tiledatt_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
+                                       m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), st),
+                     "tiledMMFloat (attention)");
+        return {out, m, iv};
+    }
+    float *ivp = const_cast<float *>(tiled_att_vector(inv, "inv", n, X));   // read only in these modes
+    if (mode == 1) {
+        TORCH_CHECK(!other.has_value() && !D.has_value(), "att_mode=\"backward\" takes no other or D");
+        auto out = torch::empty({n, X.size(1)}, f32);
+        if (transposed)
+            check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
+                                         own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), st),
+                     "tiledMMFloat (transposed, attention backward)");
+        else
+            check_rc(qgtc_tiledatt_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
+                                       ivp, out.data_ptr<float>(), out.numel(), st),
+                     "tiledMMFloat (attention backward)");
+        return {out};
+    }
+    const float *b = tiled_att_other(other, X), *d = tiled_att_vector(D, "D", n, X);
+    auto out = torch::empty({n}, f32);
+    if (transposed)
+        check_rc(qgtc_tiledatt_grad_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b, X.numel(),
+                                          N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), st),
+                 "tiledMMFloat (transposed, attention score gradient)");
+    else
+        check_rc(qgtc_tiledatt_grad_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3, sh,
+                                        ivp, d, out.data_ptr<float>(), out.numel(), st),
+                 "tiledMMFloat (attention score gradient)");
+    return {out};
+}
+
+std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                                         const std::string &att_mode, const c10::optional<torch::Tensor> &att_own,
+                                         const c10::optional<torch::Tensor> &att_nbr, const double negative_slope,
+                                         const c10::optional<torch::Tensor> &shift, const c10::optional<torch::Tensor> &inv,
+                                         const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D) {
+    CHECK_INPUT(row_ptr);
+    CHECK_INPUT(kquad);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
+    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
+    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    check_float_operand(X, n, row_ptr);
+    const int64_t T = kquad.numel();
+    return tiled_att_run(false, row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, nullptr, T ? words(tiles) : nullptr, T,
+                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D);
+}
+
+std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
+                                           const int64_t n, torch::Tensor X, const std::string &att_mode,
+                                           const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
+                                           const double negative_slope, const c10::optional<torch::Tensor> &shift,
+                                           const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
+                                           const c10::optional<torch::Tensor> &D) {
+    CHECK_INPUT(col_ptr);
+    CHECK_INPUT(col_tile);
+    CHECK_INPUT(col_rb);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
+                "col_ptr and col_tile must be int64, col_rb int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
+    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
+                "col_tile, col_rb and tiles must list the same tiles");
+    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
+                "the adjacency must be on one device");
+    check_float_operand(X, n, col_ptr);
+    const int64_t T = col_tile.numel();
+    return tiled_att_run(true, col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
+                         T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, n, X, att_mode, att_own, att_nbr,
+                         negative_slope, shift, inv, other, D);
+}
+
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)
 torch::Tensor tiled_inv_sqrt_degree(torch::Tensor deg) {
     CHECK_INPUT(deg);
@@ -1832,6 +1972,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("_tiled_mm_f32_t", &tiled_red_f32_t, "the keyword overload of _tiled_mm_f32 on the column index: the extremum over every "
           "column's neighbours, or its select", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"),
           py::arg("X"), py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false);
+    m.def("_tiled_mm_f32", &tiled_att_f32, "the `att_mode` keyword overload: the softmax-weighted sum over every row's neighbours "
+          "(\"forward\": [out, m, inv]), its gradient for X on this view (\"backward\"), the score gradients (\"grad_own\", \"grad_nbr\": "
+          "float32 [n]) and the row dot (\"rowdot\") (QGTC.tiledMMFloat(attn=) and QGTC.tiledAggregate(attn=) wrap it)",
+          py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
+          py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
+          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none());
+    m.def("_tiled_mm_f32_t", &tiled_att_f32_t, "the `att_mode` keyword overload of _tiled_mm_f32 on the column index", py::arg("col_ptr"),
+          py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
+          py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
+          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none());
     m.def("_tiled_mm_f32_src", &tiled_mm_f32_src, "float32 [n, N] = A_tiled . diag(src_scale) . X: every neighbour's row times "
           "src_scale[neighbour] as it is added (QGTC.tiledMMFloat with src_scale wraps it)", py::arg("row_ptr"), py::arg("kquad"),
           py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"));

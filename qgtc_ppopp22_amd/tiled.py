@@ -30,6 +30,12 @@ swapped, one launch too. :func:`add_self_loops` prepares an edge list for it.
 without neighbours gives +0. ``return_arg=True`` also returns the winning neighbour of every element (int32, -1 for none), and
 :func:`tiledAggregate` routes the gradient to exactly that neighbour with one gather on the other view - no atomics, the same bits on
 every launch.
+
+``attn=(att_out, att_nbr)`` on both functions is the reducer of GAT (include/qgtc.h, "Attention tiled products"): every row is the
+softmax-weighted sum of its neighbours' rows, the weight of edge (o, k) being the softmax over o's neighbours of
+``leaky_relu(att_out[o] + att_nbr[k])``. No per-edge value is stored: the weight is rebuilt from the two per-node scores inside the tile
+walk, with an exponential that is a fixed sequence of float32 operations, so forward and all three gradients (X and both scores, each a
+fold in ascending id order on ``adj`` or ``adj.T``, no atomics) are specified to the bit. ``conv.GATConv`` is the layer on top.
 """
 from __future__ import annotations
 
@@ -276,8 +282,37 @@ def _check_float_operand(adj: TiledAdjacency, X) -> None:
         raise ValueError(f"X must be contiguous; its strides are {list(X.stride())}")
 
 
+def _check_slope(negative_slope) -> float:
+    slope = float(negative_slope)
+    if not 0.0 <= slope <= 1.0:   # a NaN fails both comparisons
+        raise ValueError(f"negative_slope must lie in [0, 1], not {negative_slope!r}")
+    return slope
+
+
+def _check_attn(adj: TiledAdjacency, attn) -> tuple[torch.Tensor, torch.Tensor]:
+    if not isinstance(attn, (tuple, list)) or len(attn) != 2:
+        raise TypeError("attn must be a pair (att_out, att_nbr) of float32 [n] tensors")
+    _check_scale(adj, attn[0], "att_out")
+    _check_scale(adj, attn[1], "att_nbr")
+    return attn[0], attn[1]
+
+
+def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
+    """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
+    if adj.transposed:
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, **kw)
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, **kw)
+
+
+def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float):
+    """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch."""
+    M = tiledMMFloat(adj, att_nbr.detach().unsqueeze(1), reduce="max").reshape(adj.n)
+    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M)
+
+
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
-                 src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False):
+                 src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False, attn=None,
+                 negative_slope: float = 0.2, return_stats: bool = False):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -294,10 +329,35 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     "Extremum tiled products"): out[r, c] is the word X[v, c] of the winning neighbour v, bit for bit - the first NaN in id order,
     otherwise the lowest id among those attaining the extremum (-0 and +0 compare equal) -, and +0 for a row without neighbours.
     ``return_arg=True`` returns ``(out, arg)`` with arg int32 [n, N], the winner in the adjacency's numbering, -1 for a row without
-    neighbours. A scale with "max" / "min", ``return_arg`` with "sum" and any other ``reduce`` are a ValueError."""
+    neighbours. A scale with "max" / "min", ``return_arg`` with "sum" and any other ``reduce`` are a ValueError.
+
+    ``attn=(att_out, att_nbr)`` (float32 [n] each, like a scale) gives the softmax-weighted sum of GAT instead (include/qgtc.h,
+    "Attention tiled products"): out[o] = sum over o's neighbours k, ascending, of w[o, k] . X[k], divided by the sum of the w, with
+    w[o, k] = EXP(L(att_out[o] + att_nbr[k]) - m[o]), L the leaky ReLU of ``negative_slope`` (in [0, 1]) and m[o] the row's largest
+    logit; every operation is one float32 operation in a fixed order, EXP included, so the result is the same bits on every launch.
+    att_nbr[k] = -inf masks neighbour k (slope > 0; a row needs one unmasked neighbour); a row without neighbours gives +0.
+    ``return_stats=True`` returns ``(out, m, inv)`` with inv float32 [n] the reciprocal of the weights' sum (0 without neighbours).
+    ``attn`` with a scale, with ``reduce`` other than "sum" or with ``return_arg``, ``return_stats`` without ``attn`` and a slope
+    outside [0, 1] are a ValueError. It is a max launch on the scores plus one product launch."""
     _check(adj)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+    if attn is None:
+        if return_stats:
+            raise ValueError("return_stats needs attn: only the attention product has softmax statistics")
+    else:
+        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
+            if sc is not None:
+                raise ValueError(f"{name} cannot be combined with attn")
+        if reduce != "sum":
+            raise ValueError(f'attn cannot be combined with reduce="{reduce}"')
+        if return_arg:
+            raise ValueError("return_arg cannot be combined with attn: a weighted sum has no winning neighbour")
+        slope = _check_slope(negative_slope)
+        _check_float_operand(adj, X)
+        att_out, att_nbr = _check_attn(adj, attn)
+        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope)
+        return (out, m, inv) if return_stats else out
     if reduce == "sum":
         if return_arg:
             raise ValueError('return_arg needs reduce="max" or "min": a sum has no winning neighbour')
@@ -366,8 +426,39 @@ class _TiledExtremum(torch.autograd.Function):
         return None, dX, None
 
 
+class _TiledAttention(torch.autograd.Function):
+    """Y[o] = sum_k alpha[o, k] . X[k] with alpha the softmax of L(p[o] + q[k]) over o's neighbours. With D[o] = dY[o] . Y[o]:
+    dX[k] = sum_o alpha[o, k] . dY[o] (the product on the other view, weights rebuilt from the neighbour's m and inv), and the logit
+    of edge (o, k) gets u = alpha[o, k] . (dY[o] . X[k] - D[o]) . L'(e), which dp folds over k on this view and dq over o on the other."""
+
+    @staticmethod
+    def forward(ctx, adj, X, att_out, att_nbr, slope):
+        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True)
+        ctx.adj, ctx.slope = adj, slope
+        ctx.save_for_backward(X, att_out, att_nbr, out, m, inv)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dY):
+        X, p, q, Y, m, inv = ctx.saved_tensors
+        adj, other, slope = ctx.adj, ctx.adj.T, ctx.slope
+        need_x, need_p, need_q = ctx.needs_input_grad[1:4]
+        dY = dY.contiguous()
+        dX = dp = dq = None
+        if need_x:
+            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv)[0]
+        if need_p or need_q:
+            D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
+            if need_p:
+                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D)[0]
+            if need_q:
+                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D)[0]
+        return None, dX, dp, dq, None
+
+
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
-                   src_scale: torch.Tensor | None = None, reduce: str = "sum") -> torch.Tensor:
+                   src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2) -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
@@ -376,9 +467,26 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     With ``reduce="max"`` / ``"min"`` the forward is ``tiledMMFloat(adj, X, reduce=reduce)``; it keeps the winners, and the backward
     gives each element of dY to the neighbour that won it (under ties, all of it to the one ``arg`` names): one gather on the other
     view, its adds in ascending id order. There is no second derivative: differentiating the backward raises. A scale with them is a
-    ValueError."""
+    ValueError.
+
+    With ``attn=(att_out, att_nbr)`` the forward is ``tiledMMFloat(adj, X, attn=attn, negative_slope=negative_slope)`` and the result is
+    differentiable in X, att_out and att_nbr: the gradient for X is one product launch on the other view, the two score gradients are
+    a row dot and one launch each (att_out's on this view, att_nbr's on the other); a gradient nobody needs is not launched. All of
+    them are specified to the bit (include/qgtc.h, "Attention tiled products") and there is no second derivative. ``attn`` with a
+    scale or with ``reduce`` other than "sum" is a ValueError."""
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+    if attn is not None:
+        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
+            if sc is not None:
+                raise ValueError(f"{name} cannot be combined with attn")
+        if reduce != "sum":
+            raise ValueError(f'attn cannot be combined with reduce="{reduce}"')
+        slope = _check_slope(negative_slope)
+        _check(adj)
+        _check_float_operand(adj, X)
+        att_out, att_nbr = _check_attn(adj, attn)
+        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
         if reduce != "sum" and sc is not None:
             raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')

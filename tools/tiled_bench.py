@@ -36,7 +36,15 @@ tiledMMFloat(a, X), the comparison at the same shape, (b) the forward max withou
 on the other view, (e) forward plus backward of one tiledAggregate(reduce="max"). Medians with their 10th and 90th percentiles, and the
 ratios (b) / (a), (c) / (a), (d) / (a), (e) / (c). The winners are checked against a gather of X before timing.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max]
+`--leg attn` measures the attention products (QGTC.tiledMMFloat(attn=), QGTC.tiledAggregate(attn=)) on the reordered
+graphs, both directions, N in {64, 256}, standard-normal X and scores, launched alternately in one timed loop: (a) the `sym` float launch
+tiledMMFloat(a, X, r, c), the comparison at the same shape, (b) the attention forward (the N = 1 max launch plus the product launch),
+(c) forward plus backward of tiledAggregate(attn=) for all three gradients, (d) forward plus backward of the `sym` tiledAggregate, and
+the route without the feature, a torch edge-list scatter-softmax (amax and index_add_ with atomics, an [E, N] intermediate), (e) forward
+and (f) forward plus backward; (b) is checked close to (e) before timing. Medians with their 10th and 90th percentiles, and the ratios
+(b) / (a), (c) / (d), (e) / (b), (f) / (c).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn]
 """
 from __future__ import annotations
 
@@ -340,12 +348,82 @@ def max_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def attn_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        cells = int(adj.degrees().sum())
+        # the set cells as an edge list in the adjacency's numbering (multiplicity 2 is unset, as the packer quantises it)
+        keys, counts = torch.unique(adj.rank.index_select(0, dsrc) * n + adj.rank.index_select(0, ddst), return_counts=True)
+        keys = keys[counts != 2]
+        e_row, e_col = keys // n, keys % n
+        assert int(keys.numel()) == cells
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells} ({cells / max(1, adj.n_tiles):.1f} a tile)", flush=True)
+        xr = np.random.default_rng(1)
+        p = torch.from_numpy(xr.standard_normal(n).astype(np.float32)).cuda()
+        q = torch.from_numpy(xr.standard_normal(n).astype(np.float32)).cuda()
+        pg, qg = p.clone().requires_grad_(True), q.clone().requires_grad_(True)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                r, c = a.sym_scale(), a.T.sym_scale()
+                o, k = (e_col, e_row) if a.transposed else (e_row, e_col)
+
+                def edge_list(Xe, pe, qe):
+                    e = torch.nn.functional.leaky_relu(pe[o] + qe[k], 0.2)
+                    mx = torch.full((n,), -float("inf"), device="cuda").scatter_reduce(0, o, e.detach(), "amax")
+                    w = torch.exp(e - mx[o])
+                    alpha = w / torch.zeros(n, device="cuda").index_add_(0, o, w)[o]
+                    return torch.zeros(n, N, device="cuda").index_add_(0, o, alpha[:, None] * Xe[k])
+
+                def att_both():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, attn=(pg, qg)), (Xg, pg, qg), dY)
+
+                def sym_both():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, r, c), Xg, dY)
+
+                def edge_both():
+                    return torch.autograd.grad(edge_list(Xg, pg, qg), (Xg, pg, qg), dY)
+
+                got, ref = QGTC.tiledMMFloat(a, X, attn=(p, q)), edge_list(X, p, q)
+                assert torch.allclose(got, ref, rtol=1e-4, atol=1e-5), (N, direction, float((got - ref).abs().max()))
+                for gk, ge in zip(att_both(), edge_both()):
+                    assert torch.allclose(gk, ge, rtol=1e-3, atol=1e-4), (N, direction, float((gk - ge).abs().max()))
+                ts, ta, tab, tsb, te, teb = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X, r, c),
+                                                                      lambda: QGTC.tiledMMFloat(a, X, attn=(p, q)), att_both, sym_both,
+                                                                      lambda: edge_list(X, p, q), edge_both], reps)
+                rec["agg"].append({"N": N, "direction": direction, "sym_ms": ts, "attn_ms": ta, "attn_forward_backward_ms": tab,
+                                   "sym_forward_backward_ms": tsb, "edge_list_ms": te, "edge_list_forward_backward_ms": teb,
+                                   "attn_over_sym": round(ta[0] / ts[0], 3), "attn_fwd_bwd_over_sym_fwd_bwd": round(tab[0] / tsb[0], 3),
+                                   "edge_list_over_attn": round(te[0] / ta[0], 3),
+                                   "edge_list_fwd_bwd_over_attn_fwd_bwd": round(teb[0] / tab[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} sym {ts[0]:8.4f} [{ts[1]:.4f}, {ts[2]:.4f}]  attn {ta[0]:8.4f} [{ta[1]:.4f}, {ta[2]:.4f}] "
+                      f"({ta[0] / ts[0]:.3f}x)  attn fwd + bwd {tab[0]:8.4f} [{tab[1]:.4f}, {tab[2]:.4f}]  sym fwd + bwd {tsb[0]:8.4f} "
+                      f"({tab[0] / tsb[0]:.3f}x)  edge list {te[0]:8.4f} [{te[1]:.4f}, {te[2]:.4f}] ({te[0] / ta[0]:.2f}x attn)  edge list fwd + bwd "
+                      f"{teb[0]:8.4f} [{teb[1]:.4f}, {teb[2]:.4f}] ({teb[0] / tab[0]:.2f}x attn)", flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, keys, e_row, e_col
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn"))
     args = ap.parse_args()
 
     import torch
@@ -353,8 +431,8 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max"):
-        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg}[args.leg]
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn"):
+        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
