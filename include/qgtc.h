@@ -685,6 +685,55 @@ int qgtc_tiledatt_grad_f32_t(const int64_t *col_ptr, const int64_t *col_tile, co
                              float *out, size_t out_elems, void *stream);
 int qgtc_rowdot_f32(const float *A, const float *B, size_t ab_elems, int n, int N, float *out, size_t out_elems, void *stream);
 
+/* ---- Edge dropout: a random subgraph per launch, decided inside the tile walk ------------------------------------------------------
+ * DropEdge / neighbourhood dropout for every float product above without a second adjacency: whether cell (i, j) of A survives is a
+ * pure function of (i, j, seed), rebuilt in the kernels as the tiles are decoded. i is A's row and j A's column in the adjacency's own
+ * numbering; on the transposed view the cell is still A's, so a backward on the other view sees exactly the forward's subgraph. All
+ * arithmetic is uint32 and wraps:
+ *     mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *     k0 = seed & 0xffffffff,  k1 = seed >> 32,  K = mix32(k0) + k1
+ *     R(i) = mix32(i ^ k0),  C(j) = mix32(j ^ k1) + 0x9E3779B9,  H(i, j, seed) = mix32((R(i) ^ C(j)) + K)
+ *     kept(i, j)  <=>  H(i, j, seed) >= threshold          (threshold = floor(rate * 2^32), computed in double, for a drop rate in [0, 1))
+ * qgtc_edge_kept returns kept(i, j) (1 or 0) on the host, with the functions the kernels run; it needs no device.
+ *
+ * Masking is dropping: each _drop entry returns bit for bit what its parent returns on an adjacency packed from the kept cells only
+ * (same numbering, so the folds run over the kept neighbours in ascending id order); a dropped neighbour's row is never loaded. Nothing
+ * is rescaled. A row that loses every neighbour is a row without neighbours: +0, arg = -1, inv = 0 and m as documented above.
+ * threshold 0 keeps every cell and gives the parent's bits. Each entry is its parent's signature with `threshold, seed` before `stream`
+ * and the parent's refusals in the parent's order (qgtc_tiledmm_f32_drop / _t_drop: qgtc_tiledmm_f32_src's, with both scales nullable).
+ * The selects (qgtc_tiledsel_f32 / _t) need no mask: arg names kept neighbours only. In the attention forward `shift` must be the MASKED
+ * maximum of att_nbr (qgtc_tiledmax_f32_drop / _t_drop with N = 1 and the same threshold and seed): with the unmasked one the weights'
+ * sum may fall below 1 and inv overflow. The backward and both score gradients take the forward's (threshold, seed). */
+int qgtc_edge_kept(uint32_t i, uint32_t j, uint64_t seed, uint32_t threshold);
+int qgtc_tiledmm_f32_drop(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                          size_t x_elems, int N, const float *row_scale, const float *src_scale, float *out, size_t out_elems,
+                          uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledmm_f32_t_drop(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                            int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *row_scale,
+                            const float *src_scale, float *out, size_t out_elems, uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledmax_f32_drop(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                           size_t x_elems, int N, int op, float *out, size_t out_elems, int32_t *arg, size_t arg_elems,
+                           uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledmax_f32_t_drop(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                             int64_t n_tiles, int n, const float *X, size_t x_elems, int N, int op, float *out, size_t out_elems,
+                             int32_t *arg, size_t arg_elems, uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledatt_f32_drop(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                           size_t x_elems, int N, const float *att_own, const float *att_nbr, float negative_slope, int backward,
+                           const float *shift, float *m, float *inv, float *out, size_t out_elems, uint32_t threshold, uint64_t seed,
+                           void *stream);
+int qgtc_tiledatt_f32_t_drop(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                             int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *att_own, const float *att_nbr,
+                             float negative_slope, int backward, const float *shift, float *m, float *inv, float *out, size_t out_elems,
+                             uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledatt_grad_f32_drop(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                                const float *A, const float *B, size_t ab_elems, int N, const float *att_own, const float *att_nbr,
+                                float negative_slope, int nbr_owns, const float *m, const float *inv, const float *D, float *out,
+                                size_t out_elems, uint32_t threshold, uint64_t seed, void *stream);
+int qgtc_tiledatt_grad_f32_t_drop(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                                  int64_t n_tiles, int n, const float *A, const float *B, size_t ab_elems, int N, const float *att_own,
+                                  const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
+                                  const float *D, float *out, size_t out_elems, uint32_t threshold, uint64_t seed, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -16,6 +16,19 @@ import torch
 import QGTC  # the HIP extension; there is no fallback
 
 
+def _check_drop_rate(edge_drop) -> float:
+    rate = float(edge_drop)
+    if not 0.0 <= rate < 1.0:   # a NaN fails both comparisons
+        raise ValueError(f"edge_drop must lie in [0, 1), not {edge_drop!r}")
+    return rate
+
+
+def _draw_edge_seed() -> int:
+    """64 bits from torch's CPU generator (two 32-bit draws): follows torch.manual_seed, touches no device."""
+    hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+    return (hi << 32) | lo
+
+
 class Aggregation_Qnt(torch.autograd.Function):
     """One quantised GCN layer on packed operands: requant(A · requant(X · W)).
 
@@ -137,10 +150,21 @@ class GCNConv(torch.nn.Module):
 
     ``aggr`` is the reducer of both aggregates: "sum" (the default, under ``norm``), or "max" / "min", the element-wise extremum over
     the neighbours (``tiledAggregate(reduce=)``; the gradient goes to the neighbour that won). An extremum has no normalisation, so
-    "max" / "min" with a ``norm`` is a ValueError, and it needs a QGTC.TiledAdjacency."""
+    "max" / "min" with a ``norm`` is a ValueError, and it needs a QGTC.TiledAdjacency.
 
-    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum"):
+    ``edge_drop`` (a rate in [0, 1), default 0) is DropEdge on a QGTC.TiledAdjacency: in training mode both aggregates of a forward run
+    on one random subgraph, ``tiledAggregate(..., edge_drop=(edge_drop, seed))`` with one seed per forward - ``edge_seed`` of
+    :meth:`forward` when given, otherwise 64 bits drawn from torch's CPU generator (no device synchronisation; ``torch.manual_seed``
+    makes it repeatable). With ``aggr="sum"`` only, the row scale of both aggregates is multiplied by ``keep_scale``, the float32 nearest
+    1 / (1 - edge_drop) (for ``norm=None`` the row scale is that constant vector), which keeps the aggregate unbiased with the FULL
+    graph's degrees in ``norm``; "max" / "min" rescale nothing and never read ``keep_scale``. ``edge_seed`` is checked where it is used, by ``tiledAggregate``. The mask lives in A's own numbering (``tiledMMFloat``). In eval mode
+    the layer is the one without ``edge_drop``, bit for bit."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum", edge_drop=0.0):
         super().__init__()
+        self.edge_drop = _check_drop_rate(edge_drop)
+        self.keep_scale = float(torch.tensor(1.0 / (1.0 - self.edge_drop), dtype=torch.float64).to(torch.float32))
+        self._keep_vector = None   # norm=None under the mask: keep_scale on every row, per (n, device)
         if norm not in (None, "mean", "sym"):
             raise ValueError(f'norm must be None, "mean" or "sym", not {norm!r}')
         if aggr not in ("sum", "max", "min"):
@@ -152,29 +176,45 @@ class GCNConv(torch.nn.Module):
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
-    def forward(self, A, X):
+    def forward(self, A, X, edge_seed=None):
         if isinstance(A, QGTC.TiledAdjacency):
-            return self._forward_tiled(A, X)
+            return self._forward_tiled(A, X, edge_seed)
+        if self.training and self.edge_drop > 0.0:
+            raise NotImplementedError("edge_drop needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A")
         if self.norm is not None:
             raise NotImplementedError(f'norm="{self.norm}" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A')
         if self.aggr != "sum":
             raise NotImplementedError(f'aggr="{self.aggr}" needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A')
         return torch.mm(A, torch.mm(torch.mm(A, torch.mm(X, self.W_in)), self.W_out))
 
-    def _forward_tiled(self, A, X):
+    def _keep_row_scale(self, A, row):
+        """``row`` times keep_scale (one float32 multiply an element); for norm=None the constant vector, cached."""
+        if row is not None:
+            return row * self.keep_scale
+        v = self._keep_vector
+        if v is None or v.numel() != A.n or v.device != A.device:
+            v = self._keep_vector = torch.full((A.n,), self.keep_scale, dtype=torch.float32, device=A.device)
+        return v
+
+    def _forward_tiled(self, A, X, edge_seed=None):
         """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm`` / ``aggr``; X moves to A's numbering and the result
-        back."""
+        back. In training with edge_drop > 0 both aggregates take the same (edge_drop, seed)."""
         assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        drop = None
+        if self.training and self.edge_drop > 0.0:
+            drop = (self.edge_drop, _draw_edge_seed() if edge_seed is None else edge_seed)
         if self.aggr != "sum":
-            h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), reduce=self.aggr)
-            return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), reduce=self.aggr))
+            h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), reduce=self.aggr, edge_drop=drop)
+            return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), reduce=self.aggr, edge_drop=drop))
         row = src = None
         if self.norm == "mean":
             row = A.mean_scale()
         elif self.norm == "sym":
             row, src = A.sym_scale(), A.T.sym_scale()
-        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src)
-        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src))
+        if drop is not None:
+            row = self._keep_row_scale(A, row)
+        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src, edge_drop=drop)
+        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src, edge_drop=drop))
 
 
 class GATConv(torch.nn.Module):
@@ -184,10 +224,17 @@ class GATConv(torch.nn.Module):
     heads are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged ([n, output_dim]). Trainable in W, a_dst and
     a_src. ``A`` is the view whose rows are the receiving nodes: ``adj`` aggregates over out-neighbours, ``adj.T`` over in-neighbours;
     on a reordered adjacency X moves to its numbering and the result back. Self loops are the edge list's business
-    (QGTC.add_self_loops). One head is one launch sequence; all heads in one launch are not built."""
+    (QGTC.add_self_loops). One head is one launch sequence; all heads in one launch are not built.
 
-    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True):
+    ``edge_drop`` (a rate in [0, 1), default 0) is neighbourhood dropout: in training mode every head's softmax runs over one random
+    subgraph, ``tiledAggregate(..., attn=, edge_drop=(edge_drop, seed))`` with one seed per forward for all heads - ``edge_seed`` of
+    :meth:`forward` when given, otherwise 64 bits drawn from torch's CPU generator (no device synchronisation). The softmax
+    renormalises over the kept neighbours by itself, so nothing is rescaled; a node that loses every neighbour gives +0. The mask
+    lives in A's own numbering (``tiledMMFloat``). In eval mode the layer is the one without ``edge_drop``, bit for bit."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, edge_drop=0.0):
         super().__init__()
+        self.edge_drop = _check_drop_rate(edge_drop)
         if int(heads) < 1:
             raise ValueError(f"heads must be at least 1, not {heads!r}")
         if not 0.0 <= float(negative_slope) <= 1.0:
@@ -198,16 +245,19 @@ class GATConv(torch.nn.Module):
         self.a_dst = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
         self.a_src = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
 
-    def forward(self, A, X):
+    def forward(self, A, X, edge_seed=None):
         if not isinstance(A, QGTC.TiledAdjacency):
             raise NotImplementedError("GATConv needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
         assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
         h = torch.mm(A.to_new(X), self.W)
+        drop = None
+        if self.training and self.edge_drop > 0.0:
+            drop = (self.edge_drop, _draw_edge_seed() if edge_seed is None else edge_seed)
         outs = []
         for i in range(self.heads):
             hi = h[:, i * self.output_dim:(i + 1) * self.output_dim].contiguous()
             p, q = torch.mv(hi, self.a_dst[i]), torch.mv(hi, self.a_src[i])
-            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope))
+            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope, edge_drop=drop))
         if self.concat:
             out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
         else:

@@ -26,6 +26,8 @@
 #include <cstdio>
 #include <memory>
 #include <mutex>
+#include <optional>
+#include <utility>
 #include <vector>
 
 #include "qgtc.h"
@@ -614,8 +616,13 @@ const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, cons
     return s.data_ptr<float>();
 }
 
+// Edge dropout (include/qgtc.h, "Edge dropout"): the optional keyword `edge_drop` = (threshold, seed) of the overloads below sends the
+// call to the entry's _drop twin, which keeps cell (i, j) of A when H(i, j, seed) >= threshold; None is the call there always was.
+using EdgeDrop = std::optional<std::pair<uint32_t, uint64_t>>;
+
 torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale) {
+                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
+                               const EdgeDrop &edge_drop) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -635,7 +642,11 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
     const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
-    if (src)
+    if (edge_drop)
+        check_rc(qgtc_tiledmm_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
+                                       out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
+                 "tiledMMFloat (edge dropout)");
+    else if (src)
         check_rc(qgtc_tiledmm_f32_src(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
                                       out.numel(), current_stream(X)),
                  "tiledMMFloat (source scale)");
@@ -647,13 +658,13 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
 }
 
 torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                           const c10::optional<torch::Tensor> &row_scale) {
-    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt);
+                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop) {
+    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop);
 }
 
 torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
                                  torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
-                                 const c10::optional<torch::Tensor> &src_scale) {
+                                 const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -677,7 +688,11 @@ torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, 
     const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
-    if (src)
+    if (edge_drop)
+        check_rc(qgtc_tiledmm_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
+                                         out.data_ptr<float>(), out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
+                 "tiledMMFloat (transposed, edge dropout)");
+    else if (src)
         check_rc(qgtc_tiledmm_f32_t_src(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
                                         out.data_ptr<float>(), out.numel(), current_stream(X)),
                  "tiledMMFloat (transposed, source scale)");
@@ -689,8 +704,8 @@ torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, 
 }
 
 torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale) {
-    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt);
+                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop) {
+    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop);
 }
 
 // Extremum tiled products (qgtc_tiledmax_f32 / _t, qgtc_tiledsel_f32 / _t), the keyword overloads of _tiled_mm_f32 / _tiled_mm_f32_t:
@@ -713,7 +728,8 @@ int tiled_reduce_code(const std::string &reduce, const c10::optional<torch::Tens
 }
 
 std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                                         const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg) {
+                                         const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg,
+                                         const EdgeDrop &edge_drop) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -726,6 +742,7 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
     check_float_operand(X, n, row_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
+    TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
     c10::DeviceGuard guard(X.device());
     const int64_t T = kquad.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
@@ -741,17 +758,23 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
     }
     torch::Tensor win;
     if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    check_rc(qgtc_tiledmax_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                               out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                               current_stream(X)),
-             "tiledMMFloat (max / min)");
+    if (edge_drop)
+        check_rc(qgtc_tiledmax_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                                        out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                                        edge_drop->first, edge_drop->second, current_stream(X)),
+                 "tiledMMFloat (max / min, edge dropout)");
+    else
+        check_rc(qgtc_tiledmax_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                                   out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                                   current_stream(X)),
+                 "tiledMMFloat (max / min)");
     if (return_arg) return {out, win};
     return {out};
 }
 
 std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
                                            const int64_t n, torch::Tensor X, const std::string &reduce,
-                                           const c10::optional<torch::Tensor> &arg, const bool return_arg) {
+                                           const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -768,6 +791,7 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     check_float_operand(X, n, col_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
+    TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
     c10::DeviceGuard guard(X.device());
     const int64_t T = col_tile.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
@@ -783,10 +807,16 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     }
     torch::Tensor win;
     if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    check_rc(qgtc_tiledmax_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                                 out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                                 current_stream(X)),
-             "tiledMMFloat (transposed, max / min)");
+    if (edge_drop)
+        check_rc(qgtc_tiledmax_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code,
+                                          out.data_ptr<float>(), out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr,
+                                          return_arg ? win.numel() : 0, edge_drop->first, edge_drop->second, current_stream(X)),
+                 "tiledMMFloat (transposed, max / min, edge dropout)");
+    else
+        check_rc(qgtc_tiledmax_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                                     out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                                     current_stream(X)),
+                 "tiledMMFloat (transposed, max / min)");
     if (return_arg) return {out, win};
     return {out};
 }
@@ -825,8 +855,11 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
                                          const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
                                          const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                          const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
-                                         const c10::optional<torch::Tensor> &D) {
+                                         const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop) {
     const int mode = tiled_att_mode(att_mode);
+    const bool drop = edge_drop.has_value();
+    const uint32_t dt = drop ? edge_drop->first : 0;
+    const uint64_t ds = drop ? edge_drop->second : 0;
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     c10::DeviceGuard guard(X.device());
     const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(X.device());
@@ -834,6 +867,7 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     const float *x = X.data_ptr<float>();
     void *st = current_stream(X);
     if (mode == 4) {
+        TORCH_CHECK(!drop, "att_mode=\"rowdot\" takes no edge_drop: it walks no tiles");
         auto out = torch::empty({n}, f32);
         check_rc(qgtc_rowdot_f32(x, tiled_att_other(other, X), X.numel(), nn, N, out.data_ptr<float>(), out.numel(), st),
                  "tiledMMFloat (row dot)");
@@ -847,7 +881,16 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     if (mode == 0) {
         TORCH_CHECK(!inv.has_value() && !other.has_value() && !D.has_value(), "att_mode=\"forward\" takes no inv, other or D");
         auto out = torch::empty({n, X.size(1)}, f32), m = torch::empty({n}, f32), iv = torch::empty({n}, f32);
-        if (transposed)
+        if (drop && transposed)
+            check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
+                                              N, own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
+                                              out.numel(), dt, ds, st),
+                     "tiledMMFloat (transposed, attention, edge dropout)");
+        else if (drop)
+            check_rc(qgtc_tiledatt_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
+                                            m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), dt, ds, st),
+                     "tiledMMFloat (attention, edge dropout)");
+        else if (transposed)
             check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
                                          own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
                                          out.numel(), st),
@@ -862,7 +905,15 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     if (mode == 1) {
         TORCH_CHECK(!other.has_value() && !D.has_value(), "att_mode=\"backward\" takes no other or D");
         auto out = torch::empty({n, X.size(1)}, f32);
-        if (transposed)
+        if (drop && transposed)
+            check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
+                                              N, own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), dt, ds, st),
+                     "tiledMMFloat (transposed, attention backward, edge dropout)");
+        else if (drop)
+            check_rc(qgtc_tiledatt_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
+                                            ivp, out.data_ptr<float>(), out.numel(), dt, ds, st),
+                     "tiledMMFloat (attention backward, edge dropout)");
+        else if (transposed)
             check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
                                          own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), st),
                      "tiledMMFloat (transposed, attention backward)");
@@ -874,7 +925,16 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     }
     const float *b = tiled_att_other(other, X), *d = tiled_att_vector(D, "D", n, X);
     auto out = torch::empty({n}, f32);
-    if (transposed)
+    if (drop && transposed)
+        check_rc(qgtc_tiledatt_grad_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b,
+                                               X.numel(), N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), dt,
+                                               ds, st),
+                 "tiledMMFloat (transposed, attention score gradient, edge dropout)");
+    else if (drop)
+        check_rc(qgtc_tiledatt_grad_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3,
+                                             sh, ivp, d, out.data_ptr<float>(), out.numel(), dt, ds, st),
+                 "tiledMMFloat (attention score gradient, edge dropout)");
+    else if (transposed)
         check_rc(qgtc_tiledatt_grad_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b, X.numel(),
                                           N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), st),
                  "tiledMMFloat (transposed, attention score gradient)");
@@ -889,7 +949,8 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
                                          const std::string &att_mode, const c10::optional<torch::Tensor> &att_own,
                                          const c10::optional<torch::Tensor> &att_nbr, const double negative_slope,
                                          const c10::optional<torch::Tensor> &shift, const c10::optional<torch::Tensor> &inv,
-                                         const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D) {
+                                         const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D,
+                                         const EdgeDrop &edge_drop) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -902,7 +963,7 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
     check_float_operand(X, n, row_ptr);
     const int64_t T = kquad.numel();
     return tiled_att_run(false, row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, nullptr, T ? words(tiles) : nullptr, T,
-                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D);
+                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop);
 }
 
 std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
@@ -910,7 +971,7 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
                                            const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
                                            const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                            const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
-                                           const c10::optional<torch::Tensor> &D) {
+                                           const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -928,7 +989,7 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
     const int64_t T = col_tile.numel();
     return tiled_att_run(true, col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
                          T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, n, X, att_mode, att_own, att_nbr,
-                         negative_slope, shift, inv, other, D);
+                         negative_slope, shift, inv, other, D, edge_drop);
 }
 
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)
@@ -1960,34 +2021,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("to_float"), py::arg("row_scale") = py::none());
     m.def("_tiled_mm_f32", &tiled_mm_f32, "float32 [n, N] = A_tiled . X for a float32 X [n, N], neighbours added in ascending id order "
           "(QGTC.tiledMMFloat wraps it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::arg("row_scale") = py::none());
+          py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
           "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
-          py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none());
+          py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none());
     // the keyword overloads: a call that names `reduce` takes them, every other call is the entry above
     m.def("_tiled_mm_f32", &tiled_red_f32, "reduce \"max\" / \"min\": [out] or [out, arg], the element-wise extremum of X over every "
           "row's neighbours and the neighbour that won; reduce \"select\": [the gradient], X = dY routed by arg (QGTC.tiledMMFloat(reduce=) "
           "and QGTC.tiledAggregate's backward wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false);
+          py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false,
+          py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_red_f32_t, "the keyword overload of _tiled_mm_f32 on the column index: the extremum over every "
           "column's neighbours, or its select", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"),
-          py::arg("X"), py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false);
+          py::arg("X"), py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false,
+          py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32", &tiled_att_f32, "the `att_mode` keyword overload: the softmax-weighted sum over every row's neighbours "
           "(\"forward\": [out, m, inv]), its gradient for X on this view (\"backward\"), the score gradients (\"grad_own\", \"grad_nbr\": "
           "float32 [n]) and the row dot (\"rowdot\") (QGTC.tiledMMFloat(attn=) and QGTC.tiledAggregate(attn=) wrap it)",
           py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
           py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
-          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none());
+          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none(),
+          py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_att_f32_t, "the `att_mode` keyword overload of _tiled_mm_f32 on the column index", py::arg("col_ptr"),
           py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
           py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
-          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none());
+          py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none(),
+          py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32_src", &tiled_mm_f32_src, "float32 [n, N] = A_tiled . diag(src_scale) . X: every neighbour's row times "
           "src_scale[neighbour] as it is added (QGTC.tiledMMFloat with src_scale wraps it)", py::arg("row_ptr"), py::arg("kquad"),
-          py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"));
+          py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none());
     m.def("_tiled_mm_f32_t_src", &tiled_mm_f32_t_src, "float32 [n, N] = A_tiled^T . diag(src_scale) . X (QGTC.tiledMMFloat on adj.T with "
           "src_scale wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::arg("row_scale"), py::arg("src_scale"));
+          py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none());
     m.def("_tiled_inv_sqrt_degree", &tiled_inv_sqrt_degree, "float32 [n] = 1 / sqrt(deg), correctly rounded, 0 where deg is 0 "
           "(TiledAdjacency.sym_scale wraps it)", py::arg("deg"));
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");

@@ -105,14 +105,17 @@ __device__ __forceinline__ void tiled_att_add_rows(float (&s)[CPL], float &den, 
     }
 }
 
-template <int LPR, int CPL, bool BWD>
+// (the trailing pack of every decoder and kernel below is empty, and they are the ones that existed, or holds the edge-dropout mask of
+// tiled_drop.hip.h: a neighbour it drops is never queued)
+template <int LPR, int CPL, bool BWD, class... Drop>
 __device__ __forceinline__ void tiled_att_decode(uint32_t m, int base, int n, float (&s)[CPL], float &den, int *list, int &cnt,
-                                                 const float *__restrict__ X, int N, int c0, const TiledAtt &att, float po, float mo) {
+                                                 const float *__restrict__ X, int N, int c0, const TiledAtt &att, float po, float mo,
+                                                 Drop... drop) {
     while (m) {
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
         const int v = base + b;
-        if (v < n) {
+        if (v < n && tiled_drop_kept(v, drop...)) {
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
                 tiled_att_add_rows<LPR, CPL, BWD>(s, den, list, cnt, X, N, c0, att, po, mo);
@@ -134,11 +137,11 @@ __device__ __forceinline__ float tiled_att_shift(float po, float M, float slope)
 //   forward (BWD false)  out[o] = fl(s * inv[o]) with inv[o] = fl(1 / den), 0 for a row without neighbours; the first column chunk
 //                        also stores m[o] and inv[o];
 //   backward (BWD true)  out[k] = s, the weights normalised per term by the neighbour's own statistics.
-template <int LPR, int CPL, bool BWD>
+template <int LPR, int CPL, bool BWD, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_att_f32(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                        const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                        const float *__restrict__ X, int N, TiledAtt att, float *__restrict__ m_out,
-                                                       float *__restrict__ inv_out, float *__restrict__ out) {
+                                                       float *__restrict__ inv_out, float *__restrict__ out, Drop... drop) {
     constexpr int G = 256 / LPR, RPG = 32 / G;
     __shared__ int lists[G][RPG][TILED_F32_CAP];
     const int rb = blockIdx.x, tid = threadIdx.x;
@@ -184,7 +187,7 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32(const int64_t *__restrict
             tiled_static_for<RPG>([&](auto ri) {
                 tiled_static_for<4>([&](auto k) {
                     tiled_att_decode<LPR, CPL, BWD>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], den[ri], lists[g][ri],
-                                                    cnt[ri], X, N, c0, att, po[ri], mo[ri]);
+                                                    cnt[ri], X, N, c0, att, po[ri], mo[ri], tiled_drop_for(row0 + ri, drop)...);
                 });
             });
         }
@@ -273,15 +276,16 @@ __device__ __forceinline__ void tiled_att_grad_rows(float &acc, const float (&a)
     }
 }
 
-template <bool REG, bool NBR_OWNS>
+template <bool REG, bool NBR_OWNS, class... Drop>
 __device__ __forceinline__ void tiled_att_grad_decode(uint32_t m, int base, int n, float &acc, const float (&a)[4],
                                                       const float *__restrict__ Arow, int *list, int &cnt, const float *__restrict__ B,
-                                                      int N, int l, const TiledAtt &att, float po, float mo, float io, float Do) {
+                                                      int N, int l, const TiledAtt &att, float po, float mo, float io, float Do,
+                                                      Drop... drop) {
     while (m) {
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
         const int v = base + b;
-        if (v < n) {
+        if (v < n && tiled_drop_kept(v, drop...)) {
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
                 tiled_att_grad_rows<REG, NBR_OWNS>(acc, a, Arow, list, cnt, B, N, l, att, po, mo, io, Do);
@@ -294,11 +298,11 @@ __device__ __forceinline__ void tiled_att_grad_decode(uint32_t m, int base, int 
 // The row view: k_tiled_mm_f32's workgroup at 64 lanes a row - a wave owns 8 rows of the block and is whole on each of them, lane j on
 // the columns j + 64 cc. out is float32 [n]: out[o] = the fold of u over o's neighbours. A is the matrix of the out node's rows, B the
 // neighbours' (dp: dY and X; dq: X and dY - the products are commutative, so DOT is the same word).
-template <bool REG, bool NBR_OWNS>
+template <bool REG, bool NBR_OWNS, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_att_grad(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                         const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                         const float *__restrict__ A, const float *__restrict__ B, int N, TiledAtt att,
-                                                        float *__restrict__ out) {
+                                                        float *__restrict__ out, Drop... drop) {
     constexpr int RPG = 8;
     __shared__ int lists[4][RPG][TILED_F32_CAP];
     const int rb = blockIdx.x, tid = threadIdx.x;
@@ -349,7 +353,7 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad(const int64_t *__restric
                 tiled_static_for<4>([&](auto k) {
                     tiled_att_grad_decode<REG, NBR_OWNS>(tiled_f32_bcast<64>(w[k], ri), q * 128 + k * 32, n, acc[ri], own[ri],
                                                          A + static_cast<uint64_t>(row) * N, lists[g][ri], cnt[ri], B, N, l, att,
-                                                         po[ri], mo[ri], io[ri], Do[ri]);
+                                                         po[ri], mo[ri], io[ri], Do[ri], tiled_drop_for(row, drop)...);
                 });
             });
         }

@@ -55,12 +55,12 @@ struct TiledAttStager {
     }
 };
 
-template <int CPL, bool BWD>
+template <int CPL, bool BWD, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_att_f32_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                          const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                          uint64_t n_tiles, int n, const float *__restrict__ X, int N, TiledAtt att,
                                                          float *__restrict__ m_out, float *__restrict__ inv_out,
-                                                         float *__restrict__ out) {
+                                                         float *__restrict__ out, Drop... drop) {
     constexpr int LPR = 16, G = 256 / LPR, TS = TILED_T_TS;
     static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
     constexpr int W = LPR * CPL;   // output columns per workgroup
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32_t(const int64_t *__restri
             int cnt = 0;
 #pragma unroll
             for (int st = 0; st < TS; ++st)
-                if (m[st]) tiled_att_decode<LPR, CPL, BWD>(m[st], srb[st] * 32, n, s, den, list, cnt, X, N, c0, att, po, mo);
+                if (m[st]) tiled_att_decode<LPR, CPL, BWD>(m[st], srb[st] * 32, n, s, den, list, cnt, X, N, c0, att, po, mo, tiled_drop_for(self, drop)...);
             tiled_att_add_rows<LPR, CPL, BWD>(s, den, list, cnt, X, N, c0, att, po, mo);
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = s[cc];
@@ -141,11 +141,12 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32_t(const int64_t *__restri
 
 // the score gradient on the column view: tiled_att_grad_rows with a wave per output row, the running sum of every row in LDS between
 // rounds (written and read by lane 0 of the row's wave; every lane of the wave computes the same word)
-template <bool REG, bool NBR_OWNS>
+template <bool REG, bool NBR_OWNS, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_att_grad_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                           const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                           uint64_t n_tiles, int n, const float *__restrict__ A,
-                                                          const float *__restrict__ B, int N, TiledAtt att, float *__restrict__ out) {
+                                                          const float *__restrict__ B, int N, TiledAtt att, float *__restrict__ out,
+                                                          Drop... drop) {
     constexpr int G = 4, TS = TILED_T_TS;
     static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
     __shared__ __attribute__((aligned(16))) uint32_t mk[128 * TS];   // [tile column][staged tile]
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad_t(const int64_t *__restr
             int cnt = 0;
 #pragma unroll
             for (int st = 0; st < TS; ++st)
-                if (m[st]) tiled_att_grad_decode<REG, NBR_OWNS>(m[st], srb[st] * 32, n, s, own, Arow, list, cnt, B, N, l, att, po, mo, io, Do);
+                if (m[st]) tiled_att_grad_decode<REG, NBR_OWNS>(m[st], srb[st] * 32, n, s, own, Arow, list, cnt, B, N, l, att, po, mo, io, Do, tiled_drop_for(self, drop)...);
             tiled_att_grad_rows<REG, NBR_OWNS>(s, own, Arow, list, cnt, B, N, l, att, po, mo, io, Do);
             if (l == 0) acc[j] = s;
         }

@@ -11,15 +11,19 @@
 //
 // Every template below ends in a pack `Src...`: empty, it is the code that existed before the source scale (same arguments, the same
 // instructions); with one `const float *` (src_scale, n floats) a neighbour's value is multiplied by src_scale[neighbour] before it is
-// added - one IEEE multiply, then one IEEE add, never fused.
+// added - one IEEE multiply, then one IEEE add, never fused. The pack may END in the edge-dropout mask
+// (tiled_drop.hip.h): a neighbour the mask drops is never queued, so its row is never loaded.
 #pragma once
+
+#include "tiled_drop.hip.h"
 
 namespace {
 
 constexpr int TILED_F32_CAP = 32;   // decoded neighbour ids a row group queues in LDS before it adds their rows
 constexpr int TILED_F32_AHEAD = 4;  // rows of X whose loads are in flight before the first of them is added
 
-inline __device__ const float *tiled_f32_src(const float *src_scale) { return src_scale; }
+template <class... Mask>
+inline __device__ const float *tiled_f32_src(const float *src_scale, const Mask &...) { return src_scale; }
 
 // fl32(s + fl32(w * x)): two roundings. hipcc contracts a * b + c into one fma by default (and __fmul_rn is a plain `*` here), so the
 // pair is written under `fp contract(off)`.
@@ -38,6 +42,8 @@ __device__ __forceinline__ float tiled_f32_mul_add(float s, float w, float x) {
 template <int LPR, int CPL, class... Src>
 __device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *list, int cnt, const float *__restrict__ X, int N, int c0,
                                                    Src... src) {
+    // kept a loop: the optimizer unrolled it in some masked instantiations, which held 8 rounds of loads live (160 - 186 VGPRs)
+#pragma nounroll
     for (int j = 0; j < cnt; j += TILED_F32_AHEAD) {
         float x[TILED_F32_AHEAD][CPL];
         [[maybe_unused]] float w[TILED_F32_AHEAD];
@@ -47,14 +53,14 @@ __device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *l
             const float *__restrict__ row = X + static_cast<uint64_t>(v) * N;
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) x[u][cc] = c0 + cc * LPR < N ? row[c0 + cc * LPR] : 0.0f;
-            if constexpr (sizeof...(Src) != 0) w[u] = tiled_f32_src(src...)[v];
+            if constexpr (tiled_pack_operands<Src...>() != 0) w[u] = tiled_f32_src(src...)[v];
         }
 #pragma unroll
         for (int u = 0; u < TILED_F32_AHEAD; ++u)
             if (j + u < cnt) {
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) {
-                    if constexpr (sizeof...(Src) != 0) s[cc] = tiled_f32_mul_add(s[cc], w[u], x[u][cc]);
+                    if constexpr (tiled_pack_operands<Src...>() != 0) s[cc] = tiled_f32_mul_add(s[cc], w[u], x[u][cc]);
                     else s[cc] += x[u][cc];
                 }
             }
@@ -62,7 +68,8 @@ __device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *l
 }
 
 // the set bits of `m`, MSB first, as neighbour ids base + (leading zeros), queued in `list`; ids from n up are dropped (the format keeps
-// such cells zero; a foreign tile must not make the kernel read past X). A full queue is added at once.
+// such cells zero; a foreign tile must not make the kernel read past X), and so are the ids a mask in the pack drops. A full queue is
+// added at once.
 template <int LPR, int CPL, class... Src>
 __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, float (&s)[CPL], int *list, int &cnt,
                                                  const float *__restrict__ X, int N, int c0, Src... src) {
@@ -70,7 +77,7 @@ __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, fl
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
         const int v = base + b;
-        if (v < n) {
+        if (v < n && tiled_drop_kept(v, src...)) {
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
                 tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
-                                               src...);
+                                               tiled_drop_for(rb * 32 + g * RPG + ri, src)...);
         }
         a = an;
         q = qn;

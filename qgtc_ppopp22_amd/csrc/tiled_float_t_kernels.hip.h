@@ -14,7 +14,8 @@
 //              that order and puts the sums back. The sums of the 128 x LPR * CPL outputs live in LDS between rounds because a row
 //              is touched in few rounds and the row index is a loop variable; each word is read and written by one lane only.
 // The rows are stored once at the end; SCALED multiplies by row_scale[row] first (one IEEE single multiply). The trailing pack `Src...`
-// is tiled_float_kernels.hip.h's: empty, the kernel that existed; with src_scale, the shared adder scales every term by its source row.
+// is tiled_float_kernels.hip.h's: empty, the kernel that existed; with src_scale, the shared adder scales every term by its source row;
+// ending in the edge-dropout mask of this view (TiledDropView<true>), a dropped source row is never queued.
 #pragma once
 
 namespace {
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
             int cnt = 0;
 #pragma unroll
             for (int st = 0; st < TS; ++st)
-                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0, src...);
+                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0, tiled_drop_for(q * 128 + j, src)...);
             tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = s[cc];

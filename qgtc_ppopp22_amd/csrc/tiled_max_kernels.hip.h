@@ -111,15 +111,16 @@ struct TiledSelect {
 };
 
 // tiled_f32_decode with a reducer: the set bits of `m`, MSB first, as neighbour ids base + (leading zeros), queued in `list`; ids from n
-// up are dropped, so nothing is read past the operands. A full queue is folded at once.
-template <int LPR, int CPL, class Red>
+// up are dropped, so nothing is read past the operands, and so are the ids the edge-dropout mask drops when the trailing pack holds one
+// (tiled_drop.hip.h; empty, this is the decoder that existed). A full queue is folded at once.
+template <int LPR, int CPL, class Red, class... Drop>
 __device__ __forceinline__ void tiled_red_decode(uint32_t m, int base, int n, TiledRedState<CPL> &st, int self, int *list, int &cnt,
-                                                 const Red &red, int N, int c0) {
+                                                 const Red &red, int N, int c0, Drop... drop) {
     while (m) {
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
         const int v = base + b;
-        if (v < n) {
+        if (v < n && tiled_drop_kept(v, drop...)) {
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
                 red.template rows<LPR, CPL>(st, self, list, cnt, N, c0);
@@ -132,9 +133,10 @@ __device__ __forceinline__ void tiled_red_decode(uint32_t m, int base, int n, Ti
 // ---- the row view: out[r] = reduce over the set cells of row r ----------------------------------------------------------------------
 // k_tiled_mm_f32's workgroup: one per 32-row block and chunk of LPR * CPL output columns, a row group of LPR lanes on RPG rows, the
 // block's tiles walked once in k-quad order with the next tile's words loaded while this one is decoded.
-template <int LPR, int CPL, class Red>
+template <int LPR, int CPL, class Red, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_red_f32(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
-                                                       const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n, int N, Red red) {
+                                                       const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n, int N, Red red,
+                                                       Drop... drop) {
     constexpr int G = 256 / LPR, RPG = 32 / G;
     __shared__ int lists[G][RPG][TILED_F32_CAP];
     const int rb = blockIdx.x, tid = threadIdx.x;
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32(const int64_t *__restrict
             tiled_static_for<RPG>([&](auto ri) {
                 tiled_static_for<4>([&](auto k) {
                     tiled_red_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, st[ri], row0 + ri, lists[g][ri],
-                                               cnt[ri], red, N, c0);
+                                               cnt[ri], red, N, c0, tiled_drop_for(row0 + ri, drop)...);
                 });
             });
         }

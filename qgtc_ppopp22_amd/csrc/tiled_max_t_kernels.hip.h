@@ -13,10 +13,10 @@
 
 namespace {
 
-template <int LPR, int CPL, class Red>
+template <int LPR, int CPL, class Red, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_red_f32_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                          const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
-                                                         uint64_t n_tiles, int n, int N, Red red) {
+                                                         uint64_t n_tiles, int n, int N, Red red, Drop... drop) {
     constexpr int G = 256 / LPR, TS = TILED_T_TS;
     static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
     constexpr int W = LPR * CPL;   // output columns per workgroup
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32_t(const int64_t *__restri
             int cnt = 0;
 #pragma unroll
             for (int t = 0; t < TS; ++t)
-                if (m[t]) tiled_red_decode<LPR, CPL>(m[t], srb[t] * 32, n, st, self, list, cnt, red, N, c0);
+                if (m[t]) tiled_red_decode<LPR, CPL>(m[t], srb[t] * 32, n, st, self, list, cnt, red, N, c0, tiled_drop_for(self, drop)...);
             red.template rows<LPR, CPL>(st, self, list, cnt, N, c0);
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) {

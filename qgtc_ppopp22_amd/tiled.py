@@ -36,8 +36,15 @@ softmax-weighted sum of its neighbours' rows, the weight of edge (o, k) being th
 ``leaky_relu(att_out[o] + att_nbr[k])``. No per-edge value is stored: the weight is rebuilt from the two per-node scores inside the tile
 walk, with an exponential that is a fixed sequence of float32 operations, so forward and all three gradients (X and both scores, each a
 fold in ascending id order on ``adj`` or ``adj.T``, no atomics) are specified to the bit. ``conv.GATConv`` is the layer on top.
+
+``edge_drop=(rate, seed)`` on both functions, in every mode, aggregates over a random subgraph instead (include/qgtc.h, "Edge dropout"):
+cell (i, j) of the adjacency survives when a fixed 32-bit hash of (i, j, seed) is at least ``floor(rate * 2^32)``, decided inside the tile
+walk on either view, so nothing per edge is stored, no second adjacency is packed and the backward on the other view sees exactly the
+forward's subgraph. The result is bit for bit that of the same call on an adjacency packed from the kept edges.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -297,6 +304,32 @@ def _check_attn(adj: TiledAdjacency, attn) -> tuple[torch.Tensor, torch.Tensor]:
     return attn[0], attn[1]
 
 
+def _edge_drop_key(edge_drop):
+    """None, or (threshold, seed) of include/qgtc.h, "Edge dropout", from ``edge_drop=(rate, seed)``: threshold = floor(rate * 2^32)
+    computed in double. A non-pair or a seed that is no int is a TypeError; a rate outside [0, 1) or NaN and a seed outside [0, 2^64)
+    are a ValueError."""
+    if edge_drop is None:
+        return None
+    if not isinstance(edge_drop, (tuple, list)) or len(edge_drop) != 2:
+        raise TypeError("edge_drop must be a pair (rate, seed) or None")
+    rate, seed = edge_drop
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)):
+        raise TypeError(f"edge_drop's rate must be a float in [0, 1), not {type(rate).__name__}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"edge_drop's seed must be an int in [0, 2^64), not {type(seed).__name__}")
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:   # a NaN fails both comparisons
+        raise ValueError(f"edge_drop's rate must lie in [0, 1), not {rate!r}")
+    if not 0 <= seed < (1 << 64):
+        raise ValueError(f"edge_drop's seed must lie in [0, 2^64), not {seed!r}")
+    return int(math.floor(rate * 4294967296.0)), seed
+
+
+def _drop_kw(key) -> dict:
+    """The binding's keyword for a checked key; without a mask no keyword at all, which is the call the binding always took."""
+    return {} if key is None else {"edge_drop": key}
+
+
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
     if adj.transposed:
@@ -304,15 +337,25 @@ def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, **kw)
 
 
-def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float):
-    """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch."""
-    M = tiledMMFloat(adj, att_nbr.detach().unsqueeze(1), reduce="max").reshape(adj.n)
-    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M)
+def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, key=None):
+    """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch. Under a mask
+    (``key``, checked) both launches take it: M must be the maximum over the KEPT neighbours, or the weights' sum could fall below 1."""
+    M = _tiled_extremum(adj, att_nbr.detach().unsqueeze(1), "max", False, key)[0].reshape(adj.n)
+    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M,
+                **_drop_kw(key))
+
+
+def _tiled_extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_arg: bool, key=None):
+    """[out] or [out, arg] of the max / min launch on this view, under the mask ``key`` (checked) when there is one."""
+    if adj.transposed:
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg),
+                                    **_drop_kw(key))
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg), **_drop_kw(key))
 
 
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                  src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False, attn=None,
-                 negative_slope: float = 0.2, return_stats: bool = False):
+                 negative_slope: float = 0.2, return_stats: bool = False, edge_drop=None):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -338,8 +381,19 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     att_nbr[k] = -inf masks neighbour k (slope > 0; a row needs one unmasked neighbour); a row without neighbours gives +0.
     ``return_stats=True`` returns ``(out, m, inv)`` with inv float32 [n] the reciprocal of the weights' sum (0 without neighbours).
     ``attn`` with a scale, with ``reduce`` other than "sum" or with ``return_arg``, ``return_stats`` without ``attn`` and a slope
-    outside [0, 1] are a ValueError. It is a max launch on the scores plus one product launch."""
+    outside [0, 1] are a ValueError. It is a max launch on the scores plus one product launch.
+
+    ``edge_drop=(rate, seed)`` (rate a float in [0, 1), seed an int in [0, 2^64)), in every mode above, aggregates over a random subgraph
+    (include/qgtc.h, "Edge dropout"): cell (i, j) of the adjacency - row i, column j, on ``adj.T`` still the cell of ``adj`` - is kept when
+    the 32-bit hash H(i, j, seed) is at least floor(rate * 2^32), and the result is bit for bit the same call on
+    ``pack_edges_tiled`` of the kept edges: the folds run over the kept neighbours in ascending id order, a dropped neighbour's row is
+    never loaded, nothing is rescaled, and a row that loses every neighbour is a row without neighbours (+0, arg -1, inv 0). Rate 0
+    gives the plain call's bits. The mask is in the ADJACENCY'S OWN numbering: on a reordered adjacency i and j are the new ids, so the
+    same seed masks other edges of the original graph than it would without the reordering. The seed is a kernel argument: a captured
+    graph replays ONE mask (recapture, or draw the subgraph outside the graph, for a fresh one per step). A rate outside [0, 1) or NaN
+    and a seed outside [0, 2^64) are a ValueError, anything but a pair (or a seed that is no int) a TypeError."""
     _check(adj)
+    key = _edge_drop_key(edge_drop)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if attn is None:
@@ -356,7 +410,7 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
         slope = _check_slope(negative_slope)
         _check_float_operand(adj, X)
         att_out, att_nbr = _check_attn(adj, attn)
-        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope)
+        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope, key)
         return (out, m, inv) if return_stats else out
     if reduce == "sum":
         if return_arg:
@@ -367,21 +421,18 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
                 raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
     _check_float_operand(adj, X)
     if reduce != "sum":
-        if adj.transposed:
-            res = _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg))
-        else:
-            res = _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg))
+        res = _tiled_extremum(adj, X, reduce, return_arg, key)
         return (res[0], res[1]) if return_arg else res[0]
     if row_scale is not None:
         _check_scale(adj, row_scale)
     if src_scale is not None:
         _check_scale(adj, src_scale, "src_scale")
         if adj.transposed:
-            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale)
-        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale)
+            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key))
+        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key))
     if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale)
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale)
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, **_drop_kw(key))
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, **_drop_kw(key))
 
 
 def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
@@ -396,25 +447,25 @@ class _TiledAggregate(torch.autograd.Function):
     """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped."""
 
     @staticmethod
-    def forward(ctx, adj, X, row_scale, src_scale):
-        ctx.adj, ctx.row_scale, ctx.src_scale = adj, row_scale, src_scale
-        return tiledMMFloat(adj, X, row_scale, src_scale)
+    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None):
+        ctx.adj, ctx.row_scale, ctx.src_scale, ctx.edge_drop = adj, row_scale, src_scale, edge_drop
+        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop)
 
     @staticmethod
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
-            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale)
-        return None, dX, None, None
+            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale, edge_drop=ctx.edge_drop)
+        return None, dX, None, None, None
 
 
 class _TiledExtremum(torch.autograd.Function):
     """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
 
     @staticmethod
-    def forward(ctx, adj, X, reduce):
-        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True)
-        ctx.adj, ctx.arg = adj, arg
+    def forward(ctx, adj, X, reduce, edge_drop=None):
+        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop)
+        ctx.adj, ctx.arg = adj, arg   # the select needs no mask: arg names kept neighbours only
         return out
 
     @staticmethod
@@ -423,7 +474,7 @@ class _TiledExtremum(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[1]:
             dX = _tiled_select(ctx.adj.T, dY.contiguous(), ctx.arg)
-        return None, dX, None
+        return None, dX, None, None
 
 
 class _TiledAttention(torch.autograd.Function):
@@ -432,9 +483,9 @@ class _TiledAttention(torch.autograd.Function):
     of edge (o, k) gets u = alpha[o, k] . (dY[o] . X[k] - D[o]) . L'(e), which dp folds over k on this view and dq over o on the other."""
 
     @staticmethod
-    def forward(ctx, adj, X, att_out, att_nbr, slope):
-        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True)
-        ctx.adj, ctx.slope = adj, slope
+    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None):
+        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop)
+        ctx.adj, ctx.slope, ctx.drop_kw = adj, slope, _drop_kw(_edge_drop_key(edge_drop))
         ctx.save_for_backward(X, att_out, att_nbr, out, m, inv)
         return out
 
@@ -444,21 +495,22 @@ class _TiledAttention(torch.autograd.Function):
         X, p, q, Y, m, inv = ctx.saved_tensors
         adj, other, slope = ctx.adj, ctx.adj.T, ctx.slope
         need_x, need_p, need_q = ctx.needs_input_grad[1:4]
-        dY = dY.contiguous()
+        dY, kw = dY.contiguous(), ctx.drop_kw   # every gradient walks the forward's subgraph
         dX = dp = dq = None
         if need_x:
-            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv)[0]
+            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw)[0]
         if need_p or need_q:
             D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
             if need_p:
-                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D)[0]
+                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D, **kw)[0]
             if need_q:
-                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D)[0]
-        return None, dX, dp, dq, None
+                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw)[0]
+        return None, dX, dp, dq, None, None
 
 
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
-                   src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2) -> torch.Tensor:
+                   src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2,
+                   edge_drop=None) -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
@@ -473,7 +525,13 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     differentiable in X, att_out and att_nbr: the gradient for X is one product launch on the other view, the two score gradients are
     a row dot and one launch each (att_out's on this view, att_nbr's on the other); a gradient nobody needs is not launched. All of
     them are specified to the bit (include/qgtc.h, "Attention tiled products") and there is no second derivative. ``attn`` with a
-    scale or with ``reduce`` other than "sum" is a ValueError."""
+    scale or with ``reduce`` other than "sum" is a ValueError.
+
+    With ``edge_drop=(rate, seed)`` (as in :func:`tiledMMFloat`, every mode) the forward runs on the random subgraph and every backward
+    launch gets the same pair on the other view, where the mask is rebuilt from the same cells of the adjacency: the gradients are those
+    of the unmasked call on ``pack_edges_tiled`` of the kept edges, bit for bit. The mask is in the adjacency's own numbering (the new
+    ids on a reordered adjacency), and a captured graph replays one mask, because the seed is a kernel argument."""
+    _edge_drop_key(edge_drop)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if attn is not None:
@@ -486,15 +544,15 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
         _check(adj)
         _check_float_operand(adj, X)
         att_out, att_nbr = _check_attn(adj, attn)
-        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope)
+        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope, edge_drop)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
         if reduce != "sum" and sc is not None:
             raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
             raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to X only")
     if reduce != "sum":
-        return _TiledExtremum.apply(adj, X, reduce)
-    return _TiledAggregate.apply(adj, X, row_scale, src_scale)
+        return _TiledExtremum.apply(adj, X, reduce, edge_drop)
+    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop)
 
 
 def add_self_loops(src: torch.Tensor, dst: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:

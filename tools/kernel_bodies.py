@@ -1,0 +1,44 @@
+"""Hashes of the device code of translation units, kernel by kernel, with the names left out: two checkouts have the same kernels when
+the sorted hashes of a unit are equal (a template pack added to a kernel changes its mangled name and nothing else). Built objects are
+read from qgtc_ppopp22_amd/build/ (run build() first); gfx950 code objects are unbundled with the ROCm LLVM tools.
+
+    python tools/kernel_bodies.py qgtc_tiled_float qgtc_tiled_max ... > bodies.txt     # in each checkout, then diff the two files
+"""
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = "/opt/rocm/llvm/bin"
+
+
+def bodies(unit):
+    obj = os.path.join(ROOT, "qgtc_ppopp22_amd", "build", unit + ".hip.o")
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fatbin"), os.path.join(d, "co")
+        subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                        f"--input={fat}", f"--output={co}"], check=True)
+        text = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co], capture_output=True, text=True,
+                              check=True).stdout
+    out, cur, name = [], [], None
+    for line in text.splitlines():
+        m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", line)
+        if m:
+            if name:
+                out.append(hashlib.md5("\n".join(cur).encode()).hexdigest())
+            name, cur = m.group(1), []
+        elif name:
+            cur.append(re.sub(r"//.*$", "", re.sub(r"<[^>]*>", "", line)).strip())
+    if name:
+        out.append(hashlib.md5("\n".join(cur).encode()).hexdigest())
+    return sorted(out)
+
+
+if __name__ == "__main__":
+    for unit in sys.argv[1:]:
+        for h in bodies(unit):
+            print(unit, h)

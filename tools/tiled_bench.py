@@ -44,7 +44,16 @@ the route without the feature, a torch edge-list scatter-softmax (amax and index
 and (f) forward plus backward; (b) is checked close to (e) before timing. Medians with their 10th and 90th percentiles, and the ratios
 (b) / (a), (c) / (d), (e) / (b), (f) / (c).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn]
+`--leg drop` measures edge dropout inside the tile walk (``edge_drop=`` of QGTC.tiledMMFloat / QGTC.tiledAggregate) on the
+reordered graphs, both directions, N in {64, 256}, standard-normal X and scores, in two alternating loops. First: (a) the plain sum
+launch tiledMMFloat(a, X), (b) the masked launch at rates 0.1 and 0.5, (c) the route it replaces at rate 0.1 - filter the edge list with
+a random mask (`torch.rand`: the same rate, not the same cells as the masked launch, which does not matter for a time), pack_edges_tiled,
+(on adj.T: build the column index,) plain launch. Second, (d): forward plus backward of tiledAggregate
+for the sum with `sym` scales, max and attention, each without the mask and with it at rate 0.1. The masked sum is checked bit-equal to
+the plain launch on the adjacency packed from the kept cells before timing. Medians with their 10th and 90th percentiles, and the ratios
+(b) / (a), (b) / (c) and masked / plain of (d).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop]
 """
 from __future__ import annotations
 
@@ -418,12 +427,99 @@ def attn_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def drop_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    def mix32(x):   # include/qgtc.h, "Edge dropout", on int64 tensors kept below 2^32
+        x = x ^ (x >> 16)
+        x = (x * 0x7FEB352D) & 0xFFFFFFFF
+        x = x ^ (x >> 15)
+        x = (x * 0x846CA68B) & 0xFFFFFFFF
+        return x ^ (x >> 16)
+
+    def kept_cells(i, j, seed, rate):
+        """bool tensor: the cells (i, j) the mask keeps, for the check before timing"""
+        k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+        K = (int(mix32(torch.tensor(k0))) + k1) & 0xFFFFFFFF
+        R, C = mix32(i ^ k0), (mix32(j ^ k1) + 0x9E3779B9) & 0xFFFFFFFF
+        return mix32(((R ^ C) + K) & 0xFFFFFFFF) >= int(math.floor(rate * 4294967296.0))
+
+    rows = []
+    seed = 0x0123456789ABCDEF
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        cells = int(adj.degrees().sum())
+        # the set cells as an edge list in the adjacency's numbering (multiplicity 2 is unset, as the packer quantises it)
+        keys, counts = torch.unique(adj.rank.index_select(0, dsrc) * n + adj.rank.index_select(0, ddst), return_counts=True)
+        keys = keys[counts != 2]
+        e_row, e_col = (keys // n).contiguous(), (keys % n).contiguous()
+        assert int(keys.numel()) == cells
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells} ({cells / max(1, adj.n_tiles):.1f} a tile)", flush=True)
+        kept = {}
+        for rate in (0.1, 0.5):
+            k = kept_cells(e_row, e_col, seed, rate)
+            kept[rate] = QGTC.pack_edges_tiled(e_row[k], e_col[k], n, False)
+            rec[f"kept_fraction_{rate}"] = round(float(k.float().mean()), 4)
+        xr = np.random.default_rng(1)
+        p = torch.from_numpy(xr.standard_normal(n).astype(np.float32)).cuda()
+        q = torch.from_numpy(xr.standard_normal(n).astype(np.float32)).cuda()
+        pg, qg = p.clone().requires_grad_(True), q.clone().requires_grad_(True)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                for rate in (0.1, 0.5):
+                    ka = kept[rate].T if a.transposed else kept[rate]
+                    assert torch.equal(QGTC.tiledMMFloat(a, X, edge_drop=(rate, seed)).view(torch.int32),
+                                       QGTC.tiledMMFloat(ka, X).view(torch.int32)), (N, direction, rate)
+
+                def repack():
+                    k = torch.rand(e_row.numel(), device="cuda") >= 0.1
+                    sub = QGTC.pack_edges_tiled(e_row[k], e_col[k], n, False)
+                    return QGTC.tiledMMFloat(sub.T if a.transposed else sub, X)
+
+                ta, tb1, tb5, tc = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X),
+                                                             lambda: QGTC.tiledMMFloat(a, X, edge_drop=(0.1, seed)),
+                                                             lambda: QGTC.tiledMMFloat(a, X, edge_drop=(0.5, seed)), repack], reps)
+                r, c = a.sym_scale(), a.T.sym_scale()
+
+                def both(**kw):
+                    return lambda: torch.autograd.grad(QGTC.tiledAggregate(a, Xg, **kw), [Xg] + ([pg, qg] if "attn" in kw else []), dY)
+
+                drop = (0.1, seed)
+                ds, dsm, dx, dxm, da, dam = timed_alternating(torch, [both(row_scale=r, src_scale=c), both(row_scale=r, src_scale=c, edge_drop=drop),
+                                                                      both(reduce="max"), both(reduce="max", edge_drop=drop),
+                                                                      both(attn=(pg, qg)), both(attn=(pg, qg), edge_drop=drop)], reps)
+                rec["agg"].append({"N": N, "direction": direction, "plain_ms": ta, "masked_0.1_ms": tb1, "masked_0.5_ms": tb5,
+                                   "filter_repack_plain_ms": tc, "masked_0.1_over_plain": round(tb1[0] / ta[0], 3),
+                                   "masked_0.5_over_plain": round(tb5[0] / ta[0], 3), "masked_0.1_over_repack": round(tb1[0] / tc[0], 3),
+                                   "sym_fwd_bwd_ms": ds, "sym_fwd_bwd_masked_ms": dsm, "max_fwd_bwd_ms": dx, "max_fwd_bwd_masked_ms": dxm,
+                                   "attn_fwd_bwd_ms": da, "attn_fwd_bwd_masked_ms": dam, "sym_masked_over_plain": round(dsm[0] / ds[0], 3),
+                                   "max_masked_over_plain": round(dxm[0] / dx[0], 3), "attn_masked_over_plain": round(dam[0] / da[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} plain {ta[0]:8.4f} [{ta[1]:.4f}, {ta[2]:.4f}]  masked 0.1 {tb1[0]:8.4f} [{tb1[1]:.4f}, "
+                      f"{tb1[2]:.4f}] ({tb1[0] / ta[0]:.3f}x)  masked 0.5 {tb5[0]:8.4f} [{tb5[1]:.4f}, {tb5[2]:.4f}] ({tb5[0] / ta[0]:.3f}x)  filter + "
+                      f"pack + plain {tc[0]:8.4f} [{tc[1]:.4f}, {tc[2]:.4f}] (masked 0.1 / it {tb1[0] / tc[0]:.3f})  fwd + bwd plain / masked 0.1: "
+                      f"sym {ds[0]:.4f} / {dsm[0]:.4f}  max {dx[0]:.4f} / {dxm[0]:.4f}  attn {da[0]:.4f} / {dam[0]:.4f}", flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, keys, e_row, e_col, kept
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop"))
     args = ap.parse_args()
 
     import torch
@@ -431,8 +527,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn"):
-        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg}[args.leg]
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop"):
+        leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
+               "drop": drop_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
