@@ -734,6 +734,69 @@ int qgtc_tiledatt_grad_f32_t_drop(const int64_t *col_ptr, const int64_t *col_til
                                   const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
                                   const float *D, float *out, size_t out_elems, uint32_t threshold, uint64_t seed, void *stream);
 
+/* ---- Node masks: induced subgraphs on the whole-graph adjacency, without re-packing ------------------------------------------------------
+ * A node set is a BITMAP of int32 words [S128(n) * 4] in the bit order of a tile row: node i at word i >> 5, bit 31 - (i & 31). The
+ * length is a whole number of k-quads, so the four words beside a tile are one 16-byte aligned read; the bitmap is in the adjacency's
+ * own numbering. qgtc_node_bitmap builds it on the device from byte flags [n] (non-zero = member; one thread a word, plain stores,
+ * deterministic), with the bits at positions >= n and the pad words zero. The kernels ignore such bits anyway: their v < n / row < n
+ * guards stay. QGTC_EINVAL for a NULL pointer or n outside 1 .. 2^23, QGTC_EALIGN for words off a 16-byte boundary, QGTC_ESIZE for
+ * words_len < S128(n) * 4.
+ *
+ * On a view (the _t entries: A^T) the _nodes entries take row_mask and nbr_mask, each a bitmap or NULL = all nodes, relative to the
+ * view like row_scale / src_scale:
+ *   - output row o is computed iff o is in row_mask; otherwise it holds exactly what a row without neighbours holds: +0 in every
+ *     column (times row_scale[o], as that row would), arg -1, and the attention statistics of a neighbourless row;
+ *   - neighbour k of a computed row takes part iff k is in nbr_mask; a neighbour outside it is never queued and its row of X (and its
+ *     src_scale) is never loaded.
+ * Everything else - ascending-id order, one IEEE add per term, the unfused source scale, the tie and NaN rules of max / min - is unchanged, so the result is bit for bit the
+ * unmasked entry on an adjacency packed from the edges whose output-row end lies in row_mask and whose neighbour end lies in nbr_mask.
+ * The backward of Y = mask(A) . X on the other view takes the two masks swapped (as it takes the two scales swapped). All-ones masks, or
+ * two NULLs, give the plain entry's bits. A workgroup none of whose output rows is in row_mask reads no index and no tile.
+ * Each entry is its _drop twin's signature with (row_mask, nbr_mask, mask_words) in place of (threshold, seed), and its refusals in its
+ * order; then QGTC_ESIZE for a mask with mask_words < S128(n) * 4 and QGTC_EALIGN for a mask off a 16-byte boundary, all before any
+ * device work. Degrees of the masked graph need no entry: they are the masked N = 1 product of a column of ones (exact: n <= 2^23).
+ * The extremum: a row outside row_mask holds +0 and arg -1; the selects (qgtc_tiledsel_f32 / _t) need no mask, because arg names
+ * participating neighbours only. The attention product: a row outside row_mask holds +0, inv = 0 and m as a row without neighbours;
+ * EXP and the softmax run over the participating neighbours, so in the forward `shift` must be the MASKED maximum of att_nbr
+ * (qgtc_tiledmax_f32_nodes / _t_nodes with N = 1 and the same masks). grad_own runs on the forward's view with the forward's masks; the
+ * backward product and grad_nbr run on the other view with the two masks swapped.
+ *
+ * qgtc_tiled_inv_degree: out[i] = 1.0f / (float)deg[i] correctly rounded, 0.0f where deg[i] is 0 - the reciprocal pass of
+ * qgtc_tiled_degrees on its own (the same kernel), for the degrees of a masked graph. Refusals as qgtc_tiled_inv_sqrt_degree's. */
+int qgtc_tiled_inv_degree(const int32_t *deg, int n, float *out, void *stream);
+int qgtc_node_bitmap(const uint8_t *flags, int n, uint32_t *words, size_t words_len, void *stream);
+int qgtc_tiledmm_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                           size_t x_elems, int N, const float *row_scale, const float *src_scale, float *out, size_t out_elems,
+                           const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream);
+int qgtc_tiledmm_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                             int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *row_scale,
+                             const float *src_scale, float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask,
+                             size_t mask_words, void *stream);
+int qgtc_tiledmax_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                            size_t x_elems, int N, int op, float *out, size_t out_elems, int32_t *arg, size_t arg_elems,
+                            const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream);
+int qgtc_tiledmax_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                              int64_t n_tiles, int n, const float *X, size_t x_elems, int N, int op, float *out, size_t out_elems,
+                              int32_t *arg, size_t arg_elems, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words,
+                              void *stream);
+int qgtc_tiledatt_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                            size_t x_elems, int N, const float *att_own, const float *att_nbr, float negative_slope, int backward,
+                            const float *shift, float *m, float *inv, float *out, size_t out_elems, const uint32_t *row_mask,
+                            const uint32_t *nbr_mask, size_t mask_words, void *stream);
+int qgtc_tiledatt_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                              int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *att_own, const float *att_nbr,
+                              float negative_slope, int backward, const float *shift, float *m, float *inv, float *out, size_t out_elems,
+                              const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream);
+int qgtc_tiledatt_grad_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                                 const float *A, const float *B, size_t ab_elems, int N, const float *att_own, const float *att_nbr,
+                                 float negative_slope, int nbr_owns, const float *m, const float *inv, const float *D, float *out,
+                                 size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream);
+int qgtc_tiledatt_grad_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                                   int64_t n_tiles, int n, const float *A, const float *B, size_t ab_elems, int N, const float *att_own,
+                                   const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
+                                   const float *D, float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask,
+                                   size_t mask_words, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -23,6 +23,17 @@ def _check_drop_rate(edge_drop) -> float:
     return rate
 
 
+def _node_mask(A, nodes) -> torch.Tensor:
+    """The bitmap of ``nodes`` (bool [n], in X's numbering) in A's numbering (tiled.node_bitmap)."""
+    if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.bool:
+        raise TypeError("nodes must be a bool tensor [n] in X's numbering")
+    if nodes.dim() != 1 or nodes.numel() != A.n:
+        raise ValueError(f"nodes must have shape [{A.n}], not {list(nodes.shape)}")
+    from .tiled import node_bitmap
+
+    return node_bitmap(A.to_new(nodes), A.n)
+
+
 def _draw_edge_seed() -> int:
     """64 bits from torch's CPU generator (two 32-bit draws): follows torch.manual_seed, touches no device."""
     hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
@@ -158,7 +169,14 @@ class GCNConv(torch.nn.Module):
     makes it repeatable). With ``aggr="sum"`` only, the row scale of both aggregates is multiplied by ``keep_scale``, the float32 nearest
     1 / (1 - edge_drop) (for ``norm=None`` the row scale is that constant vector), which keeps the aggregate unbiased with the FULL
     graph's degrees in ``norm``; "max" / "min" rescale nothing and never read ``keep_scale``. ``edge_seed`` is checked where it is used, by ``tiledAggregate``. The mask lives in A's own numbering (``tiledMMFloat``). In eval mode
-    the layer is the one without ``edge_drop``, bit for bit."""
+    the layer is the one without ``edge_drop``, bit for bit.
+
+    ``nodes`` of :meth:`forward` (a bool [n] tensor in X's numbering) runs the layer pair on the INDUCED subgraph of those nodes, as a
+    Cluster-GCN batch does, on the whole graph's QGTC.TiledAdjacency and without packing anything: both aggregates take
+    ``row_mask = nbr_mask = tiled.node_bitmap(A.to_new(nodes), n)`` and ``norm`` takes the induced degrees (``A.mean_scale(row_mask=,
+    nbr_mask=)`` / ``sym_scale``). Rows outside ``nodes`` come back +0; the result is bit for bit the same layer on
+    ``pack_edges_tiled`` of the edges between the nodes. With an active ``edge_drop`` (training mode, rate > 0) or a dense ``A`` it is
+    a NotImplementedError."""
 
     def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum", edge_drop=0.0):
         super().__init__()
@@ -176,9 +194,11 @@ class GCNConv(torch.nn.Module):
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
-    def forward(self, A, X, edge_seed=None):
+    def forward(self, A, X, edge_seed=None, nodes=None):
         if isinstance(A, QGTC.TiledAdjacency):
-            return self._forward_tiled(A, X, edge_seed)
+            return self._forward_tiled(A, X, edge_seed, nodes)
+        if nodes is not None:
+            raise NotImplementedError("nodes needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A")
         if self.training and self.edge_drop > 0.0:
             raise NotImplementedError("edge_drop needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A")
         if self.norm is not None:
@@ -196,25 +216,32 @@ class GCNConv(torch.nn.Module):
             v = self._keep_vector = torch.full((A.n,), self.keep_scale, dtype=torch.float32, device=A.device)
         return v
 
-    def _forward_tiled(self, A, X, edge_seed=None):
+    def _forward_tiled(self, A, X, edge_seed=None, nodes=None):
         """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm`` / ``aggr``; X moves to A's numbering and the result
-        back. In training with edge_drop > 0 both aggregates take the same (edge_drop, seed)."""
+        back. In training with edge_drop > 0 both aggregates take the same (edge_drop, seed). With ``nodes`` both aggregates run on
+        the induced subgraph (one bitmap as row and neighbour mask) and ``norm`` takes its degrees."""
         assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
         drop = None
         if self.training and self.edge_drop > 0.0:
             drop = (self.edge_drop, _draw_edge_seed() if edge_seed is None else edge_seed)
+        mask = {}
+        if nodes is not None:
+            if drop is not None:
+                raise NotImplementedError("nodes cannot be combined with an active edge_drop: not built")
+            bm = _node_mask(A, nodes)
+            mask = {"row_mask": bm, "nbr_mask": bm}
         if self.aggr != "sum":
-            h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), reduce=self.aggr, edge_drop=drop)
-            return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), reduce=self.aggr, edge_drop=drop))
+            h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), reduce=self.aggr, edge_drop=drop, **mask)
+            return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), reduce=self.aggr, edge_drop=drop, **mask))
         row = src = None
         if self.norm == "mean":
-            row = A.mean_scale()
+            row = A.mean_scale(**mask)
         elif self.norm == "sym":
-            row, src = A.sym_scale(), A.T.sym_scale()
+            row, src = A.sym_scale(**mask), A.T.sym_scale(**mask)
         if drop is not None:
             row = self._keep_row_scale(A, row)
-        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src, edge_drop=drop)
-        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src, edge_drop=drop))
+        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), row, src, edge_drop=drop, **mask)
+        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), row, src, edge_drop=drop, **mask))
 
 
 class GATConv(torch.nn.Module):
@@ -230,7 +257,11 @@ class GATConv(torch.nn.Module):
     subgraph, ``tiledAggregate(..., attn=, edge_drop=(edge_drop, seed))`` with one seed per forward for all heads - ``edge_seed`` of
     :meth:`forward` when given, otherwise 64 bits drawn from torch's CPU generator (no device synchronisation). The softmax
     renormalises over the kept neighbours by itself, so nothing is rescaled; a node that loses every neighbour gives +0. The mask
-    lives in A's own numbering (``tiledMMFloat``). In eval mode the layer is the one without ``edge_drop``, bit for bit."""
+    lives in A's own numbering (``tiledMMFloat``). In eval mode the layer is the one without ``edge_drop``, bit for bit.
+
+    ``nodes`` of :meth:`forward` (a bool [n] tensor in X's numbering) runs every head on the induced subgraph of those nodes
+    (``row_mask = nbr_mask``, as in :class:`GCNConv`): rows outside come back +0, and the result is bit for bit the layer on
+    ``pack_edges_tiled`` of the edges between the nodes. With an active ``edge_drop`` it is a NotImplementedError."""
 
     def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, edge_drop=0.0):
         super().__init__()
@@ -245,7 +276,7 @@ class GATConv(torch.nn.Module):
         self.a_dst = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
         self.a_src = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
 
-    def forward(self, A, X, edge_seed=None):
+    def forward(self, A, X, edge_seed=None, nodes=None):
         if not isinstance(A, QGTC.TiledAdjacency):
             raise NotImplementedError("GATConv needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
         assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
@@ -253,11 +284,17 @@ class GATConv(torch.nn.Module):
         drop = None
         if self.training and self.edge_drop > 0.0:
             drop = (self.edge_drop, _draw_edge_seed() if edge_seed is None else edge_seed)
+        mask = {}
+        if nodes is not None:
+            if drop is not None:
+                raise NotImplementedError("nodes cannot be combined with an active edge_drop: not built")
+            bm = _node_mask(A, nodes)
+            mask = {"row_mask": bm, "nbr_mask": bm}
         outs = []
         for i in range(self.heads):
             hi = h[:, i * self.output_dim:(i + 1) * self.output_dim].contiguous()
             p, q = torch.mv(hi, self.a_dst[i]), torch.mv(hi, self.a_src[i])
-            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope, edge_drop=drop))
+            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope, edge_drop=drop, **mask))
         if self.concat:
             out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
         else:

@@ -102,3 +102,13 @@ int qgtc_tiled_inv_sqrt_degree(const int32_t *deg, int n, float *out, void *stre
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
+
+// the reciprocal pass of qgtc_tiled_degrees alone (k_tiled_inv_degree on one pair), for degrees that did not come from that entry
+int qgtc_tiled_inv_degree(const int32_t *deg, int n, float *out, void *stream) {
+    if (!deg || !out || n < 1 || n > TILED_MAX_N) return QGTC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(deg) | reinterpret_cast<uintptr_t>(out)) & 3u) return QGTC_EALIGN;
+    hipLaunchKernelGGL(k_tiled_inv_degree, dim3(degree_grid(static_cast<uint64_t>(n))), dim3(256), 0, static_cast<hipStream_t>(stream), deg,
+                       out, static_cast<const int32_t *>(nullptr), static_cast<float *>(nullptr), n);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}

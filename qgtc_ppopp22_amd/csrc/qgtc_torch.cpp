@@ -620,9 +620,23 @@ const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, cons
 // call to the entry's _drop twin, which keeps cell (i, j) of A when H(i, j, seed) >= threshold; None is the call there always was.
 using EdgeDrop = std::optional<std::pair<uint32_t, uint64_t>>;
 
+// Node masks (include/qgtc.h, "Node masks"): the optional keyword `node_masks` = (row_mask, nbr_mask) of the sum overloads below sends
+// the call to the entry's _nodes twin; each is an int32 bitmap of S128(n) * 4 words (tiled.node_bitmap) or None = all nodes. None, the
+// default, is the call there always was.
+using NodeMasks = std::optional<std::pair<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>>;
+
+const uint32_t *tiled_node_mask(const c10::optional<torch::Tensor> &mask, const int64_t n, const torch::Tensor &X, const char *name) {
+    if (!mask.has_value()) return nullptr;
+    const torch::Tensor &m = *mask;
+    TORCH_CHECK(m.scalar_type() == torch::kInt32 && m.dim() == 1 && m.numel() == (n + 127) / 128 * 4 && m.is_contiguous(), name,
+                " must be a contiguous int32 bitmap of S128(n) * 4 words (tiled.node_bitmap)");
+    TORCH_CHECK(m.device() == X.device(), name, " must be on the adjacency's device");
+    return words(m);
+}
+
 torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
                                const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
-                               const EdgeDrop &edge_drop) {
+                               const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -642,7 +656,14 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
     const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
-    if (edge_drop)
+    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
+    if (node_masks)
+        check_rc(qgtc_tiledmm_f32_nodes(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
+                                        out.numel(), tiled_node_mask(node_masks->first, n, X, "row_mask"),
+                                        tiled_node_mask(node_masks->second, n, X, "nbr_mask"), static_cast<size_t>((n + 127) / 128 * 4),
+                                        current_stream(X)),
+                 "tiledMMFloat (node masks)");
+    else if (edge_drop)
         check_rc(qgtc_tiledmm_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
                                        out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
                  "tiledMMFloat (edge dropout)");
@@ -658,13 +679,13 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
 }
 
 torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop) {
-    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop);
+                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
 }
 
 torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
                                  torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
-                                 const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop) {
+                                 const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -688,7 +709,14 @@ torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, 
     const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
     const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
-    if (edge_drop)
+    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
+    if (node_masks)
+        check_rc(qgtc_tiledmm_f32_t_nodes(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
+                                          out.data_ptr<float>(), out.numel(), tiled_node_mask(node_masks->first, n, X, "row_mask"),
+                                          tiled_node_mask(node_masks->second, n, X, "nbr_mask"),
+                                          static_cast<size_t>((n + 127) / 128 * 4), current_stream(X)),
+                 "tiledMMFloat (transposed, node masks)");
+    else if (edge_drop)
         check_rc(qgtc_tiledmm_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
                                          out.data_ptr<float>(), out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
                  "tiledMMFloat (transposed, edge dropout)");
@@ -704,8 +732,9 @@ torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, 
 }
 
 torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop) {
-    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop);
+                             torch::Tensor X, const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop,
+                             const NodeMasks &node_masks) {
+    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
 }
 
 // Extremum tiled products (qgtc_tiledmax_f32 / _t, qgtc_tiledsel_f32 / _t), the keyword overloads of _tiled_mm_f32 / _tiled_mm_f32_t:
@@ -729,7 +758,7 @@ int tiled_reduce_code(const std::string &reduce, const c10::optional<torch::Tens
 
 std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
                                          const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg,
-                                         const EdgeDrop &edge_drop) {
+                                         const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -743,6 +772,9 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
     TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
+    TORCH_CHECK(code != 2 || !node_masks, "reduce=\"select\" takes no node_masks: arg names participating neighbours only");
+    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
+    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
     c10::DeviceGuard guard(X.device());
     const int64_t T = kquad.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
@@ -758,7 +790,13 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
     }
     torch::Tensor win;
     if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    if (edge_drop)
+    if (node_masks)
+        check_rc(qgtc_tiledmax_f32_nodes(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
+                                         out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
+                                         tiled_node_mask(node_masks->first, n, X, "row_mask"),
+                                         tiled_node_mask(node_masks->second, n, X, "nbr_mask"), mask_words, current_stream(X)),
+                 "tiledMMFloat (max / min, node masks)");
+    else if (edge_drop)
         check_rc(qgtc_tiledmax_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
                                         out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
                                         edge_drop->first, edge_drop->second, current_stream(X)),
@@ -774,7 +812,8 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
 
 std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
                                            const int64_t n, torch::Tensor X, const std::string &reduce,
-                                           const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop) {
+                                           const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop,
+                                           const NodeMasks &node_masks) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -792,6 +831,9 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
     TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
+    TORCH_CHECK(code != 2 || !node_masks, "reduce=\"select\" takes no node_masks: arg names participating neighbours only");
+    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
+    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
     c10::DeviceGuard guard(X.device());
     const int64_t T = col_tile.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
@@ -807,7 +849,13 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     }
     torch::Tensor win;
     if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    if (edge_drop)
+    if (node_masks)
+        check_rc(qgtc_tiledmax_f32_t_nodes(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code,
+                                           out.data_ptr<float>(), out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr,
+                                           return_arg ? win.numel() : 0, tiled_node_mask(node_masks->first, n, X, "row_mask"),
+                                           tiled_node_mask(node_masks->second, n, X, "nbr_mask"), mask_words, current_stream(X)),
+                 "tiledMMFloat (transposed, max / min, node masks)");
+    else if (edge_drop)
         check_rc(qgtc_tiledmax_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code,
                                           out.data_ptr<float>(), out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr,
                                           return_arg ? win.numel() : 0, edge_drop->first, edge_drop->second, current_stream(X)),
@@ -855,9 +903,13 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
                                          const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
                                          const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                          const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
-                                         const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop) {
+                                         const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     const int mode = tiled_att_mode(att_mode);
-    const bool drop = edge_drop.has_value();
+    const bool drop = edge_drop.has_value(), nodes = node_masks.has_value();
+    TORCH_CHECK(!(drop && nodes), "node_masks cannot be combined with edge_drop: not built");
+    const uint32_t *rmask = nodes ? tiled_node_mask(node_masks->first, n, X, "row_mask") : nullptr;
+    const uint32_t *nmask = nodes ? tiled_node_mask(node_masks->second, n, X, "nbr_mask") : nullptr;
+    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
     const uint32_t dt = drop ? edge_drop->first : 0;
     const uint64_t ds = drop ? edge_drop->second : 0;
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
@@ -867,7 +919,7 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     const float *x = X.data_ptr<float>();
     void *st = current_stream(X);
     if (mode == 4) {
-        TORCH_CHECK(!drop, "att_mode=\"rowdot\" takes no edge_drop: it walks no tiles");
+        TORCH_CHECK(!drop && !nodes, "att_mode=\"rowdot\" takes no edge_drop or node_masks: it walks no tiles");
         auto out = torch::empty({n}, f32);
         check_rc(qgtc_rowdot_f32(x, tiled_att_other(other, X), X.numel(), nn, N, out.data_ptr<float>(), out.numel(), st),
                  "tiledMMFloat (row dot)");
@@ -881,7 +933,17 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     if (mode == 0) {
         TORCH_CHECK(!inv.has_value() && !other.has_value() && !D.has_value(), "att_mode=\"forward\" takes no inv, other or D");
         auto out = torch::empty({n, X.size(1)}, f32), m = torch::empty({n}, f32), iv = torch::empty({n}, f32);
-        if (drop && transposed)
+        if (nodes && transposed)
+            check_rc(qgtc_tiledatt_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
+                                               N, own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
+                                               out.numel(), rmask, nmask, mask_words, st),
+                     "tiledMMFloat (transposed, attention, node masks)");
+        else if (nodes)
+            check_rc(qgtc_tiledatt_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
+                                             m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), rmask, nmask,
+                                             mask_words, st),
+                     "tiledMMFloat (attention, node masks)");
+        else if (drop && transposed)
             check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
                                               N, own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
                                               out.numel(), dt, ds, st),
@@ -905,7 +967,16 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     if (mode == 1) {
         TORCH_CHECK(!other.has_value() && !D.has_value(), "att_mode=\"backward\" takes no other or D");
         auto out = torch::empty({n, X.size(1)}, f32);
-        if (drop && transposed)
+        if (nodes && transposed)
+            check_rc(qgtc_tiledatt_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
+                                               N, own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), rmask, nmask,
+                                               mask_words, st),
+                     "tiledMMFloat (transposed, attention backward, node masks)");
+        else if (nodes)
+            check_rc(qgtc_tiledatt_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
+                                             ivp, out.data_ptr<float>(), out.numel(), rmask, nmask, mask_words, st),
+                     "tiledMMFloat (attention backward, node masks)");
+        else if (drop && transposed)
             check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
                                               N, own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), dt, ds, st),
                      "tiledMMFloat (transposed, attention backward, edge dropout)");
@@ -925,7 +996,16 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     }
     const float *b = tiled_att_other(other, X), *d = tiled_att_vector(D, "D", n, X);
     auto out = torch::empty({n}, f32);
-    if (drop && transposed)
+    if (nodes && transposed)
+        check_rc(qgtc_tiledatt_grad_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b,
+                                                X.numel(), N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(),
+                                                rmask, nmask, mask_words, st),
+                 "tiledMMFloat (transposed, attention score gradient, node masks)");
+    else if (nodes)
+        check_rc(qgtc_tiledatt_grad_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3,
+                                              sh, ivp, d, out.data_ptr<float>(), out.numel(), rmask, nmask, mask_words, st),
+                 "tiledMMFloat (attention score gradient, node masks)");
+    else if (drop && transposed)
         check_rc(qgtc_tiledatt_grad_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b,
                                                X.numel(), N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), dt,
                                                ds, st),
@@ -950,7 +1030,7 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
                                          const c10::optional<torch::Tensor> &att_nbr, const double negative_slope,
                                          const c10::optional<torch::Tensor> &shift, const c10::optional<torch::Tensor> &inv,
                                          const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D,
-                                         const EdgeDrop &edge_drop) {
+                                         const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -963,7 +1043,7 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
     check_float_operand(X, n, row_ptr);
     const int64_t T = kquad.numel();
     return tiled_att_run(false, row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, nullptr, T ? words(tiles) : nullptr, T,
-                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop);
+                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop, node_masks);
 }
 
 std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
@@ -971,7 +1051,7 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
                                            const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
                                            const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                            const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
-                                           const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop) {
+                                           const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -989,7 +1069,7 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
     const int64_t T = col_tile.numel();
     return tiled_att_run(true, col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
                          T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, n, X, att_mode, att_own, att_nbr,
-                         negative_slope, shift, inv, other, D, edge_drop);
+                         negative_slope, shift, inv, other, D, edge_drop, node_masks);
 }
 
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)
@@ -2021,38 +2101,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("to_float"), py::arg("row_scale") = py::none());
     m.def("_tiled_mm_f32", &tiled_mm_f32, "float32 [n, N] = A_tiled . X for a float32 X [n, N], neighbours added in ascending id order "
           "(QGTC.tiledMMFloat wraps it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none());
+          py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
           "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
-          py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none());
+          py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none(),
+          py::arg("node_masks") = py::none());
     // the keyword overloads: a call that names `reduce` takes them, every other call is the entry above
     m.def("_tiled_mm_f32", &tiled_red_f32, "reduce \"max\" / \"min\": [out] or [out, arg], the element-wise extremum of X over every "
           "row's neighbours and the neighbour that won; reduce \"select\": [the gradient], X = dY routed by arg (QGTC.tiledMMFloat(reduce=) "
           "and QGTC.tiledAggregate's backward wrap it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
           py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false,
-          py::arg("edge_drop") = py::none());
+          py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_red_f32_t, "the keyword overload of _tiled_mm_f32 on the column index: the extremum over every "
           "column's neighbours, or its select", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"),
           py::arg("X"), py::kw_only(), py::arg("reduce"), py::arg("arg") = py::none(), py::arg("return_arg") = false,
-          py::arg("edge_drop") = py::none());
+          py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32", &tiled_att_f32, "the `att_mode` keyword overload: the softmax-weighted sum over every row's neighbours "
           "(\"forward\": [out, m, inv]), its gradient for X on this view (\"backward\"), the score gradients (\"grad_own\", \"grad_nbr\": "
           "float32 [n]) and the row dot (\"rowdot\") (QGTC.tiledMMFloat(attn=) and QGTC.tiledAggregate(attn=) wrap it)",
           py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
           py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
           py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none(),
-          py::arg("edge_drop") = py::none());
+          py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_att_f32_t, "the `att_mode` keyword overload of _tiled_mm_f32 on the column index", py::arg("col_ptr"),
           py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"), py::kw_only(), py::arg("att_mode"),
           py::arg("att_own") = py::none(), py::arg("att_nbr") = py::none(), py::arg("negative_slope") = 0.2,
           py::arg("shift") = py::none(), py::arg("inv") = py::none(), py::arg("other") = py::none(), py::arg("D") = py::none(),
-          py::arg("edge_drop") = py::none());
+          py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32_src", &tiled_mm_f32_src, "float32 [n, N] = A_tiled . diag(src_scale) . X: every neighbour's row times "
           "src_scale[neighbour] as it is added (QGTC.tiledMMFloat with src_scale wraps it)", py::arg("row_ptr"), py::arg("kquad"),
-          py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none());
+          py::arg("tiles"), py::arg("n"), py::arg("X"), py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none(),
+          py::arg("node_masks") = py::none());
     m.def("_tiled_mm_f32_t_src", &tiled_mm_f32_t_src, "float32 [n, N] = A_tiled^T . diag(src_scale) . X (QGTC.tiledMMFloat on adj.T with "
           "src_scale wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none());
+          py::arg("row_scale"), py::arg("src_scale"), py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
     m.def("_tiled_inv_sqrt_degree", &tiled_inv_sqrt_degree, "float32 [n] = 1 / sqrt(deg), correctly rounded, 0 where deg is 0 "
           "(TiledAdjacency.sym_scale wraps it)", py::arg("deg"));
     m.def("i8gemm", &i8gemm, "int8 MFMA GEMM (comparison path): float32 [M,N] = A[M,K] x Bt[N,K]^T, exact");

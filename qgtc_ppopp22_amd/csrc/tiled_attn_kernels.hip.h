@@ -106,7 +106,9 @@ __device__ __forceinline__ void tiled_att_add_rows(float (&s)[CPL], float &den, 
 }
 
 // (the trailing pack of every decoder and kernel below is empty, and they are the ones that existed, or holds the edge-dropout mask of
-// tiled_drop.hip.h: a neighbour it drops is never queued)
+// tiled_drop.hip.h: a neighbour it drops is never queued; or the node masks of tiled_nodes.hip.h, which act as in k_tiled_mm_f32: a
+// block without a live row takes an empty tile range and stores what rows without neighbours hold, a masked-out row loads no tile
+// rows, and the neighbour bitmap's words of the tile's k-quad are ANDed into the decode words)
 template <int LPR, int CPL, bool BWD, class... Drop>
 __device__ __forceinline__ void tiled_att_decode(uint32_t m, int base, int n, float (&s)[CPL], float &den, int *list, int &cnt,
                                                  const float *__restrict__ X, int N, int c0, const TiledAtt &att, float po, float mo,
@@ -149,8 +151,15 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32(const int64_t *__restrict
     const int l = tid % LPR, c0 = blockIdx.y * (LPR * CPL) + l;
     const int nq = step128(n);
 
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint32_t rword = 0;   // the row bitmap's word of this block
+    if constexpr (NODES) rword = tiled_nodes_word(nodes.row, rb);
+
     uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
-    if (n_tiles) {
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) walk = walk && rword != 0;
+    if (walk) {
         t0 = static_cast<uint64_t>(row_ptr[rb]);
         t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -169,30 +178,43 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32(const int64_t *__restrict
         for (int cc = 0; cc < CPL; ++cc) s[ri][cc] = 0.0f;
     });
     const uint32_t *mine = tiles + (g * RPG + (l < RPG ? l : 0)) * 4;   // lane l < RPG: row g * RPG + l of every tile
+    bool loads = l < RPG;
+    if constexpr (NODES) loads = loads && tiled_nodes_bit(rword, (g * RPG + l) & 31);
     uint4 a = make_uint4(0, 0, 0, 0);
+    [[maybe_unused]] uint4 nb = make_uint4(0, 0, 0, 0), nbn = make_uint4(0, 0, 0, 0);   // the neighbour bitmap's words of k-quad q / qn
     int q = -1;
     if (t0 < t1) {
         q = kquad[t0];
-        if (l < RPG) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if (loads) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if constexpr (NODES)
+            if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) nb = tiled_nodes_quad(nodes.nbr, q);
     }
     for (uint64_t t = t0; t < t1; ++t) {
         uint4 an = make_uint4(0, 0, 0, 0);
         int qn = -1;
         if (t + 1 < t1) {
             qn = kquad[t + 1];
-            if (l < RPG) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if (loads) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if constexpr (NODES)
+                if (static_cast<unsigned>(qn) < static_cast<unsigned>(nq)) nbn = tiled_nodes_quad(nodes.nbr, qn);
         }
-        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) {
+        bool decode = static_cast<unsigned>(q) < static_cast<unsigned>(nq);
+        if constexpr (NODES) decode = decode && (nb.x | nb.y | nb.z | nb.w) != 0;
+        if (decode) {
             const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+            [[maybe_unused]] const uint32_t nw[4] = {nb.x, nb.y, nb.z, nb.w};
             tiled_static_for<RPG>([&](auto ri) {
                 tiled_static_for<4>([&](auto k) {
-                    tiled_att_decode<LPR, CPL, BWD>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], den[ri], lists[g][ri],
-                                                    cnt[ri], X, N, c0, att, po[ri], mo[ri], tiled_drop_for(row0 + ri, drop)...);
+                    uint32_t mw = tiled_f32_bcast<LPR>(w[k], ri);
+                    if constexpr (NODES) mw &= nw[k];
+                    tiled_att_decode<LPR, CPL, BWD>(mw, q * 128 + k * 32, n, s[ri], den[ri], lists[g][ri], cnt[ri], X, N, c0, att, po[ri],
+                                                    mo[ri], tiled_drop_for(row0 + ri, drop)...);
                 });
             });
         }
         a = an;
         q = qn;
+        if constexpr (NODES) nb = nbn;
     }
     tiled_static_for<RPG>([&](auto ri) {
         tiled_att_add_rows<LPR, CPL, BWD>(s[ri], den[ri], lists[g][ri], cnt[ri], X, N, c0, att, po[ri], mo[ri]);
@@ -309,8 +331,15 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad(const int64_t *__restric
     const int g = __builtin_amdgcn_readfirstlane(tid / 64), l = tid % 64;
     const int nq = step128(n);
 
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint32_t rword = 0;   // the row bitmap's word of this block
+    if constexpr (NODES) rword = tiled_nodes_word(nodes.row, rb);
+
     uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
-    if (n_tiles) {
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) walk = walk && rword != 0;
+    if (walk) {
         t0 = static_cast<uint64_t>(row_ptr[rb]);
         t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -333,32 +362,45 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad(const int64_t *__restric
         for (int cc = 0; cc < 4; ++cc) own[ri][cc] = REG && l + cc * 64 < N ? A[static_cast<uint64_t>(row) * N + l + cc * 64] : 0.0f;
     });
     const uint32_t *mine = tiles + (g * RPG + (l < RPG ? l : 0)) * 4;   // lane l < RPG: row g * RPG + l of every tile
+    bool loads = l < RPG;
+    if constexpr (NODES) loads = loads && tiled_nodes_bit(rword, (g * RPG + l) & 31);
     uint4 a = make_uint4(0, 0, 0, 0);
+    [[maybe_unused]] uint4 nb = make_uint4(0, 0, 0, 0), nbn = make_uint4(0, 0, 0, 0);   // the neighbour bitmap's words of k-quad q / qn
     int q = -1;
     if (t0 < t1) {
         q = kquad[t0];
-        if (l < RPG) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if (loads) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if constexpr (NODES)
+            if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) nb = tiled_nodes_quad(nodes.nbr, q);
     }
     for (uint64_t t = t0; t < t1; ++t) {
         uint4 an = make_uint4(0, 0, 0, 0);
         int qn = -1;
         if (t + 1 < t1) {
             qn = kquad[t + 1];
-            if (l < RPG) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if (loads) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if constexpr (NODES)
+                if (static_cast<unsigned>(qn) < static_cast<unsigned>(nq)) nbn = tiled_nodes_quad(nodes.nbr, qn);
         }
-        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) {
+        bool decode = static_cast<unsigned>(q) < static_cast<unsigned>(nq);
+        if constexpr (NODES) decode = decode && (nb.x | nb.y | nb.z | nb.w) != 0;
+        if (decode) {
             const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+            [[maybe_unused]] const uint32_t nw[4] = {nb.x, nb.y, nb.z, nb.w};
             tiled_static_for<RPG>([&](auto ri) {
                 const int row = row0 + ri < n ? row0 + ri : n - 1;
                 tiled_static_for<4>([&](auto k) {
-                    tiled_att_grad_decode<REG, NBR_OWNS>(tiled_f32_bcast<64>(w[k], ri), q * 128 + k * 32, n, acc[ri], own[ri],
-                                                         A + static_cast<uint64_t>(row) * N, lists[g][ri], cnt[ri], B, N, l, att,
-                                                         po[ri], mo[ri], io[ri], Do[ri], tiled_drop_for(row, drop)...);
+                    uint32_t mw = tiled_f32_bcast<64>(w[k], ri);
+                    if constexpr (NODES) mw &= nw[k];
+                    tiled_att_grad_decode<REG, NBR_OWNS>(mw, q * 128 + k * 32, n, acc[ri], own[ri], A + static_cast<uint64_t>(row) * N,
+                                                         lists[g][ri], cnt[ri], B, N, l, att, po[ri], mo[ri], io[ri], Do[ri],
+                                                         tiled_drop_for(row, drop)...);
                 });
             });
         }
         a = an;
         q = qn;
+        if constexpr (NODES) nb = nbn;
     }
     tiled_static_for<RPG>([&](auto ri) {
         const int row = row0 + ri < n ? row0 + ri : n - 1;

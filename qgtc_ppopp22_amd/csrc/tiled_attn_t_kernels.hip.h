@@ -8,19 +8,24 @@
 //   product   a row group is 16 lanes on a chunk of W = 16 * CPL output columns; the state is the 128 x W running sums and, in the
 //             forward, one den per row beside them (every lane of the group holds the same den; lane 0 keeps it);
 //   gradient  a row group is a whole wave, lane j on the columns j + 64 cc, and the state is one float per output row.
+// Node masks at the end of the pack (tiled_nodes.hip.h) act as in k_tiled_mm_f32_t: the k-quad's four row-bitmap words decide from
+// blockIdx alone whether the list is walked, and the transposer role ANDs both bitmaps into a tile's words before the transpose.
 #pragma once
 
 namespace {
 
 // the transposer role both kernels share: the loads run ahead of the rounds - the list entry two rounds, the tile words one round
 // (an entry is checked when it is used, not when it is loaded: a skipped tile or row block leaves zero masks)
-struct TiledAttStager {
+template <bool NODES>
+struct TiledAttStagerOf {
     const int64_t *__restrict__ col_tile;
     const int32_t *__restrict__ col_rb;
     const uint32_t *__restrict__ tiles;
     uint64_t n_tiles, t1, tn;
     int nrb, lane, s_own, rb, rbn;
     uint4 w;
+    const uint32_t *__restrict__ nbr = nullptr;   // NODES: the neighbour bitmap (or null) and the row bitmap's words of the k-quad
+    uint4 rw = make_uint4(0, 0, 0, 0);
 
     __device__ __forceinline__ void entry(uint64_t i, uint64_t &t, int &r) const {
         t = n_tiles;
@@ -31,8 +36,15 @@ struct TiledAttStager {
         }
     }
     __device__ __forceinline__ uint4 words(uint64_t t, int &r) const {
-        if (t < n_tiles && static_cast<unsigned>(r) < static_cast<unsigned>(nrb))
-            return *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+        if (t < n_tiles && static_cast<unsigned>(r) < static_cast<unsigned>(nrb)) {
+            uint4 x = *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+            if constexpr (NODES) {
+                const uint32_t nb = nbr ? nbr[r] : 0xffffffffu;   // r < S32(n) <= S128(n) * 4
+                const uint32_t on = (nb >> lane) & 1u ? 0xffffffffu : 0u;
+                x = make_uint4(x.x & rw.x & on, x.y & rw.y & on, x.z & rw.z & on, x.w & rw.w & on);
+            }
+            return x;
+        }
         r = -1;
         return make_uint4(0, 0, 0, 0);
     }
@@ -54,6 +66,7 @@ struct TiledAttStager {
         entry(base + 2 * TILED_T_TS + s_own, tn, rbn);
     }
 };
+using TiledAttStager = TiledAttStagerOf<false>;
 
 template <int CPL, bool BWD, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_att_f32_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
@@ -80,12 +93,24 @@ __global__ __launch_bounds__(256) void k_tiled_att_f32_t(const int64_t *__restri
     }
 
     uint64_t b0 = 0, t1 = 0;   // an adjacency without tiles may come without col_ptr
-    if (n_tiles) {
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint4 rw = make_uint4(0, 0, 0, 0);   // the row bitmap's words of this k-quad
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) {
+        rw = tiled_nodes_quad(nodes.row, q);
+        walk = walk && (rw.x | rw.y | rw.z | rw.w) != 0;
+    }
+    if (walk) {
         b0 = static_cast<uint64_t>(col_ptr[q]);
         t1 = static_cast<uint64_t>(col_ptr[q + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
     }
-    TiledAttStager stg{col_tile, col_rb, tiles, n_tiles, t1, 0, (n + 31) / 32, tid & 31, tid >> 5, -1, -1, make_uint4(0, 0, 0, 0)};
+    TiledAttStagerOf<NODES> stg{col_tile, col_rb, tiles, n_tiles, t1, 0, (n + 31) / 32, tid & 31, tid >> 5, -1, -1, make_uint4(0, 0, 0, 0)};
+    if constexpr (NODES) {
+        stg.nbr = nodes.nbr;
+        stg.rw = rw;
+    }
     stg.start(b0);
     for (uint64_t base = b0; base < t1; base += TS) {
         stg.stage(base, mk, srb);
@@ -159,12 +184,24 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad_t(const int64_t *__restr
     if (tid < 128) acc[tid] = 0.0f;
 
     uint64_t b0 = 0, t1 = 0;   // an adjacency without tiles may come without col_ptr
-    if (n_tiles) {
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint4 rw = make_uint4(0, 0, 0, 0);   // the row bitmap's words of this k-quad
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) {
+        rw = tiled_nodes_quad(nodes.row, q);
+        walk = walk && (rw.x | rw.y | rw.z | rw.w) != 0;
+    }
+    if (walk) {
         b0 = static_cast<uint64_t>(col_ptr[q]);
         t1 = static_cast<uint64_t>(col_ptr[q + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
     }
-    TiledAttStager stg{col_tile, col_rb, tiles, n_tiles, t1, 0, (n + 31) / 32, tid & 31, tid >> 5, -1, -1, make_uint4(0, 0, 0, 0)};
+    TiledAttStagerOf<NODES> stg{col_tile, col_rb, tiles, n_tiles, t1, 0, (n + 31) / 32, tid & 31, tid >> 5, -1, -1, make_uint4(0, 0, 0, 0)};
+    if constexpr (NODES) {
+        stg.nbr = nodes.nbr;
+        stg.rw = rw;
+    }
     stg.start(b0);
     __syncthreads();
     for (uint64_t base = b0; base < t1; base += TS) {

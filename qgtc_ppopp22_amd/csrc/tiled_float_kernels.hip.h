@@ -12,10 +12,13 @@
 // Every template below ends in a pack `Src...`: empty, it is the code that existed before the source scale (same arguments, the same
 // instructions); with one `const float *` (src_scale, n floats) a neighbour's value is multiplied by src_scale[neighbour] before it is
 // added - one IEEE multiply, then one IEEE add, never fused. The pack may END in the edge-dropout mask
-// (tiled_drop.hip.h): a neighbour the mask drops is never queued, so its row is never loaded.
+// (tiled_drop.hip.h): a neighbour the mask drops is never queued, so its row is never loaded. Or it may end in
+// the node masks (tiled_nodes.hip.h): the neighbour bitmap is ANDed into the tile words before they are decoded,
+// and a workgroup without a live output row walks nothing.
 #pragma once
 
 #include "tiled_drop.hip.h"
+#include "tiled_nodes.hip.h"
 
 namespace {
 
@@ -96,6 +99,10 @@ __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, fl
 // thereby in tile order = ascending neighbour id. Narrow outputs take narrow groups, so that a wave keeps the loads of up to 4 rows
 // in flight at once. With LPR = 64 the tile words are wave-uniform (v_readlane) and the decode loop is scalar.
 // The rows are stored once; SCALED multiplies by row_scale[row] first (one IEEE single multiply).
+// With node masks in the pack: the workgroup reads word rb of the row bitmap (its 32 rows); when that is zero it takes an empty tile
+// range without reading row_ptr, so it only stores its +0 rows; a masked-out row of a live block does not load its tile rows (zero
+// words decode to nothing). The four neighbour-bitmap words of a tile's k-quad are loaded with the tile's kquad entry, one tile ahead,
+// and ANDed into the broadcast words; a tile whose four bitmap words are zero is not decoded at all.
 template <int LPR>
 __device__ __forceinline__ uint32_t tiled_f32_bcast(uint32_t v, int src) {
     if constexpr (LPR == 64) return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), src));
@@ -108,14 +115,17 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
                                                       const float *__restrict__ X, int N, const float *__restrict__ row_scale,
                                                       float *__restrict__ out, Src... src) {
     constexpr int G = 256 / LPR, RPG = 32 / G;   // row groups per workgroup, rows per group
+    constexpr bool NODES = tiled_has_nodes<Src...>();
+    [[maybe_unused]] TiledNodesWalk<NODES> nd;   // the node masks' state: empty without them
     __shared__ int lists[G][RPG][TILED_F32_CAP];
     const int rb = blockIdx.x, tid = threadIdx.x;
     const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
     const int l = tid % LPR, c0 = blockIdx.y * (LPR * CPL) + l;
     const int nq = step128(n);
+    if constexpr (NODES) nd.start(tiled_nodes_of(src...), rb, g * RPG + l);
 
     uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
-    if (n_tiles) {
+    if (tiled_nodes_and<NODES>(n_tiles != 0, nd.block_live())) {
         t0 = static_cast<uint64_t>(row_ptr[rb]);
         t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -133,26 +143,29 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
     int q = -1;
     if (t0 < t1) {
         q = kquad[t0];
-        if (l < RPG) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if (tiled_nodes_and<NODES>(l < RPG, nd.row_live())) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if constexpr (NODES) nd.load(nd.nb, q, nq);
     }
     for (uint64_t t = t0; t < t1; ++t) {
         uint4 an = make_uint4(0, 0, 0, 0);
         int qn = -1;
         if (t + 1 < t1) {
             qn = kquad[t + 1];
-            if (l < RPG) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if (tiled_nodes_and<NODES>(l < RPG, nd.row_live())) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if constexpr (NODES) nd.load(nd.nbn, qn, nq);
         }
-        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) {
+        if (tiled_nodes_and<NODES>(static_cast<unsigned>(q) < static_cast<unsigned>(nq), nd.tile_live())) {
             const uint32_t w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
             for (int ri = 0; ri < RPG; ++ri)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
+                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri) & nd.word(k), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
                                                tiled_drop_for(rb * 32 + g * RPG + ri, src)...);
         }
         a = an;
         q = qn;
+        if constexpr (NODES) nd.nb = nd.nbn;
     }
 #pragma unroll
     for (int ri = 0; ri < RPG; ++ri) {

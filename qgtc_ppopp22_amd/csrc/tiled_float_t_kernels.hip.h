@@ -16,6 +16,13 @@
 // The rows are stored once at the end; SCALED multiplies by row_scale[row] first (one IEEE single multiply). The trailing pack `Src...`
 // is tiled_float_kernels.hip.h's: empty, the kernel that existed; with src_scale, the shared adder scales every term by its source row;
 // ending in the edge-dropout mask of this view (TiledDropView<true>), a dropped source row is never queued.
+// Ending in the node masks (tiled_nodes.hip.h): the four row-bitmap words of k-quad q decide, from blockIdx
+// alone and before the first barrier, whether the workgroup walks its list at all (none set: an empty list, so it stores its +0 rows and
+// is done); in a live workgroup both bitmaps are ANDed into a tile's words as the transposer role loads them, BEFORE the bit transpose:
+// lane `lane` holds tile row 31 - lane, neighbour rb * 32 + 31 - lane, whose bit of word rb of the neighbour bitmap is bit `lane`, and
+// its four words cover the k-quad's 128 output rows in the bitmap's own bit order. The staged masks then hold participating neighbours
+// of computed rows only: a masked-out output row has no mask in any round and is skipped by the add loop's zero test, and the decode
+// sees no other bit. One dword per tile and half-wave, loaded with the tile's words one round ahead; nothing per neighbour.
 #pragma once
 
 namespace {
@@ -43,7 +50,15 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
 
     const int lane = tid & 31, s_own = tid >> 5;   // transposer role: half-wave s of the workgroup stages tile base + s
     uint64_t b0 = 0, t1 = 0;                       // an adjacency without tiles may come without col_ptr
-    if (n_tiles) {
+    constexpr bool NODES = tiled_has_nodes<Src...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(src...);
+    [[maybe_unused]] uint4 rw = make_uint4(0, 0, 0, 0);   // the row bitmap's words of this k-quad
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) {
+        rw = tiled_nodes_quad(nodes.row, q);
+        walk = walk && (rw.x | rw.y | rw.z | rw.w) != 0;
+    }
+    if (walk) {
         b0 = static_cast<uint64_t>(col_ptr[q]);
         t1 = static_cast<uint64_t>(col_ptr[q + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -60,8 +75,15 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
         }
     };
     auto words = [&](uint64_t t, int &rb) {
-        if (t < n_tiles && static_cast<unsigned>(rb) < static_cast<unsigned>(nrb))
-            return *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+        if (t < n_tiles && static_cast<unsigned>(rb) < static_cast<unsigned>(nrb)) {
+            uint4 r = *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+            if constexpr (NODES) {
+                const uint32_t nb = nodes.nbr ? nodes.nbr[rb] : 0xffffffffu;   // rb < S32(n) <= S128(n) * 4
+                const uint32_t on = (nb >> lane) & 1u ? 0xffffffffu : 0u;
+                r = make_uint4(r.x & rw.x & on, r.y & rw.y & on, r.z & rw.z & on, r.w & rw.w & on);
+            }
+            return r;
+        }
         rb = -1;
         return make_uint4(0, 0, 0, 0);
     };

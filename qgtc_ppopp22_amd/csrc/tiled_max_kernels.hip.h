@@ -132,7 +132,9 @@ __device__ __forceinline__ void tiled_red_decode(uint32_t m, int base, int n, Ti
 
 // ---- the row view: out[r] = reduce over the set cells of row r ----------------------------------------------------------------------
 // k_tiled_mm_f32's workgroup: one per 32-row block and chunk of LPR * CPL output columns, a row group of LPR lanes on RPG rows, the
-// block's tiles walked once in k-quad order with the next tile's words loaded while this one is decoded.
+// block's tiles walked once in k-quad order with the next tile's words loaded while this one is decoded. Node masks at the end of the
+// pack (tiled_nodes.hip.h) act as they do there: a block without a live row takes an empty tile range, a masked-out row loads no tile
+// rows, and the neighbour bitmap's words of the tile's k-quad are ANDed into the decode words.
 template <int LPR, int CPL, class Red, class... Drop>
 __global__ __launch_bounds__(256) void k_tiled_red_f32(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                        const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n, int N, Red red,
@@ -144,8 +146,15 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32(const int64_t *__restrict
     const int l = tid % LPR, c0 = blockIdx.y * (LPR * CPL) + l;
     const int nq = step128(n);
 
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint32_t rword = 0;   // the row bitmap's word of this block
+    if constexpr (NODES) rword = tiled_nodes_word(nodes.row, rb);
+
     uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
-    if (n_tiles) {
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) walk = walk && rword != 0;
+    if (walk) {
         t0 = static_cast<uint64_t>(row_ptr[rb]);
         t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -162,30 +171,43 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32(const int64_t *__restrict
     });
     const int row0 = rb * 32 + g * RPG;
     const uint32_t *mine = tiles + (g * RPG + (l < RPG ? l : 0)) * 4;   // lane l < RPG: row g * RPG + l of every tile
+    bool loads = l < RPG;
+    if constexpr (NODES) loads = loads && tiled_nodes_bit(rword, (g * RPG + l) & 31);
     uint4 a = make_uint4(0, 0, 0, 0);
+    [[maybe_unused]] uint4 nb = make_uint4(0, 0, 0, 0), nbn = make_uint4(0, 0, 0, 0);   // the neighbour bitmap's words of k-quad q / qn
     int q = -1;
     if (t0 < t1) {
         q = kquad[t0];
-        if (l < RPG) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if (loads) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
+        if constexpr (NODES)
+            if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) nb = tiled_nodes_quad(nodes.nbr, q);
     }
     for (uint64_t t = t0; t < t1; ++t) {
         uint4 an = make_uint4(0, 0, 0, 0);
         int qn = -1;
         if (t + 1 < t1) {
             qn = kquad[t + 1];
-            if (l < RPG) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if (loads) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
+            if constexpr (NODES)
+                if (static_cast<unsigned>(qn) < static_cast<unsigned>(nq)) nbn = tiled_nodes_quad(nodes.nbr, qn);
         }
-        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq)) {
+        bool decode = static_cast<unsigned>(q) < static_cast<unsigned>(nq);
+        if constexpr (NODES) decode = decode && (nb.x | nb.y | nb.z | nb.w) != 0;
+        if (decode) {
             const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+            [[maybe_unused]] const uint32_t nw[4] = {nb.x, nb.y, nb.z, nb.w};
             tiled_static_for<RPG>([&](auto ri) {
                 tiled_static_for<4>([&](auto k) {
-                    tiled_red_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri), q * 128 + k * 32, n, st[ri], row0 + ri, lists[g][ri],
-                                               cnt[ri], red, N, c0, tiled_drop_for(row0 + ri, drop)...);
+                    uint32_t m = tiled_f32_bcast<LPR>(w[k], ri);
+                    if constexpr (NODES) m &= nw[k];
+                    tiled_red_decode<LPR, CPL>(m, q * 128 + k * 32, n, st[ri], row0 + ri, lists[g][ri], cnt[ri], red, N, c0,
+                                               tiled_drop_for(row0 + ri, drop)...);
                 });
             });
         }
         a = an;
         q = qn;
+        if constexpr (NODES) nb = nbn;
     }
     tiled_static_for<RPG>([&](auto ri) {
         red.template rows<LPR, CPL>(st[ri], row0 + ri, lists[g][ri], cnt[ri], N, c0);

@@ -8,7 +8,8 @@
 // ascending neighbour id) and puts the state back. The state is Red::WORDS arrays of 128 x W words: the running value and, for the
 // extremum, the winner. Two arrays of 128 x 64 words would be 64 KB, past the static LDS of a workgroup, so the extremum runs at
 // W <= 32 (the launcher cuts wider outputs into 32-column chunks) and keeps the 32 KB of the float kernel; the select has one array
-// and keeps W <= 64.
+// and keeps W <= 64. Node masks at the end of the pack (tiled_nodes.hip.h) act as in k_tiled_mm_f32_t: the k-quad's four row-bitmap
+// words decide before the first barrier whether the list is walked, and both bitmaps are ANDed into a tile's words before the transpose.
 #pragma once
 
 namespace {
@@ -40,7 +41,15 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32_t(const int64_t *__restri
 
     const int lane = tid & 31, s_own = tid >> 5;   // transposer role: half-wave s of the workgroup stages tile base + s
     uint64_t b0 = 0, t1 = 0;                       // an adjacency without tiles may come without col_ptr
-    if (n_tiles) {
+    constexpr bool NODES = tiled_has_nodes<Drop...>();
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(drop...);
+    [[maybe_unused]] uint4 rw = make_uint4(0, 0, 0, 0);   // the row bitmap's words of this k-quad
+    bool walk = n_tiles != 0;
+    if constexpr (NODES) {
+        rw = tiled_nodes_quad(nodes.row, q);
+        walk = walk && (rw.x | rw.y | rw.z | rw.w) != 0;
+    }
+    if (walk) {
         b0 = static_cast<uint64_t>(col_ptr[q]);
         t1 = static_cast<uint64_t>(col_ptr[q + 1]);
         t1 = t1 < n_tiles ? t1 : n_tiles;
@@ -57,8 +66,15 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32_t(const int64_t *__restri
         }
     };
     auto words = [&](uint64_t t, int &rb) {
-        if (t < n_tiles && static_cast<unsigned>(rb) < static_cast<unsigned>(nrb))
-            return *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+        if (t < n_tiles && static_cast<unsigned>(rb) < static_cast<unsigned>(nrb)) {
+            uint4 r = *reinterpret_cast<const uint4 *>(tiles + t * 128 + (31 - lane) * 4);
+            if constexpr (NODES) {
+                const uint32_t nb = nodes.nbr ? nodes.nbr[rb] : 0xffffffffu;   // rb < S32(n) <= S128(n) * 4
+                const uint32_t on = (nb >> lane) & 1u ? 0xffffffffu : 0u;
+                r = make_uint4(r.x & rw.x & on, r.y & rw.y & on, r.z & rw.z & on, r.w & rw.w & on);
+            }
+            return r;
+        }
         rb = -1;
         return make_uint4(0, 0, 0, 0);
     };

@@ -41,6 +41,15 @@ fold in ascending id order on ``adj`` or ``adj.T``, no atomics) are specified to
 cell (i, j) of the adjacency survives when a fixed 32-bit hash of (i, j, seed) is at least ``floor(rate * 2^32)``, decided inside the tile
 walk on either view, so nothing per edge is stored, no second adjacency is packed and the backward on the other view sees exactly the
 forward's subgraph. The result is bit for bit that of the same call on an adjacency packed from the kept edges.
+
+``row_mask`` / ``nbr_mask`` on both functions, in every mode, aggregate over an induced subgraph without packing a second
+adjacency (include/qgtc.h, "Node masks"): each is a bitmap from :func:`node_bitmap` or None = all nodes, relative to the view like the
+scales. A row outside ``row_mask`` comes back +0, a neighbour outside ``nbr_mask`` is never loaded, a block of 32 rows (128 on ``adj.T``)
+without a live row reads no tile, and the result is bit for bit the unmasked call on ``pack_edges_tiled`` of the edges between the two
+sets. The backward takes the two masks swapped. ``adj.degrees()``, ``mean_scale()`` and ``sym_scale()`` take the same two keywords and
+give the masked graph's. That covers Cluster-GCN batches on the whole-graph adjacency (``conv.GCNConv.forward(nodes=)``), a last layer
+on the labelled nodes only, and node dropout. Every mode takes them: under "max" / "min" a row outside ``row_mask`` has arg -1, and the
+attention's softmax runs over the participating neighbours.
 """
 from __future__ import annotations
 
@@ -48,12 +57,48 @@ import math
 
 import torch
 
-from . import load_ext
+import ctypes
+
+from . import lib_path, load_ext
 
 _ext = load_ext()
+_lib = None
+
+
+def _c_abi():
+    """libqgtc_hip.so through ctypes, for the two entries the extension does not bind: qgtc_node_bitmap and
+    qgtc_tiled_inv_degree. Loaded on first use; the extension has loaded the same library already."""
+    global _lib
+    if _lib is None:
+        L = ctypes.CDLL(lib_path())
+        P, I, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+        L.qgtc_node_bitmap.argtypes, L.qgtc_node_bitmap.restype = [P, I, P, SZ, P], I
+        L.qgtc_tiled_inv_degree.argtypes, L.qgtc_tiled_inv_degree.restype = [P, I, P, P], I
+        L.qgtc_strerror.argtypes, L.qgtc_strerror.restype = [I], ctypes.c_char_p
+        _lib = L
+    return _lib
+
+
+def _c_call(what: str, on: torch.Tensor, fn, *args) -> None:
+    """One C entry on ``torch.cuda.current_stream()`` of the operand's device (the stream handle is the entry's last argument): it
+    enqueues and returns, like the extension's own calls, and can be captured into a graph."""
+    if not on.is_cuda:
+        raise ValueError(f"{what} needs its operand on a GPU, not on {on.device}")
+    with torch.cuda.device(on.device):
+        rc = fn(*args, ctypes.c_void_p(torch.cuda.current_stream(on.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{what}: {_c_abi().qgtc_strerror(rc).decode()} (rc {rc})")
+
+
+def _inv_degree(deg: torch.Tensor) -> torch.Tensor:
+    """float32 [n] = 1 / deg, correctly rounded, 0 where deg is 0: the reciprocal kernel of the degrees alone (qgtc_tiled_inv_degree)."""
+    deg = deg.contiguous()
+    out = torch.empty(deg.numel(), dtype=torch.float32, device=deg.device)
+    _c_call("the reciprocal of the degrees", deg, _c_abi().qgtc_tiled_inv_degree, deg.data_ptr(), deg.numel(), out.data_ptr())
+    return out
 
 __all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat", "tiledAggregate",
-           "add_self_loops"]
+           "add_self_loops", "node_bitmap"]
 
 
 class TiledAdjacency:
@@ -125,23 +170,41 @@ class TiledAdjacency:
             base._degrees = _ext._tiled_degrees(base.row_ptr, base.kquad, base.tiles, base.n)
         return base._degrees
 
-    def degrees(self) -> torch.Tensor:
+    def _masked_degrees(self, row_mask, nbr_mask) -> torch.Tensor:
+        """int32 [n]: the terms the masked sum on this view adds per row - one masked N = 1 launch on a column of ones (exact: a degree
+        is at most 2^23). Not cached."""
+        ones = torch.ones((self.n, 1), dtype=torch.float32, device=self.device)
+        return tiledMMFloat(self, ones, row_mask=row_mask, nbr_mask=nbr_mask).reshape(self.n).to(torch.int32)
+
+    def degrees(self, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None) -> torch.Tensor:
         """int32 [n]: the set cells in every row of this view - the out-degree on ``adj``, the in-degree on ``adj.T`` -, which is the
         number of terms tiledMM2Int sums for that row (cells of multiplicity 2 are unset and do not count; self loops do). In the
         adjacency's numbering (:meth:`to_old` moves it). One device call computes both directions on first use; ``adj`` and
-        ``adj.T`` share the result."""
+        ``adj.T`` share the result.
+
+        With ``row_mask`` / ``nbr_mask`` (bitmaps of :func:`node_bitmap`, relative to this view, or None = all nodes) the degrees of the
+        masked graph: the neighbours in ``nbr_mask`` of every row in ``row_mask``, 0 for the other rows - what the unmasked method
+        gives on ``pack_edges_tiled`` of the edges between the two sets. One masked N = 1 launch on a column of ones, not cached."""
+        if row_mask is not None or nbr_mask is not None:
+            return self._masked_degrees(row_mask, nbr_mask)
         return self._degree_tensors()[1 if self.transposed else 0]
 
-    def mean_scale(self) -> torch.Tensor:
+    def mean_scale(self, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None) -> torch.Tensor:
         """float32 [n]: 1 / degrees(), correctly rounded, 0 where the degree is 0 - the ``row_scale`` that turns tiledMM2Bit /
-        tiledMM2Int on this view into the mean over neighbours."""
+        tiledMM2Int on this view into the mean over neighbours. With ``row_mask`` / ``nbr_mask`` the masked graph's (as in
+        :meth:`degrees`; not cached; the reciprocal is the same kernel's)."""
+        if row_mask is not None or nbr_mask is not None:
+            return _inv_degree(self._masked_degrees(row_mask, nbr_mask))
         return self._degree_tensors()[3 if self.transposed else 2]
 
-    def sym_scale(self) -> torch.Tensor:
+    def sym_scale(self, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None) -> torch.Tensor:
         """float32 [n]: 1 / sqrt(degrees()) of this view, both operations correctly rounded, 0 where the degree is 0. With
         ``row_scale=adj.sym_scale(), src_scale=adj.T.sym_scale()`` tiledMMFloat / tiledAggregate on ``adj`` give
         D_out^-1/2 . A . D_in^-1/2 (on ``adj.T`` swap the two views): on a symmetric edge list the GCN normalisation
-        D^-1/2 . A . D^-1/2. Computed for both directions on first use; ``adj`` and ``adj.T`` share the result."""
+        D^-1/2 . A . D^-1/2. Computed for both directions on first use; ``adj`` and ``adj.T`` share the result. With ``row_mask`` /
+        ``nbr_mask`` the masked graph's (as in :meth:`degrees`; not cached; the same inverse-square-root kernel)."""
+        if row_mask is not None or nbr_mask is not None:
+            return _ext._tiled_inv_sqrt_degree(self._masked_degrees(row_mask, nbr_mask))
         base = self._other if self.transposed else self
         if base._sym is None:
             deg = self._degree_tensors()
@@ -330,6 +393,63 @@ def _drop_kw(key) -> dict:
     return {} if key is None else {"edge_drop": key}
 
 
+def node_bitmap(nodes: torch.Tensor, n: int) -> torch.Tensor:
+    """int32 [S128(n) * 4]: the bitmap of a node set (include/qgtc.h, "Node masks"; node i at word i >> 5, bit 31 - (i & 31), pad bits
+    zero), on the device of ``nodes`` (a GPU), built by one small kernel on the current stream (the C entry qgtc_node_bitmap, called
+    through ctypes: the extension binds no new name for it). ``nodes`` is a bool [n] tensor, or an int64 tensor of node ids in any
+    order, duplicates allowed; an id outside 0 .. n - 1 is a ValueError (one host read), any other dtype a TypeError. The ids are the
+    ADJACENCY'S: on a reordered adjacency move a bool mask over with ``adj.to_new(mask)`` first (an id list i becomes
+    ``adj.rank[i]``)."""
+    n = int(n)
+    if not isinstance(nodes, torch.Tensor):
+        raise TypeError(f"nodes must be a torch.Tensor (bool [n] or int64 ids), not {type(nodes).__name__}")
+    if not 1 <= n <= (1 << 23):
+        raise ValueError(f"n must lie in [1, 2^23], not {n}")
+    if nodes.dtype == torch.bool:
+        if nodes.dim() != 1 or nodes.numel() != n:
+            raise ValueError(f"a bool nodes must have shape [{n}], not {list(nodes.shape)}")
+        flags = nodes.contiguous()
+    elif nodes.dtype == torch.int64:
+        if nodes.dim() != 1:
+            raise ValueError(f"an id list must have one dimension, not {nodes.dim()}")
+        if nodes.numel() and not bool(((nodes >= 0) & (nodes < n)).all()):
+            raise ValueError(f"nodes holds an id outside 0 .. {n - 1}")
+        flags = torch.zeros(n, dtype=torch.bool, device=nodes.device)
+        flags[nodes] = True   # duplicates write the same value
+    else:
+        raise TypeError(f"nodes must be bool or int64, not {nodes.dtype}")
+    out = torch.empty((n + 127) // 128 * 4, dtype=torch.int32, device=flags.device)
+    _c_call("node_bitmap", flags, _c_abi().qgtc_node_bitmap, flags.data_ptr(), n, out.data_ptr(), out.numel())
+    return out
+
+
+def _check_mask(adj: TiledAdjacency, mask, name: str) -> None:
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor (the int32 bitmap of tiled.node_bitmap) or None")
+    if mask.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32 (tiled.node_bitmap), not {mask.dtype}")
+    words = (adj.n + 127) // 128 * 4
+    if mask.dim() != 1 or mask.numel() != words:
+        raise ValueError(f"{name} must have shape [{words}] (S128(n) * 4 words), not {list(mask.shape)}")
+    if mask.device != adj.device:
+        raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {mask.device}")
+    if not mask.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _nodes_kw(adj: TiledAdjacency, row_mask, nbr_mask, key) -> dict:
+    """The binding's keyword for checked masks; without a mask no keyword at all, which is the call the binding always took."""
+    if row_mask is None and nbr_mask is None:
+        return {}
+    if row_mask is not None:
+        _check_mask(adj, row_mask, "row_mask")
+    if nbr_mask is not None:
+        _check_mask(adj, nbr_mask, "nbr_mask")
+    if key is not None:
+        raise ValueError("row_mask / nbr_mask cannot be combined with edge_drop: not built")
+    return {"node_masks": (row_mask, nbr_mask)}
+
+
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
     if adj.transposed:
@@ -337,25 +457,29 @@ def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, **kw)
 
 
-def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, key=None):
+def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, key=None,
+                     nodes_kw: dict | None = None):
     """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch. Under a mask
-    (``key``, checked) both launches take it: M must be the maximum over the KEPT neighbours, or the weights' sum could fall below 1."""
-    M = _tiled_extremum(adj, att_nbr.detach().unsqueeze(1), "max", False, key)[0].reshape(adj.n)
+    (``key`` or ``nodes_kw``, checked) both launches take it: M must be the maximum over the KEPT neighbours, or the weights' sum
+    could fall below 1."""
+    M = _tiled_extremum(adj, att_nbr.detach().unsqueeze(1), "max", False, key, nodes_kw)[0].reshape(adj.n)
     return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M,
-                **_drop_kw(key))
+                **_drop_kw(key), **(nodes_kw or {}))
 
 
-def _tiled_extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_arg: bool, key=None):
-    """[out] or [out, arg] of the max / min launch on this view, under the mask ``key`` (checked) when there is one."""
+def _tiled_extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_arg: bool, key=None, nodes_kw: dict | None = None):
+    """[out] or [out, arg] of the max / min launch on this view, under the mask ``key`` or ``nodes_kw`` (checked) when there is one."""
+    kw = {**_drop_kw(key), **(nodes_kw or {})}
     if adj.transposed:
         return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg),
-                                    **_drop_kw(key))
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg), **_drop_kw(key))
+                                    **kw)
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg), **kw)
 
 
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                  src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False, attn=None,
-                 negative_slope: float = 0.2, return_stats: bool = False, edge_drop=None):
+                 negative_slope: float = 0.2, return_stats: bool = False, edge_drop=None, row_mask: torch.Tensor | None = None,
+                 nbr_mask: torch.Tensor | None = None):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -391,9 +515,20 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     gives the plain call's bits. The mask is in the ADJACENCY'S OWN numbering: on a reordered adjacency i and j are the new ids, so the
     same seed masks other edges of the original graph than it would without the reordering. The seed is a kernel argument: a captured
     graph replays ONE mask (recapture, or draw the subgraph outside the graph, for a fresh one per step). A rate outside [0, 1) or NaN
-    and a seed outside [0, 2^64) are a ValueError, anything but a pair (or a seed that is no int) a TypeError."""
+    and a seed outside [0, 2^64) are a ValueError, anything but a pair (or a seed that is no int) a TypeError.
+
+    ``row_mask`` / ``nbr_mask`` (int32 bitmaps of :func:`node_bitmap`, each optional, relative to this view like the scales, in the
+    adjacency's own numbering), in every mode above, restrict the fold to a subgraph (include/qgtc.h, "Node masks"): row o is computed
+    iff o is in ``row_mask`` and holds what a row without neighbours holds otherwise (+0, times row_scale[o]; arg -1; inv 0); neighbour
+    k takes part iff k is in ``nbr_mask``, and a neighbour outside it is never
+    loaded, so a NaN in its row reaches nothing. The result is bit for bit the same call on ``pack_edges_tiled`` of the edges whose row
+    end lies in ``row_mask`` and whose neighbour end lies in ``nbr_mask``; all-ones masks give the plain call's bits. A 32-row block
+    (on ``adj.T``: a 128-row k-quad) without a live row reads no tile. The masks are kernel arguments read on the device: a captured
+    graph follows the bitmap's contents. Another dtype is a TypeError; another length, device or a non-contiguous mask a ValueError; a
+    mask with ``edge_drop`` a ValueError (not built)."""
     _check(adj)
     key = _edge_drop_key(edge_drop)
+    nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if attn is None:
@@ -410,7 +545,7 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
         slope = _check_slope(negative_slope)
         _check_float_operand(adj, X)
         att_out, att_nbr = _check_attn(adj, attn)
-        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope, key)
+        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope, key, nodes_kw)
         return (out, m, inv) if return_stats else out
     if reduce == "sum":
         if return_arg:
@@ -421,18 +556,19 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
                 raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
     _check_float_operand(adj, X)
     if reduce != "sum":
-        res = _tiled_extremum(adj, X, reduce, return_arg, key)
+        res = _tiled_extremum(adj, X, reduce, return_arg, key, nodes_kw)
         return (res[0], res[1]) if return_arg else res[0]
     if row_scale is not None:
         _check_scale(adj, row_scale)
     if src_scale is not None:
         _check_scale(adj, src_scale, "src_scale")
         if adj.transposed:
-            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key))
-        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key))
+            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key),
+                                            **nodes_kw)
+        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key), **nodes_kw)
     if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, **_drop_kw(key))
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, **_drop_kw(key))
+        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, **_drop_kw(key), **nodes_kw)
+    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, **_drop_kw(key), **nodes_kw)
 
 
 def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
@@ -444,28 +580,31 @@ def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> t
 
 
 class _TiledAggregate(torch.autograd.Function):
-    """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped."""
+    """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped - and
+    node masks swapped: a neighbour of the forward is an output row of the backward."""
 
     @staticmethod
-    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None):
+    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None, row_mask=None, nbr_mask=None):
         ctx.adj, ctx.row_scale, ctx.src_scale, ctx.edge_drop = adj, row_scale, src_scale, edge_drop
-        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop)
+        ctx.row_mask, ctx.nbr_mask = row_mask, nbr_mask
+        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask)
 
     @staticmethod
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
-            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale, edge_drop=ctx.edge_drop)
-        return None, dX, None, None, None
+            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale, edge_drop=ctx.edge_drop,
+                              row_mask=ctx.nbr_mask, nbr_mask=ctx.row_mask)
+        return None, dX, None, None, None, None, None
 
 
 class _TiledExtremum(torch.autograd.Function):
     """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
 
     @staticmethod
-    def forward(ctx, adj, X, reduce, edge_drop=None):
-        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop)
-        ctx.adj, ctx.arg = adj, arg   # the select needs no mask: arg names kept neighbours only
+    def forward(ctx, adj, X, reduce, edge_drop=None, row_mask=None, nbr_mask=None):
+        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask)
+        ctx.adj, ctx.arg = adj, arg   # the select needs no mask: arg names kept (participating) neighbours only
         return out
 
     @staticmethod
@@ -474,7 +613,7 @@ class _TiledExtremum(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[1]:
             dX = _tiled_select(ctx.adj.T, dY.contiguous(), ctx.arg)
-        return None, dX, None, None
+        return None, dX, None, None, None, None
 
 
 class _TiledAttention(torch.autograd.Function):
@@ -483,9 +622,14 @@ class _TiledAttention(torch.autograd.Function):
     of edge (o, k) gets u = alpha[o, k] . (dY[o] . X[k] - D[o]) . L'(e), which dp folds over k on this view and dq over o on the other."""
 
     @staticmethod
-    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None):
-        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop)
+    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None, row_mask=None, nbr_mask=None):
+        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop,
+                                   row_mask=row_mask, nbr_mask=nbr_mask)
         ctx.adj, ctx.slope, ctx.drop_kw = adj, slope, _drop_kw(_edge_drop_key(edge_drop))
+        # node masks: unchanged on this view (grad_own), swapped on the other (the backward product and grad_nbr)
+        ctx.kw_here = ctx.kw_other = {}
+        if row_mask is not None or nbr_mask is not None:
+            ctx.kw_here, ctx.kw_other = {"node_masks": (row_mask, nbr_mask)}, {"node_masks": (nbr_mask, row_mask)}
         ctx.save_for_backward(X, att_out, att_nbr, out, m, inv)
         return out
 
@@ -498,19 +642,21 @@ class _TiledAttention(torch.autograd.Function):
         dY, kw = dY.contiguous(), ctx.drop_kw   # every gradient walks the forward's subgraph
         dX = dp = dq = None
         if need_x:
-            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw)[0]
+            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **ctx.kw_other)[0]
         if need_p or need_q:
             D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
             if need_p:
-                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D, **kw)[0]
+                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D, **kw,
+                          **ctx.kw_here)[0]
             if need_q:
-                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw)[0]
-        return None, dX, dp, dq, None, None
+                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw,
+                          **ctx.kw_other)[0]
+        return None, dX, dp, dq, None, None, None, None
 
 
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                    src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2,
-                   edge_drop=None) -> torch.Tensor:
+                   edge_drop=None, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None) -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
@@ -530,7 +676,16 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     With ``edge_drop=(rate, seed)`` (as in :func:`tiledMMFloat`, every mode) the forward runs on the random subgraph and every backward
     launch gets the same pair on the other view, where the mask is rebuilt from the same cells of the adjacency: the gradients are those
     of the unmasked call on ``pack_edges_tiled`` of the kept edges, bit for bit. The mask is in the adjacency's own numbering (the new
-    ids on a reordered adjacency), and a captured graph replays one mask, because the seed is a kernel argument."""
+    ids on a reordered adjacency), and a captured graph replays one mask, because the seed is a kernel argument.
+
+    With ``row_mask`` / ``nbr_mask`` (as in :func:`tiledMMFloat`, every mode) the forward runs on the masked graph and the backward is
+    the product on the other view with the masks swapped, like the scales: the gradient of the unmasked call on ``pack_edges_tiled`` of
+    the edges between the two sets, bit for bit - rows of X outside ``nbr_mask`` get +0 (times src_scale). The extremum's select needs
+    no mask (arg names participants only); the attention takes its softmax shift from the masked max launch, passes the masks unchanged
+    to att_out's gradient and swapped to the gradient for X and att_nbr's."""
+    if row_mask is not None or nbr_mask is not None:
+        _check(adj)
+        _nodes_kw(adj, row_mask, nbr_mask, _edge_drop_key(edge_drop))
     _edge_drop_key(edge_drop)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
@@ -544,15 +699,15 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
         _check(adj)
         _check_float_operand(adj, X)
         att_out, att_nbr = _check_attn(adj, attn)
-        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope, edge_drop)
+        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope, edge_drop, row_mask, nbr_mask)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
         if reduce != "sum" and sc is not None:
             raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
             raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to X only")
     if reduce != "sum":
-        return _TiledExtremum.apply(adj, X, reduce, edge_drop)
-    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop)
+        return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask)
+    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask)
 
 
 def add_self_loops(src: torch.Tensor, dst: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:

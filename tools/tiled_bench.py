@@ -53,7 +53,17 @@ for the sum with `sym` scales, max and attention, each without the mask and with
 the plain launch on the adjacency packed from the kept cells before timing. Medians with their 10th and 90th percentiles, and the ratios
 (b) / (a), (b) / (c) and masked / plain of (d).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop]
+`--leg nodes` measures node masks inside the tile walk (``row_mask=`` / ``nbr_mask=`` of QGTC.tiledMMFloat / QGTC.tiledAggregate;
+DESIGN.md 6.15e) on the reordered graphs, both directions, N in {64, 256}, standard-normal X, under four node sets in the adjacency's
+numbering: (i) a contiguous eighth of the ids, (ii) a random eighth of the 128-id communities, (iii) a random eighth of the nodes - the
+worst case, every block stays live -, each as row and neighbour mask at once (the induced subgraph), and (iv) a random half of the nodes
+as the row mask alone. Three alternating loops: first (a) the plain launch, the four masked launches and (c) the masked launch with
+all-ones bitmaps; second (b), the route each masked launch replaces - filter the edge list by the two sets, pack_edges_tiled, (on adj.T:
+build the column index,) plain launch; third, forward plus backward of tiledAggregate with `sym` scales, plain and under (i) - (iii).
+Every masked sum is checked bit-equal to the plain launch on the re-packed adjacency before timing. Medians with their 10th and 90th
+percentiles, the share of live workgroups of each mask, and the ratios masked / (a) and masked / (b).
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes]
 """
 from __future__ import annotations
 
@@ -514,12 +524,96 @@ def drop_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def nodes_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+    from qgtc_ppopp22_amd.tiled import node_bitmap
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        # the set cells as an edge list in the adjacency's numbering (multiplicity 2 is unset, as the packer quantises it)
+        keys, counts = torch.unique(adj.rank.index_select(0, dsrc) * n + adj.rank.index_select(0, ddst), return_counts=True)
+        keys = keys[counts != 2]
+        e_row, e_col = (keys // n).contiguous(), (keys % n).contiguous()
+        mr = np.random.default_rng(11)
+        ids = np.arange(n)
+        quads = (n + 127) // 128
+        sets = {"contiguous_eighth": ids < n // 8,
+                "community_eighth": np.isin(ids // 128, mr.permutation(quads)[: max(1, quads // 8)]),
+                "random_eighth": mr.random(n) < 0.125,
+                "rows_half": mr.random(n) < 0.5}
+        ones = node_bitmap(torch.ones(n, dtype=torch.bool, device="cuda"), n)
+        masks = {}
+        for kind, f in sets.items():
+            fl = torch.from_numpy(f).cuda()
+            bm = node_bitmap(fl, n)
+            masks[kind] = (fl, None, bm, None) if kind == "rows_half" else (fl, fl, bm, bm)
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": int(keys.numel()), "tiles": adj.n_tiles,
+               "node_share": {k: round(float(f.mean()), 4) for k, f in sets.items()}, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {int(keys.numel())}", flush=True)
+        xr = np.random.default_rng(1)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                e_out, e_nbr = (e_col, e_row) if a.transposed else (e_row, e_col)
+
+                def induced(kind):
+                    R, S = masks[kind][:2]
+                    k = R[e_out] if S is None else R[e_out] & S[e_nbr]
+                    sub = QGTC.pack_edges_tiled(e_row[k], e_col[k], n, False)
+                    return sub.T if a.transposed else sub
+
+                def masked(kind):
+                    return lambda: QGTC.tiledMMFloat(a, X, row_mask=masks[kind][2], nbr_mask=masks[kind][3])
+
+                out = {"N": N, "direction": direction}
+                for kind in sets:
+                    assert torch.equal(masked(kind)().view(torch.int32), QGTC.tiledMMFloat(induced(kind), X).view(torch.int32)), (N, direction, kind)
+                    # one workgroup a k-quad on adj.T, a 32-row block on adj
+                    words = masks[kind][2].view(-1, 4) if a.transposed else masks[kind][2][: (n + 31) // 32].view(-1, 1)
+                    out[f"live_workgroups_{kind}"] = round(float((words != 0).any(dim=1).float().mean()), 4)
+                assert torch.equal(QGTC.tiledMMFloat(a, X, row_mask=ones, nbr_mask=ones).view(torch.int32), QGTC.tiledMMFloat(a, X).view(torch.int32))
+                kinds = list(sets)
+                ta, *tm, to = timed_alternating(torch, [lambda: QGTC.tiledMMFloat(a, X)] + [masked(k) for k in kinds]
+                                                + [lambda: QGTC.tiledMMFloat(a, X, row_mask=ones, nbr_mask=ones)], reps)
+                tr = timed_alternating(torch, [(lambda k=k: QGTC.tiledMMFloat(induced(k), X)) for k in kinds], reps)
+                r, c = a.sym_scale(), a.T.sym_scale()
+
+                def both(**kw):
+                    return lambda: torch.autograd.grad(QGTC.tiledAggregate(a, Xg, r, c, **kw), [Xg], dY)
+
+                fb = timed_alternating(torch, [both()] + [both(row_mask=masks[k][2], nbr_mask=masks[k][3]) for k in kinds[:3]], reps)
+                out.update({"plain_ms": ta, "all_ones_masked_ms": to, "all_ones_over_plain": round(to[0] / ta[0], 3), "sym_fwd_bwd_ms": fb[0]})
+                line = f"{name:9s} N={N:<4d} {direction:10s} plain {ta[0]:.4f} [{ta[1]:.4f}, {ta[2]:.4f}]  all ones {to[0]:.4f} ({to[0] / ta[0]:.3f}x)"
+                for i, k in enumerate(kinds):
+                    out.update({f"masked_{k}_ms": tm[i], f"filter_repack_plain_{k}_ms": tr[i], f"masked_{k}_over_plain": round(tm[i][0] / ta[0], 3),
+                                f"masked_{k}_over_repack": round(tm[i][0] / tr[i][0], 3)})
+                    line += f"  {k} {tm[i][0]:.4f} [{tm[i][1]:.4f}, {tm[i][2]:.4f}] ({tm[i][0] / ta[0]:.3f}x plain, {tm[i][0] / tr[i][0]:.3f}x repack {tr[i][0]:.4f})"
+                for i, k in enumerate(kinds[:3]):
+                    out.update({f"sym_fwd_bwd_{k}_ms": fb[i + 1], f"sym_fwd_bwd_{k}_over_plain": round(fb[i + 1][0] / fb[0][0], 3)})
+                    line += f"  fwd+bwd {k} {fb[i + 1][0]:.4f} / plain {fb[0][0]:.4f}"
+                rec["agg"].append(out)
+                print(line, flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, keys, e_row, e_col, masks
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes"))
     args = ap.parse_args()
 
     import torch
@@ -527,9 +621,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
