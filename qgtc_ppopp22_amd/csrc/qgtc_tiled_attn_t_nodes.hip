@@ -1,7 +1,7 @@
 // qgtc_tiled_attn_t_nodes.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the softmax-weighted sum over
 // the neighbours in nbr_mask, of the columns in row_mask of the tile-compressed adjacency, and its gradients on this view (the
-// instantiations of tiled_attn_t_kernels.hip.h with the node masks; include/qgtc.h, "Node masks"), and their
-// launchers. The masks are relative to the view: row_mask names output rows (A's columns).
+// instantiations of tiled_attn_t_kernels.hip.h with the node masks; include/qgtc.h, "Node masks").
+// The masks are relative to the view: row_mask names output rows (A's columns).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -18,80 +18,29 @@
 #include "tiled_attn_kernels.hip.h"
 #include "tiled_attn_t_kernels.hip.h"
 
-namespace {
-
-using Mask = TiledNodes;
-
-// the variant choices of qgtc_tiled_attn_t.hip
-template <bool BWD>
-int tiled_att_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
-                         int n, const float *X, int N, const TiledAtt &att, float *m, float *inv, float *out, const Mask &mask,
-                         hipStream_t st) {
-    const dim3 block(256);
-    const int width = N <= 16 ? 16 : (N <= 32 ? 32 : 64);
-    const dim3 grid(step128(n), (N + width - 1) / width);
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-#define QGTC_TILED_ATT_T_LAUNCH(CPL)                                                                                                   \
-    hipLaunchKernelGGL((k_tiled_att_f32_t<CPL, BWD, Mask>), grid, block, 0, st, col_ptr, col_tile, col_rb, tiles, nt, n, X, N, att, m, \
-                       inv, out, mask)
-    switch (width) {
-        case 16: QGTC_TILED_ATT_T_LAUNCH(1); break;
-        case 32: QGTC_TILED_ATT_T_LAUNCH(2); break;
-        default: QGTC_TILED_ATT_T_LAUNCH(4); break;
-    }
-#undef QGTC_TILED_ATT_T_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-template <bool NBR_OWNS>
-int tiled_att_grad_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
-                          int n, const float *A, const float *B, int N, const TiledAtt &att, float *out, const Mask &mask,
-                          hipStream_t st) {
-    const dim3 block(256), grid(step128(n));
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-    if (N <= 256)
-        hipLaunchKernelGGL((k_tiled_att_grad_t<true, NBR_OWNS, Mask>), grid, block, 0, st, col_ptr, col_tile, col_rb, tiles, nt, n, A, B, N,
-                           att, out, mask);
-    else
-        hipLaunchKernelGGL((k_tiled_att_grad_t<false, NBR_OWNS, Mask>), grid, block, 0, st, col_ptr, col_tile, col_rb, tiles, nt, n, A, B, N,
-                           att, out, mask);
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-}  // namespace
-
 int qgtc_tiledatt_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
-                             int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *att_own, const float *att_nbr,
-                             float negative_slope, int backward, const float *shift, float *m, float *inv, float *out, size_t out_elems,
-                             const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
-    if (backward < 0 || backward > 1) return QGTC_EINVAL;
-    const float *const vec[] = {att_own, att_nbr, shift, inv, backward ? shift : m};
-    int rc = tiled_att_args_ok(col_ptr && col_tile && col_rb, tiles, n_tiles, n, X, x_elems, N, out, out_elems,
-                                     static_cast<size_t>(N > 0 ? N : 0), negative_slope, vec);
+                              int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *att_own, const float *att_nbr,
+                              float negative_slope, int backward, const float *shift, float *m, float *inv, float *out, size_t out_elems,
+                              const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
+    const TiledColIndex ix{col_ptr, col_tile, col_rb};
+    int rc = tiled_att_f32_args_ok(ix.ok(), tiles, n_tiles, n, X, x_elems, N, att_own, att_nbr, negative_slope, backward, shift, m, inv, out,
+                                   out_elems);
     if (rc == QGTC_OK) rc = tiled_nodes_args_ok(row_mask, nbr_mask, mask_words, n);
     if (rc != QGTC_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const TiledAtt att{att_own, att_nbr, shift, backward ? inv : nullptr, nullptr, negative_slope};   // the forward only writes inv
-    const Mask mask{row_mask, nbr_mask};
-    return backward ? tiled_att_f32_t_nodes<true>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, att, nullptr, nullptr, out, mask, st)
-                    : tiled_att_f32_t_nodes<false>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, att, m, inv, out, mask, st);
+    return tiled_att_f32_run(ix, tiles, n_tiles, n, X, N, att_own, att_nbr, negative_slope, backward, shift, m, inv, out, stream,
+                             TiledNodes{row_mask, nbr_mask});
 }
 
 int qgtc_tiledatt_grad_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
-                                  int64_t n_tiles, int n, const float *A, const float *B, size_t ab_elems, int N, const float *att_own,
-                                  const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
-                                  const float *D, float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
-    if (nbr_owns < 0 || nbr_owns > 1) return QGTC_EINVAL;
-    const float *const vec[] = {B, att_own, att_nbr, m, inv, D};
-    int rc = tiled_att_args_ok(col_ptr && col_tile && col_rb, tiles, n_tiles, n, A, ab_elems, N, out, out_elems, 1, negative_slope,
-                                     vec);
+                                   int64_t n_tiles, int n, const float *A, const float *B, size_t ab_elems, int N, const float *att_own,
+                                   const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
+                                   const float *D, float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask,
+                                   size_t mask_words, void *stream) {
+    const TiledColIndex ix{col_ptr, col_tile, col_rb};
+    int rc = tiled_att_grad_args_ok(ix.ok(), tiles, n_tiles, n, A, B, ab_elems, N, att_own, att_nbr, negative_slope, nbr_owns, m, inv, D, out,
+                                    out_elems);
     if (rc == QGTC_OK) rc = tiled_nodes_args_ok(row_mask, nbr_mask, mask_words, n);
     if (rc != QGTC_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const TiledAtt att{att_own, att_nbr, m, inv, D, negative_slope};
-    const Mask mask{row_mask, nbr_mask};
-    return nbr_owns ? tiled_att_grad_t_nodes<true>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, A, B, N, att, out, mask, st)
-                    : tiled_att_grad_t_nodes<false>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, A, B, N, att, out, mask, st);
+    return tiled_att_grad_run(ix, tiles, n_tiles, n, A, B, N, att_own, att_nbr, negative_slope, nbr_owns, m, inv, D, out, stream,
+                             TiledNodes{row_mask, nbr_mask});
 }

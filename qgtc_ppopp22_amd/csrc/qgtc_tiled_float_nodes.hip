@@ -1,7 +1,7 @@
 // qgtc_tiled_float_nodes.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the float product of the
 // tile-compressed adjacency under node masks, out = diag(row_scale) . (A_tiled restricted to row_mask x nbr_mask) . diag(src_scale) . X
 // (the instantiations of tiled_float_kernels.hip.h whose pack ends in the masks; include/qgtc.h, "Node masks"; DESIGN.md section
-// 6.15e), its launcher, and the kernel that turns byte flags into a node bitmap.
+// 6.15e), and the kernel that turns byte flags into a node bitmap.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -14,29 +14,6 @@
 #include "tiled_float_kernels.hip.h"
 
 namespace {
-
-// the variant choice of qgtc_tiled_float.hip's tiled_mm_f32; the pack is (src_scale, masks) or (masks)
-template <bool SCALED, class... Src>
-int tiled_mm_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N,
-                      const float *row_scale, float *out, hipStream_t st, Src... src) {
-    const dim3 block(256);
-    const int width = N <= 16 ? 16 : (N <= 32 ? 32 : (N <= 64 ? 64 : (N <= 128 ? 128 : 256)));   // output columns per workgroup
-    const dim3 grid((n + 31) / 32, (N + width - 1) / width);
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-#define QGTC_TILED_F32_LAUNCH(LPR, CPL)                                                                                               \
-    hipLaunchKernelGGL((k_tiled_mm_f32<LPR, CPL, SCALED, Src...>), grid, block, 0, st, row_ptr, kquad, tiles, nt, n, X, N, row_scale, \
-                       out, src...)
-    switch (width) {
-        case 16: QGTC_TILED_F32_LAUNCH(16, 1); break;
-        case 32: QGTC_TILED_F32_LAUNCH(16, 2); break;
-        case 64: QGTC_TILED_F32_LAUNCH(16, 4); break;
-        case 128: QGTC_TILED_F32_LAUNCH(32, 4); break;
-        default: QGTC_TILED_F32_LAUNCH(64, 4); break;
-    }
-#undef QGTC_TILED_F32_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
 
 // one thread a word: flags 32 w .. 32 w + 31, MSB first; flags from n up do not exist and give zero bits, so pad bits and pad words are 0
 __global__ __launch_bounds__(256) void k_node_bitmap(const uint8_t *__restrict__ flags, int n, uint32_t *__restrict__ words, int n_words) {
@@ -65,14 +42,9 @@ int qgtc_node_bitmap(const uint8_t *flags, int n, uint32_t *words, size_t words_
 int qgtc_tiledmm_f32_nodes(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
                            size_t x_elems, int N, const float *row_scale, const float *src_scale, float *out, size_t out_elems,
                            const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
-    int rc = tiled_f32_args_ok(row_ptr && kquad, tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems, src_scale);
+    const TiledRowIndex ix{row_ptr, kquad};
+    int rc = tiled_f32_args_ok(ix.ok(), tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems, src_scale);
     if (rc == QGTC_OK) rc = tiled_nodes_args_ok(row_mask, nbr_mask, mask_words, n);
     if (rc != QGTC_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const TiledNodes mask{row_mask, nbr_mask};
-    if (src_scale)
-        return row_scale ? tiled_mm_f32_nodes<true>(row_ptr, kquad, tiles, n_tiles, n, X, N, row_scale, out, st, src_scale, mask)
-                         : tiled_mm_f32_nodes<false>(row_ptr, kquad, tiles, n_tiles, n, X, N, nullptr, out, st, src_scale, mask);
-    return row_scale ? tiled_mm_f32_nodes<true>(row_ptr, kquad, tiles, n_tiles, n, X, N, row_scale, out, st, mask)
-                     : tiled_mm_f32_nodes<false>(row_ptr, kquad, tiles, n_tiles, n, X, N, nullptr, out, st, mask);
+    return tiled_mm_f32_masked(ix, tiles, n_tiles, n, X, N, row_scale, src_scale, out, stream, TiledNodes{row_mask, nbr_mask});
 }

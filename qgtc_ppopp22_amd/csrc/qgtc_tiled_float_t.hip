@@ -1,6 +1,6 @@
 // qgtc_tiled_float_t.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the transposed product of the
 // tile-compressed adjacency with a float32 right operand, out = A_tiled^T . X with an optional per-row scale
-// (tiled_float_t_kernels.hip.h), and its launcher.
+// (tiled_float_t_kernels.hip.h, which has its launcher).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -15,36 +15,10 @@
 #include "tiled_float_kernels.hip.h"
 #include "tiled_float_t_kernels.hip.h"
 
-namespace {
-
-// columns per lane by N (16 lanes per output row); past 64 columns the output is cut into 64-column chunks
-// (tests/tiled_float_model.py, FLOAT_TRANSPOSED_VARIANTS, states the same choice)
-template <bool SCALED>
-int tiled_mm_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
-                   int n, const float *X, int N, const float *row_scale, float *out, hipStream_t st) {
-    const dim3 block(256);
-    const int width = N <= 16 ? 16 : (N <= 32 ? 32 : 64);
-    const dim3 grid(step128(n), (N + width - 1) / width);
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-#define QGTC_TILED_F32_T_LAUNCH(CPL) \
-    hipLaunchKernelGGL((k_tiled_mm_f32_t<16, CPL, SCALED>), grid, block, 0, st, col_ptr, col_tile, col_rb, tiles, nt, n, X, N, row_scale, out)
-    switch (width) {
-        case 16: QGTC_TILED_F32_T_LAUNCH(1); break;
-        case 32: QGTC_TILED_F32_T_LAUNCH(2); break;
-        default: QGTC_TILED_F32_T_LAUNCH(4); break;
-    }
-#undef QGTC_TILED_F32_T_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-}  // namespace
-
 int qgtc_tiledmm_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
                        int n, const float *X, size_t x_elems, int N, const float *row_scale, float *out, size_t out_elems, void *stream) {
-    const int rc = tiled_f32_args_ok(col_ptr && col_tile && col_rb, tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems);
+    const TiledColIndex ix{col_ptr, col_tile, col_rb};
+    const int rc = tiled_f32_args_ok(ix.ok(), tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems);
     if (rc != QGTC_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    return row_scale ? tiled_mm_f32_t<true>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, row_scale, out, st)
-                     : tiled_mm_f32_t<false>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, nullptr, out, st);
+    return tiled_mm_f32_run(ix, tiles, n_tiles, n, X, N, row_scale, out, stream);
 }

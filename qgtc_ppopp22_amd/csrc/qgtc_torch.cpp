@@ -634,9 +634,16 @@ const uint32_t *tiled_node_mask(const c10::optional<torch::Tensor> &mask, const 
     return words(m);
 }
 
-torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
-                               const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+// The adjacency of the float-family bindings below, checked and as the raw pointers of its view (the bindings take them apart:
+// `const auto [rp, kq, tw, T] = ...`); without tiles (T = 0) the per-tile pointers are null. What a binding checks of its other
+// arguments comes after this, in the binding.
+struct TiledRowView {
+    const int64_t *row_ptr;
+    const int32_t *kquad;
+    const uint32_t *tiles;
+    int64_t T;
+};
+TiledRowView tiled_row_view(const torch::Tensor &row_ptr, const torch::Tensor &kquad, const torch::Tensor &tiles, const int64_t n) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
     CHECK_INPUT(tiles);
@@ -646,15 +653,45 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
     TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
     TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
     TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    const int64_t T = kquad.numel();
+    return {row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T};
+}
+
+struct TiledColView {
+    const int64_t *col_ptr, *col_tile;
+    const int32_t *col_rb;
+    const uint32_t *tiles;
+    int64_t T;
+};
+TiledColView tiled_col_view(const torch::Tensor &col_ptr, const torch::Tensor &col_tile, const torch::Tensor &col_rb,
+                            const torch::Tensor &tiles, const int64_t n) {
+    CHECK_INPUT(col_ptr);
+    CHECK_INPUT(col_tile);
+    CHECK_INPUT(col_rb);
+    CHECK_INPUT(tiles);
+    check_bits_tensor(tiles, "tiles");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
+                "col_ptr and col_tile must be int64, col_rb int32");
+    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
+    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
+    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
+                "col_tile, col_rb and tiles must list the same tiles");
+    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
+                "the adjacency must be on one device");
+    const int64_t T = col_tile.numel();
+    return {col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr, T ? col_rb.data_ptr<int32_t>() : nullptr,
+            T ? words(tiles) : nullptr, T};
+}
+
+torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
+                               const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
     check_float_operand(X, n, row_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     c10::DeviceGuard guard(X.device());
-    const int64_t T = kquad.numel();
     const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int64_t *rp = row_ptr.data_ptr<int64_t>();
-    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
     TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
     if (node_masks)
@@ -686,28 +723,12 @@ torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Te
 torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
                                  torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
                                  const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    CHECK_INPUT(col_ptr);
-    CHECK_INPUT(col_tile);
-    CHECK_INPUT(col_rb);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
-                "col_ptr and col_tile must be int64, col_rb int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
-    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
-                "col_tile, col_rb and tiles must list the same tiles");
-    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
-                "the adjacency must be on one device");
+    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
     check_float_operand(X, n, col_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     c10::DeviceGuard guard(X.device());
-    const int64_t T = col_tile.numel();
     const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int64_t *cp = col_ptr.data_ptr<int64_t>(), *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
-    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
     TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
     if (node_masks)
@@ -759,15 +780,7 @@ int tiled_reduce_code(const std::string &reduce, const c10::optional<torch::Tens
 std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
                                          const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg,
                                          const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    CHECK_INPUT(row_ptr);
-    CHECK_INPUT(kquad);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
-    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
     check_float_operand(X, n, row_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
@@ -776,11 +789,7 @@ std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kq
     TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
     const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
     c10::DeviceGuard guard(X.device());
-    const int64_t T = kquad.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int64_t *rp = row_ptr.data_ptr<int64_t>();
-    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
     if (code == 2) {
         check_rc(qgtc_tiledsel_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
@@ -814,19 +823,7 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
                                            const int64_t n, torch::Tensor X, const std::string &reduce,
                                            const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop,
                                            const NodeMasks &node_masks) {
-    CHECK_INPUT(col_ptr);
-    CHECK_INPUT(col_tile);
-    CHECK_INPUT(col_rb);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
-                "col_ptr and col_tile must be int64, col_rb int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
-    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
-                "col_tile, col_rb and tiles must list the same tiles");
-    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
-                "the adjacency must be on one device");
+    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
     check_float_operand(X, n, col_ptr);
     TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
@@ -835,11 +832,7 @@ std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor 
     TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
     const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
     c10::DeviceGuard guard(X.device());
-    const int64_t T = col_tile.numel();
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int64_t *cp = col_ptr.data_ptr<int64_t>(), *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
-    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
     const int N = static_cast<int>(X.size(1));
     if (code == 2) {
         check_rc(qgtc_tiledsel_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
@@ -929,98 +922,73 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     TORCH_CHECK(slope >= 0.0f && slope <= 1.0f, "negative_slope must lie in [0, 1]");
     const float *own = tiled_att_vector(att_own, "att_own", n, X), *nbr = tiled_att_vector(att_nbr, "att_nbr", n, X);
     const float *sh = tiled_att_vector(shift, "shift", n, X);
-    const int64_t *p0 = static_cast<const int64_t *>(i0);
+    // row view: row_ptr, kquad; column view: col_ptr, col_tile, col_rb
+    const int64_t *p0 = static_cast<const int64_t *>(i0), *ct = static_cast<const int64_t *>(i1);
+    const int32_t *kq = static_cast<const int32_t *>(i1), *cr = static_cast<const int32_t *>(i2);
+    // the sum, forward (backward 0: m and inv are written) or backward (1: no m, inv is read): one entry per mask and view
+    const auto sum = [&](const int backward, float *m, float *iv, torch::Tensor &out) {
+        float *o = out.data_ptr<float>();
+        const size_t on = out.numel(), xn = X.numel();
+        if (nodes && transposed)
+            check_rc(qgtc_tiledatt_f32_t_nodes(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, rmask, nmask,
+                                               mask_words, st),
+                     backward ? "tiledMMFloat (transposed, attention backward, node masks)"
+                              : "tiledMMFloat (transposed, attention, node masks)");
+        else if (nodes)
+            check_rc(qgtc_tiledatt_f32_nodes(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, rmask, nmask, mask_words,
+                                             st),
+                     backward ? "tiledMMFloat (attention backward, node masks)" : "tiledMMFloat (attention, node masks)");
+        else if (drop && transposed)
+            check_rc(qgtc_tiledatt_f32_t_drop(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, dt, ds, st),
+                     backward ? "tiledMMFloat (transposed, attention backward, edge dropout)"
+                              : "tiledMMFloat (transposed, attention, edge dropout)");
+        else if (drop)
+            check_rc(qgtc_tiledatt_f32_drop(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, dt, ds, st),
+                     backward ? "tiledMMFloat (attention backward, edge dropout)" : "tiledMMFloat (attention, edge dropout)");
+        else if (transposed)
+            check_rc(qgtc_tiledatt_f32_t(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, st),
+                     backward ? "tiledMMFloat (transposed, attention backward)" : "tiledMMFloat (transposed, attention)");
+        else
+            check_rc(qgtc_tiledatt_f32(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, st),
+                     backward ? "tiledMMFloat (attention backward)" : "tiledMMFloat (attention)");
+    };
     if (mode == 0) {
         TORCH_CHECK(!inv.has_value() && !other.has_value() && !D.has_value(), "att_mode=\"forward\" takes no inv, other or D");
         auto out = torch::empty({n, X.size(1)}, f32), m = torch::empty({n}, f32), iv = torch::empty({n}, f32);
-        if (nodes && transposed)
-            check_rc(qgtc_tiledatt_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
-                                               N, own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
-                                               out.numel(), rmask, nmask, mask_words, st),
-                     "tiledMMFloat (transposed, attention, node masks)");
-        else if (nodes)
-            check_rc(qgtc_tiledatt_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
-                                             m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), rmask, nmask,
-                                             mask_words, st),
-                     "tiledMMFloat (attention, node masks)");
-        else if (drop && transposed)
-            check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
-                                              N, own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
-                                              out.numel(), dt, ds, st),
-                     "tiledMMFloat (transposed, attention, edge dropout)");
-        else if (drop)
-            check_rc(qgtc_tiledatt_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
-                                            m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), dt, ds, st),
-                     "tiledMMFloat (attention, edge dropout)");
-        else if (transposed)
-            check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
-                                         own, nbr, slope, 0, sh, m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(),
-                                         out.numel(), st),
-                     "tiledMMFloat (transposed, attention)");
-        else
-            check_rc(qgtc_tiledatt_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 0, sh,
-                                       m.data_ptr<float>(), iv.data_ptr<float>(), out.data_ptr<float>(), out.numel(), st),
-                     "tiledMMFloat (attention)");
+        sum(0, m.data_ptr<float>(), iv.data_ptr<float>(), out);
         return {out, m, iv};
     }
     float *ivp = const_cast<float *>(tiled_att_vector(inv, "inv", n, X));   // read only in these modes
     if (mode == 1) {
         TORCH_CHECK(!other.has_value() && !D.has_value(), "att_mode=\"backward\" takes no other or D");
         auto out = torch::empty({n, X.size(1)}, f32);
-        if (nodes && transposed)
-            check_rc(qgtc_tiledatt_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
-                                               N, own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), rmask, nmask,
-                                               mask_words, st),
-                     "tiledMMFloat (transposed, attention backward, node masks)");
-        else if (nodes)
-            check_rc(qgtc_tiledatt_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
-                                             ivp, out.data_ptr<float>(), out.numel(), rmask, nmask, mask_words, st),
-                     "tiledMMFloat (attention backward, node masks)");
-        else if (drop && transposed)
-            check_rc(qgtc_tiledatt_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(),
-                                              N, own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), dt, ds, st),
-                     "tiledMMFloat (transposed, attention backward, edge dropout)");
-        else if (drop)
-            check_rc(qgtc_tiledatt_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
-                                            ivp, out.data_ptr<float>(), out.numel(), dt, ds, st),
-                     "tiledMMFloat (attention backward, edge dropout)");
-        else if (transposed)
-            check_rc(qgtc_tiledatt_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, X.numel(), N,
-                                         own, nbr, slope, 1, sh, nullptr, ivp, out.data_ptr<float>(), out.numel(), st),
-                     "tiledMMFloat (transposed, attention backward)");
-        else
-            check_rc(qgtc_tiledatt_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, X.numel(), N, own, nbr, slope, 1, sh, nullptr,
-                                       ivp, out.data_ptr<float>(), out.numel(), st),
-                     "tiledMMFloat (attention backward)");
+        sum(1, nullptr, ivp, out);
         return {out};
     }
     const float *b = tiled_att_other(other, X), *d = tiled_att_vector(D, "D", n, X);
     auto out = torch::empty({n}, f32);
+    float *o = out.data_ptr<float>();
+    const size_t on = out.numel(), xn = X.numel();
+    const int nbr_owns = mode == 3;
     if (nodes && transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t_nodes(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b,
-                                                X.numel(), N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(),
-                                                rmask, nmask, mask_words, st),
+        check_rc(qgtc_tiledatt_grad_f32_t_nodes(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, rmask, nmask,
+                                                mask_words, st),
                  "tiledMMFloat (transposed, attention score gradient, node masks)");
     else if (nodes)
-        check_rc(qgtc_tiledatt_grad_f32_nodes(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3,
-                                              sh, ivp, d, out.data_ptr<float>(), out.numel(), rmask, nmask, mask_words, st),
+        check_rc(qgtc_tiledatt_grad_f32_nodes(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, rmask, nmask,
+                                              mask_words, st),
                  "tiledMMFloat (attention score gradient, node masks)");
     else if (drop && transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t_drop(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b,
-                                               X.numel(), N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), dt,
-                                               ds, st),
+        check_rc(qgtc_tiledatt_grad_f32_t_drop(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, dt, ds, st),
                  "tiledMMFloat (transposed, attention score gradient, edge dropout)");
     else if (drop)
-        check_rc(qgtc_tiledatt_grad_f32_drop(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3,
-                                             sh, ivp, d, out.data_ptr<float>(), out.numel(), dt, ds, st),
+        check_rc(qgtc_tiledatt_grad_f32_drop(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, dt, ds, st),
                  "tiledMMFloat (attention score gradient, edge dropout)");
     else if (transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t(p0, static_cast<const int64_t *>(i1), static_cast<const int32_t *>(i2), tw, T, nn, x, b, X.numel(),
-                                          N, own, nbr, slope, mode == 3, sh, ivp, d, out.data_ptr<float>(), out.numel(), st),
+        check_rc(qgtc_tiledatt_grad_f32_t(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, st),
                  "tiledMMFloat (transposed, attention score gradient)");
     else
-        check_rc(qgtc_tiledatt_grad_f32(p0, static_cast<const int32_t *>(i1), tw, T, nn, x, b, X.numel(), N, own, nbr, slope, mode == 3, sh,
-                                        ivp, d, out.data_ptr<float>(), out.numel(), st),
+        check_rc(qgtc_tiledatt_grad_f32(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, st),
                  "tiledMMFloat (attention score gradient)");
     return {out};
 }
@@ -1031,19 +999,10 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
                                          const c10::optional<torch::Tensor> &shift, const c10::optional<torch::Tensor> &inv,
                                          const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D,
                                          const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    CHECK_INPUT(row_ptr);
-    CHECK_INPUT(kquad);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
-    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
     check_float_operand(X, n, row_ptr);
-    const int64_t T = kquad.numel();
-    return tiled_att_run(false, row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, nullptr, T ? words(tiles) : nullptr, T,
-                         n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop, node_masks);
+    return tiled_att_run(false, rp, kq, nullptr, tw, T, n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop,
+                         node_masks);
 }
 
 std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
@@ -1052,24 +1011,10 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
                                            const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                            const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
                                            const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    CHECK_INPUT(col_ptr);
-    CHECK_INPUT(col_tile);
-    CHECK_INPUT(col_rb);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
-                "col_ptr and col_tile must be int64, col_rb int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
-    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
-                "col_tile, col_rb and tiles must list the same tiles");
-    TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
-                "the adjacency must be on one device");
+    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
     check_float_operand(X, n, col_ptr);
-    const int64_t T = col_tile.numel();
-    return tiled_att_run(true, col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
-                         T ? col_rb.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T, n, X, att_mode, att_own, att_nbr,
-                         negative_slope, shift, inv, other, D, edge_drop, node_masks);
+    return tiled_att_run(true, cp, ct, cr, tw, T, n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop,
+                         node_masks);
 }
 
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)

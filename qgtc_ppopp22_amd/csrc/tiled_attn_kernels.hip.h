@@ -1,7 +1,8 @@
 // tiled_attn_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_attn.hip and qgtc_tiled_attn_t.hip, after
 // tiled_float_kernels.hip.h and tiled_max_kernels.hip.h): the softmax-weighted sum over a row's neighbours on the tile-compressed 1-bit
 // adjacency, as in GAT, and its three gradients (include/qgtc.h, "Attention tiled products") - the fixed
-// float32 exponential, the weight of an edge, the in-order adders, the kernels on the row view, the row dot and the argument checks.
+// float32 exponential, the weight of an edge, the in-order adders, the kernels on the row view, the row dot, the argument checks
+// and the launchers.
 //
 // The walk is the float product's (tiled_float_kernels.hip.h): a tile is read as a compressed neighbour list, decoded MSB first =
 // ascending neighbour id, the ids are queued in LDS and the addressed rows are loaded TILED_F32_AHEAD at a time. The weight of edge
@@ -440,6 +441,73 @@ inline int tiled_att_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_til
     const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);
     if (x_elems < need || out_elems < static_cast<size_t>(n) * out_need_cols) return QGTC_ESIZE;
     return QGTC_OK;
+}
+
+// what qgtc_tiledatt_f32 / qgtc_tiledatt_grad_f32 and their twins on either view and under either mask check of their own arguments
+inline int tiled_att_f32_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, size_t x_elems, int N,
+                                 const float *att_own, const float *att_nbr, float negative_slope, int backward, const float *shift,
+                                 const float *m, const float *inv, const float *out, size_t out_elems) {
+    if (backward < 0 || backward > 1) return QGTC_EINVAL;
+    const float *const vec[] = {att_own, att_nbr, shift, inv, backward ? shift : m};
+    return tiled_att_args_ok(index_ok, tiles, n_tiles, n, X, x_elems, N, out, out_elems, static_cast<size_t>(N > 0 ? N : 0), negative_slope,
+                             vec);
+}
+inline int tiled_att_grad_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const float *A, const float *B,
+                                  size_t ab_elems, int N, const float *att_own, const float *att_nbr, float negative_slope, int nbr_owns,
+                                  const float *m, const float *inv, const float *D, const float *out, size_t out_elems) {
+    if (nbr_owns < 0 || nbr_owns > 1) return QGTC_EINVAL;
+    const float *const vec[] = {B, att_own, att_nbr, m, inv, D};
+    return tiled_att_args_ok(index_ok, tiles, n_tiles, n, A, ab_elems, N, out, out_elems, 1, negative_slope, vec);
+}
+
+// ---- the launchers of k_tiled_att_f32 (the shapes are the float product's: tiled_row_width_switch) and k_tiled_att_grad ------------------
+template <bool BWD, class... Drop>
+int tiled_att_f32_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, const TiledAtt &att,
+                         float *m, float *inv, float *out, hipStream_t st, Drop... drop) {
+    tiled_row_width_switch(N, [&](auto lpr, auto cpl) {
+        constexpr int LPR = decltype(lpr)::value, CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_att_f32<LPR, CPL, BWD, Drop...>), tiled_row_grid(n, N, LPR * CPL), dim3(256), 0, st, ix.row_ptr, ix.kquad,
+                           tiles, static_cast<uint64_t>(n_tiles), n, X, N, att, m, inv, out, drop...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// the out node's row in registers (REG) up to N = 256, read again per neighbour beyond (tests/tiled_attn_model.py, ATT_GRAD_VARIANTS)
+template <bool NBR_OWNS, class... Drop>
+int tiled_att_grad_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *A, const float *B, int N,
+                          const TiledAtt &att, float *out, hipStream_t st, Drop... drop) {
+    const dim3 block(256), grid((n + 31) / 32);
+    const uint64_t nt = static_cast<uint64_t>(n_tiles);
+    if (N <= 256)
+        hipLaunchKernelGGL((k_tiled_att_grad<true, NBR_OWNS, Drop...>), grid, block, 0, st, ix.row_ptr, ix.kquad, tiles, nt, n, A, B, N, att,
+                           out, drop...);
+    else
+        hipLaunchKernelGGL((k_tiled_att_grad<false, NBR_OWNS, Drop...>), grid, block, 0, st, ix.row_ptr, ix.kquad, tiles, nt, n, A, B, N, att,
+                           out, drop...);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// ---- what the attention entries run on either view (`Index`) after their argument checks, under the mask in the pack if there is one ----
+template <class Index, class... Drop>
+int tiled_att_f32_run(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, const float *att_own,
+                      const float *att_nbr, float negative_slope, int backward, const float *shift, float *m, float *inv, float *out,
+                      void *stream, Drop... drop) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const TiledAtt att{att_own, att_nbr, shift, backward ? inv : nullptr, nullptr, negative_slope};   // the forward only writes inv
+    return backward ? tiled_att_f32_launch<true>(ix, tiles, n_tiles, n, X, N, att, nullptr, nullptr, out, st, drop...)
+                    : tiled_att_f32_launch<false>(ix, tiles, n_tiles, n, X, N, att, m, inv, out, st, drop...);
+}
+
+template <class Index, class... Drop>
+int tiled_att_grad_run(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *A, const float *B, int N,
+                       const float *att_own, const float *att_nbr, float negative_slope, int nbr_owns, const float *m, const float *inv,
+                       const float *D, float *out, void *stream, Drop... drop) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const TiledAtt att{att_own, att_nbr, m, inv, D, negative_slope};
+    return nbr_owns ? tiled_att_grad_launch<true>(ix, tiles, n_tiles, n, A, B, N, att, out, st, drop...)
+                    : tiled_att_grad_launch<false>(ix, tiles, n_tiles, n, A, B, N, att, out, st, drop...);
 }
 
 }  // namespace

@@ -237,4 +237,34 @@ __global__ __launch_bounds__(256) void k_tiled_att_grad_t(const int64_t *__restr
     if (tid < 128 && q * 128 + tid < n) out[q * 128 + tid] = acc[tid];
 }
 
+// ---- the launchers of k_tiled_att_f32_t (the shapes are the transposed float product's: tiled_col_width_switch) and k_tiled_att_grad_t:
+// tiled_att_f32_launch and tiled_att_grad_launch on the column view ------------------------------------------------------------------------
+template <bool BWD, class... Drop>
+int tiled_att_f32_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, const TiledAtt &att,
+                         float *m, float *inv, float *out, hipStream_t st, Drop... drop) {
+    tiled_col_width_switch(N, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_att_f32_t<CPL, BWD, Drop...>), tiled_col_grid(n, N, 16 * CPL), dim3(256), 0, st, ix.col_ptr, ix.col_tile,
+                           ix.col_rb, tiles, static_cast<uint64_t>(n_tiles), n, X, N, att, m, inv, out, drop...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// REG as on the row view (tests/tiled_attn_model.py, ATT_GRAD_VARIANTS)
+template <bool NBR_OWNS, class... Drop>
+int tiled_att_grad_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *A, const float *B, int N,
+                          const TiledAtt &att, float *out, hipStream_t st, Drop... drop) {
+    const dim3 block(256), grid(step128(n));
+    const uint64_t nt = static_cast<uint64_t>(n_tiles);
+    if (N <= 256)
+        hipLaunchKernelGGL((k_tiled_att_grad_t<true, NBR_OWNS, Drop...>), grid, block, 0, st, ix.col_ptr, ix.col_tile, ix.col_rb, tiles, nt, n,
+                           A, B, N, att, out, drop...);
+    else
+        hipLaunchKernelGGL((k_tiled_att_grad_t<false, NBR_OWNS, Drop...>), grid, block, 0, st, ix.col_ptr, ix.col_tile, ix.col_rb, tiles, nt, n,
+                           A, B, N, att, out, drop...);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
 }  // namespace

@@ -1,7 +1,8 @@
 // tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float.hip, qgtc_tiled_float_t.hip and their _src twins): the
 // product of the tile-compressed 1-bit adjacency with a FLOAT32 right operand, out = A_tiled . X (include/qgtc.h, "Float tiled
-// products"; DESIGN.md sections 6.14, 6.15) - the in-order row adder both directions share, the forward kernel and the argument checks
-// of the entries.
+// products"; DESIGN.md sections 6.14, 6.15) - the in-order row adder both directions share, the forward kernel, the argument checks
+// of the entries and, for every float, extremum and attention unit, the host side of a launch: the views' index structs, the kernel
+// shapes by N and this family's launcher.
 //
 // The bit products AND + popcount whole 128-bit tile rows because their operand is bit planes. Here the operand is floats and the
 // tiles of real graphs are nearly empty (about 9 of 4096 cells), so a tile is read as a compressed neighbour list: the set bits of a
@@ -16,6 +17,8 @@
 // the node masks (tiled_nodes.hip.h): the neighbour bitmap is ANDed into the tile words before they are decoded,
 // and a workgroup without a live output row walks nothing.
 #pragma once
+
+#include <type_traits>
 
 #include "tiled_drop.hip.h"
 #include "tiled_nodes.hip.h"
@@ -195,6 +198,89 @@ inline int tiled_f32_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_til
     const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);
     if (x_elems < need || out_elems < need) return QGTC_ESIZE;
     return QGTC_OK;
+}
+
+// ---- the host side every float, extremum and attention unit shares: the two views' index arrays and their kernel shapes by N -----------
+// Each kernel family has ONE launcher, at the foot of the family's header; it ends in the kernel's own trailing pack and forwards it, so
+// a masked launch takes the shape its plain parent takes. The launchers of the two views are overloads on
+// these structs, and the templates above them are written once for both views.
+struct TiledRowIndex {
+    const int64_t *row_ptr;
+    const int32_t *kquad;
+    bool ok() const { return row_ptr && kquad; }   // the `index_ok` of the argument checks
+};
+struct TiledColIndex {
+    const int64_t *col_ptr, *col_tile;
+    const int32_t *col_rb;
+    bool ok() const { return col_ptr && col_tile && col_rb; }
+};
+
+template <int V>
+using tiled_int = std::integral_constant<int, V>;
+
+// The row view: lanes per output row (LPR) and columns per lane (CPL) by N, for the float sum, the extremum / select and the attention
+// sum alike; launch(LPR, CPL) gets them as integral constants and makes one workgroup per 32-row block and LPR * CPL output columns
+// (tiled_row_grid). tests/tiled_float_model.py FLOAT_FORWARD_VARIANTS, tiled_max_model.py MAX_FORWARD_VARIANTS and tiled_attn_model.py
+// ATT_FORWARD_VARIANTS state the same choice.
+template <class F>
+void tiled_row_width_switch(int N, F &&launch) {
+    const int width = N <= 16 ? 16 : (N <= 32 ? 32 : (N <= 64 ? 64 : (N <= 128 ? 128 : 256)));   // output columns per workgroup
+    switch (width) {
+        case 16: launch(tiled_int<16>{}, tiled_int<1>{}); break;
+        case 32: launch(tiled_int<16>{}, tiled_int<2>{}); break;
+        case 64: launch(tiled_int<16>{}, tiled_int<4>{}); break;
+        case 128: launch(tiled_int<32>{}, tiled_int<4>{}); break;
+        default: launch(tiled_int<64>{}, tiled_int<4>{}); break;
+    }
+}
+inline dim3 tiled_row_grid(int n, int N, int width) { return dim3((n + 31) / 32, (N + width - 1) / width); }
+
+// The column view: 16 lanes per output row and CPL columns per lane by N, one workgroup per k-quad and 16 * CPL output columns
+// (tiled_col_grid); past WIDEST columns the output is cut into chunks of WIDEST. The float sum, the select and the attention sum go to
+// 64; the extremum keeps two words of state a column and stops at 32. tests/tiled_float_model.py FLOAT_TRANSPOSED_VARIANTS,
+// tiled_max_model.py MAX_TRANSPOSED_VARIANTS / SELECT_TRANSPOSED_VARIANTS and tiled_attn_model.py ATT_TRANSPOSED_VARIANTS state the same.
+template <int WIDEST = 64, class F>
+void tiled_col_width_switch(int N, F &&launch) {
+    static_assert(WIDEST == 32 || WIDEST == 64, "16 lanes a row, 2 or 4 columns a lane at the most");
+    const int width = N <= 16 ? 16 : (N <= 32 ? 32 : WIDEST);
+    switch (width) {
+        case 16: launch(tiled_int<1>{}); break;
+        case 32: launch(tiled_int<2>{}); break;
+        default:
+            if constexpr (WIDEST == 64) launch(tiled_int<4>{});
+            break;
+    }
+}
+inline dim3 tiled_col_grid(int n, int N, int width) { return dim3(step128(n), (N + width - 1) / width); }
+
+// ---- the launcher of k_tiled_mm_f32 and what the entries of the float sum share -------------------------------------------------------
+template <bool SCALED, class... Pack>
+int tiled_mm_f32_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N,
+                        const float *row_scale, float *out, hipStream_t st, Pack... pack) {
+    tiled_row_width_switch(N, [&](auto lpr, auto cpl) {
+        constexpr int LPR = decltype(lpr)::value, CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_mm_f32<LPR, CPL, SCALED, Pack...>), tiled_row_grid(n, N, LPR * CPL), dim3(256), 0, st, ix.row_ptr,
+                           ix.kquad, tiles, static_cast<uint64_t>(n_tiles), n, X, N, row_scale, out, pack...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// either view (`Index`), after the argument checks: SCALED by row_scale, the pack - nothing, (src_scale), (mask) or (src_scale, mask) -
+// as the caller made it. An entry instantiates the kernels of the packs it passes and no others.
+template <class Index, class... Pack>
+int tiled_mm_f32_run(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, const float *row_scale,
+                     float *out, void *stream, Pack... pack) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return row_scale ? tiled_mm_f32_launch<true>(ix, tiles, n_tiles, n, X, N, row_scale, out, st, pack...)
+                     : tiled_mm_f32_launch<false>(ix, tiles, n_tiles, n, X, N, nullptr, out, st, pack...);
+}
+// under a mask the source scale is optional: it joins the pack when it is there
+template <class Index, class Mask>
+int tiled_mm_f32_masked(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, const float *row_scale,
+                        const float *src_scale, float *out, void *stream, const Mask &mask) {
+    return src_scale ? tiled_mm_f32_run(ix, tiles, n_tiles, n, X, N, row_scale, out, stream, src_scale, mask)
+                     : tiled_mm_f32_run(ix, tiles, n_tiles, n, X, N, row_scale, out, stream, mask);
 }
 
 }  // namespace

@@ -140,4 +140,18 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
     }
 }
 
+// ---- the launcher of k_tiled_mm_f32_t: tiled_mm_f32_launch on the column view (tiled_float_kernels.hip.h has the row view's and the
+// templates the entries of both views share) ----------------------------------------------------------------------------------------------
+template <bool SCALED, class... Pack>
+int tiled_mm_f32_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N,
+                        const float *row_scale, float *out, hipStream_t st, Pack... pack) {
+    tiled_col_width_switch(N, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_mm_f32_t<16, CPL, SCALED, Pack...>), tiled_col_grid(n, N, 16 * CPL), dim3(256), 0, st, ix.col_ptr,
+                           ix.col_tile, ix.col_rb, tiles, static_cast<uint64_t>(n_tiles), n, X, N, row_scale, out, pack...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
 }  // namespace

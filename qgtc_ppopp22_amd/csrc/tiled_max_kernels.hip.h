@@ -1,7 +1,7 @@
 // tiled_max_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_max.hip and qgtc_tiled_max_t.hip, after
 // tiled_float_kernels.hip.h): the element-wise maximum / minimum over a row's neighbours on the tile-compressed 1-bit adjacency and the
 // gather that is its gradient (include/qgtc.h, "Extremum tiled products") - the two reducers, the in-order fold
-// both directions share, the kernel on the row view and the argument checks of the entries.
+// both directions share, the kernel on the row view, the argument checks of the entries and the launcher.
 //
 // The walk is the float product's (tiled_float_kernels.hip.h): a tile is read as a compressed neighbour list, decoded MSB first =
 // ascending neighbour id, the ids are queued in LDS and the addressed rows are loaded TILED_F32_AHEAD at a time. What changes is what
@@ -235,6 +235,28 @@ inline int tiled_red_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_til
     if (rc != QGTC_OK) return rc;
     if (arg && arg_elems < static_cast<size_t>(n) * static_cast<size_t>(N)) return QGTC_ESIZE;
     return QGTC_OK;
+}
+
+// ---- the launcher of k_tiled_red_f32 (the shapes are the float product's: tiled_row_width_switch) and the extremum entries' choice --------
+template <class Red, class... Drop>
+int tiled_red_f32_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, int N, const Red &red, hipStream_t st,
+                         Drop... drop) {
+    tiled_row_width_switch(N, [&](auto lpr, auto cpl) {
+        constexpr int LPR = decltype(lpr)::value, CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_red_f32<LPR, CPL, Red, Drop...>), tiled_row_grid(n, N, LPR * CPL), dim3(256), 0, st, ix.row_ptr, ix.kquad,
+                           tiles, static_cast<uint64_t>(n_tiles), n, N, red, drop...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// either view (`Index`), after the argument checks: the maximum (op 0) or the minimum (op 1), under the mask in the pack if there is one
+template <class Index, class... Drop>
+int tiled_extremum_run(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, int N, int op, float *out,
+                       int32_t *arg, void *stream, Drop... drop) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    return op ? tiled_red_f32_launch(ix, tiles, n_tiles, n, N, TiledExtremum<true>{X, out, arg}, st, drop...)
+              : tiled_red_f32_launch(ix, tiles, n_tiles, n, N, TiledExtremum<false>{X, out, arg}, st, drop...);
 }
 
 }  // namespace

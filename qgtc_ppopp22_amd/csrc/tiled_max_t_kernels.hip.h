@@ -135,4 +135,19 @@ __global__ __launch_bounds__(256) void k_tiled_red_f32_t(const int64_t *__restri
     }
 }
 
+// ---- the launcher of k_tiled_red_f32_t: tiled_red_f32_launch on the column view. The extremum keeps two words of state a column and
+// stops at 32 columns a workgroup; the select keeps one and goes to 64 like the float product ----------------------------------------
+template <class Red, class... Drop>
+int tiled_red_f32_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, int N, const Red &red, hipStream_t st,
+                         Drop... drop) {
+    static_assert(sizeof...(Drop) == 0 || Red::WORDS == 2, "a mask goes with the extremum: two words of state a column, 32 columns a workgroup");
+    tiled_col_width_switch<Red::WORDS == 2 ? 32 : 64>(N, [&](auto cpl) {
+        constexpr int CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((k_tiled_red_f32_t<16, CPL, Red, Drop...>), tiled_col_grid(n, N, 16 * CPL), dim3(256), 0, st, ix.col_ptr,
+                           ix.col_tile, ix.col_rb, tiles, static_cast<uint64_t>(n_tiles), n, N, red, drop...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
 }  // namespace

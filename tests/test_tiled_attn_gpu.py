@@ -79,7 +79,8 @@ def _check_views(torch, qgtc, src, dst, n, X, p, q, dY, slope, what, adj=None, f
 
 # ---- 1. the sweep: every variant of both views and both modes, and of the score gradient ---------------------------------------------
 def test_the_sweep_hits_every_variant():
-    """Against tests/tiled_attn_model.py's copy of the launchers' switches (qgtc_tiled_attn.hip, qgtc_tiled_attn_t.hip). The backward
+    """Against tests/tiled_attn_model.py's copy of the launchers' switches (tiled_attn_kernels.hip.h, tiled_attn_t_kernels.hip.h). The
+    backward
     mode of the product runs on the other view at the same N, so a sweep over both views covers both modes of both tables."""
     for transposed, variants in ((False, ATT_FORWARD_VARIANTS), (True, ATT_TRANSPOSED_VARIANTS)):
         assert sorted({att_variant(N, transposed) for N in SWEEP_N}) == sorted(variants)

@@ -102,8 +102,9 @@ def _check(torch, qgtc, src, dst, n, N, rate, seed, rng, what, adj=None, repack=
 
 # ---- 1. the sweep ---------------------------------------------------------------------------------------------------------------------------
 def test_the_sweep_reaches_every_launcher_variant():
-    """Against the models' copies of the launchers' switches: the masked launchers of qgtc_tiled_float_drop.hip, qgtc_tiled_float_t_drop.hip,
-    qgtc_tiled_max_drop.hip, qgtc_tiled_attn_drop.hip and qgtc_tiled_attn_t_drop.hip choose as their parents do. Every case runs the plain
+    """Against the models' copies of the launchers' switches: the entries of qgtc_tiled_float_drop.hip, qgtc_tiled_float_t_drop.hip,
+    qgtc_tiled_max_drop.hip, qgtc_tiled_attn_drop.hip and qgtc_tiled_attn_t_drop.hip go through their parents' launchers (one per kernel
+    family, at the foot of its tiled_*_kernels.hip.h), so they choose as their parents do. Every case runs the plain
     sum, each scale alone and both (all four packs of the float kernels), max and min, and the attention forward on both views."""
     for transposed, fl, mx, at in ((False, FLOAT_FORWARD_VARIANTS, MAX_FORWARD_VARIANTS, ATT_FORWARD_VARIANTS),
                                    (True, FLOAT_TRANSPOSED_VARIANTS, MAX_TRANSPOSED_VARIANTS, ATT_TRANSPOSED_VARIANTS)):

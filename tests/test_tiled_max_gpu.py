@@ -114,7 +114,8 @@ def _tied(rng, n, N):
 
 # ---- 1. the sweep: every variant, both ops, both views, both ways in, and the select --------------------------------------------------
 def test_the_sweep_hits_every_variant():
-    """Against tests/tiled_max_model.py's copy of the launchers' switches (qgtc_tiled_max.hip, qgtc_tiled_max_t.hip), not against the
+    """Against tests/tiled_max_model.py's copy of the launchers' switches (tiled_max_kernels.hip.h, tiled_max_t_kernels.hip.h), not against
+    the
     launchers themselves: a width changed there must be changed in the model too, or this still passes."""
     for transposed, select, variants in ((False, False, MAX_FORWARD_VARIANTS), (True, False, MAX_TRANSPOSED_VARIANTS),
                                          (False, True, SELECT_FORWARD_VARIANTS), (True, True, SELECT_TRANSPOSED_VARIANTS)):

@@ -11,9 +11,10 @@ from tiled_max_model import MAX, extremum_f32
 F32 = np.float32
 
 # (lanes per output row, columns per lane) of the product launchers by output width N, forward and backward mode alike: the float
-# product's variants on the row view (qgtc_tiled_attn.hip) and on the column view (qgtc_tiled_attn_t.hip). A hand-kept copy of the
-# launchers' switches, as tiled_float_model.py's are. The score gradient has two variants on either view: the out node's row in
-# registers up to N = 256, read again per neighbour beyond.
+# product's variants on the row view (tiled_attn_kernels.hip.h, tiled_att_f32_launch) and on the column view
+# (tiled_attn_t_kernels.hip.h, tiled_att_f32_launch), both through the switches of tiled_float_kernels.hip.h. A hand-kept copy of those
+# switches, as tiled_float_model.py's are. The score gradient has two variants on either view (tiled_att_grad_launch in the same two
+# headers): the out node's row in registers up to N = 256, read again per neighbour beyond.
 ATT_FORWARD_VARIANTS = ((16, 1), (16, 2), (16, 4), (32, 4), (64, 4))
 ATT_TRANSPOSED_VARIANTS = ((16, 1), (16, 2), (16, 4))
 ATT_GRAD_VARIANTS = ("registers", "reread")

@@ -6,9 +6,10 @@ import numpy as np
 
 from tiled_model import set_cells
 
-# (lanes per output row, columns per lane) of k_tiled_mm_f32 by output width N (qgtc_tiled_float.hip, tiled_mm_f32: 16 / 32 / 64 / 128
-# columns a workgroup up to those N, 256-column chunks beyond), and of k_tiled_mm_f32_t (qgtc_tiled_float_t.hip, tiled_mm_f32_t:
-# 16 / 32 columns a workgroup up to those N, 64-column chunks beyond)
+# (lanes per output row, columns per lane) of k_tiled_mm_f32 by output width N (tiled_float_kernels.hip.h, tiled_row_width_switch:
+# 16 / 32 / 64 / 128 columns a workgroup up to those N, 256-column chunks beyond), and of k_tiled_mm_f32_t (the same header,
+# tiled_col_width_switch: 16 / 32 columns a workgroup up to those N, 64-column chunks beyond). Every pack - plain, source scale,
+# edge dropout, node masks - goes through that one switch.
 FLOAT_FORWARD_VARIANTS = ((16, 1), (16, 2), (16, 4), (32, 4), (64, 4))
 FLOAT_TRANSPOSED_VARIANTS = ((16, 1), (16, 2), (16, 4))
 

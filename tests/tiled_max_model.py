@@ -9,9 +9,11 @@ from tiled_float_model import neighbour_lists
 MAX, MIN = 0, 1
 
 # (lanes per output row, columns per lane) of the launchers by output width N: the row view takes the float product's variants for both
-# kernels (qgtc_tiled_max.hip), the column view's extremum stops at 32 columns a workgroup (two words of LDS state a column) and its
-# select goes to 64 like the float product (qgtc_tiled_max_t.hip). These tables are a hand-kept copy of the launchers' switches, as
-# tiled_float_model.py's are: whoever changes a width in qgtc_tiled_max*.hip changes it here, or the sweep's coverage claim goes stale.
+# kernels (tiled_max_kernels.hip.h, tiled_red_f32_launch, through tiled_float_kernels.hip.h's tiled_row_width_switch), the column view's
+# extremum stops at 32 columns a workgroup (two words of LDS state a column) and its select goes to 64 like the float product
+# (tiled_max_t_kernels.hip.h, tiled_red_f32_launch: tiled_col_width_switch with WIDEST 32 / 64). These tables are a hand-kept copy of
+# those two switches, as tiled_float_model.py's are: whoever changes a width there changes it here, or the sweep's coverage claim goes
+# stale.
 MAX_FORWARD_VARIANTS = ((16, 1), (16, 2), (16, 4), (32, 4), (64, 4))
 MAX_TRANSPOSED_VARIANTS = ((16, 1), (16, 2))
 SELECT_FORWARD_VARIANTS = MAX_FORWARD_VARIANTS

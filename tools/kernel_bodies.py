@@ -3,6 +3,9 @@ the sorted hashes of a unit are equal (a template pack added to a kernel changes
 read from qgtc_ppopp22_amd/build/ (run build() first); gfx950 code objects are unbundled with the ROCm LLVM tools.
 
     python tools/kernel_bodies.py qgtc_tiled_float qgtc_tiled_max ... > bodies.txt     # in each checkout, then diff the two files
+
+With --names every line is `unit hash name`, sorted by the kernel's mangled name: two checkouts whose outputs are equal instantiate the
+same kernels in every unit, under the same names, with the same instructions (a refactor of the host side must leave it so).
 """
 import hashlib
 import os
@@ -15,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/llvm/bin"
 
 
-def bodies(unit):
+def named_bodies(unit):
+    """[(mangled name, hash of the body)] of the unit's kernels, in the code object's order"""
     obj = os.path.join(ROOT, "qgtc_ppopp22_amd", "build", unit + ".hip.o")
     with tempfile.TemporaryDirectory() as d:
         fat, co = os.path.join(d, "fatbin"), os.path.join(d, "co")
@@ -29,16 +33,25 @@ def bodies(unit):
         m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", line)
         if m:
             if name:
-                out.append(hashlib.md5("\n".join(cur).encode()).hexdigest())
+                out.append((name, hashlib.md5("\n".join(cur).encode()).hexdigest()))
             name, cur = m.group(1), []
         elif name:
             cur.append(re.sub(r"//.*$", "", re.sub(r"<[^>]*>", "", line)).strip())
     if name:
-        out.append(hashlib.md5("\n".join(cur).encode()).hexdigest())
-    return sorted(out)
+        out.append((name, hashlib.md5("\n".join(cur).encode()).hexdigest()))
+    return out
+
+
+def bodies(unit):
+    return sorted(h for _, h in named_bodies(unit))
 
 
 if __name__ == "__main__":
-    for unit in sys.argv[1:]:
-        for h in bodies(unit):
-            print(unit, h)
+    names = "--names" in sys.argv[1:]
+    for unit in (a for a in sys.argv[1:] if a != "--names"):
+        if names:
+            for name, h in sorted(named_bodies(unit)):
+                print(unit, h, name)
+        else:
+            for h in bodies(unit):
+                print(unit, h)
