@@ -797,6 +797,60 @@ int qgtc_tiledatt_grad_f32_t_nodes(const int64_t *col_ptr, const int64_t *col_ti
                                    const float *D, float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask,
                                    size_t mask_words, void *stream);
 
+/* ---- Edge values: a float32 per stored cell of the tiled adjacency, the weighted sum and the per-edge dot (SDDMM) ----------------------
+ * A weighted graph is a tiled adjacency plus a float32 vector `values` of n_values = nnz elements, nnz the number of set bits of the
+ * tiles. The SLOT of cell (i, j) is its rank when the set bits are listed by tile id, then tile row, then column ascending (MSB first
+ * within a word, as the decode goes). It depends on the tiles alone and not on the view, so one array serves A and A^T. Two index arrays
+ * make a slot computable from a tile row's four words:
+ *   val_ptr  int64 [T + 1]   the exclusive prefix sum of the tiles' bit counts (val_ptr[T] = nnz);
+ *   val_row  int16 [T, 32]   within tile t, the set bits in the rows above r (at most 31 * 128 = 3968);
+ *   slot(t, r, c) = val_ptr[t] + val_row[t][r] + popcount(the bits of row r before column c).
+ * That is 72 bytes beside a 512-byte tile. Slots are held in 32 bits inside the kernels: every entry that takes n_values refuses n_values > 2^31 - 1
+ * (QGTC_EINVAL).
+ *
+ * qgtc_tiled_value_index writes counts[t] = the set bits of tile t (int64 [T]) and val_row. The scan of counts into val_ptr is the
+ * CALLER'S (an exclusive prefix sum with the total appended: torch.cumsum in the Python package). QGTC_EINVAL for a negative n_tiles or
+ * a missing pointer (all three may be NULL when n_tiles is 0), QGTC_EALIGN for tiles off 16 bytes, counts off 8 or val_row off 2.
+ * qgtc_tiled_edge_slots: slot[e] (int64 [n_edges]) of the cell (src[e], dst[e]) - a binary search of kquad within row block src >> 5 for
+ * k-quad dst >> 7, then the cell's bit -, or -1 where the cell is not set (multiplicity 2 quantised it to 0, or the edge is not in the
+ * graph) or an id lies outside [0, n): nothing is read outside the arrays. Ids are the adjacency's own numbering.
+ * qgtc_tiled_edge_endpoints: the inverse, row[s] / col[s] (int32 [n_values]) = the cell of slot s, in the adjacency's numbering; a slot
+ * from n_values up is not written.
+ * Both: QGTC_EINVAL for n outside 1 .. 2^23, a negative n_tiles, tiles without row_ptr / kquad / tiles / val_ptr / val_row or a missing
+ * src / dst / slot (row / col) when there are edges (values); QGTC_EALIGN for tiles off 16 bytes, val_ptr / src / dst / slot off 8,
+ * row / col off 4, val_row off 2.
+ *
+ * qgtc_tiledmm_f32_edge / _t_edge: the arguments of qgtc_tiledmm_f32 / _t, then (val_ptr, val_row, values, n_values):
+ *   out[i] = row_scale[i] . sum over i's neighbours j of the view, ASCENDING, of fl(values[slot of the cell] * X[j])
+ * - the term of the source scale, one IEEE multiply, then one IEEE add, never fused; only the factor's address is new. With all values
+ * 1.0 the result is the plain entry's bits; with values[s] = c[col of s] it is qgtc_tiledmm_f32_src with src_scale = c, and with
+ * values[s] = c[row of s] it is qgtc_tiledmm_f32_t_src. Refusals as qgtc_tiledmm_f32's in its order, with QGTC_EINVAL also for missing
+ * val_ptr / val_row / values when n_tiles > 0 and QGTC_EALIGN also for values off 4 bytes, val_ptr off 8, val_row off 2. A slot outside
+ * [0, n_values) - a foreign index - reads nothing and counts as 0.
+ *
+ * qgtc_tiled_sddmm_f32: out[slot(i, j)] = DOT(A[i], B[j]) for every stored cell (i, j) of A_tiled, DOT exactly that of "Attention tiled
+ * products" (64 strided partial sums t_l over the columns l, l + 64, ..., each from +0 by one unfused multiply and add a column, then
+ * the xor butterfly h = 32 .. 1). Every slot below n_values is written exactly once with a plain store; no atomics. Only the row view
+ * exists: on A^T the cell is the same and the operands swap. It is the gradient for `values` of the weighted sum (A = diag(row_scale) . dY,
+ * B = X), a link score, and the building block of dot-product attention. Refusals in the same order: QGTC_EINVAL as above with A, B, out;
+ * QGTC_EALIGN for A / B / out off 4 bytes; QGTC_ESIZE for ab_elems (A and B each) < n * N. */
+int qgtc_tiled_value_index(const uint32_t *tiles, int64_t n_tiles, int64_t *counts, int16_t *val_row, void *stream);
+int qgtc_tiled_edge_slots(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                          const int64_t *val_ptr, const int16_t *val_row, const int64_t *src, const int64_t *dst, size_t n_edges,
+                          int64_t *slot, void *stream);
+int qgtc_tiled_edge_endpoints(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                              const int64_t *val_ptr, const int16_t *val_row, int32_t *row, int32_t *col, size_t n_values, void *stream);
+int qgtc_tiledmm_f32_edge(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *X,
+                          size_t x_elems, int N, const float *row_scale, float *out, size_t out_elems, const int64_t *val_ptr,
+                          const int16_t *val_row, const float *values, size_t n_values, void *stream);
+int qgtc_tiledmm_f32_t_edge(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                            int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *row_scale, float *out,
+                            size_t out_elems, const int64_t *val_ptr, const int16_t *val_row, const float *values, size_t n_values,
+                            void *stream);
+int qgtc_tiled_sddmm_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const float *A,
+                         const float *B, size_t ab_elems, int N, const int64_t *val_ptr, const int16_t *val_row, float *out,
+                         size_t n_values, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

@@ -176,7 +176,12 @@ class GCNConv(torch.nn.Module):
     ``row_mask = nbr_mask = tiled.node_bitmap(A.to_new(nodes), n)`` and ``norm`` takes the induced degrees (``A.mean_scale(row_mask=,
     nbr_mask=)`` / ``sym_scale``). Rows outside ``nodes`` come back +0; the result is bit for bit the same layer on
     ``pack_edges_tiled`` of the edges between the nodes. With an active ``edge_drop`` (training mode, rate > 0) or a dense ``A`` it is
-    a NotImplementedError."""
+    a NotImplementedError.
+
+    ``edge_weight`` of :meth:`forward` (float32 [nnz] in slot order, ``tiled.edge_values``) weighs every edge of a
+    QGTC.TiledAdjacency: both aggregates are ``tiledAggregate(..., edge_weight=)``, differentiable in the weights too. It is accepted
+    with ``norm=None`` and ``aggr="sum"`` only and without ``nodes`` or an active ``edge_drop``; anything else is a ValueError: normalise
+    the weights beforehand (``tiled.edge_endpoints`` gives every slot's row and column)."""
 
     def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum", edge_drop=0.0):
         super().__init__()
@@ -194,9 +199,13 @@ class GCNConv(torch.nn.Module):
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
-    def forward(self, A, X, edge_seed=None, nodes=None):
+    def forward(self, A, X, edge_seed=None, nodes=None, edge_weight=None):
         if isinstance(A, QGTC.TiledAdjacency):
+            if edge_weight is not None:
+                return self._forward_weighted(A, X, edge_weight, nodes)
             return self._forward_tiled(A, X, edge_seed, nodes)
+        if edge_weight is not None:
+            raise ValueError("edge_weight needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A: put the weights into A")
         if nodes is not None:
             raise NotImplementedError("nodes needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A")
         if self.training and self.edge_drop > 0.0:
@@ -215,6 +224,17 @@ class GCNConv(torch.nn.Module):
         if v is None or v.numel() != A.n or v.device != A.device:
             v = self._keep_vector = torch.full((A.n,), self.keep_scale, dtype=torch.float32, device=A.device)
         return v
+
+    def _forward_weighted(self, A, X, edge_weight, nodes=None):
+        """agg(agg(X . W_in) . W_out) with agg = tiledAggregate(edge_weight=): the plain weighted sum, nothing else."""
+        assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        for what, on in ((f"norm={self.norm!r}", self.norm is not None), (f'aggr="{self.aggr}"', self.aggr != "sum"),
+                         ("nodes", nodes is not None), ("an active edge_drop", self.training and self.edge_drop > 0.0)):
+            if on:
+                raise ValueError(f"edge_weight cannot be combined with {what}: not built - normalise the weights beforehand "
+                                 "(tiled.edge_endpoints gives every slot's row and column)")
+        h = QGTC.tiledAggregate(A, torch.mm(A.to_new(X), self.W_in), edge_weight=edge_weight)
+        return A.to_old(QGTC.tiledAggregate(A, torch.mm(h, self.W_out), edge_weight=edge_weight))
 
     def _forward_tiled(self, A, X, edge_seed=None, nodes=None):
         """agg(agg(X . W_in) . W_out) with agg = tiledAggregate under ``norm`` / ``aggr``; X moves to A's numbering and the result

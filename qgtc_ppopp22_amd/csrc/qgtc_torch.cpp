@@ -27,6 +27,7 @@
 #include <memory>
 #include <mutex>
 #include <optional>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -715,9 +716,48 @@ torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch
     return out;
 }
 
+// Edge values (include/qgtc.h, "Edge values"): the optional keyword `edge_values` = (val_ptr, val_row, values) of the two sum overloads
+// sends the call to the entry's _edge twin; None, the default, is the call there always was. The three tensors are checked here:
+// val_ptr int64 [T + 1], val_row int16 [T, 32], values float32 [nnz], contiguous, on X's device.
+using EdgeValues = std::optional<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>;
+
+struct TiledEdgeView {
+    const int64_t *val_ptr;
+    const int16_t *val_row;
+    const float *values;
+    size_t n_values;
+};
+TiledEdgeView tiled_edge_view(const EdgeValues &edge_values, const int64_t T, const torch::Tensor &X, const EdgeDrop &edge_drop,
+                              const NodeMasks &node_masks) {
+    TORCH_CHECK(!edge_drop && !node_masks, "edge_values cannot be combined with edge_drop or node_masks: not built");
+    const auto &[vp, vr, vals] = *edge_values;
+    TORCH_CHECK(vp.scalar_type() == torch::kInt64 && vp.dim() == 1 && vp.numel() == T + 1 && vp.is_contiguous(),
+                "val_ptr must be a contiguous int64 tensor of T + 1 elements");
+    TORCH_CHECK(vr.scalar_type() == torch::kInt16 && vr.numel() == T * 32 && vr.is_contiguous(),
+                "val_row must be a contiguous int16 tensor of [T, 32]");
+    TORCH_CHECK(vals.scalar_type() == torch::kFloat32 && vals.dim() == 1 && vals.is_contiguous(),
+                "the edge values must be a contiguous float32 vector");
+    TORCH_CHECK(vp.device() == X.device() && vr.device() == X.device() && vals.device() == X.device(),
+                "the edge values and their index must be on the adjacency's device");
+    return {vp.data_ptr<int64_t>(), T ? vr.data_ptr<int16_t>() : nullptr, vals.numel() ? vals.data_ptr<float>() : nullptr,
+            static_cast<size_t>(vals.numel())};
+}
+
 torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
+                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks,
+                           const EdgeValues &edge_values) {
+    if (!edge_values) return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
+    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
+    check_float_operand(X, n, row_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    c10::DeviceGuard guard(X.device());
+    const float *sc = tiled_row_scale(row_scale, n, X);
+    const TiledEdgeView ev = tiled_edge_view(edge_values, T, X, edge_drop, node_masks);
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    check_rc(qgtc_tiledmm_f32_edge(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
+                                   out.data_ptr<float>(), out.numel(), ev.val_ptr, ev.val_row, ev.values, ev.n_values, current_stream(X)),
+             "tiledMMFloat (edge values)");
+    return out;
 }
 
 torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
@@ -754,8 +794,20 @@ torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, 
 
 torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
                              torch::Tensor X, const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop,
-                             const NodeMasks &node_masks) {
-    return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
+                             const NodeMasks &node_masks, const EdgeValues &edge_values) {
+    if (!edge_values) return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
+    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
+    check_float_operand(X, n, col_ptr);
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    c10::DeviceGuard guard(X.device());
+    const float *sc = tiled_row_scale(row_scale, n, X);
+    const TiledEdgeView ev = tiled_edge_view(edge_values, T, X, edge_drop, node_masks);
+    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
+    check_rc(qgtc_tiledmm_f32_t_edge(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
+                                     out.data_ptr<float>(), out.numel(), ev.val_ptr, ev.val_row, ev.values, ev.n_values,
+                                     current_stream(X)),
+             "tiledMMFloat (transposed, edge values)");
+    return out;
 }
 
 // Extremum tiled products (qgtc_tiledmax_f32 / _t, qgtc_tiledsel_f32 / _t), the keyword overloads of _tiled_mm_f32 / _tiled_mm_f32_t:
@@ -2046,11 +2098,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("to_float"), py::arg("row_scale") = py::none());
     m.def("_tiled_mm_f32", &tiled_mm_f32, "float32 [n, N] = A_tiled . X for a float32 X [n, N], neighbours added in ascending id order "
           "(QGTC.tiledMMFloat wraps it)", py::arg("row_ptr"), py::arg("kquad"), py::arg("tiles"), py::arg("n"), py::arg("X"),
-          py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none());
+          py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none(), py::arg("node_masks") = py::none(),
+          py::arg("edge_values") = py::none());
     m.def("_tiled_mm_f32_t", &tiled_mm_f32_t, "float32 [n, N] = A_tiled^T . X for a float32 X [n, N] from the column index and the same "
           "tiles (QGTC.tiledMMFloat on adj.T wraps it)", py::arg("col_ptr"), py::arg("col_tile"), py::arg("col_rb"), py::arg("tiles"),
           py::arg("n"), py::arg("X"), py::arg("row_scale") = py::none(), py::arg("edge_drop") = py::none(),
-          py::arg("node_masks") = py::none());
+          py::arg("node_masks") = py::none(), py::arg("edge_values") = py::none());
     // the keyword overloads: a call that names `reduce` takes them, every other call is the entry above
     m.def("_tiled_mm_f32", &tiled_red_f32, "reduce \"max\" / \"min\": [out] or [out, arg], the element-wise extremum of X over every "
           "row's neighbours and the neighbour that won; reduce \"select\": [the gradient], X = dY routed by arg (QGTC.tiledMMFloat(reduce=) "

@@ -15,13 +15,16 @@
 // added - one IEEE multiply, then one IEEE add, never fused. The pack may END in the edge-dropout mask
 // (tiled_drop.hip.h): a neighbour the mask drops is never queued, so its row is never loaded. Or it may end in
 // the node masks (tiled_nodes.hip.h): the neighbour bitmap is ANDed into the tile words before they are decoded,
-// and a workgroup without a live output row walks nothing.
+// and a workgroup without a live output row walks nothing. Or it may end in the edge values (tiled_edge.hip.h; DESIGN.md section
+// 6.15g): the decoder queues every neighbour's slot beside its id and the adder multiplies the neighbour's row by values[slot], as it
+// would by a source scale.
 #pragma once
 
 #include <type_traits>
 
 #include "tiled_drop.hip.h"
 #include "tiled_nodes.hip.h"
+#include "tiled_edge.hip.h"
 
 namespace {
 
@@ -59,7 +62,8 @@ __device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *l
             const float *__restrict__ row = X + static_cast<uint64_t>(v) * N;
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) x[u][cc] = c0 + cc * LPR < N ? row[c0 + cc * LPR] : 0.0f;
-            if constexpr (tiled_pack_operands<Src...>() != 0) w[u] = tiled_f32_src(src...)[v];
+            if constexpr (tiled_has_edge<Src...>()) w[u] = tiled_edge_value(j + u < cnt ? j + u : cnt - 1, src...);
+            else if constexpr (tiled_pack_operands<Src...>() != 0) w[u] = tiled_f32_src(src...)[v];
         }
 #pragma unroll
         for (int u = 0; u < TILED_F32_AHEAD; ++u)
@@ -79,11 +83,14 @@ __device__ __forceinline__ void tiled_f32_add_rows(float (&s)[CPL], const int *l
 template <int LPR, int CPL, class... Src>
 __device__ __forceinline__ void tiled_f32_decode(uint32_t m, int base, int n, float (&s)[CPL], int *list, int &cnt,
                                                  const float *__restrict__ X, int N, int c0, Src... src) {
+    [[maybe_unused]] int k = 0;   // with edge values: the set bits of the word consumed so far
     while (m) {
         const int b = __builtin_clz(m);
         m &= ~(0x80000000u >> b);
         const int v = base + b;
+        if constexpr (tiled_has_edge<Src...>()) ++k;
         if (v < n && tiled_drop_kept(v, src...)) {
+            if constexpr (tiled_has_edge<Src...>()) tiled_edge_queue(cnt, b, k - 1, src...);
             list[cnt++] = v;
             if (cnt == TILED_F32_CAP) {
                 tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
@@ -121,6 +128,14 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
     constexpr bool NODES = tiled_has_nodes<Src...>();
     [[maybe_unused]] TiledNodesWalk<NODES> nd;   // the node masks' state: empty without them
     __shared__ int lists[G][RPG][TILED_F32_CAP];
+    constexpr bool EDGE = tiled_has_edge<Src...>();
+    [[maybe_unused]] int *slots = nullptr;   // with edge values: the slots of this row group's queued neighbours, [RPG][TILED_F32_CAP]
+    if constexpr (EDGE) {
+        __shared__ int edge_slots[G][RPG][TILED_F32_CAP];
+        slots = &edge_slots[threadIdx.x / LPR][0][0];
+    }
+    [[maybe_unused]] const TiledEdge ed = tiled_edge_of(src...);
+    [[maybe_unused]] int vp = 0, vr = 0;   // val_ptr of the tile being decoded; lane l < RPG: val_row of its row of that tile
     const int rb = blockIdx.x, tid = threadIdx.x;
     const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
     const int l = tid % LPR, c0 = blockIdx.y * (LPR * CPL) + l;
@@ -148,31 +163,57 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32(const int64_t *__restrict_
         q = kquad[t0];
         if (tiled_nodes_and<NODES>(l < RPG, nd.row_live())) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
         if constexpr (NODES) nd.load(nd.nb, q, nq);
+        if constexpr (EDGE) {
+            vp = static_cast<int>(ed.val_ptr[t0]);
+            if (l < RPG) vr = ed.val_row[t0 * 32 + g * RPG + l];
+        }
     }
     for (uint64_t t = t0; t < t1; ++t) {
         uint4 an = make_uint4(0, 0, 0, 0);
         int qn = -1;
+        [[maybe_unused]] int vpn = 0, vrn = 0;
         if (t + 1 < t1) {
             qn = kquad[t + 1];
             if (tiled_nodes_and<NODES>(l < RPG, nd.row_live())) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
             if constexpr (NODES) nd.load(nd.nbn, qn, nq);
+            if constexpr (EDGE) {
+                vpn = static_cast<int>(ed.val_ptr[t + 1]);
+                if (l < RPG) vrn = ed.val_row[(t + 1) * 32 + g * RPG + l];
+            }
         }
         if (tiled_nodes_and<NODES>(static_cast<unsigned>(q) < static_cast<unsigned>(nq), nd.tile_live())) {
             const uint32_t w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-            for (int ri = 0; ri < RPG; ++ri)
+            for (int ri = 0; ri < RPG; ++ri) {
+                if constexpr (EDGE) {
+                    int sb = vp + static_cast<int>(tiled_f32_bcast<LPR>(static_cast<uint32_t>(vr), ri));   // the slot of the row's next set bit
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri) & nd.word(k), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
-                                               tiled_drop_for(rb * 32 + g * RPG + ri, src)...);
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t wk = tiled_f32_bcast<LPR>(w[k], ri);
+                        tiled_f32_decode<LPR, CPL>(wk, q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N, c0,
+                                                   tiled_edge_for(TiledEdgeAtRow{slots + ri * TILED_F32_CAP, sb}, src)...);
+                        sb += __builtin_popcount(wk);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        tiled_f32_decode<LPR, CPL>(tiled_f32_bcast<LPR>(w[k], ri) & nd.word(k), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], X, N,
+                                                   c0, tiled_drop_for(rb * 32 + g * RPG + ri, src)...);
+                }
+            }
         }
         a = an;
         q = qn;
         if constexpr (NODES) nd.nb = nd.nbn;
+        if constexpr (EDGE) {
+            vp = vpn;
+            vr = vrn;
+        }
     }
 #pragma unroll
     for (int ri = 0; ri < RPG; ++ri) {
-        tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0, src...);
+        if constexpr (EDGE) tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0, tiled_edge_for(TiledEdgeAtFlush{slots + ri * TILED_F32_CAP}, src)...);
+        else tiled_f32_add_rows<LPR, CPL>(s[ri], lists[g][ri], cnt[ri], X, N, c0, src...);
         const int row = rb * 32 + g * RPG + ri;
         if (row < n) {
             float sc = 1.0f;

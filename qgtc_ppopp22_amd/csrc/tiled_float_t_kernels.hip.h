@@ -23,6 +23,9 @@
 // its four words cover the k-quad's 128 output rows in the bitmap's own bit order. The staged masks then hold participating neighbours
 // of computed rows only: a masked-out output row has no mask in any round and is skipped by the add loop's zero test, and the decode
 // sees no other bit. One dword per tile and half-wave, loaded with the tile's words one round ahead; nothing per neighbour.
+// Ending in the edge values (tiled_edge.hip.h): a column mask does not say what lies left of a cell in its tile
+// row, so the transposer role also keeps the round's raw words in LDS (8 tiles x 512 bytes), with each tile's val_ptr and its 32 val_row
+// entries, loaded with the words one round ahead; the decoder then finds the slot of (tile row b, this column) from them.
 #pragma once
 
 namespace {
@@ -39,6 +42,20 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
     constexpr int W = LPR * CPL;   // output columns per workgroup
     __shared__ float acc[128 * W];
     __shared__ int lists[G][TILED_F32_CAP];
+    constexpr bool EDGE = tiled_has_edge<Src...>();
+    // with edge values: the slots of this row group's queued neighbours [TILED_F32_CAP]; the round's words before the transpose and their
+    // val_row, [staged tile][tile row]; the staged tiles' val_ptr
+    [[maybe_unused]] int *slots = nullptr, *evr = nullptr, *evp = nullptr;
+    [[maybe_unused]] uint32_t *raw = nullptr;
+    if constexpr (EDGE) {
+        __shared__ int edge_slots[G][TILED_F32_CAP], edge_vr[TS * 32], edge_vp[TS];
+        __shared__ __attribute__((aligned(16))) uint32_t edge_raw[TS * 32 * 4];
+        slots = edge_slots[threadIdx.x / LPR];
+        evr = edge_vr;
+        evp = edge_vp;
+        raw = edge_raw;
+    }
+    [[maybe_unused]] const TiledEdge ed = tiled_edge_of(src...);
     const int q = blockIdx.x, tid = threadIdx.x;
     const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
     const int l = tid % LPR, c0 = blockIdx.y * W + l;
@@ -87,6 +104,15 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
         rb = -1;
         return make_uint4(0, 0, 0, 0);
     };
+    // with edge values: val_row of this lane's tile row and the tile's val_ptr, after words() has checked the entry (rb < 0: none)
+    [[maybe_unused]] int vr = 0, vp = 0;
+    [[maybe_unused]] auto evals = [&](uint64_t t, int rb) {
+        vr = vp = 0;
+        if (rb >= 0) {
+            vr = ed.val_row[t * 32 + (31 - lane)];
+            vp = static_cast<int>(ed.val_ptr[t]);
+        }
+    };
     uint64_t tn;
     int rb, rbn;
     {
@@ -94,16 +120,23 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
         entry(b0 + s_own, tc, rb);
         entry(b0 + TS + s_own, tn, rbn);
         w = words(tc, rb);
+        if constexpr (EDGE) evals(tc, rb);
     }
     for (uint64_t base = b0; base < t1; base += TS) {
         {
             uint32_t v[4] = {w.x, w.y, w.z, w.w};
+            if constexpr (EDGE) {
+                *reinterpret_cast<uint4 *>(raw + (s_own * 32 + 31 - lane) * 4) = w;
+                evr[s_own * 32 + 31 - lane] = vr;
+                if (lane == 0) evp[s_own] = vp;
+            }
             tiled_t_transpose(v, lane);
 #pragma unroll
             for (int k = 0; k < 4; ++k) mk[(k * 32 + 31 - lane) * TS + s_own] = v[k];
             if (lane == 0) srb[s_own] = rb;
             rb = rbn;
             w = words(tn, rb);
+            if constexpr (EDGE) evals(tn, rb);
             entry(base + 2 * TS + s_own, tn, rbn);
         }
         __syncthreads();
@@ -118,8 +151,14 @@ __global__ __launch_bounds__(256) void k_tiled_mm_f32_t(const int64_t *__restric
             int cnt = 0;
 #pragma unroll
             for (int st = 0; st < TS; ++st)
-                if (m[st]) tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0, tiled_drop_for(q * 128 + j, src)...);
-            tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
+                if (m[st]) {
+                    if constexpr (EDGE)
+                        tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0,
+                                                   tiled_edge_for(TiledEdgeAtCol{slots, raw + st * 128, evr + st * 32, evp[st], j}, src)...);
+                    else tiled_f32_decode<LPR, CPL>(m[st], srb[st] * 32, n, s, list, cnt, X, N, c0, tiled_drop_for(q * 128 + j, src)...);
+                }
+            if constexpr (EDGE) tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, tiled_edge_for(TiledEdgeAtFlush{slots}, src)...);
+            else tiled_f32_add_rows<LPR, CPL>(s, list, cnt, X, N, c0, src...);
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) acc[j * W + cc * LPR + l] = s[cc];
         }

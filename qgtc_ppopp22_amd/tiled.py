@@ -50,6 +50,16 @@ sets. The backward takes the two masks swapped. ``adj.degrees()``, ``mean_scale(
 give the masked graph's. That covers Cluster-GCN batches on the whole-graph adjacency (``conv.GCNConv.forward(nodes=)``), a last layer
 on the labelled nodes only, and node dropout. Every mode takes them: under "max" / "min" a row outside ``row_mask`` has arg -1, and the
 attention's softmax runs over the participating neighbours.
+
+``edge_weight=values`` on :func:`tiledMMFloat` / :func:`tiledAggregate` (sum only) weighs every edge (include/qgtc.h, "Edge values"):
+``values`` is a float32 [nnz] vector with one element per stored cell, in SLOT order - tile id, then tile row, then column ascending -
+which depends on the tiles alone, so the same vector serves ``adj`` and ``adj.T``. :func:`edge_values` builds it from an edge list and
+its weights, :func:`edge_slots` gives the slot of every edge of a list, :func:`edge_endpoints` the cell of every slot (for normalising
+weights in torch: ``w * r[row] * c[col]``). ``out[i] = row_scale[i] * sum over j ascending of fl(values[slot(i, j)] * X[j])``: one
+float32 multiply, then one add, never fused, as with ``src_scale``. :func:`tiledSDDMM` is the reverse primitive, one dot product per
+stored cell, ``out[slot(i, j)] = DOT(A[i], B[j])`` with the attention's DOT; :func:`tiledAggregate` uses it for the gradient with respect
+to the values, so a weighted aggregate is differentiable in X and in the weights, bit for bit the same on every run and without
+atomics. ``edge_weight`` with ``src_scale``, ``edge_drop``, node masks, ``reduce="max"`` / ``"min"`` or ``attn`` is refused: not built.
 """
 from __future__ import annotations
 
@@ -66,14 +76,20 @@ _lib = None
 
 
 def _c_abi():
-    """libqgtc_hip.so through ctypes, for the two entries the extension does not bind: qgtc_node_bitmap and
-    qgtc_tiled_inv_degree. Loaded on first use; the extension has loaded the same library already."""
+    """libqgtc_hip.so through ctypes, for the entries the extension does not bind: qgtc_node_bitmap,
+    qgtc_tiled_inv_degree and the edge-value index and SDDMM entries. Loaded on first use; the extension has loaded the same library
+    already."""
     global _lib
     if _lib is None:
         L = ctypes.CDLL(lib_path())
         P, I, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
         L.qgtc_node_bitmap.argtypes, L.qgtc_node_bitmap.restype = [P, I, P, SZ, P], I
         L.qgtc_tiled_inv_degree.argtypes, L.qgtc_tiled_inv_degree.restype = [P, I, P, P], I
+        I64 = ctypes.c_int64
+        L.qgtc_tiled_value_index.argtypes, L.qgtc_tiled_value_index.restype = [P, I64, P, P, P], I
+        L.qgtc_tiled_edge_slots.argtypes, L.qgtc_tiled_edge_slots.restype = [P, P, P, I64, I, P, P, P, P, SZ, P, P], I
+        L.qgtc_tiled_edge_endpoints.argtypes, L.qgtc_tiled_edge_endpoints.restype = [P, P, P, I64, I, P, P, P, P, SZ, P], I
+        L.qgtc_tiled_sddmm_f32.argtypes, L.qgtc_tiled_sddmm_f32.restype = [P, P, P, I64, I, P, P, SZ, I, P, P, P, SZ, P], I
         L.qgtc_strerror.argtypes, L.qgtc_strerror.restype = [I], ctypes.c_char_p
         _lib = L
     return _lib
@@ -98,7 +114,7 @@ def _inv_degree(deg: torch.Tensor) -> torch.Tensor:
     return out
 
 __all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat", "tiledAggregate",
-           "add_self_loops", "node_bitmap"]
+           "add_self_loops", "node_bitmap", "edge_slots", "edge_endpoints", "edge_values", "tiledSDDMM"]
 
 
 class TiledAdjacency:
@@ -129,6 +145,8 @@ class TiledAdjacency:
         self._other = None   # the transposed view (built on first use), or, on that view, the adjacency it transposes
         self._degrees = None  # [out_deg, in_deg, out_inv, in_inv], kept on the untransposed adjacency for both views
         self._sym = None      # [out, in] inverse square roots of the degrees, beside them
+        self._val_index = None  # (val_ptr, val_row, nnz) of the edge values, kept on the untransposed adjacency for both views
+        self._endpoints = None  # (row, col) of every slot, beside it
 
     @property
     def T(self) -> "TiledAdjacency":
@@ -450,6 +468,152 @@ def _nodes_kw(adj: TiledAdjacency, row_mask, nbr_mask, key) -> dict:
     return {"node_masks": (row_mask, nbr_mask)}
 
 
+def _value_index(adj: TiledAdjacency):
+    """(val_ptr int64 [T + 1], val_row int16 [T, 32], nnz) of include/qgtc.h, "Edge values": one kernel for the tiles' bit counts and the
+    in-tile row prefix, ``torch.cumsum`` for the scan, one host read for nnz. Built on first use and kept on the untransposed adjacency
+    for both views."""
+    base = adj._other if adj.transposed else adj
+    if base._val_index is None:
+        T = base.n_tiles
+        counts = torch.empty(T, dtype=torch.int64, device=base.device)
+        val_row = torch.empty((T, 32), dtype=torch.int16, device=base.device)
+        if T:
+            _c_call("the edge-value index", base.tiles, _c_abi().qgtc_tiled_value_index, base.tiles.data_ptr(), T, counts.data_ptr(),
+                    val_row.data_ptr())
+        val_ptr = torch.zeros(T + 1, dtype=torch.int64, device=base.device)
+        if T:
+            val_ptr[1:] = torch.cumsum(counts, 0)
+        nnz = int(val_ptr[-1].item())
+        if nnz >= (1 << 31):
+            raise ValueError(f"the adjacency stores {nnz} cells: edge values are built for fewer than 2^31")
+        base._val_index = (val_ptr, val_row, nnz)
+    return base._val_index
+
+
+def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, nodes_kw=None, reduce: str = "sum", attn=None) -> None:
+    """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself."""
+    for name, on in (("src_scale", src_scale is not None), ("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)),
+                     (f'reduce="{reduce}"', reduce != "sum"), ("attn", attn is not None)):
+        if on:
+            raise ValueError(f"edge_weight cannot be combined with {name}: not built")
+    if not isinstance(values, torch.Tensor):
+        raise TypeError("edge_weight must be a torch.Tensor (float32 [nnz], tiled.edge_values) or None")
+    if values.dtype != torch.float32:
+        raise TypeError(f"edge_weight must be float32, not {values.dtype}")
+    if values.device != adj.device:
+        raise ValueError(f"edge_weight must be on the adjacency's device {adj.device}, not {values.device}")
+    nnz = _value_index(adj)[2]
+    if values.dim() != 1 or values.numel() != nnz:
+        raise ValueError(f"edge_weight must have shape [{nnz}] (one value per stored cell), not {list(values.shape)}")
+    if not values.is_contiguous():
+        raise ValueError("edge_weight must be contiguous")
+
+
+def _base(adj: TiledAdjacency) -> TiledAdjacency:
+    return adj._other if adj.transposed else adj
+
+
+def edge_slots(adj: TiledAdjacency, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """int64 [E]: the slot of the cell of every edge (src[e] -> dst[e]) of an edge list, -1 where the cell is not stored - the edge is
+    not in the graph, multiplicity 2 quantised it to 0, or an id lies outside 0 .. n - 1 (include/qgtc.h, "Edge values"). ``src`` /
+    ``dst`` are int64 [E] on the adjacency's device, in the EDGE LIST'S numbering with the row end first, whichever view ``adj`` is (on a
+    reordered adjacency they are mapped through ``rank`` first). One kernel on the current stream: a binary search per edge."""
+    _check(adj)
+    base = _base(adj)
+    for name, t in (("src", src), ("dst", dst)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+            raise TypeError(f"{name} must be a one-dimensional int64 torch.Tensor")
+        if t.device != base.device:
+            raise ValueError(f"{name} must be on the adjacency's device {base.device}, not {t.device}")
+    if src.numel() != dst.numel():
+        raise ValueError("src and dst must have the same length")
+    n = base.n
+    if base.rank is not None and src.numel():
+        ok_s, ok_d = (src >= 0) & (src < n), (dst >= 0) & (dst < n)
+        src = torch.where(ok_s, base.rank.index_select(0, src.clamp(0, n - 1)), src)
+        dst = torch.where(ok_d, base.rank.index_select(0, dst.clamp(0, n - 1)), dst)
+    src, dst = src.contiguous(), dst.contiguous()
+    val_ptr, val_row, _ = _value_index(base)
+    out = torch.empty(src.numel(), dtype=torch.int64, device=base.device)
+    if src.numel():
+        T = base.n_tiles
+        _c_call("edge_slots", src, _c_abi().qgtc_tiled_edge_slots, base.row_ptr.data_ptr(), base.kquad.data_ptr() if T else None,
+                base.tiles.data_ptr() if T else None, T, n, val_ptr.data_ptr(), val_row.data_ptr() if T else None, src.data_ptr(),
+                dst.data_ptr(), src.numel(), out.data_ptr())
+    return out
+
+
+def edge_endpoints(adj: TiledAdjacency) -> tuple[torch.Tensor, torch.Tensor]:
+    """(row, col), int32 [nnz] each: the cell of ``adj`` (untransposed, whichever view is passed) that every slot belongs to, in the
+    ADJACENCY'S numbering (``adj.perm[row]`` gives the edge list's ids). For normalising weights in torch,
+    ``values * r[row.long()] * c[col.long()]``. One kernel on first use; cached for both views."""
+    _check(adj)
+    base = _base(adj)
+    if base._endpoints is None:
+        val_ptr, val_row, nnz = _value_index(base)
+        row = torch.empty(nnz, dtype=torch.int32, device=base.device)
+        col = torch.empty(nnz, dtype=torch.int32, device=base.device)
+        if nnz:
+            _c_call("edge_endpoints", base.tiles, _c_abi().qgtc_tiled_edge_endpoints, base.row_ptr.data_ptr(), base.kquad.data_ptr(),
+                    base.tiles.data_ptr(), base.n_tiles, base.n, val_ptr.data_ptr(), val_row.data_ptr(), row.data_ptr(), col.data_ptr(), nnz)
+        base._endpoints = (row, col)
+    return base._endpoints
+
+
+def edge_values(adj: TiledAdjacency, src: torch.Tensor, dst: torch.Tensor, weight: torch.Tensor, validate: bool = True) -> torch.Tensor:
+    """float32 [nnz]: the ``edge_weight`` vector of an edge list with one weight per edge - zeros with ``weight[e]`` written at the slot
+    of edge e (:func:`edge_slots`; ids in the edge list's numbering). With ``validate`` (one host read, like
+    ``pack_edges_tiled(validate=True)``) an edge without a stored cell, a cell named by two edges and a stored cell no edge names are
+    each a ValueError; without it edges without a cell are skipped and which of two duplicates wins is unspecified."""
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.dim() != 1:
+        raise TypeError("weight must be a one-dimensional float32 torch.Tensor")
+    slots = edge_slots(adj, src, dst)
+    if weight.numel() != slots.numel():
+        raise ValueError(f"weight must have one element per edge ({slots.numel()}), not {weight.numel()}")
+    if weight.device != slots.device:
+        raise ValueError(f"weight must be on the adjacency's device {slots.device}, not {weight.device}")
+    nnz = _value_index(adj)[2]
+    values = torch.zeros(nnz, dtype=torch.float32, device=slots.device)
+    found = slots >= 0
+    if validate:
+        hits = torch.zeros(nnz, dtype=torch.int64, device=slots.device)
+        hits.index_add_(0, slots[found], torch.ones_like(slots[found]))
+        absent, dup, unnamed = (int(v) for v in torch.stack([(~found).sum(), (hits > 1).sum(), (hits == 0).sum()]).tolist())
+        if absent:
+            raise ValueError(f"{absent} edge(s) have no stored cell in the adjacency (absent, quantised to 0, or an id out of range)")
+        if dup:
+            raise ValueError(f"{dup} stored cell(s) are named by more than one edge")
+        if unnamed:
+            raise ValueError(f"{unnamed} stored cell(s) are named by no edge: every cell needs a weight")
+    values[slots[found]] = weight[found]
+    return values
+
+
+def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """float32 [nnz] in slot order: ``out[slot(i, j)] = DOT(A[i], B[j])`` for every stored cell (i, j) of this view - on ``adj`` row i of A
+    with row j of B; on ``adj.T`` the cell is the same one of ``adj`` and the operands swap, so the same kernel runs. DOT is the
+    attention's (include/qgtc.h, "Attention tiled products"): 64 strided partial sums, then the xor butterfly, every step one float32
+    operation, so the result is the same bits on every launch. Each slot is written once, without atomics. A and B are float32 [n, N],
+    contiguous, on the adjacency's device, in the adjacency's numbering. It is the gradient of a weighted aggregate for its weights, a
+    link score, and the building block of dot-product attention."""
+    _check(adj)
+    _check_float_operand(adj, A)
+    if not isinstance(B, torch.Tensor) or B.dtype != torch.float32:
+        raise TypeError("B must be a float32 torch.Tensor")
+    if B.shape != A.shape or B.device != A.device or not B.is_contiguous():
+        raise ValueError(f"B must be contiguous, on A's device and of A's shape {list(A.shape)}, not {list(B.shape)}")
+    if adj.transposed:
+        A, B = B, A
+    base = _base(adj)
+    val_ptr, val_row, nnz = _value_index(base)
+    out = torch.empty(nnz, dtype=torch.float32, device=base.device)
+    if nnz:
+        _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_f32, base.row_ptr.data_ptr(), base.kquad.data_ptr(), base.tiles.data_ptr(),
+                base.n_tiles, base.n, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), val_ptr.data_ptr(), val_row.data_ptr(), out.data_ptr(),
+                nnz)
+    return out
+
+
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
     if adj.transposed:
@@ -479,7 +643,7 @@ def _tiled_extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_ar
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                  src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False, attn=None,
                  negative_slope: float = 0.2, return_stats: bool = False, edge_drop=None, row_mask: torch.Tensor | None = None,
-                 nbr_mask: torch.Tensor | None = None):
+                 nbr_mask: torch.Tensor | None = None, edge_weight: torch.Tensor | None = None):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -525,10 +689,32 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     end lies in ``row_mask`` and whose neighbour end lies in ``nbr_mask``; all-ones masks give the plain call's bits. A 32-row block
     (on ``adj.T``: a 128-row k-quad) without a live row reads no tile. The masks are kernel arguments read on the device: a captured
     graph follows the bitmap's contents. Another dtype is a TypeError; another length, device or a non-contiguous mask a ValueError; a
-    mask with ``edge_drop`` a ValueError (not built)."""
+    mask with ``edge_drop`` a ValueError (not built).
+
+    ``edge_weight`` (float32 [nnz] in slot order, from :func:`edge_values`; include/qgtc.h, "Edge values") weighs every edge:
+    ``out[i] = row_scale[i] * sum over i's neighbours j of this view, ascending, of fl(values[slot] * X[j])``, the slot being that of
+    the cell of ``adj`` whichever the view - one float32 multiply, then the add, not fused. All ones give the plain call's bits;
+    ``values = c[col]`` (:func:`edge_endpoints`) gives ``src_scale=c`` on ``adj``. ``row_scale`` stays available. The values are a
+    kernel argument read on the device: a captured graph follows their contents. Another dtype is a TypeError; another length or
+    device or a non-contiguous vector a ValueError; ``edge_weight`` with ``src_scale``, ``edge_drop``, a node mask, ``reduce`` other than
+    "sum" or ``attn`` a ValueError (not built: fold a source scale into the weights with :func:`edge_endpoints`)."""
     _check(adj)
     key = _edge_drop_key(edge_drop)
     nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
+    if edge_weight is not None:
+        if reduce not in ("sum", "max", "min"):
+            raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn)
+        if return_arg or return_stats:
+            raise ValueError("return_arg / return_stats cannot be combined with edge_weight: not built")
+        _check_float_operand(adj, X)
+        if row_scale is not None:
+            _check_scale(adj, row_scale)
+        val_ptr, val_row, _ = _value_index(adj)
+        ev = (val_ptr, val_row, edge_weight)
+        if adj.transposed:
+            return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, edge_values=ev)
+        return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, edge_values=ev)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if attn is None:
@@ -598,6 +784,32 @@ class _TiledAggregate(torch.autograd.Function):
         return None, dX, None, None, None, None, None
 
 
+class _TiledWeighted(torch.autograd.Function):
+    """Y = diag(r) . (A o W) . X with W the edge values: dX = (A o W)^T . diag(r) . dY, the weighted product on the other view, and
+    dW[slot(i, j)] = DOT(r[i] dY[i], X[j]), one SDDMM - each launched only when its gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, adj, X, row_scale, values):
+        ctx.adj, ctx.row_scale = adj, row_scale
+        ctx.save_for_backward(X, values)
+        return tiledMMFloat(adj, X, row_scale, edge_weight=values)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dY):
+        X, values = ctx.saved_tensors
+        dX = dV = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
+            dY = dY.contiguous()
+            if ctx.row_scale is not None:
+                dY = ctx.row_scale[:, None] * dY
+            if ctx.needs_input_grad[1]:
+                dX = tiledMMFloat(ctx.adj.T, dY, edge_weight=values)
+            if ctx.needs_input_grad[3]:
+                dV = tiledSDDMM(ctx.adj, dY, X)
+        return None, dX, None, dV
+
+
 class _TiledExtremum(torch.autograd.Function):
     """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
 
@@ -656,7 +868,8 @@ class _TiledAttention(torch.autograd.Function):
 
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                    src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2,
-                   edge_drop=None, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None) -> torch.Tensor:
+                   edge_drop=None, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None,
+                   edge_weight: torch.Tensor | None = None) -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
@@ -682,7 +895,22 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     the product on the other view with the masks swapped, like the scales: the gradient of the unmasked call on ``pack_edges_tiled`` of
     the edges between the two sets, bit for bit - rows of X outside ``nbr_mask`` get +0 (times src_scale). The extremum's select needs
     no mask (arg names participants only); the attention takes its softmax shift from the masked max launch, passes the masks unchanged
-    to att_out's gradient and swapped to the gradient for X and att_nbr's."""
+    to att_out's gradient and swapped to the gradient for X and att_nbr's.
+
+    With ``edge_weight=values`` (as in :func:`tiledMMFloat`, the sum only) the result is differentiable in X and in ``values``:
+    ``dX = tiledMMFloat(other view, r[:, None] * dY, edge_weight=values)`` and ``dvalues = tiledSDDMM(adj, r[:, None] * dY, X)``, with r
+    the ``row_scale`` (the elementwise pre-multiply is a torch operation and happens only when there is one). A gradient nobody needs
+    is not launched; both are specified to the bit and there is no second derivative. The combinations :func:`tiledMMFloat` refuses are
+    refused here."""
+    if edge_weight is not None:
+        _check(adj)
+        key = _edge_drop_key(edge_drop)
+        if reduce not in ("sum", "max", "min"):
+            raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+        _check_edge_weight(adj, edge_weight, src_scale, key, row_mask is not None or nbr_mask is not None, reduce, attn)
+        if isinstance(row_scale, torch.Tensor) and row_scale.requires_grad:
+            raise ValueError("row_scale must not require a gradient: tiledAggregate differentiates with respect to X and edge_weight only")
+        return _TiledWeighted.apply(adj, X, row_scale, edge_weight)
     if row_mask is not None or nbr_mask is not None:
         _check(adj)
         _nodes_kw(adj, row_mask, nbr_mask, _edge_drop_key(edge_drop))

@@ -63,7 +63,15 @@ build the column index,) plain launch; third, forward plus backward of tiledAggr
 Every masked sum is checked bit-equal to the plain launch on the re-packed adjacency before timing. Medians with their 10th and 90th
 percentiles, the share of live workgroups of each mask, and the ratios masked / (a) and masked / (b).
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes]
+`--leg edge` measures the edge values (``edge_weight=`` of QGTC.tiledMMFloat / QGTC.tiledAggregate, tiled.tiledSDDMM) on
+the reordered graphs, both directions, N in {64, 256}, standard-normal X and weights. One alternating loop: the weighted launch, the
+``src_scale`` launch of the same shape (the same multiply and add per term: the weighted launch adds 4 bytes an edge and 72 bytes a
+tile of traffic), the plain launch, tiledSDDMM, the attention's grad_own launch (the same walk and dot, folded instead of stored),
+forward plus both gradients of tiledAggregate(edge_weight=), and the edge-list route (index_select, multiply, index_add_ with its
+autograd backward, which is not bit-reproducible). Once per graph: the value index plus edge_slots of the whole edge list against
+pack_edges_tiled. The weighted sum is checked against the edge-list route before timing. Medians with their 10th and 90th percentiles.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge]
 """
 from __future__ import annotations
 
@@ -608,12 +616,86 @@ def nodes_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def edge_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+
+        def index_and_slots():
+            base = QGTC.TiledAdjacency(n, adj.row_ptr, adj.kquad, adj.tiles, adj.perm, adj.rank)
+            return tiled.edge_slots(base, dsrc, ddst)
+
+        rs, rd = adj.rank.index_select(0, dsrc), adj.rank.index_select(0, ddst)   # the packing alone, without the reordering
+        pack_ms, index_ms = timed_alternating(torch, [lambda: QGTC.pack_edges_tiled(rs, rd, n, False), index_and_slots], max(3, reps // 3))
+        e_row, e_col = (v.long() for v in tiled.edge_endpoints(adj))
+        nnz = int(e_row.numel())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": nnz, "tiles": adj.n_tiles,
+               "pack_ms": pack_ms, "value_index_and_edge_slots_ms": index_ms,
+               "extra_bytes_over_src_scale": 4 * nnz + 72 * adj.n_tiles - 4 * n, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {nnz}; pack {pack_ms[0]:.4f} ms, value index + edge_slots {index_ms[0]:.4f} ms", flush=True)
+        xr = np.random.default_rng(1)
+        w = torch.from_numpy(xr.standard_normal(nnz).astype(np.float32)).cuda()
+        c = torch.from_numpy(xr.standard_normal(n).astype(np.float32)).cuda()
+        z = torch.zeros(n, device="cuda")
+        wg = w.clone().requires_grad_(True)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                o, k = (e_col, e_row) if a.transposed else (e_row, e_col)
+
+                def edge_list(Xe, we):
+                    return torch.zeros(n, N, device="cuda").index_add_(0, o, we[:, None] * Xe.index_select(0, k))
+
+                def weighted_both():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, edge_weight=wg), (Xg, wg), dY)
+
+                def edge_both():
+                    return torch.autograd.grad(edge_list(Xg, wg), (Xg, wg), dY)
+
+                def grad_own():   # the attention's score gradient on this view: the same walk and dot, folded per row
+                    return tiled._att(a, dY, att_mode="grad_own", att_own=z, att_nbr=z, negative_slope=0.2, shift=z, inv=c, other=X, D=z)
+
+                got, ref = QGTC.tiledMMFloat(a, X, edge_weight=w), edge_list(X, w)
+                assert torch.allclose(got, ref, rtol=1e-4, atol=1e-4), (N, direction, float((got - ref).abs().max()))
+                for gk, ge in zip(weighted_both(), edge_both()):
+                    assert torch.allclose(gk, ge, rtol=1e-3, atol=1e-3), (N, direction, float((gk - ge).abs().max()))
+                tw, ts, tp, td, tg, twb, te, teb = timed_alternating(torch, [
+                    lambda: QGTC.tiledMMFloat(a, X, edge_weight=w), lambda: QGTC.tiledMMFloat(a, X, src_scale=c), lambda: QGTC.tiledMMFloat(a, X),
+                    lambda: tiled.tiledSDDMM(a, dY, X), grad_own, weighted_both, lambda: edge_list(X, w), edge_both], reps)
+                plain_bytes = 512 * adj.n_tiles + 4 * nnz * N + 4 * n * N
+                rec["agg"].append({"N": N, "direction": direction, "weighted_ms": tw, "src_scale_ms": ts, "plain_ms": tp, "sddmm_ms": td,
+                                   "attn_grad_own_ms": tg, "weighted_forward_backward_ms": twb, "edge_list_ms": te,
+                                   "edge_list_forward_backward_ms": teb, "weighted_over_src_scale": round(tw[0] / ts[0], 3),
+                                   "byte_ratio": round((plain_bytes + 4 * nnz + 72 * adj.n_tiles) / (plain_bytes + 4 * nnz), 3),
+                                   "sddmm_over_grad_own": round(td[0] / tg[0], 3), "edge_list_over_weighted": round(te[0] / tw[0], 3),
+                                   "edge_list_fwd_bwd_over_weighted_fwd_bwd": round(teb[0] / twb[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} weighted {tw[0]:8.4f} [{tw[1]:.4f}, {tw[2]:.4f}]  src_scale {ts[0]:8.4f} "
+                      f"[{ts[1]:.4f}, {ts[2]:.4f}] ({tw[0] / ts[0]:.3f}x)  plain {tp[0]:8.4f}  sddmm {td[0]:8.4f} [{td[1]:.4f}, {td[2]:.4f}]  "
+                      f"grad_own {tg[0]:8.4f} ({td[0] / tg[0]:.3f}x)  fwd + both grads {twb[0]:8.4f} [{twb[1]:.4f}, {twb[2]:.4f}]  edge list "
+                      f"{te[0]:8.4f} ({te[0] / tw[0]:.2f}x)  edge list fwd + bwd {teb[0]:8.4f} ({teb[0] / twb[0]:.2f}x)", flush=True)
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, e_row, e_col, w, wg
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge"))
     args = ap.parse_args()
 
     import torch
@@ -621,9 +703,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
