@@ -433,239 +433,46 @@ std::vector<torch::Tensor> reorder_nodes(torch::Tensor src, torch::Tensor dst, c
     return {perm, rank};
 }
 
-// row_scale of the scaled tiled products: float32 [n], contiguous, on bit_X's device (the Python wrappers check the same before they
-// get here, with the exception types their callers expect)
-const float *tiled_row_scale(const c10::optional<torch::Tensor> &row_scale, const int64_t n, const torch::Tensor &bit_X) {
-    if (!row_scale.has_value()) return nullptr;
-    const torch::Tensor &s = *row_scale;
-    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
-                "row_scale must be a contiguous float32 tensor of n elements");
-    TORCH_CHECK(s.device() == bit_X.device(), "row_scale must be on the adjacency's device");
-    return s.data_ptr<float>();
-}
-
-torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor bit_X,
-                       const int N, const int bit2, const int output_bit, const bool to_float,
-                       const c10::optional<torch::Tensor> &row_scale) {
-    CHECK_INPUT(row_ptr);
-    CHECK_INPUT(kquad);
-    CHECK_INPUT(tiles);
-    CHECK_INPUT(bit_X);
-    check_bits_tensor(bit_X, "bit_X");
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
-    TORCH_CHECK(row_ptr.device() == bit_X.device() && kquad.device() == bit_X.device() && tiles.device() == bit_X.device(),
-                "the adjacency and bit_X must be on the same device");
-    TORCH_CHECK(N > 0, "bad dimensions");
-    c10::DeviceGuard guard(bit_X.device());
-    const int nn = static_cast<int>(n);
-    const int64_t T = kquad.numel();
-    const int32_t *kq = T ? kquad.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
-    const float *sc = tiled_row_scale(row_scale, n, bit_X);
-    if (to_float) {
-        auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
-        if (sc)
-            check_rc(qgtc_tiledmm2int_scaled(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, sc,
-                                             out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
-                     "tiledMM2Int (scaled)");
-        else
-            check_rc(qgtc_tiledmm2int(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
-                                      out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
-                     "tiledMM2Int");
-        return out;
-    }
-    auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
-                            torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
-    if (sc)
-        check_rc(qgtc_tiledmm2bit_scaled(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit, sc,
-                                         words_mut(out), out.numel(), current_stream(bit_X)),
-                 "tiledMM2Bit (scaled)");
-    else
-        check_rc(qgtc_tiledmm2bit(row_ptr.data_ptr<int64_t>(), kq, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
-                                  words_mut(out), out.numel(), current_stream(bit_X)),
-                 "tiledMM2Bit");
-    return out;
-}
-
-// Degrees of a tiled adjacency in both directions and their reciprocals (qgtc_tiled_degrees):
-// [out_deg int32 [n], in_deg int32 [n], out_inv float32 [n], in_inv float32 [n]], one device call, no host read.
-std::vector<torch::Tensor> tiled_degrees(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n) {
-    CHECK_INPUT(row_ptr);
-    CHECK_INPUT(kquad);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
-    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
-    c10::DeviceGuard guard(row_ptr.device());
-    const auto dev = row_ptr.device();
-    const int64_t T = kquad.numel();
-    auto out_deg = torch::empty({n}, torch::TensorOptions().dtype(torch::kInt32).device(dev)), in_deg = torch::empty_like(out_deg);
-    auto out_inv = torch::empty({n}, torch::TensorOptions().dtype(torch::kFloat32).device(dev)), in_inv = torch::empty_like(out_inv);
-    check_rc(qgtc_tiled_degrees(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T,
-                                static_cast<int>(n), out_deg.data_ptr<int32_t>(), in_deg.data_ptr<int32_t>(), out_inv.data_ptr<float>(),
-                                in_inv.data_ptr<float>(), current_stream(row_ptr)),
-             "tiled degrees");
-    return {out_deg, in_deg, out_inv, in_inv};
-}
-
-// Transposed tiled adjacency (qgtc_tiled_colindex, qgtc_tiledmm2*_t): [col_ptr int64 [S128(n)+1], col_tile int64 [T], col_rb int32 [T]]
-// from row_ptr and kquad, with no host read; and requant(A_tiled^T . X) from the index and the same tiles.
-std::vector<torch::Tensor> tiled_colindex(torch::Tensor row_ptr, torch::Tensor kquad, const int64_t n) {
-    CHECK_INPUT(row_ptr);
-    CHECK_INPUT(kquad);
-    TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(row_ptr.device() == kquad.device(), "row_ptr and kquad must be on the same device");
-    c10::DeviceGuard guard(row_ptr.device());
-    const auto dev = row_ptr.device();
-    const int64_t T = kquad.numel();
-    auto col_ptr = torch::empty({(n + 127) / 128 + 1}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    auto col_tile = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    auto col_rb = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
-    const size_t work_words = qgtc_tiled_colindex_work_words(T);
-    TORCH_CHECK(!T || work_words, "tiled colindex: no usable device");
-    torch::Tensor work;
-    if (work_words) work = torch::empty({static_cast<int64_t>(work_words)}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
-    check_rc(qgtc_tiled_colindex(row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T, static_cast<int>(n),
-                                 col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr,
-                                 T ? col_rb.data_ptr<int32_t>() : nullptr, work.defined() ? words_mut(work) : nullptr, work_words,
-                                 current_stream(row_ptr)),
-             "tiled colindex");
-    return {col_ptr, col_tile, col_rb};
-}
-
-torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                         torch::Tensor bit_X, const int N, const int bit2, const int output_bit, const bool to_float,
-                         const c10::optional<torch::Tensor> &row_scale) {
-    CHECK_INPUT(col_ptr);
-    CHECK_INPUT(col_tile);
-    CHECK_INPUT(col_rb);
-    CHECK_INPUT(tiles);
-    CHECK_INPUT(bit_X);
-    check_bits_tensor(bit_X, "bit_X");
-    check_bits_tensor(tiles, "tiles");
-    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt64 && col_tile.scalar_type() == torch::kInt64 && col_rb.scalar_type() == torch::kInt32,
-                "col_ptr and col_tile must be int64, col_rb int32");
-    TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
-    TORCH_CHECK(col_ptr.numel() == (n + 127) / 128 + 1, "col_ptr must have S128(n) + 1 entries");
-    TORCH_CHECK(col_tile.numel() == col_rb.numel() && tiles.numel() == col_tile.numel() * 128,
-                "col_tile, col_rb and tiles must list the same tiles");
-    TORCH_CHECK(col_ptr.device() == bit_X.device() && col_tile.device() == bit_X.device() && col_rb.device() == bit_X.device() &&
-                    tiles.device() == bit_X.device(),
-                "the adjacency and bit_X must be on the same device");
-    TORCH_CHECK(N > 0 && bit2 >= 1 && bit2 <= 8, "bad dimensions");
-    TORCH_CHECK(bit_X.numel() >= static_cast<int64_t>(bit2) * P128(N) * S128(static_cast<int>(n)) * 4,
-                "bit_X must hold bit2 x PAD128(N) x S128(n)*4 words (val2bit(X, bit2, True, False))");
-    c10::DeviceGuard guard(bit_X.device());
-    const int nn = static_cast<int>(n);
-    const int64_t T = col_tile.numel();
-    const int64_t *ct = T ? col_tile.data_ptr<int64_t>() : nullptr;
-    const int32_t *cr = T ? col_rb.data_ptr<int32_t>() : nullptr;
-    const uint32_t *tw = T ? words(tiles) : nullptr;
-    const float *sc = tiled_row_scale(row_scale, n, bit_X);
-    if (to_float) {
-        auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
-        if (sc)
-            check_rc(qgtc_tiledmm2int_t_scaled(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, sc,
-                                               out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
-                     "tiledMM2Int (transposed, scaled)");
-        else
-            check_rc(qgtc_tiledmm2int_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
-                                        out.data_ptr<float>(), out.numel(), current_stream(bit_X)),
-                     "tiledMM2Int (transposed)");
-        return out;
-    }
-    auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
-                            torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
-    if (sc)
-        check_rc(qgtc_tiledmm2bit_t_scaled(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2,
-                                           output_bit, sc, words_mut(out), out.numel(), current_stream(bit_X)),
-                 "tiledMM2Bit (transposed, scaled)");
-    else
-        check_rc(qgtc_tiledmm2bit_t(col_ptr.data_ptr<int64_t>(), ct, cr, tw, T, nn, words(bit_X), bit_X.numel(), N, bit2, output_bit,
-                                    words_mut(out), out.numel(), current_stream(bit_X)),
-                 "tiledMM2Bit (transposed)");
-    return out;
-}
-
-// Float tiled products (qgtc_tiledmm_f32 / _t): float32 [n, N] = A_tiled . X (A_tiled^T . X) for a float32 X [n, N], the neighbours'
-// rows added in ascending id order; with row_scale every row is multiplied by row_scale[row] (QGTC.tiledMMFloat checks the same
-// conditions first, with the exception types its callers expect).
-void check_float_operand(const torch::Tensor &X, const int64_t n, const torch::Tensor &index) {
-    CHECK_INPUT(X);
-    TORCH_CHECK(X.scalar_type() == torch::kFloat32 && X.dim() == 2 && X.size(0) == n && X.size(1) >= 1,
-                "X must be a contiguous float32 tensor [n, N] with N >= 1");
-    TORCH_CHECK(X.device() == index.device(), "the adjacency and X must be on the same device");
-}
-
-// src_scale (qgtc_tiledmm_f32_src / _t_src): every neighbour's row is multiplied by src_scale[neighbour] as it is added (one multiply, one
-// add, not fused). Without it the entries and arguments are the ones the bindings always used.
-const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, const int64_t n, const torch::Tensor &X) {
-    if (!src_scale.has_value()) return nullptr;
-    const torch::Tensor &s = *src_scale;
-    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
-                "src_scale must be a contiguous float32 tensor of n elements");
-    TORCH_CHECK(s.device() == X.device(), "src_scale must be on the adjacency's device");
-    return s.data_ptr<float>();
-}
-
-// Edge dropout (include/qgtc.h, "Edge dropout"): the optional keyword `edge_drop` = (threshold, seed) of the overloads below sends the
-// call to the entry's _drop twin, which keeps cell (i, j) of A when H(i, j, seed) >= threshold; None is the call there always was.
-using EdgeDrop = std::optional<std::pair<uint32_t, uint64_t>>;
-
-// Node masks (include/qgtc.h, "Node masks"): the optional keyword `node_masks` = (row_mask, nbr_mask) of the sum overloads below sends
-// the call to the entry's _nodes twin; each is an int32 bitmap of S128(n) * 4 words (tiled.node_bitmap) or None = all nodes. None, the
-// default, is the call there always was.
-using NodeMasks = std::optional<std::pair<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>>;
-
-const uint32_t *tiled_node_mask(const c10::optional<torch::Tensor> &mask, const int64_t n, const torch::Tensor &X, const char *name) {
-    if (!mask.has_value()) return nullptr;
-    const torch::Tensor &m = *mask;
-    TORCH_CHECK(m.scalar_type() == torch::kInt32 && m.dim() == 1 && m.numel() == (n + 127) / 128 * 4 && m.is_contiguous(), name,
-                " must be a contiguous int32 bitmap of S128(n) * 4 words (tiled.node_bitmap)");
-    TORCH_CHECK(m.device() == X.device(), name, " must be on the adjacency's device");
-    return words(m);
-}
-
-// The adjacency of the float-family bindings below, checked and as the raw pointers of its view (the bindings take them apart:
-// `const auto [rp, kq, tw, T] = ...`); without tiles (T = 0) the per-tile pointers are null. What a binding checks of its other
-// arguments comes after this, in the binding.
-struct TiledRowView {
-    const int64_t *row_ptr;
-    const int32_t *kquad;
+// ---- The tiled bindings: one view type, one mask type, each body once -----------------------------------------------
+// TiledView is the adjacency as a call sees it: the checked index arrays of the row view (row_ptr, kquad) or of the column view (col_ptr,
+// col_tile, col_rb), typed, with the shared tile words; without tiles (T = 0) the per-tile pointers are null. on_view() is the one place
+// that hands them to a C entry - the row entry or its _t twin, each followed by the same remaining arguments -, so an index array cannot
+// reach an entry of the other view: kquad is int32 and col_tile int64, the swap does not compile. What a binding checks of its other
+// arguments comes after the view, in the body.
+struct TiledView {
+    bool transposed;
+    const int64_t *ptr;        // row_ptr [S32(n) + 1], or col_ptr [S128(n) + 1]
+    const int32_t *kquad;      // the row view's
+    const int64_t *col_tile;   // the column view's
+    const int32_t *col_rb;     // the column view's
     const uint32_t *tiles;
     int64_t T;
+    c10::Device device;
 };
-TiledRowView tiled_row_view(const torch::Tensor &row_ptr, const torch::Tensor &kquad, const torch::Tensor &tiles, const int64_t n) {
+
+// tiles: null for _tiled_colindex, which reads the index alone
+TiledView tiled_row_view(const torch::Tensor &row_ptr, const torch::Tensor &kquad, const torch::Tensor *tiles_or_null, const int64_t n) {
     CHECK_INPUT(row_ptr);
     CHECK_INPUT(kquad);
-    CHECK_INPUT(tiles);
-    check_bits_tensor(tiles, "tiles");
     TORCH_CHECK(row_ptr.scalar_type() == torch::kInt64 && kquad.scalar_type() == torch::kInt32, "row_ptr must be int64, kquad int32");
     TORCH_CHECK(n >= 1 && n <= (int64_t{1} << 23), "n must lie in [1, 2^23]");
     TORCH_CHECK(row_ptr.numel() == (n + 31) / 32 + 1, "row_ptr must have S32(n) + 1 entries");
-    TORCH_CHECK(tiles.numel() == kquad.numel() * 128, "tiles must hold 128 words per tile");
-    TORCH_CHECK(row_ptr.device() == kquad.device() && row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+    TORCH_CHECK(row_ptr.device() == kquad.device(), "the adjacency must be on one device");
     const int64_t T = kquad.numel();
-    return {row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, T ? words(tiles) : nullptr, T};
+    const uint32_t *tw = nullptr;
+    if (tiles_or_null) {
+        const torch::Tensor &tiles = *tiles_or_null;
+        CHECK_INPUT(tiles);
+        check_bits_tensor(tiles, "tiles");
+        TORCH_CHECK(tiles.numel() == T * 128, "tiles must hold 128 words per tile");
+        TORCH_CHECK(row_ptr.device() == tiles.device(), "the adjacency must be on one device");
+        tw = T ? words(tiles) : nullptr;
+    }
+    return {false, row_ptr.data_ptr<int64_t>(), T ? kquad.data_ptr<int32_t>() : nullptr, nullptr, nullptr, tw, T, row_ptr.device()};
 }
 
-struct TiledColView {
-    const int64_t *col_ptr, *col_tile;
-    const int32_t *col_rb;
-    const uint32_t *tiles;
-    int64_t T;
-};
-TiledColView tiled_col_view(const torch::Tensor &col_ptr, const torch::Tensor &col_tile, const torch::Tensor &col_rb,
-                            const torch::Tensor &tiles, const int64_t n) {
+TiledView tiled_col_view(const torch::Tensor &col_ptr, const torch::Tensor &col_tile, const torch::Tensor &col_rb,
+                         const torch::Tensor &tiles, const int64_t n) {
     CHECK_INPUT(col_ptr);
     CHECK_INPUT(col_tile);
     CHECK_INPUT(col_rb);
@@ -680,40 +487,216 @@ TiledColView tiled_col_view(const torch::Tensor &col_ptr, const torch::Tensor &c
     TORCH_CHECK(col_ptr.device() == col_tile.device() && col_ptr.device() == col_rb.device() && col_ptr.device() == tiles.device(),
                 "the adjacency must be on one device");
     const int64_t T = col_tile.numel();
-    return {col_ptr.data_ptr<int64_t>(), T ? col_tile.data_ptr<int64_t>() : nullptr, T ? col_rb.data_ptr<int32_t>() : nullptr,
-            T ? words(tiles) : nullptr, T};
+    return {true, col_ptr.data_ptr<int64_t>(), nullptr, T ? col_tile.data_ptr<int64_t>() : nullptr, T ? col_rb.data_ptr<int32_t>() : nullptr,
+            T ? words(tiles) : nullptr, T, col_ptr.device()};
 }
 
-torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
-                               const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
-    check_float_operand(X, n, row_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
-    c10::DeviceGuard guard(X.device());
-    const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
-    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int N = static_cast<int>(X.size(1));
+// row_entry(row_ptr, kquad, tiles, T, rest...) or col_entry(col_ptr, col_tile, col_rb, tiles, T, rest...)
+template <class RowEntry, class ColEntry, class... Rest>
+int on_view(const TiledView &v, RowEntry row_entry, ColEntry col_entry, Rest... rest) {
+    return v.transposed ? col_entry(v.ptr, v.col_tile, v.col_rb, v.tiles, v.T, rest...) : row_entry(v.ptr, v.kquad, v.tiles, v.T, rest...);
+}
+
+// Edge dropout (include/qgtc.h, "Edge dropout"): the optional keyword `edge_drop` = (threshold, seed) of the overloads below sends the
+// call to the entry's _drop twin, which keeps cell (i, j) of A when H(i, j, seed) >= threshold; None is the call there always was.
+using EdgeDrop = std::optional<std::pair<uint32_t, uint64_t>>;
+
+// Node masks (include/qgtc.h, "Node masks"): the optional keyword `node_masks` = (row_mask, nbr_mask) of the overloads below sends
+// the call to the entry's _nodes twin; each is an int32 bitmap of S128(n) * 4 words (tiled.node_bitmap) or None = all nodes. None, the
+// default, is the call there always was.
+using NodeMasks = std::optional<std::pair<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>>;
+
+const uint32_t *tiled_node_mask(const c10::optional<torch::Tensor> &mask, const int64_t n, const torch::Tensor &X, const char *name) {
+    if (!mask.has_value()) return nullptr;
+    const torch::Tensor &m = *mask;
+    TORCH_CHECK(m.scalar_type() == torch::kInt32 && m.dim() == 1 && m.numel() == (n + 127) / 128 * 4 && m.is_contiguous(), name,
+                " must be a contiguous int32 bitmap of S128(n) * 4 words (tiled.node_bitmap)");
+    TORCH_CHECK(m.device() == X.device(), name, " must be on the adjacency's device");
+    return words(m);
+}
+
+// TiledMask is the mask of a call, built once from the two keywords and checked: none, edge dropout or node masks (the two together are
+// not built). A new kind of mask is a case here, its trailing arguments in tiled_launch() and a column in the entry tables.
+struct TiledMask {
+    enum Kind { NONE, DROP, NODES } kind;
+    uint32_t threshold;                        // DROP
+    uint64_t seed;
+    const uint32_t *row_mask, *nbr_mask;       // NODES
+    size_t mask_words;
+};
+TiledMask tiled_mask(const EdgeDrop &edge_drop, const NodeMasks &node_masks, const int64_t n, const torch::Tensor &X) {
     TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
+    if (edge_drop) return {TiledMask::DROP, edge_drop->first, edge_drop->second, nullptr, nullptr, 0};
     if (node_masks)
-        check_rc(qgtc_tiledmm_f32_nodes(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
-                                        out.numel(), tiled_node_mask(node_masks->first, n, X, "row_mask"),
-                                        tiled_node_mask(node_masks->second, n, X, "nbr_mask"), static_cast<size_t>((n + 127) / 128 * 4),
-                                        current_stream(X)),
-                 "tiledMMFloat (node masks)");
-    else if (edge_drop)
-        check_rc(qgtc_tiledmm_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
-                                       out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
-                 "tiledMMFloat (edge dropout)");
-    else if (src)
-        check_rc(qgtc_tiledmm_f32_src(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src, out.data_ptr<float>(),
-                                      out.numel(), current_stream(X)),
-                 "tiledMMFloat (source scale)");
-    else
-        check_rc(qgtc_tiledmm_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, out.data_ptr<float>(),
-                                  out.numel(), current_stream(X)),
-                 "tiledMMFloat");
+        return {TiledMask::NODES, 0, 0, tiled_node_mask(node_masks->first, n, X, "row_mask"),
+                tiled_node_mask(node_masks->second, n, X, "nbr_mask"), static_cast<size_t>((n + 127) / 128 * 4)};
+    return {TiledMask::NONE, 0, 0, nullptr, nullptr, 0};
+}
+
+// The C entries of one kernel family by (view, mask). Every masked entry takes the plain entry's arguments, then the mask's, then the
+// stream (include/qgtc.h), so tiled_launch() calls the family's entry for this view and mask with `args...` and appends the rest. A new
+// family is one table.
+template <class R, class RD, class RN, class C, class CD, class CN>
+struct TiledEntries {
+    R row;
+    RD row_drop;
+    RN row_nodes;
+    C col;
+    CD col_drop;
+    CN col_nodes;
+};
+template <class R, class RD, class RN, class C, class CD, class CN>
+TiledEntries(R, RD, RN, C, CD, CN) -> TiledEntries<R, RD, RN, C, CD, CN>;
+
+constexpr TiledEntries kTiledSum{qgtc_tiledmm_f32_src,   qgtc_tiledmm_f32_drop,   qgtc_tiledmm_f32_nodes,
+                                 qgtc_tiledmm_f32_t_src, qgtc_tiledmm_f32_t_drop, qgtc_tiledmm_f32_t_nodes};
+constexpr TiledEntries kTiledMax{qgtc_tiledmax_f32,   qgtc_tiledmax_f32_drop,   qgtc_tiledmax_f32_nodes,
+                                 qgtc_tiledmax_f32_t, qgtc_tiledmax_f32_t_drop, qgtc_tiledmax_f32_t_nodes};
+constexpr TiledEntries kTiledAtt{qgtc_tiledatt_f32,   qgtc_tiledatt_f32_drop,   qgtc_tiledatt_f32_nodes,
+                                 qgtc_tiledatt_f32_t, qgtc_tiledatt_f32_t_drop, qgtc_tiledatt_f32_t_nodes};
+constexpr TiledEntries kTiledAttGrad{qgtc_tiledatt_grad_f32,   qgtc_tiledatt_grad_f32_drop,   qgtc_tiledatt_grad_f32_nodes,
+                                     qgtc_tiledatt_grad_f32_t, qgtc_tiledatt_grad_f32_t_drop, qgtc_tiledatt_grad_f32_t_nodes};
+
+template <class Entries, class... Args>
+int tiled_launch(const Entries &e, const TiledView &v, const TiledMask &m, void *stream, Args... args) {
+    switch (m.kind) {
+        case TiledMask::DROP: return on_view(v, e.row_drop, e.col_drop, args..., m.threshold, m.seed, stream);
+        case TiledMask::NODES: return on_view(v, e.row_nodes, e.col_nodes, args..., m.row_mask, m.nbr_mask, m.mask_words, stream);
+        default: return on_view(v, e.row, e.col, args..., stream);
+    }
+}
+
+// check_rc under the label "<op> (transposed, <what>, <mask kind>)" with the parts that apply; composed only once an entry has refused
+void check_tiled_rc(const int rc, const char *op, const TiledView &v, const char *what = nullptr,
+                    const TiledMask::Kind mask = TiledMask::NONE) {
+    if (rc == QGTC_OK) return;
+    std::string label = op;
+    const char *sep = " (";
+    for (const char *part : {v.transposed ? "transposed" : nullptr, what,
+                             mask == TiledMask::DROP ? "edge dropout" : (mask == TiledMask::NODES ? "node masks" : nullptr)})
+        if (part) {
+            label += sep;
+            label += part;
+            sep = ", ";
+        }
+    if (sep[0] == ',') label += ")";
+    check_rc(rc, label.c_str());
+}
+
+// row_scale of the scaled tiled products: float32 [n], contiguous, on bit_X's device (the Python wrappers check the same before they
+// get here, with the exception types their callers expect)
+const float *tiled_row_scale(const c10::optional<torch::Tensor> &row_scale, const int64_t n, const torch::Tensor &bit_X) {
+    if (!row_scale.has_value()) return nullptr;
+    const torch::Tensor &s = *row_scale;
+    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
+                "row_scale must be a contiguous float32 tensor of n elements");
+    TORCH_CHECK(s.device() == bit_X.device(), "row_scale must be on the adjacency's device");
+    return s.data_ptr<float>();
+}
+
+// Bit tiled products (qgtc_tiledmm2bit / 2int, their _t and _scaled twins): requant(A_tiled . X) on the row view, requant(A_tiled^T . X)
+// on the column view, from the same tiles.
+torch::Tensor tiled_mm_on(const TiledView &v, const int64_t n, const torch::Tensor &bit_X, const int N, const int bit2, const int output_bit,
+                          const bool to_float, const c10::optional<torch::Tensor> &row_scale) {
+    CHECK_INPUT(bit_X);
+    check_bits_tensor(bit_X, "bit_X");
+    TORCH_CHECK(v.device == bit_X.device(), "the adjacency and bit_X must be on the same device");
+    TORCH_CHECK(N > 0, "bad dimensions");
+    if (v.transposed) {   // what the column view has always refused here; on the row view the C entry and the kernel's guarded loads decide
+        TORCH_CHECK(bit2 >= 1 && bit2 <= 8, "bad dimensions");
+        TORCH_CHECK(bit_X.numel() >= static_cast<int64_t>(bit2) * P128(N) * S128(static_cast<int>(n)) * 4,
+                    "bit_X must hold bit2 x PAD128(N) x S128(n)*4 words (val2bit(X, bit2, True, False))");
+    }
+    c10::DeviceGuard guard(bit_X.device());
+    const int nn = static_cast<int>(n);
+    const float *sc = tiled_row_scale(row_scale, n, bit_X);
+    const uint32_t *x = words(bit_X);
+    const size_t xw = bit_X.numel();
+    void *st = current_stream(bit_X);
+    if (to_float) {
+        auto out = torch::empty({n, N}, torch::TensorOptions().dtype(torch::kFloat32).device(bit_X.device()));
+        float *o = out.data_ptr<float>();
+        const size_t on = out.numel();
+        check_tiled_rc(sc ? on_view(v, qgtc_tiledmm2int_scaled, qgtc_tiledmm2int_t_scaled, nn, x, xw, N, bit2, sc, o, on, st)
+                          : on_view(v, qgtc_tiledmm2int, qgtc_tiledmm2int_t, nn, x, xw, N, bit2, o, on, st),
+                       "tiledMM2Int", v, sc ? "scaled" : nullptr);
+        return out;
+    }
+    auto out = torch::empty({static_cast<int64_t>(output_bit) * P8(nn), S128(N) * 4},
+                            torch::TensorOptions().dtype(torch::kInt32).device(bit_X.device()));
+    uint32_t *o = words_mut(out);
+    const size_t on = out.numel();
+    check_tiled_rc(sc ? on_view(v, qgtc_tiledmm2bit_scaled, qgtc_tiledmm2bit_t_scaled, nn, x, xw, N, bit2, output_bit, sc, o, on, st)
+                      : on_view(v, qgtc_tiledmm2bit, qgtc_tiledmm2bit_t, nn, x, xw, N, bit2, output_bit, o, on, st),
+                   "tiledMM2Bit", v, sc ? "scaled" : nullptr);
     return out;
+}
+
+torch::Tensor tiled_mm(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor bit_X,
+                       const int N, const int bit2, const int output_bit, const bool to_float,
+                       const c10::optional<torch::Tensor> &row_scale) {
+    return tiled_mm_on(tiled_row_view(row_ptr, kquad, &tiles, n), n, bit_X, N, bit2, output_bit, to_float, row_scale);
+}
+
+torch::Tensor tiled_mm_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                         torch::Tensor bit_X, const int N, const int bit2, const int output_bit, const bool to_float,
+                         const c10::optional<torch::Tensor> &row_scale) {
+    return tiled_mm_on(tiled_col_view(col_ptr, col_tile, col_rb, tiles, n), n, bit_X, N, bit2, output_bit, to_float, row_scale);
+}
+
+// Degrees of a tiled adjacency in both directions and their reciprocals (qgtc_tiled_degrees):
+// [out_deg int32 [n], in_deg int32 [n], out_inv float32 [n], in_inv float32 [n]], one device call, no host read.
+std::vector<torch::Tensor> tiled_degrees(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n) {
+    const TiledView v = tiled_row_view(row_ptr, kquad, &tiles, n);
+    c10::DeviceGuard guard(v.device);
+    auto out_deg = torch::empty({n}, torch::TensorOptions().dtype(torch::kInt32).device(v.device)), in_deg = torch::empty_like(out_deg);
+    auto out_inv = torch::empty({n}, torch::TensorOptions().dtype(torch::kFloat32).device(v.device)), in_inv = torch::empty_like(out_inv);
+    check_rc(qgtc_tiled_degrees(v.ptr, v.kquad, v.tiles, v.T, static_cast<int>(n), out_deg.data_ptr<int32_t>(), in_deg.data_ptr<int32_t>(),
+                                out_inv.data_ptr<float>(), in_inv.data_ptr<float>(), current_stream(row_ptr)),
+             "tiled degrees");
+    return {out_deg, in_deg, out_inv, in_inv};
+}
+
+// Transposed tiled adjacency (qgtc_tiled_colindex): [col_ptr int64 [S128(n)+1], col_tile int64 [T], col_rb int32 [T]] from row_ptr and
+// kquad, with no host read; the column view of every product reads the same tiles through it.
+std::vector<torch::Tensor> tiled_colindex(torch::Tensor row_ptr, torch::Tensor kquad, const int64_t n) {
+    const TiledView v = tiled_row_view(row_ptr, kquad, nullptr, n);
+    c10::DeviceGuard guard(v.device);
+    const int64_t T = v.T;
+    auto col_ptr = torch::empty({(n + 127) / 128 + 1}, torch::TensorOptions().dtype(torch::kInt64).device(v.device));
+    auto col_tile = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt64).device(v.device));
+    auto col_rb = torch::empty({T}, torch::TensorOptions().dtype(torch::kInt32).device(v.device));
+    const size_t work_words = qgtc_tiled_colindex_work_words(T);
+    TORCH_CHECK(!T || work_words, "tiled colindex: no usable device");
+    torch::Tensor work;
+    if (work_words) work = torch::empty({static_cast<int64_t>(work_words)}, torch::TensorOptions().dtype(torch::kInt32).device(v.device));
+    check_rc(qgtc_tiled_colindex(v.ptr, v.kquad, T, static_cast<int>(n), col_ptr.data_ptr<int64_t>(),
+                                 T ? col_tile.data_ptr<int64_t>() : nullptr, T ? col_rb.data_ptr<int32_t>() : nullptr,
+                                 work.defined() ? words_mut(work) : nullptr, work_words, current_stream(row_ptr)),
+             "tiled colindex");
+    return {col_ptr, col_tile, col_rb};
+}
+
+// Float tiled products (qgtc_tiledmm_f32 / _t): float32 [n, N] = A_tiled . X (A_tiled^T . X) for a float32 X [n, N], the neighbours'
+// rows added in ascending id order; with row_scale every row is multiplied by row_scale[row] (QGTC.tiledMMFloat checks the same
+// conditions first, with the exception types its callers expect).
+void check_float_operand(const torch::Tensor &X, const int64_t n, const TiledView &v) {
+    CHECK_INPUT(X);
+    TORCH_CHECK(X.scalar_type() == torch::kFloat32 && X.dim() == 2 && X.size(0) == n && X.size(1) >= 1,
+                "X must be a contiguous float32 tensor [n, N] with N >= 1");
+    TORCH_CHECK(X.device() == v.device, "the adjacency and X must be on the same device");
+    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+}
+
+// src_scale (qgtc_tiledmm_f32_src / _t_src): every neighbour's row is multiplied by src_scale[neighbour] as it is added (one multiply, one
+// add, not fused). Without it the entries and arguments are the ones the bindings always used.
+const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, const int64_t n, const torch::Tensor &X) {
+    if (!src_scale.has_value()) return nullptr;
+    const torch::Tensor &s = *src_scale;
+    TORCH_CHECK(s.scalar_type() == torch::kFloat32 && s.dim() == 1 && s.numel() == n && s.is_contiguous(),
+                "src_scale must be a contiguous float32 tensor of n elements");
+    TORCH_CHECK(s.device() == X.device(), "src_scale must be on the adjacency's device");
+    return s.data_ptr<float>();
 }
 
 // Edge values (include/qgtc.h, "Edge values"): the optional keyword `edge_values` = (val_ptr, val_row, values) of the two sum overloads
@@ -743,71 +726,61 @@ TiledEdgeView tiled_edge_view(const EdgeValues &edge_values, const int64_t T, co
             static_cast<size_t>(vals.numel())};
 }
 
-torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks,
+// The sum on a view: plain, with a source scale, under a mask, or with edge values (which take no source scale and no mask)
+torch::Tensor tiled_sum_on(const TiledView &v, const int64_t n, const torch::Tensor &X, const c10::optional<torch::Tensor> &row_scale,
+                           const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks,
                            const EdgeValues &edge_values) {
-    if (!edge_values) return tiled_mm_f32_src(row_ptr, kquad, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
-    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
-    check_float_operand(X, n, row_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    check_float_operand(X, n, v);
     c10::DeviceGuard guard(X.device());
-    const float *sc = tiled_row_scale(row_scale, n, X);
-    const TiledEdgeView ev = tiled_edge_view(edge_values, T, X, edge_drop, node_masks);
-    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    check_rc(qgtc_tiledmm_f32_edge(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
-                                   out.data_ptr<float>(), out.numel(), ev.val_ptr, ev.val_row, ev.values, ev.n_values, current_stream(X)),
-             "tiledMMFloat (edge values)");
+    const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
+    const int nn = static_cast<int>(n), N = static_cast<int>(X.size(1));
+    const float *x = X.data_ptr<float>();
+    const size_t xn = X.numel();
+    void *st = current_stream(X);
+    const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(X.device());
+    if (edge_values) {
+        const TiledEdgeView ev = tiled_edge_view(edge_values, v.T, X, edge_drop, node_masks);
+        auto out = torch::empty({n, X.size(1)}, f32);
+        check_tiled_rc(on_view(v, qgtc_tiledmm_f32_edge, qgtc_tiledmm_f32_t_edge, nn, x, xn, N, sc, out.data_ptr<float>(),
+                               static_cast<size_t>(out.numel()), ev.val_ptr, ev.val_row, ev.values, ev.n_values, st),
+                       "tiledMMFloat", v, "edge values");
+        return out;
+    }
+    const TiledMask mask = tiled_mask(edge_drop, node_masks, n, X);
+    auto out = torch::empty({n, X.size(1)}, f32);
+    float *o = out.data_ptr<float>();
+    const size_t on = out.numel();
+    // without a mask and a source scale the entry is the one the bindings always used, which takes no src_scale
+    check_tiled_rc(mask.kind == TiledMask::NONE && !src ? on_view(v, qgtc_tiledmm_f32, qgtc_tiledmm_f32_t, nn, x, xn, N, sc, o, on, st)
+                                                        : tiled_launch(kTiledSum, v, mask, st, nn, x, xn, N, sc, src, o, on),
+                   "tiledMMFloat", v, src ? "source scale" : nullptr, mask.kind);
     return out;
 }
 
-torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
-                                 torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
-                                 const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
-    check_float_operand(X, n, col_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
-    c10::DeviceGuard guard(X.device());
-    const float *sc = tiled_row_scale(row_scale, n, X), *src = tiled_src_scale(src_scale, n, X);
-    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int N = static_cast<int>(X.size(1));
-    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
-    if (node_masks)
-        check_rc(qgtc_tiledmm_f32_t_nodes(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
-                                          out.data_ptr<float>(), out.numel(), tiled_node_mask(node_masks->first, n, X, "row_mask"),
-                                          tiled_node_mask(node_masks->second, n, X, "nbr_mask"),
-                                          static_cast<size_t>((n + 127) / 128 * 4), current_stream(X)),
-                 "tiledMMFloat (transposed, node masks)");
-    else if (edge_drop)
-        check_rc(qgtc_tiledmm_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
-                                         out.data_ptr<float>(), out.numel(), edge_drop->first, edge_drop->second, current_stream(X)),
-                 "tiledMMFloat (transposed, edge dropout)");
-    else if (src)
-        check_rc(qgtc_tiledmm_f32_t_src(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, src,
-                                        out.data_ptr<float>(), out.numel(), current_stream(X)),
-                 "tiledMMFloat (transposed, source scale)");
-    else
-        check_rc(qgtc_tiledmm_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, sc, out.data_ptr<float>(),
-                                    out.numel(), current_stream(X)),
-                 "tiledMMFloat (transposed)");
-    return out;
+torch::Tensor tiled_mm_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                           const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks,
+                           const EdgeValues &edge_values) {
+    return tiled_sum_on(tiled_row_view(row_ptr, kquad, &tiles, n), n, X, row_scale, c10::nullopt, edge_drop, node_masks, edge_values);
 }
 
 torch::Tensor tiled_mm_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
                              torch::Tensor X, const c10::optional<torch::Tensor> &row_scale, const EdgeDrop &edge_drop,
                              const NodeMasks &node_masks, const EdgeValues &edge_values) {
-    if (!edge_values) return tiled_mm_f32_t_src(col_ptr, col_tile, col_rb, tiles, n, X, row_scale, c10::nullopt, edge_drop, node_masks);
-    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
-    check_float_operand(X, n, col_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
-    c10::DeviceGuard guard(X.device());
-    const float *sc = tiled_row_scale(row_scale, n, X);
-    const TiledEdgeView ev = tiled_edge_view(edge_values, T, X, edge_drop, node_masks);
-    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    check_rc(qgtc_tiledmm_f32_t_edge(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), static_cast<int>(X.size(1)), sc,
-                                     out.data_ptr<float>(), out.numel(), ev.val_ptr, ev.val_row, ev.values, ev.n_values,
-                                     current_stream(X)),
-             "tiledMMFloat (transposed, edge values)");
-    return out;
+    return tiled_sum_on(tiled_col_view(col_ptr, col_tile, col_rb, tiles, n), n, X, row_scale, c10::nullopt, edge_drop, node_masks,
+                        edge_values);
+}
+
+torch::Tensor tiled_mm_f32_src(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                               const c10::optional<torch::Tensor> &row_scale, const c10::optional<torch::Tensor> &src_scale,
+                               const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    return tiled_sum_on(tiled_row_view(row_ptr, kquad, &tiles, n), n, X, row_scale, src_scale, edge_drop, node_masks, std::nullopt);
+}
+
+torch::Tensor tiled_mm_f32_t_src(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles, const int64_t n,
+                                 torch::Tensor X, const c10::optional<torch::Tensor> &row_scale,
+                                 const c10::optional<torch::Tensor> &src_scale, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    return tiled_sum_on(tiled_col_view(col_ptr, col_tile, col_rb, tiles, n), n, X, row_scale, src_scale, edge_drop, node_masks,
+                        std::nullopt);
 }
 
 // Extremum tiled products (qgtc_tiledmax_f32 / _t, qgtc_tiledsel_f32 / _t), the keyword overloads of _tiled_mm_f32 / _tiled_mm_f32_t:
@@ -829,89 +802,47 @@ int tiled_reduce_code(const std::string &reduce, const c10::optional<torch::Tens
     return 2;
 }
 
-std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
-                                         const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg,
-                                         const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
-    check_float_operand(X, n, row_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+std::vector<torch::Tensor> tiled_red_on(const TiledView &v, const int64_t n, const torch::Tensor &X, const std::string &reduce,
+                                        const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop,
+                                        const NodeMasks &node_masks) {
+    check_float_operand(X, n, v);
     const int code = tiled_reduce_code(reduce, arg, return_arg, X);
     TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
     TORCH_CHECK(code != 2 || !node_masks, "reduce=\"select\" takes no node_masks: arg names participating neighbours only");
-    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
-    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
+    const TiledMask mask = tiled_mask(edge_drop, node_masks, n, X);
     c10::DeviceGuard guard(X.device());
     auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int N = static_cast<int>(X.size(1));
+    const int nn = static_cast<int>(n), N = static_cast<int>(X.size(1));
+    const float *x = X.data_ptr<float>();
+    float *o = out.data_ptr<float>();
+    const size_t xn = X.numel(), on = out.numel();
+    void *st = current_stream(X);
     if (code == 2) {
-        check_rc(qgtc_tiledsel_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
-                                   arg->numel(), out.data_ptr<float>(), out.numel(), current_stream(X)),
-                 "tiledMMFloat (select)");
+        check_tiled_rc(on_view(v, qgtc_tiledsel_f32, qgtc_tiledsel_f32_t, nn, x, xn, N, arg->data_ptr<int32_t>(),
+                               static_cast<size_t>(arg->numel()), o, on, st),
+                       "tiledMMFloat", v, "select");
         return {out};
     }
     torch::Tensor win;
     if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    if (node_masks)
-        check_rc(qgtc_tiledmax_f32_nodes(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                                         out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                                         tiled_node_mask(node_masks->first, n, X, "row_mask"),
-                                         tiled_node_mask(node_masks->second, n, X, "nbr_mask"), mask_words, current_stream(X)),
-                 "tiledMMFloat (max / min, node masks)");
-    else if (edge_drop)
-        check_rc(qgtc_tiledmax_f32_drop(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                                        out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                                        edge_drop->first, edge_drop->second, current_stream(X)),
-                 "tiledMMFloat (max / min, edge dropout)");
-    else
-        check_rc(qgtc_tiledmax_f32(rp, kq, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                                   out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                                   current_stream(X)),
-                 "tiledMMFloat (max / min)");
+    check_tiled_rc(tiled_launch(kTiledMax, v, mask, st, nn, x, xn, N, code, o, on, return_arg ? win.data_ptr<int32_t>() : nullptr,
+                                static_cast<size_t>(return_arg ? win.numel() : 0)),
+                   "tiledMMFloat", v, "max / min", mask.kind);
     if (return_arg) return {out, win};
     return {out};
+}
+
+std::vector<torch::Tensor> tiled_red_f32(torch::Tensor row_ptr, torch::Tensor kquad, torch::Tensor tiles, const int64_t n, torch::Tensor X,
+                                         const std::string &reduce, const c10::optional<torch::Tensor> &arg, const bool return_arg,
+                                         const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    return tiled_red_on(tiled_row_view(row_ptr, kquad, &tiles, n), n, X, reduce, arg, return_arg, edge_drop, node_masks);
 }
 
 std::vector<torch::Tensor> tiled_red_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
                                            const int64_t n, torch::Tensor X, const std::string &reduce,
                                            const c10::optional<torch::Tensor> &arg, const bool return_arg, const EdgeDrop &edge_drop,
                                            const NodeMasks &node_masks) {
-    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
-    check_float_operand(X, n, col_ptr);
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
-    const int code = tiled_reduce_code(reduce, arg, return_arg, X);
-    TORCH_CHECK(code != 2 || !edge_drop, "reduce=\"select\" takes no edge_drop: arg names kept neighbours only");
-    TORCH_CHECK(code != 2 || !node_masks, "reduce=\"select\" takes no node_masks: arg names participating neighbours only");
-    TORCH_CHECK(!(edge_drop && node_masks), "node_masks cannot be combined with edge_drop: not built");
-    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
-    c10::DeviceGuard guard(X.device());
-    auto out = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(X.device()));
-    const int N = static_cast<int>(X.size(1));
-    if (code == 2) {
-        check_rc(qgtc_tiledsel_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, arg->data_ptr<int32_t>(),
-                                     arg->numel(), out.data_ptr<float>(), out.numel(), current_stream(X)),
-                 "tiledMMFloat (transposed, select)");
-        return {out};
-    }
-    torch::Tensor win;
-    if (return_arg) win = torch::empty({n, X.size(1)}, torch::TensorOptions().dtype(torch::kInt32).device(X.device()));
-    if (node_masks)
-        check_rc(qgtc_tiledmax_f32_t_nodes(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code,
-                                           out.data_ptr<float>(), out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr,
-                                           return_arg ? win.numel() : 0, tiled_node_mask(node_masks->first, n, X, "row_mask"),
-                                           tiled_node_mask(node_masks->second, n, X, "nbr_mask"), mask_words, current_stream(X)),
-                 "tiledMMFloat (transposed, max / min, node masks)");
-    else if (edge_drop)
-        check_rc(qgtc_tiledmax_f32_t_drop(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code,
-                                          out.data_ptr<float>(), out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr,
-                                          return_arg ? win.numel() : 0, edge_drop->first, edge_drop->second, current_stream(X)),
-                 "tiledMMFloat (transposed, max / min, edge dropout)");
-    else
-        check_rc(qgtc_tiledmax_f32_t(cp, ct, cr, tw, T, static_cast<int>(n), X.data_ptr<float>(), X.numel(), N, code, out.data_ptr<float>(),
-                                     out.numel(), return_arg ? win.data_ptr<int32_t>() : nullptr, return_arg ? win.numel() : 0,
-                                     current_stream(X)),
-                 "tiledMMFloat (transposed, max / min)");
-    if (return_arg) return {out, win};
-    return {out};
+    return tiled_red_on(tiled_col_view(col_ptr, col_tile, col_rb, tiles, n), n, X, reduce, arg, return_arg, edge_drop, node_masks);
 }
 
 // Attention tiled products (qgtc_tiledatt_f32 / _t, qgtc_tiledatt_grad_f32 / _t, qgtc_rowdot_f32), the `att_mode` keyword overloads of
@@ -942,67 +873,35 @@ int tiled_att_mode(const std::string &mode) {
     return -1;
 }
 
-// idx: the index pointers of the view (row view: row_ptr, kquad, NULL; column view: col_ptr, col_tile, col_rb)
-std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, const void *i1, const void *i2, const uint32_t *tw,
-                                         const int64_t T, const int64_t n, const torch::Tensor &X, const std::string &att_mode,
-                                         const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
-                                         const double negative_slope, const c10::optional<torch::Tensor> &shift,
-                                         const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
-                                         const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+std::vector<torch::Tensor> tiled_att_on(const TiledView &v, const int64_t n, const torch::Tensor &X, const std::string &att_mode,
+                                        const c10::optional<torch::Tensor> &att_own, const c10::optional<torch::Tensor> &att_nbr,
+                                        const double negative_slope, const c10::optional<torch::Tensor> &shift,
+                                        const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
+                                        const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
+    check_float_operand(X, n, v);
     const int mode = tiled_att_mode(att_mode);
-    const bool drop = edge_drop.has_value(), nodes = node_masks.has_value();
-    TORCH_CHECK(!(drop && nodes), "node_masks cannot be combined with edge_drop: not built");
-    const uint32_t *rmask = nodes ? tiled_node_mask(node_masks->first, n, X, "row_mask") : nullptr;
-    const uint32_t *nmask = nodes ? tiled_node_mask(node_masks->second, n, X, "nbr_mask") : nullptr;
-    const size_t mask_words = static_cast<size_t>((n + 127) / 128 * 4);
-    const uint32_t dt = drop ? edge_drop->first : 0;
-    const uint64_t ds = drop ? edge_drop->second : 0;
-    TORCH_CHECK(X.size(1) <= INT32_MAX, "N is too large");
+    const TiledMask mask = tiled_mask(edge_drop, node_masks, n, X);
     c10::DeviceGuard guard(X.device());
     const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(X.device());
     const int N = static_cast<int>(X.size(1)), nn = static_cast<int>(n);
     const float *x = X.data_ptr<float>();
+    const size_t xn = X.numel();
     void *st = current_stream(X);
     if (mode == 4) {
-        TORCH_CHECK(!drop && !nodes, "att_mode=\"rowdot\" takes no edge_drop or node_masks: it walks no tiles");
+        TORCH_CHECK(mask.kind == TiledMask::NONE, "att_mode=\"rowdot\" takes no edge_drop or node_masks: it walks no tiles");
         auto out = torch::empty({n}, f32);
-        check_rc(qgtc_rowdot_f32(x, tiled_att_other(other, X), X.numel(), nn, N, out.data_ptr<float>(), out.numel(), st),
-                 "tiledMMFloat (row dot)");
+        check_rc(qgtc_rowdot_f32(x, tiled_att_other(other, X), xn, nn, N, out.data_ptr<float>(), out.numel(), st), "tiledMMFloat (row dot)");
         return {out};
     }
     const float slope = static_cast<float>(negative_slope);
     TORCH_CHECK(slope >= 0.0f && slope <= 1.0f, "negative_slope must lie in [0, 1]");
     const float *own = tiled_att_vector(att_own, "att_own", n, X), *nbr = tiled_att_vector(att_nbr, "att_nbr", n, X);
     const float *sh = tiled_att_vector(shift, "shift", n, X);
-    // row view: row_ptr, kquad; column view: col_ptr, col_tile, col_rb
-    const int64_t *p0 = static_cast<const int64_t *>(i0), *ct = static_cast<const int64_t *>(i1);
-    const int32_t *kq = static_cast<const int32_t *>(i1), *cr = static_cast<const int32_t *>(i2);
-    // the sum, forward (backward 0: m and inv are written) or backward (1: no m, inv is read): one entry per mask and view
+    // the sum, forward (backward 0: m and inv are written) or backward (1: no m, inv is read)
     const auto sum = [&](const int backward, float *m, float *iv, torch::Tensor &out) {
-        float *o = out.data_ptr<float>();
-        const size_t on = out.numel(), xn = X.numel();
-        if (nodes && transposed)
-            check_rc(qgtc_tiledatt_f32_t_nodes(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, rmask, nmask,
-                                               mask_words, st),
-                     backward ? "tiledMMFloat (transposed, attention backward, node masks)"
-                              : "tiledMMFloat (transposed, attention, node masks)");
-        else if (nodes)
-            check_rc(qgtc_tiledatt_f32_nodes(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, rmask, nmask, mask_words,
-                                             st),
-                     backward ? "tiledMMFloat (attention backward, node masks)" : "tiledMMFloat (attention, node masks)");
-        else if (drop && transposed)
-            check_rc(qgtc_tiledatt_f32_t_drop(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, dt, ds, st),
-                     backward ? "tiledMMFloat (transposed, attention backward, edge dropout)"
-                              : "tiledMMFloat (transposed, attention, edge dropout)");
-        else if (drop)
-            check_rc(qgtc_tiledatt_f32_drop(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, dt, ds, st),
-                     backward ? "tiledMMFloat (attention backward, edge dropout)" : "tiledMMFloat (attention, edge dropout)");
-        else if (transposed)
-            check_rc(qgtc_tiledatt_f32_t(p0, ct, cr, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, st),
-                     backward ? "tiledMMFloat (transposed, attention backward)" : "tiledMMFloat (transposed, attention)");
-        else
-            check_rc(qgtc_tiledatt_f32(p0, kq, tw, T, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, o, on, st),
-                     backward ? "tiledMMFloat (attention backward)" : "tiledMMFloat (attention)");
+        check_tiled_rc(tiled_launch(kTiledAtt, v, mask, st, nn, x, xn, N, own, nbr, slope, backward, sh, m, iv, out.data_ptr<float>(),
+                                    static_cast<size_t>(out.numel())),
+                       "tiledMMFloat", v, backward ? "attention backward" : "attention", mask.kind);
     };
     if (mode == 0) {
         TORCH_CHECK(!inv.has_value() && !other.has_value() && !D.has_value(), "att_mode=\"forward\" takes no inv, other or D");
@@ -1019,29 +918,9 @@ std::vector<torch::Tensor> tiled_att_run(const bool transposed, const void *i0, 
     }
     const float *b = tiled_att_other(other, X), *d = tiled_att_vector(D, "D", n, X);
     auto out = torch::empty({n}, f32);
-    float *o = out.data_ptr<float>();
-    const size_t on = out.numel(), xn = X.numel();
-    const int nbr_owns = mode == 3;
-    if (nodes && transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t_nodes(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, rmask, nmask,
-                                                mask_words, st),
-                 "tiledMMFloat (transposed, attention score gradient, node masks)");
-    else if (nodes)
-        check_rc(qgtc_tiledatt_grad_f32_nodes(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, rmask, nmask,
-                                              mask_words, st),
-                 "tiledMMFloat (attention score gradient, node masks)");
-    else if (drop && transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t_drop(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, dt, ds, st),
-                 "tiledMMFloat (transposed, attention score gradient, edge dropout)");
-    else if (drop)
-        check_rc(qgtc_tiledatt_grad_f32_drop(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, dt, ds, st),
-                 "tiledMMFloat (attention score gradient, edge dropout)");
-    else if (transposed)
-        check_rc(qgtc_tiledatt_grad_f32_t(p0, ct, cr, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, st),
-                 "tiledMMFloat (transposed, attention score gradient)");
-    else
-        check_rc(qgtc_tiledatt_grad_f32(p0, kq, tw, T, nn, x, b, xn, N, own, nbr, slope, nbr_owns, sh, ivp, d, o, on, st),
-                 "tiledMMFloat (attention score gradient)");
+    check_tiled_rc(tiled_launch(kTiledAttGrad, v, mask, st, nn, x, b, xn, N, own, nbr, slope, /*nbr_owns=*/static_cast<int>(mode == 3), sh, ivp,
+                                d, out.data_ptr<float>(), static_cast<size_t>(out.numel())),
+                   "tiledMMFloat", v, "attention score gradient", mask.kind);
     return {out};
 }
 
@@ -1051,10 +930,8 @@ std::vector<torch::Tensor> tiled_att_f32(torch::Tensor row_ptr, torch::Tensor kq
                                          const c10::optional<torch::Tensor> &shift, const c10::optional<torch::Tensor> &inv,
                                          const c10::optional<torch::Tensor> &other, const c10::optional<torch::Tensor> &D,
                                          const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    const auto [rp, kq, tw, T] = tiled_row_view(row_ptr, kquad, tiles, n);
-    check_float_operand(X, n, row_ptr);
-    return tiled_att_run(false, rp, kq, nullptr, tw, T, n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop,
-                         node_masks);
+    return tiled_att_on(tiled_row_view(row_ptr, kquad, &tiles, n), n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D,
+                        edge_drop, node_masks);
 }
 
 std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor col_tile, torch::Tensor col_rb, torch::Tensor tiles,
@@ -1063,10 +940,8 @@ std::vector<torch::Tensor> tiled_att_f32_t(torch::Tensor col_ptr, torch::Tensor 
                                            const double negative_slope, const c10::optional<torch::Tensor> &shift,
                                            const c10::optional<torch::Tensor> &inv, const c10::optional<torch::Tensor> &other,
                                            const c10::optional<torch::Tensor> &D, const EdgeDrop &edge_drop, const NodeMasks &node_masks) {
-    const auto [cp, ct, cr, tw, T] = tiled_col_view(col_ptr, col_tile, col_rb, tiles, n);
-    check_float_operand(X, n, col_ptr);
-    return tiled_att_run(true, cp, ct, cr, tw, T, n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv, other, D, edge_drop,
-                         node_masks);
+    return tiled_att_on(tiled_col_view(col_ptr, col_tile, col_rb, tiles, n), n, X, att_mode, att_own, att_nbr, negative_slope, shift, inv,
+                        other, D, edge_drop, node_masks);
 }
 
 // float32 [n] = 1 / sqrt(deg), both operations correctly rounded, 0 where the degree is 0 (qgtc_tiled_inv_sqrt_degree)

@@ -324,19 +324,28 @@ def _check_scale(adj: TiledAdjacency, row_scale, name: str = "row_scale") -> Non
         raise ValueError(f"{name} must be contiguous")
 
 
+_ON_T = {"_tiled_mm": "_tiled_mm_t", "_tiled_mm_f32": "_tiled_mm_f32_t", "_tiled_mm_f32_src": "_tiled_mm_f32_t_src"}
+
+
+def _call(adj: TiledAdjacency, name: str, *args, **kw):
+    """The binding ``name`` on the view of ``adj``: ``name`` itself after (row_ptr, kquad, tiles, n) or, on ``adj.T``, its twin of
+    ``_ON_T`` after (col_ptr, col_tile, col_rb, tiles, n). The one place that tells the views apart for the extension. Without a
+    keyword the binding gets no keyword dictionary at all: pybind11 searches a dictionary, even an empty one, for every argument left
+    to its default."""
+    if adj.transposed:
+        fn, view = getattr(_ext, _ON_T[name]), (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n)
+    else:
+        fn, view = getattr(_ext, name), (adj.row_ptr, adj.kquad, adj.tiles, adj.n)
+    return fn(*view, *args, **kw) if kw else fn(*view, *args)
+
+
 def _tiled(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int, to_float: bool, row_scale) -> torch.Tensor:
     _check(adj)
     if row_scale is None:
         # exactly the unscaled call
-        if adj.transposed:
-            return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit),
-                                    to_float)
-        return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), to_float)
+        return _call(adj, "_tiled_mm", bit_X, int(N), int(bit2), int(output_bit), to_float)
     _check_scale(adj, row_scale)
-    if adj.transposed:
-        return _ext._tiled_mm_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit),
-                                to_float, row_scale)
-    return _ext._tiled_mm(adj.row_ptr, adj.kquad, adj.tiles, adj.n, bit_X, int(N), int(bit2), int(output_bit), to_float, row_scale)
+    return _call(adj, "_tiled_mm", bit_X, int(N), int(bit2), int(output_bit), to_float, row_scale)
 
 
 def tiledMM2Bit(adj: TiledAdjacency, bit_X: torch.Tensor, N: int, bit2: int, output_bit: int,
@@ -616,28 +625,68 @@ def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.T
 
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
-    if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, **kw)
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, **kw)
+    return _call(adj, "_tiled_mm_f32", X, **kw)
 
 
-def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, key=None,
-                     nodes_kw: dict | None = None):
+def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, mask_kw: dict):
     """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch. Under a mask
-    (``key`` or ``nodes_kw``, checked) both launches take it: M must be the maximum over the KEPT neighbours, or the weights' sum
-    could fall below 1."""
-    M = _tiled_extremum(adj, att_nbr.detach().unsqueeze(1), "max", False, key, nodes_kw)[0].reshape(adj.n)
-    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M,
-                **_drop_kw(key), **(nodes_kw or {}))
+    (``mask_kw``, the checked keyword of the binding) both launches take it: M must be the maximum over the KEPT neighbours, or the
+    weights' sum could fall below 1."""
+    M = _call(adj, "_tiled_mm_f32", att_nbr.detach().unsqueeze(1), reduce="max", return_arg=False, **mask_kw)[0].reshape(adj.n)
+    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M, **mask_kw)
 
 
-def _tiled_extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_arg: bool, key=None, nodes_kw: dict | None = None):
-    """[out] or [out, arg] of the max / min launch on this view, under the mask ``key`` or ``nodes_kw`` (checked) when there is one."""
-    kw = {**_drop_kw(key), **(nodes_kw or {})}
-    if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg),
-                                    **kw)
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, reduce=reduce, return_arg=bool(return_arg), **kw)
+def _scale_name(row_scale) -> str:
+    """The scale a refusal names when one is set: ``row_scale`` before ``src_scale``."""
+    return "src_scale" if row_scale is None else "row_scale"
+
+
+def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop, row_mask,
+             nbr_mask, edge_weight):
+    """(mode, mask_kw, slope) of a call of :func:`tiledMMFloat` / :func:`tiledAggregate`, or the refusal it earns. ``mode`` is
+    "weighted" (``edge_weight``), "attention" (``attn``), "extremum" (``reduce`` "max" / "min") or "sum" (plain or scaled); ``mask_kw``
+    the binding's keyword of the checked mask, ``edge_drop`` or ``node_masks`` - without a mask no keyword at all, which is the call the
+    binding always took -; ``slope`` the checked ``negative_slope`` of the attention. This is the one table of what may be combined, in
+    the order the refusals are made: the masks, ``reduce``, then per mode what it does not take and its operands. A new variant adds its
+    row here."""
+    _check(adj)
+    key = _edge_drop_key(edge_drop)
+    nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
+    mask_kw = nodes_kw if key is None else _drop_kw(key)   # never both: _nodes_kw refuses a mask with edge_drop
+    if reduce not in ("sum", "max", "min"):
+        raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
+    if edge_weight is not None:
+        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn)
+        if return_arg or return_stats:
+            raise ValueError("return_arg / return_stats cannot be combined with edge_weight: not built")
+        mode = "weighted"
+    elif attn is not None:
+        if row_scale is not None or src_scale is not None:
+            raise ValueError(f"{_scale_name(row_scale)} cannot be combined with attn")
+        if reduce != "sum":
+            raise ValueError(f'attn cannot be combined with reduce="{reduce}"')
+        if return_arg:
+            raise ValueError("return_arg cannot be combined with attn: a weighted sum has no winning neighbour")
+        slope = _check_slope(negative_slope)
+        _check_float_operand(adj, X)
+        _check_attn(adj, attn)
+        return "attention", mask_kw, slope
+    elif return_stats:
+        raise ValueError("return_stats needs attn: only the attention product has softmax statistics")
+    elif reduce == "sum":
+        if return_arg:
+            raise ValueError('return_arg needs reduce="max" or "min": a sum has no winning neighbour')
+        mode = "sum"
+    else:
+        if row_scale is not None or src_scale is not None:
+            raise ValueError(f'{_scale_name(row_scale)} cannot be combined with reduce="{reduce}"')
+        mode = "extremum"
+    _check_float_operand(adj, X)
+    if row_scale is not None:
+        _check_scale(adj, row_scale)
+    if src_scale is not None:
+        _check_scale(adj, src_scale, "src_scale")
+    return mode, mask_kw, None
 
 
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
@@ -698,71 +747,26 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     kernel argument read on the device: a captured graph follows their contents. Another dtype is a TypeError; another length or
     device or a non-contiguous vector a ValueError; ``edge_weight`` with ``src_scale``, ``edge_drop``, a node mask, ``reduce`` other than
     "sum" or ``attn`` a ValueError (not built: fold a source scale into the weights with :func:`edge_endpoints`)."""
-    _check(adj)
-    key = _edge_drop_key(edge_drop)
-    nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
-    if edge_weight is not None:
-        if reduce not in ("sum", "max", "min"):
-            raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
-        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn)
-        if return_arg or return_stats:
-            raise ValueError("return_arg / return_stats cannot be combined with edge_weight: not built")
-        _check_float_operand(adj, X)
-        if row_scale is not None:
-            _check_scale(adj, row_scale)
-        val_ptr, val_row, _ = _value_index(adj)
-        ev = (val_ptr, val_row, edge_weight)
-        if adj.transposed:
-            return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, edge_values=ev)
-        return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, edge_values=ev)
-    if reduce not in ("sum", "max", "min"):
-        raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
-    if attn is None:
-        if return_stats:
-            raise ValueError("return_stats needs attn: only the attention product has softmax statistics")
-    else:
-        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
-            if sc is not None:
-                raise ValueError(f"{name} cannot be combined with attn")
-        if reduce != "sum":
-            raise ValueError(f'attn cannot be combined with reduce="{reduce}"')
-        if return_arg:
-            raise ValueError("return_arg cannot be combined with attn: a weighted sum has no winning neighbour")
-        slope = _check_slope(negative_slope)
-        _check_float_operand(adj, X)
-        att_out, att_nbr = _check_attn(adj, attn)
-        out, m, inv = _tiled_attention(adj, X, att_out, att_nbr, slope, key, nodes_kw)
-        return (out, m, inv) if return_stats else out
-    if reduce == "sum":
-        if return_arg:
-            raise ValueError('return_arg needs reduce="max" or "min": a sum has no winning neighbour')
-    else:
-        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
-            if sc is not None:
-                raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
-    _check_float_operand(adj, X)
-    if reduce != "sum":
-        res = _tiled_extremum(adj, X, reduce, return_arg, key, nodes_kw)
+    mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop,
+                                    row_mask, nbr_mask, edge_weight)
+    if mode == "sum":
+        if src_scale is not None:
+            return _call(adj, "_tiled_mm_f32_src", X, row_scale, src_scale, **mask_kw)
+        return _call(adj, "_tiled_mm_f32", X, row_scale, **mask_kw)
+    if mode == "extremum":
+        res = _call(adj, "_tiled_mm_f32", X, reduce=reduce, return_arg=bool(return_arg), **mask_kw)
         return (res[0], res[1]) if return_arg else res[0]
-    if row_scale is not None:
-        _check_scale(adj, row_scale)
-    if src_scale is not None:
-        _check_scale(adj, src_scale, "src_scale")
-        if adj.transposed:
-            return _ext._tiled_mm_f32_t_src(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key),
-                                            **nodes_kw)
-        return _ext._tiled_mm_f32_src(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, src_scale, **_drop_kw(key), **nodes_kw)
-    if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, X, row_scale, **_drop_kw(key), **nodes_kw)
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, X, row_scale, **_drop_kw(key), **nodes_kw)
+    if mode == "attention":
+        out, m, inv = _tiled_attention(adj, X, attn[0], attn[1], slope, mask_kw)
+        return (out, m, inv) if return_stats else out
+    val_ptr, val_row, _ = _value_index(adj)   # "weighted"
+    return _call(adj, "_tiled_mm_f32", X, row_scale, edge_values=(val_ptr, val_row, edge_weight))
 
 
 def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
     """float32 [n, N]: row v adds, in ascending id order, dY[r] of its neighbours r where arg[r] names v (include/qgtc.h, "Extremum
     tiled products", the select). On the other view of a max / min forward with that forward's arg it is the gradient for X."""
-    if adj.transposed:
-        return _ext._tiled_mm_f32_t(adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles, adj.n, dY, reduce="select", arg=arg)[0]
-    return _ext._tiled_mm_f32(adj.row_ptr, adj.kquad, adj.tiles, adj.n, dY, reduce="select", arg=arg)[0]
+    return _call(adj, "_tiled_mm_f32", dY, reduce="select", arg=arg)[0]
 
 
 class _TiledAggregate(torch.autograd.Function):
@@ -902,38 +906,17 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     the ``row_scale`` (the elementwise pre-multiply is a torch operation and happens only when there is one). A gradient nobody needs
     is not launched; both are specified to the bit and there is no second derivative. The combinations :func:`tiledMMFloat` refuses are
     refused here."""
-    if edge_weight is not None:
-        _check(adj)
-        key = _edge_drop_key(edge_drop)
-        if reduce not in ("sum", "max", "min"):
-            raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
-        _check_edge_weight(adj, edge_weight, src_scale, key, row_mask is not None or nbr_mask is not None, reduce, attn)
-        if isinstance(row_scale, torch.Tensor) and row_scale.requires_grad:
-            raise ValueError("row_scale must not require a gradient: tiledAggregate differentiates with respect to X and edge_weight only")
-        return _TiledWeighted.apply(adj, X, row_scale, edge_weight)
-    if row_mask is not None or nbr_mask is not None:
-        _check(adj)
-        _nodes_kw(adj, row_mask, nbr_mask, _edge_drop_key(edge_drop))
-    _edge_drop_key(edge_drop)
-    if reduce not in ("sum", "max", "min"):
-        raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
-    if attn is not None:
-        for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
-            if sc is not None:
-                raise ValueError(f"{name} cannot be combined with attn")
-        if reduce != "sum":
-            raise ValueError(f'attn cannot be combined with reduce="{reduce}"')
-        slope = _check_slope(negative_slope)
-        _check(adj)
-        _check_float_operand(adj, X)
-        att_out, att_nbr = _check_attn(adj, attn)
-        return _TiledAttention.apply(adj, X, att_out, att_nbr, slope, edge_drop, row_mask, nbr_mask)
+    mode, _, slope = _resolve(adj, X, row_scale, src_scale, reduce, False, attn, negative_slope, False, edge_drop, row_mask, nbr_mask,
+                              edge_weight)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
-        if reduce != "sum" and sc is not None:
-            raise ValueError(f'{name} cannot be combined with reduce="{reduce}"')
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
-            raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to X only")
-    if reduce != "sum":
+            wrt = "X and edge_weight" if mode == "weighted" else "X"
+            raise ValueError(f"{name} must not require a gradient: tiledAggregate differentiates with respect to {wrt} only")
+    if mode == "weighted":
+        return _TiledWeighted.apply(adj, X, row_scale, edge_weight)
+    if mode == "attention":
+        return _TiledAttention.apply(adj, X, attn[0], attn[1], slope, edge_drop, row_mask, nbr_mask)
+    if mode == "extremum":
         return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask)
     return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask)
 
