@@ -1,7 +1,7 @@
 """In-tree build of the native pieces (called by __graft_entry__.build()).
 
-  libqgtc_hip.so                    hipcc --offload-arch=gfx950  csrc/qgtc_hip.hip + qgtc_mfma.hip + qgtc_fp4.hip + qgtc_wide.hip + qgtc_epoch.hip + qgtc_chainx.hip + qgtc_stream.hip + qgtc_tiled.hip + qgtc_tiled_t.hip + qgtc_tiled_scaled.hip + qgtc_tiled_t_scaled.hip + qgtc_tiled_float.hip + qgtc_tiled_float_t.hip + qgtc_tiled_float_src.hip + qgtc_tiled_float_t_src.hip + qgtc_tiled_max.hip + qgtc_tiled_max_t.hip + qgtc_tiled_attn.hip + qgtc_tiled_attn_t.hip + qgtc_tiled_float_drop.hip + qgtc_tiled_float_t_drop.hip + qgtc_tiled_max_drop.hip + qgtc_tiled_attn_drop.hip + qgtc_tiled_attn_t_drop.hip + qgtc_tiled_float_nodes.hip + qgtc_tiled_float_t_nodes.hip + qgtc_tiled_max_nodes.hip + qgtc_tiled_attn_nodes.hip + qgtc_tiled_attn_t_nodes.hip + qgtc_tiled_float_edge.hip + qgtc_tiled_float_t_edge.hip + qgtc_tiled_sddmm.hip + qgtc_reorder.hip (thirty-three translation
-                                    units compiled in parallel; they include csrc/*.hip.h, the kernels)
+  libqgtc_hip.so                    hipcc --offload-arch=gfx950  the translation units csrc/*.hip that HIP_UNITS below lists, compiled
+                                    in parallel; they include csrc/*.hip.h, the kernels
   QGTC.cpython-*.so                 g++                          csrc/qgtc_torch.cpp (pybind11 binding)
 
 Both land next to this file so that they travel with the repo snapshot to the GPU box (they are

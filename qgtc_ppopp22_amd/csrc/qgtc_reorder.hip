@@ -11,14 +11,10 @@
 #include "qgtc.h"
 
 #include "common.hip.h"
+#include "tiled_args.hip.h"   // TILED_MAX_N and the 1-D grid rule
 #include "reorder_kernels.hip.h"
 
 namespace {
-
-int reorder_grid(uint64_t items) {
-    const uint64_t b = (items + 255) / 256;
-    return static_cast<int>(b < 8192 ? (b ? b : 1) : 8192);
-}
 
 size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
@@ -76,9 +72,9 @@ int qgtc_reorder_nodes(const int64_t *src, const int64_t *dst, size_t n_edges, i
     if (bad_index) FILL_TRY(bad_index, 0, sizeof(int), st);
     if (!n_edges || !sweeps) {   // no neighbour entries or no sweep: every label stays the node's own id
         if (n_edges && bad_index)
-            hipLaunchKernelGGL(k_reorder_check, dim3(reorder_grid(n_edges)), dim3(256), 0, st, src, dst, static_cast<uint64_t>(n_edges), n,
+            hipLaunchKernelGGL(k_reorder_check, dim3(tiled_grid_1d(n_edges)), dim3(256), 0, st, src, dst, static_cast<uint64_t>(n_edges), n,
                                bad_index);
-        hipLaunchKernelGGL(k_reorder_identity, dim3(reorder_grid(n)), dim3(256), 0, st, n, perm, rank);
+        hipLaunchKernelGGL(k_reorder_identity, dim3(tiled_grid_1d(n)), dim3(256), 0, st, n, perm, rank);
         HIP_TRY(hipGetLastError());
         return QGTC_OK;
     }
@@ -97,27 +93,27 @@ int qgtc_reorder_nodes(const int64_t *src, const int64_t *dst, size_t n_edges, i
     FILL_TRY(size, 0, static_cast<size_t>(n) * 8, st);
     FILL_TRY(changed, 0, REORDER_MAX_SWEEPS * 4, st);
     // symmetrised neighbour lists
-    hipLaunchKernelGGL(k_reorder_entry_keys, dim3(reorder_grid(e)), dim3(256), 0, st, src, dst, e, n, A, bad_index);
+    hipLaunchKernelGGL(k_reorder_entry_keys, dim3(tiled_grid_1d(e)), dim3(256), 0, st, src, dst, e, n, A, bad_index);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, m, 0, REORDER_KEY_BITS, st));
-    hipLaunchKernelGGL(k_reorder_offsets, dim3(reorder_grid(m + 1)), dim3(256), 0, st, B, m, n, off, nbr);
+    hipLaunchKernelGGL(k_reorder_offsets, dim3(tiled_grid_1d(m + 1)), dim3(256), 0, st, B, m, n, off, nbr);
     // the nodes by (degree class, parity, id)
-    hipLaunchKernelGGL(k_reorder_class_keys, dim3(reorder_grid(n)), dim3(256), 0, st, off, n, A);
+    hipLaunchKernelGGL(k_reorder_class_keys, dim3(tiled_grid_1d(n)), dim3(256), 0, st, off, n, A);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, static_cast<size_t>(n), 0, REORDER_CLASS_BITS, st));
-    hipLaunchKernelGGL(k_reorder_segments, dim3(reorder_grid(static_cast<uint64_t>(n) + 1)), dim3(256), 0, st, B, n, order, seg);
-    hipLaunchKernelGGL(k_reorder_init, dim3(reorder_grid(n)), dim3(256), 0, st, n, label);
+    hipLaunchKernelGGL(k_reorder_segments, dim3(tiled_grid_1d(static_cast<uint64_t>(n) + 1)), dim3(256), 0, st, B, n, order, seg);
+    hipLaunchKernelGGL(k_reorder_init, dim3(tiled_grid_1d(n)), dim3(256), 0, st, n, label);
     // the sweeps: queued without a read-back; the launches after an early stop return at once
     uint32_t *hkey = reinterpret_cast<uint32_t *>(A), *hcount = reinterpret_cast<uint32_t *>(B);
-    const int g = reorder_grid(static_cast<uint64_t>(n) * 4);
+    const int g = tiled_grid_1d(static_cast<uint64_t>(n) * 4);
     for (int t = 0; t < sweeps; ++t) {
         int *cur = size + (t & 1) * static_cast<size_t>(n), *next = size + ((t + 1) & 1) * static_cast<size_t>(n);
         hipLaunchKernelGGL(k_reorder_sweep, dim3(g), dim3(256), 0, st, t, n, off, nbr, order, seg, label, prop, cur, changed, hkey,
                            hcount);
-        hipLaunchKernelGGL(k_reorder_accept, dim3(reorder_grid(n)), dim3(256), 0, st, t, n, cap, label, prop, cur, next, changed);
+        hipLaunchKernelGGL(k_reorder_accept, dim3(tiled_grid_1d(n)), dim3(256), 0, st, t, n, cap, label, prop, cur, next, changed);
     }
     // perm = the nodes by (label, id), rank its inverse
-    hipLaunchKernelGGL(k_reorder_rank_keys, dim3(reorder_grid(n)), dim3(256), 0, st, label, n, A);
+    hipLaunchKernelGGL(k_reorder_rank_keys, dim3(tiled_grid_1d(n)), dim3(256), 0, st, label, n, A);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, static_cast<size_t>(n), 0, REORDER_KEY_BITS, st));
-    hipLaunchKernelGGL(k_reorder_perm, dim3(reorder_grid(n)), dim3(256), 0, st, B, n, perm, rank);
+    hipLaunchKernelGGL(k_reorder_perm, dim3(tiled_grid_1d(n)), dim3(256), 0, st, B, n, perm, rank);
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }

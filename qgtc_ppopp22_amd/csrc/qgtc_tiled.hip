@@ -16,14 +16,8 @@
 #include "common.hip.h"
 #include "bitmm_popcount.hip.h"   // requant (templates only: nothing is instantiated here)
 #include "tiled_kernels.hip.h"
-#include "tiled_args.hip.h"
 
 namespace {
-
-int tiled_grid(uint64_t items) {
-    const uint64_t b = (items + 255) / 256;
-    return static_cast<int>(b < 8192 ? (b ? b : 1) : 8192);
-}
 
 // bytes of rocPRIM temporary storage for n_edges keys: the larger of the sort's and the scan's (the queries look at the current
 // device; false when they fail)
@@ -64,7 +58,7 @@ int qgtc_tiled_count(const int64_t *src, const int64_t *dst, size_t n_edges, int
     void *temp = reinterpret_cast<char *>(work) + tiled_temp_offset_bytes(e);
     size_t temp_bytes = 0;
     if (!tiled_temp_bytes(e, temp_bytes)) return QGTC_ENODEVICE;
-    const int g = tiled_grid(e);
+    const int g = tiled_grid_1d(e);
     hipLaunchKernelGGL(k_tiled_keys, dim3(g), dim3(256), 0, st, src, dst, e, n, nq, A, bad_index);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, e, 0, TILED_KEY_BITS, st));
     hipLaunchKernelGGL(k_tiled_flags, dim3(g), dim3(256), 0, st, B, e, C);
@@ -90,53 +84,20 @@ int qgtc_tiled_fill(size_t n_edges, int n, int64_t n_tiles, int32_t *kquad, uint
     const uint64_t e = n_edges;
     const uint64_t *A = reinterpret_cast<const uint64_t *>(work), *B = A + e, *C = B + e;
     FILL_TRY(tiles, 0, static_cast<size_t>(n_tiles) * 512, st);
-    hipLaunchKernelGGL(k_tiled_fill, dim3(tiled_grid(e)), dim3(256), 0, st, C, A, B, e, step128(n), static_cast<uint64_t>(n_tiles),
+    hipLaunchKernelGGL(k_tiled_fill, dim3(tiled_grid_1d(e)), dim3(256), 0, st, C, A, B, e, step128(n), static_cast<uint64_t>(n_tiles),
                        kquad, tiles);
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
 
-namespace {
-
-template <int MODE>
-int tiled_mm(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
-             size_t x_words, int N, int bit2, int ob, void *out, hipStream_t st) {
-    const int nrb = (n + 31) / 32;
-    const float maxv = std::ldexp(1.0f, ob), maxm1 = maxv - 1.0f;
-    const dim3 block(256);
-    // rows a thread owns: the narrowest layout whose columns cover min(N, 128)
-    const int R = N <= 16 ? 2 : (N <= 32 ? 4 : (N <= 64 ? 8 : 16));
-    const dim3 grid(nrb, R == 16 ? step128(N) : 1);
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-#define QGTC_TILED_LAUNCH(RR)                                                                                                   \
-    hipLaunchKernelGGL((k_tiled_mm<RR, MODE>), grid, block, 0, st, row_ptr, kquad, tiles, nt, n, X, static_cast<uint64_t>(x_words), \
-                       N, bit2, ob, maxv, maxm1, out)
-    switch (R) {
-        case 2: QGTC_TILED_LAUNCH(2); break;
-        case 4: QGTC_TILED_LAUNCH(4); break;
-        case 8: QGTC_TILED_LAUNCH(8); break;
-        default: QGTC_TILED_LAUNCH(16); break;
-    }
-#undef QGTC_TILED_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-}  // namespace
-
 int qgtc_tiledmm2bit(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
                      size_t x_words, int N, int bit2, int output_bit, uint32_t *out, size_t out_words, void *stream) {
-    const int rc = tiled_mm_args_ok(row_ptr, kquad, tiles, n_tiles, n, X, N, bit2, out);
-    if (rc != QGTC_OK) return rc;
-    if (!bits_ok(output_bit)) return QGTC_EINVAL;
-    if (out_words < qgtc_rows_words(n, N, output_bit)) return QGTC_ESIZE;
-    return tiled_mm<0>(row_ptr, kquad, tiles, n_tiles, n, X, x_words, N, bit2, output_bit, out, static_cast<hipStream_t>(stream));
+    const TiledRowIndex ix{row_ptr, kquad};
+    return tiled_mm_entry<0>(ix, tiles, n_tiles, n, X, x_words, N, bit2, output_bit, out, out_words, stream);
 }
 
 int qgtc_tiledmm2int(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X,
                      size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream) {
-    const int rc = tiled_mm_args_ok(row_ptr, kquad, tiles, n_tiles, n, X, N, bit2, out);
-    if (rc != QGTC_OK) return rc;
-    if (out_elems < static_cast<size_t>(n) * N) return QGTC_ESIZE;
-    return tiled_mm<2>(row_ptr, kquad, tiles, n_tiles, n, X, x_words, N, bit2, 1, out, static_cast<hipStream_t>(stream));
+    const TiledRowIndex ix{row_ptr, kquad};
+    return tiled_mm_entry<2>(ix, tiles, n_tiles, n, X, x_words, N, bit2, 1, out, out_elems, stream);
 }

@@ -35,7 +35,7 @@ int qgtc_tiledatt_grad_f32(const int64_t *row_ptr, const int32_t *kquad, const u
 }
 
 int qgtc_rowdot_f32(const float *A, const float *B, size_t ab_elems, int n, int N, float *out, size_t out_elems, void *stream) {
-    if (!A || !B || !out || n < 1 || n > (1 << 23) || N < 1) return QGTC_EINVAL;
+    if (!A || !B || !out || n < 1 || n > TILED_MAX_N || N < 1) return QGTC_EINVAL;
     if (!aligned4(A) || !aligned4(B) || !aligned4(out)) return QGTC_EALIGN;
     if (ab_elems < static_cast<size_t>(n) * static_cast<size_t>(N) || out_elems < static_cast<size_t>(n)) return QGTC_ESIZE;
     hipLaunchKernelGGL(k_rowdot_f32, dim3((n + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), A, B, n, N, out);

@@ -97,8 +97,8 @@ __global__ __launch_bounds__(256) void k_tiled_edge_endpoints(const int64_t *__r
 
 // what the three index entries check of the adjacency
 inline int tiled_edge_adj_ok(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n) {
-    if (n < 1 || n > (1 << 23) || n_tiles < 0 || (n_tiles && (!row_ptr || !kquad || !tiles))) return QGTC_EINVAL;
-    if (tiles && !aligned16(tiles)) return QGTC_EALIGN;
+    if (tiled_adj_malformed(TiledRowIndex{row_ptr, kquad}.ok(), tiles, n_tiles, n)) return QGTC_EINVAL;
+    if (tiled_adj_misaligned(tiles)) return QGTC_EALIGN;
     return QGTC_OK;
 }
 

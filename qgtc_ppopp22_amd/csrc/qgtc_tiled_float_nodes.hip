@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_node_bitmap(const uint8_t *__restrict__
 }  // namespace
 
 int qgtc_node_bitmap(const uint8_t *flags, int n, uint32_t *words, size_t words_len, void *stream) {
-    if (!flags || !words || n < 1 || n > (1 << 23)) return QGTC_EINVAL;
+    if (!flags || !words || n < 1 || n > TILED_MAX_N) return QGTC_EINVAL;
     if (!aligned16(words)) return QGTC_EALIGN;
     const int n_words = step128(n) * 4;
     if (words_len < static_cast<size_t>(n_words)) return QGTC_ESIZE;

@@ -148,8 +148,8 @@ int qgtc_tiled_sddmm_f32(const int64_t *row_ptr, const int32_t *kquad, const uin
                          size_t n_values, void *stream) {
     const TiledRowIndex ix{row_ptr, kquad};
     int rc = QGTC_OK;
-    if (!A || !B || (n_values && !out) || n < 1 || n > (1 << 23) || N < 1 || n_tiles < 0 || (n_tiles && (!ix.ok() || !tiles))) rc = QGTC_EINVAL;
-    else if ((tiles && !aligned16(tiles)) || !aligned4(A) || !aligned4(B) || !aligned4(out)) rc = QGTC_EALIGN;
+    if (!A || !B || (n_values && !out) || N < 1 || tiled_adj_malformed(ix.ok(), tiles, n_tiles, n)) rc = QGTC_EINVAL;
+    else if (tiled_adj_misaligned(tiles) || !aligned4(A) || !aligned4(B) || !aligned4(out)) rc = QGTC_EALIGN;
     else if (ab_elems < static_cast<size_t>(n) * static_cast<size_t>(N)) rc = QGTC_ESIZE;
     rc = tiled_edge_rc(rc, tiled_edge_index_ok(val_ptr, val_row, n_tiles, n_values));
     if (rc != QGTC_OK) return rc;

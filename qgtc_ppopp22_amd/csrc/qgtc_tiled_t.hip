@@ -15,16 +15,10 @@
 #include "common.hip.h"
 #include "bitmm_popcount.hip.h"   // requant (templates only: nothing is instantiated here)
 #include "tiled_t_kernels.hip.h"
-#include "tiled_args.hip.h"
 
 namespace {
 
 constexpr int64_t TILED_T_MAX_TILES = int64_t{1} << 40;   // tile ids fit 40 bits, k-quads 17: a sort key fits 57
-
-int tiled_t_grid(uint64_t items) {
-    const uint64_t b = (items + 255) / 256;
-    return static_cast<int>(b < 8192 ? (b ? b : 1) : 8192);
-}
 
 unsigned bit_width(uint64_t v) {
     unsigned b = 0;
@@ -70,7 +64,7 @@ int qgtc_tiled_colindex(const int64_t *row_ptr, const int32_t *kquad, int64_t n_
     void *temp = reinterpret_cast<char *>(work) + colindex_temp_offset_bytes(t);
     size_t temp_bytes = 0;
     if (!colindex_temp_bytes(t, temp_bytes)) return QGTC_ENODEVICE;
-    const int g = tiled_t_grid(t);
+    const int g = tiled_grid_1d(t);
     hipLaunchKernelGGL(k_tiled_col_keys, dim3(g), dim3(256), 0, st, kquad, t, nq, tile_bits, A);
     HIP_TRY(rocprim::radix_sort_keys(temp, temp_bytes, A, B, t, 0, end_bit, st));
     hipLaunchKernelGGL(k_tiled_col_index, dim3(g), dim3(256), 0, st, B, t, tile_bits, row_ptr, nrb, nq, col_ptr, col_tile, col_rb);
@@ -78,48 +72,15 @@ int qgtc_tiled_colindex(const int64_t *row_ptr, const int32_t *kquad, int64_t n_
     return QGTC_OK;
 }
 
-namespace {
-
-template <int MODE>
-int tiled_mm_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles, int n,
-               const uint32_t *X, size_t x_words, int N, int bit2, int ob, void *out, hipStream_t st) {
-    const float maxv = std::ldexp(1.0f, ob), maxm1 = maxv - 1.0f;
-    const dim3 block(256);
-    // rows of the k-quad a thread owns: the narrowest layout whose columns cover min(N, 128)
-    const int R = N <= 16 ? 8 : (N <= 32 ? 16 : (N <= 64 ? 32 : 64));
-    const dim3 grid(step128(n), R == 64 ? step128(N) : 1);
-    const uint64_t nt = static_cast<uint64_t>(n_tiles);
-#define QGTC_TILED_T_LAUNCH(RR)                                                                                                    \
-    hipLaunchKernelGGL((k_tiled_mm_t<RR, MODE>), grid, block, 0, st, col_ptr, col_tile, col_rb, tiles, nt, n, X,                   \
-                       static_cast<uint64_t>(x_words), N, bit2, ob, maxv, maxm1, out)
-    switch (R) {
-        case 8: QGTC_TILED_T_LAUNCH(8); break;
-        case 16: QGTC_TILED_T_LAUNCH(16); break;
-        case 32: QGTC_TILED_T_LAUNCH(32); break;
-        default: QGTC_TILED_T_LAUNCH(64); break;
-    }
-#undef QGTC_TILED_T_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return QGTC_OK;
-}
-
-}  // namespace
-
 int qgtc_tiledmm2bit_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
                        int n, const uint32_t *X, size_t x_words, int N, int bit2, int output_bit, uint32_t *out, size_t out_words,
                        void *stream) {
-    const int rc = tiled_mm_t_args_ok(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, bit2, out);
-    if (rc != QGTC_OK) return rc;
-    if (!bits_ok(output_bit)) return QGTC_EINVAL;
-    if (out_words < qgtc_rows_words(n, N, output_bit)) return QGTC_ESIZE;
-    return tiled_mm_t<0>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, x_words, N, bit2, output_bit, out,
-                         static_cast<hipStream_t>(stream));
+    const TiledColIndex ix{col_ptr, col_tile, col_rb};
+    return tiled_mm_entry<0>(ix, tiles, n_tiles, n, X, x_words, N, bit2, output_bit, out, out_words, stream);
 }
 
 int qgtc_tiledmm2int_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
                        int n, const uint32_t *X, size_t x_words, int N, int bit2, float *out, size_t out_elems, void *stream) {
-    const int rc = tiled_mm_t_args_ok(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, N, bit2, out);
-    if (rc != QGTC_OK) return rc;
-    if (out_elems < static_cast<size_t>(n) * N) return QGTC_ESIZE;
-    return tiled_mm_t<2>(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, x_words, N, bit2, 1, out, static_cast<hipStream_t>(stream));
+    const TiledColIndex ix{col_ptr, col_tile, col_rb};
+    return tiled_mm_entry<2>(ix, tiles, n_tiles, n, X, x_words, N, bit2, 1, out, out_elems, stream);
 }

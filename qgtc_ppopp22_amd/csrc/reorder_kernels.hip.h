@@ -11,7 +11,7 @@
 
 namespace {
 
-constexpr int REORDER_MAX_N = 1 << 23;
+constexpr int REORDER_MAX_N = TILED_MAX_N;   // tiled_args.hip.h, included before this file: node ids fit the 23 bits of the keys below
 constexpr int REORDER_MAX_SWEEPS = 64;
 constexpr uint64_t REORDER_INVALID = (1ull << 46) - 1;   // entry key of a skipped edge: sorts after every valid key (u = v = 2^23 - 1)
 constexpr unsigned REORDER_KEY_BITS = 46;

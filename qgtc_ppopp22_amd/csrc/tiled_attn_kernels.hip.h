@@ -434,8 +434,8 @@ inline int tiled_att_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_til
     if (!tiled_att_slope_ok(slope)) return QGTC_EINVAL;
     for (const float *v : vec)
         if (!v) return QGTC_EINVAL;
-    if (!X || !out || n < 1 || n > (1 << 23) || N < 1 || n_tiles < 0 || (n_tiles && (!index_ok || !tiles))) return QGTC_EINVAL;
-    if ((tiles && !aligned16(tiles)) || !aligned4(X) || !aligned4(out)) return QGTC_EALIGN;
+    if (!X || !out || N < 1 || tiled_adj_malformed(index_ok, tiles, n_tiles, n)) return QGTC_EINVAL;
+    if (tiled_adj_misaligned(tiles) || !aligned4(X) || !aligned4(out)) return QGTC_EALIGN;
     for (const float *v : vec)
         if (!aligned4(v)) return QGTC_EALIGN;
     const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);

@@ -1,8 +1,8 @@
-// tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_float.hip, qgtc_tiled_float_t.hip and their _src twins): the
+// tiled_float_kernels.hip.h — part of libqgtc_hip.so (included by every float, extremum, attention, edge-value and SDDMM unit): the
 // product of the tile-compressed 1-bit adjacency with a FLOAT32 right operand, out = A_tiled . X (include/qgtc.h, "Float tiled
 // products"; DESIGN.md sections 6.14, 6.15) - the in-order row adder both directions share, the forward kernel, the argument checks
-// of the entries and, for every float, extremum and attention unit, the host side of a launch: the views' index structs, the kernel
-// shapes by N and this family's launcher.
+// of the entries and, for every float, extremum and attention unit, the host side of a launch: the kernel shapes by N and this family's
+// launcher (the views' index structs and the graph part of a check are tiled_args.hip.h's).
 //
 // The bit products AND + popcount whole 128-bit tile rows because their operand is bit planes. Here the operand is floats and the
 // tiles of real graphs are nearly empty (about 9 of 4096 cells), so a tile is read as a compressed neighbour list: the set bits of a
@@ -20,8 +20,7 @@
 // would by a source scale.
 #pragma once
 
-#include <type_traits>
-
+#include "tiled_args.hip.h"
 #include "tiled_drop.hip.h"
 #include "tiled_nodes.hip.h"
 #include "tiled_edge.hip.h"
@@ -233,32 +232,19 @@ inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3
 // `index_ok`: every index array of the direction is there (they and `tiles` may be NULL only when n_tiles is 0)
 inline int tiled_f32_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const float *X, size_t x_elems, int N,
                              const float *row_scale, const float *out, size_t out_elems, const float *src_scale = nullptr) {
-    if (!X || !out || n < 1 || n > (1 << 23) || N < 1 || n_tiles < 0 || (n_tiles && (!index_ok || !tiles))) return QGTC_EINVAL;
-    if ((tiles && !aligned16(tiles)) || !aligned4(X) || !aligned4(out) || !aligned4(row_scale) || !aligned4(src_scale))
+    if (!X || !out || N < 1 || tiled_adj_malformed(index_ok, tiles, n_tiles, n)) return QGTC_EINVAL;
+    if (tiled_adj_misaligned(tiles) || !aligned4(X) || !aligned4(out) || !aligned4(row_scale) || !aligned4(src_scale))
         return QGTC_EALIGN;
     const size_t need = static_cast<size_t>(n) * static_cast<size_t>(N);
     if (x_elems < need || out_elems < need) return QGTC_ESIZE;
     return QGTC_OK;
 }
 
-// ---- the host side every float, extremum and attention unit shares: the two views' index arrays and their kernel shapes by N -----------
+// ---- the host side every float, extremum and attention unit shares: the kernel shapes by N of the two views ----------------------------
 // Each kernel family has ONE launcher, at the foot of the family's header; it ends in the kernel's own trailing pack and forwards it, so
 // a masked launch takes the shape its plain parent takes. The launchers of the two views are overloads on
-// these structs, and the templates above them are written once for both views.
-struct TiledRowIndex {
-    const int64_t *row_ptr;
-    const int32_t *kquad;
-    bool ok() const { return row_ptr && kquad; }   // the `index_ok` of the argument checks
-};
-struct TiledColIndex {
-    const int64_t *col_ptr, *col_tile;
-    const int32_t *col_rb;
-    bool ok() const { return col_ptr && col_tile && col_rb; }
-};
-
-template <int V>
-using tiled_int = std::integral_constant<int, V>;
-
+// TiledRowIndex / TiledColIndex (tiled_args.hip.h), and the templates above them are written once for both views.
+//
 // The row view: lanes per output row (LPR) and columns per lane (CPL) by N, for the float sum, the extremum / select and the attention
 // sum alike; launch(LPR, CPL) gets them as integral constants and makes one workgroup per 32-row block and LPR * CPL output columns
 // (tiled_row_grid). tests/tiled_float_model.py FLOAT_FORWARD_VARIANTS, tiled_max_model.py MAX_FORWARD_VARIANTS and tiled_attn_model.py

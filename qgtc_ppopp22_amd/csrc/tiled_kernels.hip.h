@@ -1,5 +1,6 @@
-// tiled_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled.hip): the tile-compressed adjacency of a whole graph
-// (include/qgtc.h, "Tile-compressed adjacency"; DESIGN.md sections 4 and 6.10) - its packer and its product.
+// tiled_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled.hip and qgtc_tiled_scaled.hip): the tile-compressed adjacency of a
+// whole graph (include/qgtc.h, "Tile-compressed adjacency"; DESIGN.md sections 4 and 6.10) - its packer, its product and, at the foot,
+// the product's launcher.
 //
 // Format: a one-plane n x n adjacency as the OCCUPIED 512-byte tiles [32 rows][4 words] of its 32-row x 128-column grid, block-sparse
 // like BSR: row_ptr[32-row block] (int64, S32(n) + 1 entries), kquad[tile] (ascending within a row block), tiles[tile][32][4].
@@ -9,6 +10,8 @@
 // the cell is set when the run is 1 or >= 3 long (the 1-bit quantiser of the summed matrix, the words qgtc_pack_edge_list gives). The
 // set cells are compacted, the first cell of every tile is flagged, and one exclusive scan of those flags numbers the tiles.
 #pragma once
+
+#include "tiled_args.hip.h"
 
 namespace {
 
@@ -196,6 +199,34 @@ __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ ro
                     *reinterpret_cast<const uint4 *>(&st[k * 4]);
         }
     }
+}
+
+// ---- the launcher of k_tiled_mm ----------------------------------------------------------------------------------------------------------
+// rows a thread owns (R) by N: the narrowest layout whose columns cover min(N, 128); launch(R) gets it as an integral constant
+template <class F>
+void tiled_mm_rows_switch(int N, F &&launch) {
+    switch (N <= 16 ? 2 : (N <= 32 ? 4 : (N <= 64 ? 8 : 16))) {
+        case 2: launch(tiled_int<2>{}); break;
+        case 4: launch(tiled_int<4>{}); break;
+        case 8: launch(tiled_int<8>{}); break;
+        default: launch(tiled_int<16>{}); break;
+    }
+}
+
+// It ends in the kernel's own trailing pack and forwards it: empty is the plain kernel, (row_scale) the scaled one
+// (DESIGN.md section 6.15f).
+template <int MODE, class... Scale>
+int tiled_mm_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N,
+                    int bit2, int ob, void *out, hipStream_t st, Scale... scale) {
+    const TiledClamp clamp(ob);
+    tiled_mm_rows_switch(N, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        hipLaunchKernelGGL((k_tiled_mm<R, MODE, Scale...>), dim3((n + 31) / 32, R == 16 ? step128(N) : 1), dim3(256), 0, st, ix.row_ptr,
+                           ix.kquad, tiles, static_cast<uint64_t>(n_tiles), n, X, static_cast<uint64_t>(x_words), N, bit2, ob, clamp.maxv,
+                           clamp.maxm1, out, scale...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
 }
 
 }  // namespace

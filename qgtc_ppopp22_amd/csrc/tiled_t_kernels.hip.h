@@ -1,11 +1,14 @@
-// tiled_t_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_t.hip): the transposed product of the tile-compressed
+// tiled_t_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_t.hip and qgtc_tiled_t_scaled.hip, and for the bit transpose by
+// qgtc_tiled_scaled.hip and the column-view float, extremum and attention units): the transposed product of the tile-compressed
 // adjacency, requant(A_tiled^T . X), from the same tiles (include/qgtc.h, "Transposed tiled adjacency") - the
-// column index that lists the tiles by k-quad, and the product kernel.
+// column index that lists the tiles by k-quad, the product kernel and, at the foot, its launcher.
 //
 // Column index: one radix sort of the keys (kquad << tile_bits | tile id) orders the tiles by (k-quad, tile id); a tile id already
 // orders the tiles of one k-quad by row block. k_tiled_col_index then writes col_tile, col_rb (a binary search of row_ptr) and col_ptr
 // (the first entry of every k-quad writes its start and those of the empty k-quads before it; the last entry writes the end).
 #pragma once
+
+#include "tiled_args.hip.h"
 
 namespace {
 
@@ -209,6 +212,34 @@ __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ 
             __syncthreads();
         }
     }
+}
+
+// ---- the launcher of k_tiled_mm_t --------------------------------------------------------------------------------------------------------
+// rows of the k-quad a thread owns (R) by N: the narrowest layout whose columns cover min(N, 128); launch(R) gets it as an integral
+// constant
+template <class F>
+void tiled_mm_t_rows_switch(int N, F &&launch) {
+    switch (N <= 16 ? 8 : (N <= 32 ? 16 : (N <= 64 ? 32 : 64))) {
+        case 8: launch(tiled_int<8>{}); break;
+        case 16: launch(tiled_int<16>{}); break;
+        case 32: launch(tiled_int<32>{}); break;
+        default: launch(tiled_int<64>{}); break;
+    }
+}
+
+// the column view's overload of tiled_kernels.hip.h's launcher: the pack is empty or (row_scale)
+template <int MODE, class... Scale>
+int tiled_mm_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N,
+                    int bit2, int ob, void *out, hipStream_t st, Scale... scale) {
+    const TiledClamp clamp(ob);
+    tiled_mm_t_rows_switch(N, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        hipLaunchKernelGGL((k_tiled_mm_t<R, MODE, Scale...>), dim3(step128(n), R == 64 ? step128(N) : 1), dim3(256), 0, st, ix.col_ptr,
+                           ix.col_tile, ix.col_rb, tiles, static_cast<uint64_t>(n_tiles), n, X, static_cast<uint64_t>(x_words), N, bit2, ob,
+                           clamp.maxv, clamp.maxm1, out, scale...);
+    });
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
 }
 
 }  // namespace

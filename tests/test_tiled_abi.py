@@ -4,7 +4,7 @@ import ctypes
 
 import pytest
 
-EINVAL, ESIZE = 1, 2
+EINVAL, ESIZE, EALIGN = 1, 2, 3
 P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
@@ -58,3 +58,22 @@ def test_products_refuse_bad_arguments(lib):
     assert lib.qgtc_tiledmm2bit(p, p, p, 1, 100, p, 1 << 16, 8, 2, 33, p, 1 << 16, None) == EINVAL   # output_bit > 32
     assert lib.qgtc_tiledmm2bit(p, p, p, 1, 100, p, 1 << 16, 8, 2, 4, p, 10, None) == ESIZE          # out too small
     assert lib.qgtc_tiledmm2int(p, p, p, 1, 100, p, 1 << 16, 8, 2, p, 799, None) == ESIZE            # out too small
+
+
+@pytest.mark.parametrize("which", ["bit", "int"])
+def test_products_need_row_ptr_and_keep_the_order_of_refusals(lib, which):
+    """The bit kernels read row_ptr without looking at n_tiles, so the entries want it even for an adjacency without tiles; and of two
+    faults the invalid argument is reported before the misaligned one, and either before the short output."""
+    keep, p = _buf(1 << 16)
+    big = 1 << 16
+
+    def fn(rp=p, kq=p, tl=p, T=1, X=p, w=2, ob=2, out_size=big):
+        tail = (w, ob, p, out_size, None) if which == "bit" else (w, p, out_size, None)
+        return getattr(lib, "qgtc_tiledmm2" + which)(rp, kq, tl, T, 100, X, big, 8, *tail)
+
+    assert fn(rp=None, kq=None, tl=None, T=0) == EINVAL       # no row_ptr, no tiles
+    assert fn(rp=None, T=0) == EINVAL
+    assert fn(w=9, out_size=10) == EINVAL                     # bit2 > 8 and a short output
+    assert fn(X=p + 4, out_size=10) == EALIGN                 # X off a 16-byte boundary and a short output
+    if which == "bit":
+        assert fn(X=p + 4, ob=33) == EALIGN                   # the shared check (X misaligned) comes before the entry's own (output_bit)

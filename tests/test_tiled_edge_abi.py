@@ -72,6 +72,7 @@ def test_edge_slots_refuses_bad_arguments(lib, p):
         assert f(**{name: p + 4}) == EALIGN, name
     assert f(vr=p + 1) == EALIGN
     assert f(tl=p + 4, src=None) == EINVAL        # invalid before misaligned
+    assert f(n=1 << 23, tl=p + 4) == EALIGN and f(n=1 << 23, slot=p + 4) == EALIGN   # n = 2^23 is in range: the next refusal is reached
     assert f(E=0, src=None, dst=None, slot=None) == OK
 
 
@@ -132,3 +133,5 @@ def test_sddmm_refuses_bad_arguments(lib, p):
     assert f(vp=p + 4) == EALIGN and f(vr=p + 1) == EALIGN
     assert f(ab=799) == ESIZE
     assert f(ab=799, A=p + 2) == EALIGN and f(ab=799, B=None) == EINVAL
+    assert f(n=1 << 23, ab=799) == ESIZE          # n = 2^23 is in range: the next refusal is reached
+    assert f(ab=799, tl=p + 4) == EALIGN          # misaligned tile words before short operands

@@ -59,6 +59,7 @@ def test_float_products_refuse_bad_arguments(lib, transposed):
     assert fn(ok, 1, 1 << 23, 1 << 20, x_elems=(1 << 43) - 1, out_elems=1 << 43) == ESIZE   # n * N does not wrap in 32 bits
     assert fn(ok[:-1] + (p + 4,), 1, 100, 8) == EALIGN        # tiles off a 16-byte boundary
     assert fn(ok[:-1] + (p + 8,), 1, 100, 8) == EALIGN
+    assert fn(ok[:-1] + (p + 4,), 1, 100, 8, out_elems=799) == EALIGN   # ... before a short output
     for off in (1, 2, 3):
         assert fn(ok, 1, 100, 8, X=p + off) == EALIGN         # X off a 4-byte boundary
         assert fn(ok, 1, 100, 8, out=p + off) == EALIGN       # out off a 4-byte boundary

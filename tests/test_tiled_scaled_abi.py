@@ -43,6 +43,8 @@ def test_degrees_refuse_bad_arguments(lib):
     assert call(p, p, p, 1, 100, p, None, None, p, None) == EINVAL            # in_inv without in_deg
     assert call(p, p, p, 1, 100, None, None, p, p, None) == EINVAL            # reciprocals alone
     assert call(p, p, p + 4, 1, 100, p, p, p, p, None) == EALIGN              # tiles off a 16-byte boundary
+    assert call(p, p, p + 4, 1, 1 << 23, p, p, p, p, None) == EALIGN          # n = 2^23 is in range: the next refusal is reached
+    assert call(p, p, p + 4, 1, 100, None, None, p, p, None) == EINVAL        # invalid before misaligned
 
 
 @pytest.mark.parametrize("transposed", [False, True])
@@ -81,3 +83,12 @@ def test_scaled_products_refuse_bad_arguments(lib, which, transposed):
         assert fn(ok, 1, 100, 8, 2, ob=4, out_words=4 * 104 * 4 - 1) == ESIZE   # one word short of 4 planes x 104 rows
     else:
         assert fn(ok, 1, 100, 8, 2, out_words=799) == ESIZE   # one float short of 100 x 8
+    # the bit kernels read row_ptr / col_ptr without looking at n_tiles: wanted even for an adjacency without tiles
+    assert fn((None,) * len(ok), 0, 100, 8, 2) == EINVAL
+    assert fn((None,) + ok[1:], 0, 100, 8, 2) == EINVAL
+    # two faults at once: the shared check (invalid, then misaligned) before the entry's own (row_scale, output_bit), and the short output last
+    assert fn(ok, 1, 100, 8, 2, X=p + 4, scale=None) == EALIGN
+    assert fn(ok, 1, 100, 8, 9, out_words=10) == EINVAL
+    assert fn(ok, 1, 100, 8, 2, scale=None, out_words=10) == EINVAL
+    if which == "bit":
+        assert fn(ok, 1, 100, 8, 2, X=p + 4, ob=33) == EALIGN

@@ -5,7 +5,7 @@ import ctypes
 
 import pytest
 
-EINVAL, ESIZE, ENODEVICE = 1, 2, 5
+EINVAL, ESIZE, EALIGN, ENODEVICE = 1, 2, 3, 5
 P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
@@ -87,3 +87,22 @@ def test_products_refuse_bad_arguments(lib, which):
     # the C-ABI mirrors of the forward entries refuse the same way (the transposed entries add no domain of their own)
     assert lib.qgtc_tiledmm2bit_t(p, p, p, p, 1, 100, None, big, 8, 2, 2, p, big, None) == EINVAL   # no X
     assert lib.qgtc_tiledmm2int_t(p, p, p, p, 1, 100, p, big, 8, 2, None, big, None) == EINVAL      # no out
+
+
+@pytest.mark.parametrize("which", ["bit", "int"])
+def test_products_need_col_ptr_and_keep_the_order_of_refusals(lib, which):
+    """The bit kernels read col_ptr without looking at n_tiles, so the entries want it even for an adjacency without tiles; and of two
+    faults the invalid argument is reported before the misaligned one, and either before the short output."""
+    keep, p = _buf(1 << 16)
+    big = 1 << 16
+
+    def fn(cp=p, ct=p, cr=p, tl=p, T=1, X=p, w=2, ob=2, out_size=big):
+        tail = (w, ob, p, out_size, None) if which == "bit" else (w, p, out_size, None)
+        return getattr(lib, f"qgtc_tiledmm2{which}_t")(cp, ct, cr, tl, T, 100, X, big, 8, *tail)
+
+    assert fn(cp=None, ct=None, cr=None, tl=None, T=0) == EINVAL   # no col_ptr, no tiles
+    assert fn(cp=None, T=0) == EINVAL
+    assert fn(w=9, out_size=10) == EINVAL                     # bit2 > 8 and a short output
+    assert fn(X=p + 4, out_size=10) == EALIGN                 # X off a 16-byte boundary and a short output
+    if which == "bit":
+        assert fn(X=p + 4, ob=33) == EALIGN                   # the shared check (X misaligned) comes before the entry's own (output_bit)

@@ -1,6 +1,7 @@
 """Host cost of one tiled call, Python to launch: microseconds of issue time per call in a host-bound loop (4000 back-to-back calls,
 best of 5; the per_call loop of tools/call_cost.py) on a 40-node adjacency and X [40, 16], where the kernels are negligible. One row
-per mode of tiledMMFloat and one for tiledMM2Int, each on adj and adj.T.
+per mode of tiledMMFloat and one for each of the four launchers of the bit products (tiledMM2Int / tiledMM2Bit, plain and with a
+row_scale), each on adj and adj.T.
     python tools/tiled_call_cost.py OUT.json"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,7 +22,10 @@ CALLS = {"plain": lambda a: Q.tiledMMFloat(a, X),
          "node_masks": lambda a: Q.tiledMMFloat(a, X, row_mask=mask, nbr_mask=mask),
          "max": lambda a: Q.tiledMMFloat(a, X, reduce="max"),
          "attn": lambda a: Q.tiledMMFloat(a, X, attn=(zeros, scale)),
-         "tiledMM2Int": lambda a: Q.tiledMM2Int(a, bit_X, N, bit2)}
+         "tiledMM2Int": lambda a: Q.tiledMM2Int(a, bit_X, N, bit2),
+         "tiledMM2Bit": lambda a: Q.tiledMM2Bit(a, bit_X, N, bit2, 2),
+         "tiledMM2Int scaled": lambda a: Q.tiledMM2Int(a, bit_X, N, bit2, scale),
+         "tiledMM2Bit scaled": lambda a: Q.tiledMM2Bit(a, bit_X, N, bit2, 2, scale)}
 
 
 def per_call(fn, a, reps=4000):
