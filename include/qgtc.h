@@ -661,6 +661,8 @@ int qgtc_tiledsel_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const i
  *               (qgtc_tiledatt_grad_f32 / _t, nbr_owns = 0: A = dY, B = X, att_own = p, att_nbr = q)
  *     dq[k]     the fold of u over o ascending on the other view
  *               (qgtc_tiledatt_grad_f32 / _t, nbr_owns = 1: A = X, B = dY, att_own = q, att_nbr = p; m, inv, D are the neighbour's)
+ * The derivative of L at e = 0 exactly (+0 or -0) is therefore a, the negative slope, as L itself takes the fl(a * e) branch there:
+ * the convention of torch.nn.functional.leaky_relu, whose derivative is 1 for e > 0 and a otherwise.
  * Every fold starts from +0 and adds one term at a time. No atomics: all results are functions of the inputs alone, the same bits on
  * every launch and every kernel variant, and equal the NumPy model of tests/tiled_attn_model.py bit for bit.
  *
