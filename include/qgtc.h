@@ -853,6 +853,42 @@ int qgtc_tiled_sddmm_f32(const int64_t *row_ptr, const int32_t *kquad, const uin
                          const float *B, size_t ab_elems, int N, const int64_t *val_ptr, const int16_t *val_row, float *out,
                          size_t n_values, void *stream);
 
+/* ---- Edge softmax: a vector of per-edge logits normalised over each node's neighbourhood, and its gradient ----------------------------
+ * `logits`, `alpha` and `g` are float32 [n_values] in SLOT order ("Edge values"); slots depend on the tiles alone, so the same vectors
+ * serve both views. On the row view the OWNER of cell (i, j) is row i; on the column view (_t) it is column j. An owner's cells are
+ * taken in ascending id of the other end - ascending neighbour id, as in every float product. EXP is the exponential of "Attention
+ * tiled products"; no operation is fused.
+ *   forward, for an owner o with cells k = 1 .. d in that order:
+ *     m[o]   = l_1, then m = l_k > m ? l_k : m for k = 2 .. d (the first of equal values wins: the bits of m are specified);
+ *     w_k    = EXP(fl(l_k - m[o]));
+ *     den    = the in-order fold from +0 of w_k, one float32 add each;
+ *     inv[o] = den > 0 ? 1 / den : 0, IEEE division (the expression of the attention forward);
+ *     alpha[slot_k] = fl(w_k * inv[o]).
+ *   An owner without cells writes nothing to alpha and has m = +0 and inv = 0. l_k = -inf gives alpha = +0 for that edge, provided the
+ *   owner has one finite logit. A NaN or +inf logit gives unspecified values for that owner's cells only and touches no memory outside
+ *   the arrays; the same holds for an owner whose logits are all -inf. `m` and `inv` (float32 [n]) are optional outputs (NULL: not
+ *   wanted); when given, all n elements are written, also when there are no tiles.
+ *   gradient, given alpha and g = dL/dalpha:
+ *     t_k  = fl(alpha_k * g_k);   S[o] = the in-order fold from +0 of t_k;   out[slot_k] = fl(alpha_k * fl(g_k - S[o])).
+ * Every slot below n_values is written exactly once with a plain store, on either view; no atomics. A slot outside [0, n_values) - a
+ * foreign index - is never dereferenced: the cell is skipped.
+ * Refusals before any device work: QGTC_EINVAL for n outside 1 .. 2^23, a negative n_tiles, tiles without the view's index arrays /
+ * tiles / val_ptr / val_row, values without logits / alpha (alpha / g / out), or n_values > 2^31 - 1; then QGTC_EALIGN for tiles off
+ * 16 bytes, val_ptr off 8, val_row off 2 or a float array off 4. n_tiles == 0 or n_values == 0 returns QGTC_OK after filling m / inv
+ * (where given) with +0. */
+int qgtc_tiled_edge_softmax_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                                const int64_t *val_ptr, const int16_t *val_row, const float *logits, float *alpha, size_t n_values,
+                                float *m, float *inv, void *stream);
+int qgtc_tiled_edge_softmax_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                                  int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row, const float *logits,
+                                  float *alpha, size_t n_values, float *m, float *inv, void *stream);
+int qgtc_tiled_edge_softmax_grad_f32(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n,
+                                     const int64_t *val_ptr, const int16_t *val_row, const float *alpha, const float *g, float *out,
+                                     size_t n_values, void *stream);
+int qgtc_tiled_edge_softmax_grad_f32_t(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles,
+                                       int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row, const float *alpha,
+                                       const float *g, float *out, size_t n_values, void *stream);
+
 /* ---- Node reordering: ids that keep a tiled adjacency compact --------------------------------------------------------------------
  * The tiled format only pays off when a node's neighbours have nearby ids: under random ids nearly every edge occupies a tile of its
  * own (512 bytes an edge). qgtc_reorder_nodes renumbers the nodes on the device from a raw edge list with any ids:

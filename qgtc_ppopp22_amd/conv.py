@@ -320,3 +320,42 @@ class GATConv(torch.nn.Module):
         else:
             out = outs[0] if self.heads == 1 else torch.stack(outs).mean(dim=0)
         return A.to_old(out)
+
+
+class TransformerConv(torch.nn.Module):
+    """One dot-product attention layer on a whole graph's QGTC.TiledAdjacency (the message passing of a graph Transformer, Shi et al.,
+    2021, without its skip connection): q = X . W_q, k = X . W_k, v = X . W_v, and per head the receiving node i takes
+    ``sum over its neighbours j of softmax_j(q_i . k_j / sqrt(output_dim)) * v_j`` - ``tiled.tiledEdgeAttention(A, q_head, k_head,
+    v_head)``: an SDDMM, the edge softmax and the weighted sum, every launch of forward and backward specified to the bit and without
+    atomics. The heads run one after the other and are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged
+    ([n, output_dim]). Trainable in W_q, W_k and W_v. ``A`` is the view whose rows are the receiving nodes: ``adj`` attends over
+    out-neighbours, ``adj.T`` over in-neighbours; on a reordered adjacency X moves to its numbering and the result back. A node without
+    neighbours gives +0; self loops are the edge list's business (QGTC.add_self_loops).
+
+    There is no dropout and there are no node masks: the aggregate takes the weights through ``edge_weight``, which accepts neither."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True):
+        super().__init__()
+        if int(heads) < 1:
+            raise ValueError(f"heads must be at least 1, not {heads!r}")
+        self.input_dim, self.output_dim, self.heads, self.concat = int(input_dim), int(output_dim), int(heads), bool(concat)
+        for name in ("W_q", "W_k", "W_v"):
+            setattr(self, name, torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5))
+
+    def forward(self, A, X):
+        if not isinstance(A, QGTC.TiledAdjacency):
+            raise NotImplementedError("TransformerConv needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
+        assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        from .tiled import tiledEdgeAttention
+
+        Xn = A.to_new(X)
+        q, k, v = torch.mm(Xn, self.W_q), torch.mm(Xn, self.W_k), torch.mm(Xn, self.W_v)
+        outs = []
+        for i in range(self.heads):
+            cols = slice(i * self.output_dim, (i + 1) * self.output_dim)
+            outs.append(tiledEdgeAttention(A, q[:, cols].contiguous(), k[:, cols].contiguous(), v[:, cols].contiguous()))
+        if self.concat:
+            out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
+        else:
+            out = outs[0] if self.heads == 1 else torch.stack(outs).mean(dim=0)
+        return A.to_old(out)

@@ -60,6 +60,13 @@ float32 multiply, then one add, never fused, as with ``src_scale``. :func:`tiled
 stored cell, ``out[slot(i, j)] = DOT(A[i], B[j])`` with the attention's DOT; :func:`tiledAggregate` uses it for the gradient with respect
 to the values, so a weighted aggregate is differentiable in X and in the weights, bit for bit the same on every run and without
 atomics. ``edge_weight`` with ``src_scale``, ``edge_drop``, node masks, ``reduce="max"`` / ``"min"`` or ``attn`` is refused: not built.
+
+:func:`tiledEdgeSoftmax` is the step between the two (include/qgtc.h, "Edge softmax"): it normalises a float32 [nnz] vector of per-edge
+logits over each node's neighbourhood - a row's cells on ``adj``, a column's on ``adj.T`` - in one launch, with the attention's
+exponential and the sum in ascending neighbour id, so forward and gradient are specified to the bit and use no atomics. A ``-inf``
+logit masks its edge. :func:`tiledEdgeScores` is :func:`tiledSDDMM` under autograd (its two gradients are weighted products with the
+incoming gradient as the weights), and :func:`tiledEdgeAttention` composes the three into dot-product attention over the edges,
+``softmax(scale * Q K^T restricted to the edges) . V``, differentiable in Q, K and V. ``conv.TransformerConv`` is the layer on top.
 """
 from __future__ import annotations
 
@@ -90,6 +97,10 @@ def _c_abi():
         L.qgtc_tiled_edge_slots.argtypes, L.qgtc_tiled_edge_slots.restype = [P, P, P, I64, I, P, P, P, P, SZ, P, P], I
         L.qgtc_tiled_edge_endpoints.argtypes, L.qgtc_tiled_edge_endpoints.restype = [P, P, P, I64, I, P, P, P, P, SZ, P], I
         L.qgtc_tiled_sddmm_f32.argtypes, L.qgtc_tiled_sddmm_f32.restype = [P, P, P, I64, I, P, P, SZ, I, P, P, P, SZ, P], I
+        L.qgtc_tiled_edge_softmax_f32.argtypes, L.qgtc_tiled_edge_softmax_f32.restype = [P, P, P, I64, I, P, P, P, P, SZ, P, P, P], I
+        L.qgtc_tiled_edge_softmax_f32_t.argtypes, L.qgtc_tiled_edge_softmax_f32_t.restype = [P, P, P, P, I64, I, P, P, P, P, SZ, P, P, P], I
+        L.qgtc_tiled_edge_softmax_grad_f32.argtypes, L.qgtc_tiled_edge_softmax_grad_f32.restype = [P, P, P, I64, I, P, P, P, P, P, SZ, P], I
+        L.qgtc_tiled_edge_softmax_grad_f32_t.argtypes, L.qgtc_tiled_edge_softmax_grad_f32_t.restype = [P, P, P, P, I64, I, P, P, P, P, P, SZ, P], I
         L.qgtc_strerror.argtypes, L.qgtc_strerror.restype = [I], ctypes.c_char_p
         _lib = L
     return _lib
@@ -114,7 +125,8 @@ def _inv_degree(deg: torch.Tensor) -> torch.Tensor:
     return out
 
 __all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat", "tiledAggregate",
-           "add_self_loops", "node_bitmap", "edge_slots", "edge_endpoints", "edge_values", "tiledSDDMM"]
+           "add_self_loops", "node_bitmap", "edge_slots", "edge_endpoints", "edge_values", "tiledSDDMM", "tiledEdgeSoftmax",
+           "tiledEdgeScores", "tiledEdgeAttention"]
 
 
 class TiledAdjacency:
@@ -919,6 +931,145 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     if mode == "extremum":
         return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask)
     return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask)
+
+
+def _check_edge_vector(adj: TiledAdjacency, values, name: str) -> int:
+    """The checks of ``edge_weight`` on a per-edge vector of another name; returns nnz."""
+    if not isinstance(values, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor (float32 [nnz], in slot order)")
+    if values.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, not {values.dtype}")
+    if values.device != adj.device:
+        raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {values.device}")
+    nnz = _value_index(adj)[2]
+    if values.dim() != 1 or values.numel() != nnz:
+        raise ValueError(f"{name} must have shape [{nnz}] (one value per stored cell), not {list(values.shape)}")
+    if not values.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return nnz
+
+
+def _esoftmax_view(adj: TiledAdjacency, grad: bool):
+    """(entry, the view's index pointers and tiles, n_tiles, n, val_ptr, val_row) of the edge softmax or its gradient on this view."""
+    base, L = _base(adj), _c_abi()
+    val_ptr, val_row, _ = _value_index(base)
+    T = base.n_tiles
+    if adj.transposed:
+        fn = L.qgtc_tiled_edge_softmax_grad_f32_t if grad else L.qgtc_tiled_edge_softmax_f32_t
+        view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles)
+    else:
+        fn = L.qgtc_tiled_edge_softmax_grad_f32 if grad else L.qgtc_tiled_edge_softmax_f32
+        view = (adj.row_ptr, adj.kquad, adj.tiles)
+    ptrs = tuple(t.data_ptr() if T else None for t in view)
+    return fn, ptrs + (T, adj.n, val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
+
+
+def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
+    """(alpha, m, inv) of qgtc_tiled_edge_softmax_f32 / _t: one launch on the current stream."""
+    nnz = logits.numel()
+    alpha = torch.empty(nnz, dtype=torch.float32, device=adj.device)
+    m = torch.empty(adj.n, dtype=torch.float32, device=adj.device)
+    inv = torch.empty(adj.n, dtype=torch.float32, device=adj.device)
+    fn, head = _esoftmax_view(adj, False)
+    _c_call("tiledEdgeSoftmax", m, fn, *head, logits.data_ptr() if nnz else None, alpha.data_ptr() if nnz else None, nnz, m.data_ptr(),
+            inv.data_ptr())
+    return alpha, m, inv
+
+
+def _edge_softmax_grad(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """out[slot] = alpha . (g - S[owner]) of qgtc_tiled_edge_softmax_grad_f32 / _t: one launch on the current stream."""
+    nnz = alpha.numel()
+    out = torch.empty(nnz, dtype=torch.float32, device=adj.device)
+    if nnz:
+        fn, head = _esoftmax_view(adj, True)
+        _c_call("the gradient of tiledEdgeSoftmax", alpha, fn, *head, alpha.data_ptr(), g.data_ptr(), out.data_ptr(), nnz)
+    return out
+
+
+class _TiledEdgeSoftmax(torch.autograd.Function):
+    """alpha = softmax of the logits over each owner's cells: dlogits[k] = alpha[k] . (g[k] - sum over the owner's cells of alpha . g),
+    the grad entry on the same view."""
+
+    @staticmethod
+    def forward(ctx, adj, logits):
+        alpha, m, inv = _edge_softmax(adj, logits)
+        ctx.adj = adj
+        ctx.save_for_backward(alpha)
+        ctx.mark_non_differentiable(m, inv)
+        return alpha, m, inv
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gm, _gi):
+        alpha, = ctx.saved_tensors
+        dl = None
+        if ctx.needs_input_grad[1]:
+            dl = _edge_softmax_grad(ctx.adj, alpha, g.contiguous())
+        return None, dl
+
+
+def tiledEdgeSoftmax(adj: TiledAdjacency, logits: torch.Tensor, return_stats: bool = False):
+    """float32 [nnz] in slot order: the softmax of a per-edge vector over each node's neighbourhood (include/qgtc.h, "Edge softmax").
+    On ``adj`` the softmax runs over each row's out-neighbours, on ``adj.T`` over each node's in-neighbours; the vectors are the same on
+    both views. ``alpha[k] = EXP(l_k - m[o]) * inv[o]`` with m the owner's largest logit and inv the reciprocal of the in-order sum of
+    the exponentials over the owner's cells in ascending neighbour id: a fixed sequence of float32 operations, so the result is the same
+    bits on every launch; one kernel, no atomics. A ``-inf`` logit masks its edge. With ``return_stats`` the result is ``(alpha, m,
+    inv)``, float32 [n] each (+0 and 0 for a node without cells). Differentiable in ``logits`` (one launch on the same view, specified
+    to the bit too; no second derivative). ``logits`` is float32 [nnz], contiguous, on the adjacency's device: a wrong dtype is a
+    TypeError, a wrong shape, device or stride a ValueError."""
+    _check(adj)
+    _check_edge_vector(adj, logits, "logits")
+    alpha, m, inv = _TiledEdgeSoftmax.apply(adj, logits)
+    return (alpha, m, inv) if return_stats else alpha
+
+
+class _TiledEdgeScores(torch.autograd.Function):
+    """s[slot(i, j)] = DOT(A[i], B[j]) on the view: dA = (view o g) . B and dB = (view o g)^T . A, the weighted products with the incoming
+    gradient as the weights - each launched only when its gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, adj, A, B):
+        ctx.adj = adj
+        ctx.save_for_backward(A, B)
+        return tiledSDDMM(adj, A, B)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        A, B = ctx.saved_tensors
+        dA = dB = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g = g.contiguous()
+            if ctx.needs_input_grad[1]:
+                dA = tiledMMFloat(ctx.adj, B, edge_weight=g)
+            if ctx.needs_input_grad[2]:
+                dB = tiledMMFloat(ctx.adj.T, A, edge_weight=g)
+        return None, dA, dB
+
+
+def tiledEdgeScores(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """:func:`tiledSDDMM` under ``torch.autograd``: float32 [nnz] in slot order, ``out[slot(i, j)] = DOT(A[i], B[j])`` for the cells
+    (i, j) of this view, differentiable in A and B. With g the incoming gradient, ``dA = tiledMMFloat(adj, B, edge_weight=g)`` and
+    ``dB = tiledMMFloat(adj.T, A, edge_weight=g)``: one launch each, only when needed, both specified to the bit; no second
+    derivative."""
+    _check(adj)
+    _check_float_operand(adj, A)
+    return _TiledEdgeScores.apply(adj, A, B)
+
+
+def tiledEdgeAttention(adj: TiledAdjacency, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, scale: float | None = None) -> torch.Tensor:
+    """Dot-product attention over the graph's edges, float32 [n, N]: row i of the view receives
+    ``sum over its neighbours j of softmax_j(scale * DOT(Q[i], K[j])) * V[j]`` - the composition
+    ``tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, tiledEdgeScores(adj, Q, K) * scale))``: an SDDMM, one float32 torch
+    multiply per slot, the edge softmax and the weighted sum. ``scale`` defaults to ``1 / sqrt(Q.size(1))``. Differentiable in Q, K and
+    V; every launch of the forward and the backward is specified to the bit and none uses atomics. Q and K are float32 [n, d], V is
+    float32 [n, N], in the adjacency's numbering; the rows of the view are the receiving nodes (``adj.T``: a node attends over its
+    in-neighbours)."""
+    _check(adj)
+    _check_float_operand(adj, Q)
+    scale = 1.0 / math.sqrt(Q.size(1)) if scale is None else float(scale)
+    logits = tiledEdgeScores(adj, Q, K) * scale
+    return tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, logits))
 
 
 def add_self_loops(src: torch.Tensor, dst: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:

@@ -71,7 +71,14 @@ forward plus both gradients of tiledAggregate(edge_weight=), and the edge-list r
 autograd backward, which is not bit-reproducible). Once per graph: the value index plus edge_slots of the whole edge list against
 pack_edges_tiled. The weighted sum is checked against the edge-list route before timing. Medians with their 10th and 90th percentiles.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge]
+`--leg esoftmax` measures the edge softmax (tiled.tiledEdgeSoftmax and its gradient, tiled.tiledEdgeAttention) on the
+reordered graphs, both directions, d = N in {64, 256}, logits 3 * standard normal. Two alternating loops: first the softmax launch, its
+gradient launch, tiledSDDMM and the weighted launch of the same shape, each alone; second tiledEdgeAttention forward and forward plus
+all three gradients against the edge-list route (index_select, a row dot, scatter_reduce amax, exp, index_add_ twice, with its
+autograd backward, which is not bit-reproducible). The attention is checked against the edge-list route before timing. Medians with
+their 10th and 90th percentiles.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax]
 """
 from __future__ import annotations
 
@@ -690,12 +697,82 @@ def edge_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def esoftmax_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        e_row, e_col = (v.long() for v in tiled.edge_endpoints(adj))
+        nnz = int(e_row.numel())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": nnz, "tiles": adj.n_tiles,
+               "max_block_tiles": adj.max_block_tiles, "max_col_tiles": t.max_block_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {nnz}, longest row list {adj.max_block_tiles}, longest column list "
+              f"{t.max_block_tiles}", flush=True)
+        xr = np.random.default_rng(1)
+        logits = torch.from_numpy((3 * xr.standard_normal(nnz)).astype(np.float32)).cuda()
+        gl = torch.from_numpy(xr.standard_normal(nnz).astype(np.float32)).cuda()
+        for N in (64, 256):   # d = N: the width of Q and K and of V
+            scale = 1.0 / math.sqrt(N)
+            Q, K, V, dY = (torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda() for _ in range(4))
+            Qg, Kg, Vg = (x.clone().requires_grad_(True) for x in (Q, K, V))
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                o, k = (e_col, e_row) if a.transposed else (e_row, e_col)
+                alpha = tiled.tiledEdgeSoftmax(a, logits)
+
+                def edge_list(Qe, Ke, Ve):
+                    s = (Qe.index_select(0, o) * Ke.index_select(0, k)).sum(dim=1) * scale
+                    top = torch.full((n,), float("-inf"), device="cuda").scatter_reduce(0, o, s.detach(), "amax")
+                    w = torch.exp(s - top.index_select(0, o))
+                    den = torch.zeros(n, device="cuda").index_add_(0, o, w)
+                    return torch.zeros(n, N, device="cuda").index_add_(0, o, (w / den.index_select(0, o))[:, None] * Ve.index_select(0, k))
+
+                def att_both():
+                    return torch.autograd.grad(tiled.tiledEdgeAttention(a, Qg, Kg, Vg), (Qg, Kg, Vg), dY)
+
+                def edge_both():
+                    return torch.autograd.grad(edge_list(Qg, Kg, Vg), (Qg, Kg, Vg), dY)
+
+                got, ref = tiled.tiledEdgeAttention(a, Q, K, V), edge_list(Q, K, V)
+                assert torch.allclose(got, ref, rtol=1e-3, atol=1e-4), (N, direction, float((got - ref).abs().max()))
+                for gk, ge in zip(att_both(), edge_both()):
+                    assert torch.allclose(gk, ge, rtol=1e-3, atol=1e-3), (N, direction, float((gk - ge).abs().max()))
+                tsm, tsg, tsd, tw = timed_alternating(torch, [
+                    lambda: tiled.tiledEdgeSoftmax(a, logits), lambda: tiled._edge_softmax_grad(a, alpha, gl),
+                    lambda: tiled.tiledSDDMM(a, Q, K), lambda: QGTC.tiledMMFloat(a, V, edge_weight=alpha)], reps)
+                taf, tab, tef, teb = timed_alternating(torch, [lambda: tiled.tiledEdgeAttention(a, Q, K, V), att_both,
+                                                               lambda: edge_list(Q, K, V), edge_both], reps)
+                rec["agg"].append({"N": N, "direction": direction, "softmax_ms": tsm, "softmax_grad_ms": tsg, "sddmm_ms": tsd,
+                                   "weighted_ms": tw, "attention_forward_ms": taf, "attention_forward_backward_ms": tab,
+                                   "edge_list_forward_ms": tef, "edge_list_forward_backward_ms": teb,
+                                   "softmax_over_sddmm": round(tsm[0] / tsd[0], 3), "softmax_over_weighted": round(tsm[0] / tw[0], 3),
+                                   "grad_over_sddmm": round(tsg[0] / tsd[0], 3), "grad_over_weighted": round(tsg[0] / tw[0], 3),
+                                   "edge_list_over_attention_forward": round(tef[0] / taf[0], 3),
+                                   "edge_list_over_attention_forward_backward": round(teb[0] / tab[0], 3)})
+                print(f"{name:9s} N={N:<4d} {direction:10s} softmax {tsm[0]:8.4f} [{tsm[1]:.4f}, {tsm[2]:.4f}]  its gradient {tsg[0]:8.4f} "
+                      f"[{tsg[1]:.4f}, {tsg[2]:.4f}]  sddmm {tsd[0]:8.4f} [{tsd[1]:.4f}, {tsd[2]:.4f}] ({tsm[0] / tsd[0]:.3f}x, "
+                      f"{tsg[0] / tsd[0]:.3f}x)  weighted {tw[0]:8.4f} [{tw[1]:.4f}, {tw[2]:.4f}] ({tsm[0] / tw[0]:.3f}x, {tsg[0] / tw[0]:.3f}x)  "
+                      f"attention fwd {taf[0]:8.4f} [{taf[1]:.4f}, {taf[2]:.4f}]  fwd + bwd {tab[0]:8.4f} [{tab[1]:.4f}, {tab[2]:.4f}]  "
+                      f"edge list fwd {tef[0]:8.4f} ({tef[0] / taf[0]:.2f}x)  fwd + bwd {teb[0]:8.4f} ({teb[0] / tab[0]:.2f}x)", flush=True)
+            del Q, K, V, dY, Qg, Kg, Vg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, e_row, e_col, logits, gl
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax"))
     args = ap.parse_args()
 
     import torch
@@ -703,9 +780,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
