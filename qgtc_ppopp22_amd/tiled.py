@@ -76,34 +76,15 @@ import torch
 
 import ctypes
 
-from . import lib_path, load_ext
+from . import cabi, load_ext
 
 _ext = load_ext()
-_lib = None
 
 
-def _c_abi():
-    """libqgtc_hip.so through ctypes, for the entries the extension does not bind: qgtc_node_bitmap,
-    qgtc_tiled_inv_degree and the edge-value index and SDDMM entries. Loaded on first use; the extension has loaded the same library
-    already."""
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(lib_path())
-        P, I, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        L.qgtc_node_bitmap.argtypes, L.qgtc_node_bitmap.restype = [P, I, P, SZ, P], I
-        L.qgtc_tiled_inv_degree.argtypes, L.qgtc_tiled_inv_degree.restype = [P, I, P, P], I
-        I64 = ctypes.c_int64
-        L.qgtc_tiled_value_index.argtypes, L.qgtc_tiled_value_index.restype = [P, I64, P, P, P], I
-        L.qgtc_tiled_edge_slots.argtypes, L.qgtc_tiled_edge_slots.restype = [P, P, P, I64, I, P, P, P, P, SZ, P, P], I
-        L.qgtc_tiled_edge_endpoints.argtypes, L.qgtc_tiled_edge_endpoints.restype = [P, P, P, I64, I, P, P, P, P, SZ, P], I
-        L.qgtc_tiled_sddmm_f32.argtypes, L.qgtc_tiled_sddmm_f32.restype = [P, P, P, I64, I, P, P, SZ, I, P, P, P, SZ, P], I
-        L.qgtc_tiled_edge_softmax_f32.argtypes, L.qgtc_tiled_edge_softmax_f32.restype = [P, P, P, I64, I, P, P, P, P, SZ, P, P, P], I
-        L.qgtc_tiled_edge_softmax_f32_t.argtypes, L.qgtc_tiled_edge_softmax_f32_t.restype = [P, P, P, P, I64, I, P, P, P, P, SZ, P, P, P], I
-        L.qgtc_tiled_edge_softmax_grad_f32.argtypes, L.qgtc_tiled_edge_softmax_grad_f32.restype = [P, P, P, I64, I, P, P, P, P, P, SZ, P], I
-        L.qgtc_tiled_edge_softmax_grad_f32_t.argtypes, L.qgtc_tiled_edge_softmax_grad_f32_t.restype = [P, P, P, P, I64, I, P, P, P, P, P, SZ, P], I
-        L.qgtc_strerror.argtypes, L.qgtc_strerror.restype = [I], ctypes.c_char_p
-        _lib = L
-    return _lib
+# libqgtc_hip.so through ctypes, every signature from include/qgtc.h, for the entries the extension does not bind: qgtc_node_bitmap,
+# qgtc_tiled_inv_degree and the edge-value index, SDDMM and edge-softmax entries. Loaded on first use; the extension has loaded the same
+# library already.
+_c_abi = cabi.load
 
 
 def _c_call(what: str, on: torch.Tensor, fn, *args) -> None:

@@ -170,18 +170,8 @@ class QgtcLoaderBatch(ctypes.Structure):
 ENGINE_FLAGS = {"popcount": 0x0, "mfma": 0x8, "auto": 0x10}
 
 
-def c_library():
-    """libqgtc_hip.so as ctypes sees it (no GPU needed to load it or to call its host-only entries)."""
-    import qgtc_ppopp22_amd
-
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_bitmm_route.restype = L.qgtc_bitmm_batched_route.restype = ctypes.c_char_p
-    for f in (L.qgtc_rows_words, L.qgtc_cols_words, L.qgtc_adj_tiles_words, L.qgtc_chain_words, L.qgtc_weight_codes_words, L.qgtc_occupancy_words,
-              L.qgtc_load_work_words):
-        f.restype = ctypes.c_size_t
-    return L
-
-
 def kernel_behind(M, K, N, a=1, w=1, ob=1, mode=0, engine="auto"):
     """The kernel family a single launch of this shape takes (qgtc_bitmm_route: the rule functions the launchers switch on)."""
-    return c_library().qgtc_bitmm_route(M, K, N, a, w, ob, mode, ENGINE_FLAGS[engine]).decode()
+    from qgtc_ppopp22_amd import cabi
+
+    return cabi.load().qgtc_bitmm_route(M, K, N, a, w, ob, mode, ENGINE_FLAGS[engine]).decode()

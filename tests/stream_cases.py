@@ -16,12 +16,12 @@ Everything is compared bit for bit. Importing this module needs neither a GPU no
 CASES on the CPU).
 """
 import contextlib
-import ctypes
 import types
 
 import numpy as np
 
-from helpers import (QgtcLoaderBatch, QgtcProblem, c_library, edge_floats, kernel_behind, oracle_chain, rand_q)
+from helpers import (QgtcLoaderBatch, QgtcProblem, edge_floats, kernel_behind, oracle_chain, rand_q)
+from qgtc_ppopp22_amd import cabi
 from qgtc_ppopp22_amd.shapes import cols_shape, rows_shape
 
 FILLER_MIN_MS = 5.0          # the head start of a probe: filler work on the side stream, timed with HIP events once per device
@@ -922,28 +922,6 @@ def _plan_bind(env):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # C entries with an explicit stream handle (ctypes, raw device pointers): the current stream stays the default one
 # ---------------------------------------------------------------------------------------------------------------------------------------
-vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-
-
-def raw_library():
-    L = c_library()
-    L.qgtc_val2bit.argtypes = [vp, ci, ci, ci, ci, ci, vp, sz, vp]
-    L.qgtc_bitmm2bit.argtypes = [vp, sz, vp, sz] + [ci] * 6 + [vp, sz, ctypes.c_uint, vp]
-    L.qgtc_bitmm2int.argtypes = [vp, sz, vp, sz] + [ci] * 6 + [vp, sz, ctypes.c_uint, vp]
-    L.qgtc_pack_edges.argtypes = [vp, vp, sz, ci, ci, ci, vp, sz, vp]
-    L.qgtc_tiledmm2bit_t.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ci, vp, sz, ci, ci, ci, vp, sz, vp]
-    L.qgtc_tiledmm_f32_src.argtypes = [vp, vp, vp, ctypes.c_int64, ci, vp, sz, ci, vp, vp, vp, sz, vp]
-    L.qgtc_tiledmm_f32_t_src.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ci, vp, sz, ci, vp, vp, vp, sz, vp]
-    L.qgtc_tiled_degrees.argtypes = [vp, vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, vp]
-    L.qgtc_tiled_colindex_work_words.restype = sz
-    L.qgtc_tiled_colindex_work_words.argtypes = [ctypes.c_int64]
-    L.qgtc_tiled_colindex.argtypes = [vp, vp, ctypes.c_int64, ci, vp, vp, vp, vp, sz, vp]
-    L.qgtc_gcn_chain_batched.argtypes = [vp, vp, ci] + [ci] * 4 + [ci] * 6 + [ctypes.c_uint, vp]
-    L.qgtc_load_batches.argtypes = [vp, ci, ci, ctypes.c_uint64, vp, vp, vp, ci, ci, vp, sz, vp, vp, ctypes.c_uint, vp, sz, vp]
-    L.qgtc_load_work_words.argtypes = [ci, ci, ctypes.c_uint64]
-    return L
-
-
 def _out(env, n, dtype):
     """A caller-owned output of n elements with a 64-word canary behind it."""
     t = env.torch
@@ -959,7 +937,7 @@ def raw_case(id, entry):
 
 @raw_case("qgtc_val2bit-rows", "qgtc_val2bit")
 def _raw_val2bit(env, H=37, W=130, nbits=3, cm=0):
-    L, xs = raw_library(), _val2bit_inputs(37, 130, 3, 201)
+    L, xs = cabi.load(), _val2bit_inputs(37, 130, 3, 201)
     buf, out = _empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_rows_words(H, W, nbits)), env.torch.int32)
     return Live(env.torch, [buf], [[x] for x in xs], [[env.O.val2bit(x, nbits, False, False)] for x in xs], outs=[out],
                 raw=lambda st: L.qgtc_val2bit(buf.data_ptr(), H, W, nbits, 0, 0, out.data_ptr(), out.numel(), st))
@@ -968,7 +946,7 @@ def _raw_val2bit(env, H=37, W=130, nbits=3, cm=0):
 @raw_case("qgtc_val2bit-cols", "qgtc_val2bit")
 def _raw_val2bit_cols(env):
     H, W, nbits = 130, 37, 2
-    L, xs = raw_library(), _val2bit_inputs(H, W, nbits, 202)
+    L, xs = cabi.load(), _val2bit_inputs(H, W, nbits, 202)
     buf, out = _empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_cols_words(H, W, nbits, 0)), env.torch.int32)
     return Live(env.torch, [buf], [[x] for x in xs], [[env.O.val2bit(x, nbits, True, False)] for x in xs], outs=[out],
                 raw=lambda st: L.qgtc_val2bit(buf.data_ptr(), H, W, nbits, 1, 0, out.data_ptr(), out.numel(), st))
@@ -978,7 +956,7 @@ def _raw_mm(entry, dims, flags, cols=False):
     M, K, N, a, w, ob = dims
 
     def build(env):
-        L, O, t = raw_library(), env.O, env.torch
+        L, O, t = cabi.load(), env.O, env.torch
         ops = [_mm_operands(O, M, K, N, a, w, 210 + k, ob=ob) for k in range(4)]
         bufs = [_i32(env, rows_shape(M, K, a)), _i32(env, cols_shape(K, N, w))]
         if entry == "qgtc_bitmm2int":
@@ -1007,7 +985,7 @@ def _raw_pack_edges(env):
     The four contents have the same number of distinct cells."""
     from oracle.qgtc_oracle import np_pack_edges
 
-    L, H, W, nbits, n_cells = raw_library(), 200, 333, 3, 900
+    L, H, W, nbits, n_cells = cabi.load(), 200, 333, 3, 900
     contents, want = [], []
     for k in range(4):
         rng = np.random.default_rng(220 + k)
@@ -1026,8 +1004,7 @@ def _raw_pack_edge_list(env):
     """The raw edge list behind QGTC.pack_edges(..., nbits=1, validate=False): three cleared bitmaps, atomic ORs, one finishing pass."""
     from oracle.qgtc_oracle import np_pack_edges
 
-    L, H, W, n_edges = raw_library(), 300, 333, 2000
-    L.qgtc_pack_edge_list.argtypes = [vp, vp, sz, ci, ci, vp, sz, vp, sz, vp, vp]
+    L, H, W, n_edges = cabi.load(), 300, 333, 2000
     contents, want = [], []
     for k in range(4):
         rng = np.random.default_rng(225 + k)
@@ -1048,7 +1025,7 @@ def _raw_pack_edge_list(env):
 def _raw_colindex(env):
     from tiled_model import np_colindex
 
-    L, gs, t = raw_library(), cache_graphs(), env.torch
+    L, gs, t = cabi.load(), cache_graphs(), env.torch
     bufs = _adjacency_buffers(env, gs)[:2]
     T, nq = int(bufs[1].numel()), CACHE_N // 128
     outs = [_out(env, nq + 1, t.int64), _out(env, T, t.int64), _out(env, T, t.int32)]
@@ -1063,7 +1040,7 @@ def _raw_colindex(env):
 def _raw_degrees(env):
     from tiled_scaled_model import degrees, mean_scale
 
-    L, gs, t, n = raw_library(), cache_graphs(), env.torch, CACHE_N
+    L, gs, t, n = cabi.load(), cache_graphs(), env.torch, CACHE_N
     bufs = _adjacency_buffers(env, gs)
     T = int(bufs[1].numel())
     outs = [_out(env, n, t.int32), _out(env, n, t.int32), _out(env, n, t.float32), _out(env, n, t.float32)]
@@ -1082,7 +1059,7 @@ def _raw_tiled_product(entry):
         from tiled_scaled_model import degrees
         from tiled_sym_model import aggregate_f32_src, inv_sqrt_degree
 
-        L, gs, t, n, O = raw_library(), cache_graphs(), env.torch, CACHE_N, env.O
+        L, gs, t, n, O = cabi.load(), cache_graphs(), env.torch, CACHE_N, env.O
         N, bit2, ob = 40, 2, 3
         adj = _adjacency_buffers(env, gs)
         T = int(adj[1].numel())
@@ -1127,7 +1104,7 @@ for _entry in ("qgtc_tiledmm2bit_t", "qgtc_tiledmm_f32_src", "qgtc_tiledmm_f32_t
 def _raw_chain(env, flags=0x10):
     """As tests/test_abi_gpu.py::test_chain_entry_with_raw_descriptors: host-written descriptors; T (the aggregation's right operand)
     and the next layer's weight change with the content."""
-    L, O, t = raw_library(), env.O, env.torch
+    L, O, t = cabi.load(), env.O, env.torch
     act, wb, f1, f2, ns = 2, 2, 128, 96, [150, 333, 40]
     rng = np.random.default_rng(240)
     As = [O.pack((rng.random((n, n)) < 1.5 / n).astype(np.int32), 1, False) for n in ns]     # sparse: the sums stay below the clamp
@@ -1158,7 +1135,7 @@ def _raw_load_batches(with_work):
     """As tests/test_loader_gpu.py::test_load_batches_through_the_raw_abi: the features change with the content, and the edges move
     inside their batches (the same edge counts). Without a work buffer the entry clears `zero` itself (hipMemsetAsync) and ORs into it."""
     def build(env):
-        L, O, t = raw_library(), env.O, env.torch
+        L, O, t = cabi.load(), env.O, env.torch
         sizes, F, bits = [70, 257, 5], 20, 2
         rng = np.random.default_rng(250)
         ecounts = [int(rng.integers(n, 8 * n)) for n in sizes]

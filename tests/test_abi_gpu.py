@@ -11,7 +11,7 @@ from helpers import QgtcBatch, QgtcExpandJob, QgtcOperand, QgtcPackJob, QgtcProb
 
 pytestmark = pytest.mark.gpu
 
-u32p, f32p, vp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float), ctypes.c_void_p
+u32p, f32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float)
 
 
 @pytest.fixture(scope="module")
@@ -19,19 +19,9 @@ def lib():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_rows_words.restype = ctypes.c_size_t
-    L.qgtc_rows_words.argtypes = [ctypes.c_int] * 3
-    L.qgtc_cols_words.restype = ctypes.c_size_t
-    L.qgtc_cols_words.argtypes = [ctypes.c_int] * 4
-    L.qgtc_val2bit.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    L.qgtc_bitmm2bit.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t] + [ctypes.c_int] * 6 + [vp, ctypes.c_size_t, ctypes.c_uint, vp]
-    L.qgtc_bitmm2int.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t] + [ctypes.c_int] * 6 + [vp, ctypes.c_size_t, ctypes.c_uint, vp]
-    L.qgtc_bit2val.argtypes = [vp, ctypes.c_size_t] + [ctypes.c_int] * 5 + [vp, vp]
-    L.qgtc_strerror.restype = ctypes.c_char_p
-    return L
+    return cabi.load()
 
 
 def _dev(torch, n, dtype):
@@ -84,7 +74,6 @@ def test_layer_entry_with_raw_descriptors(lib, oracle, flags):
     include/qgtc.h), raw device pointers - against the oracle's two products."""
     import torch
     assert ctypes.sizeof(QgtcProblem) == 72   # three pointers, two u64, five i32 (+4 padding), one pointer
-    lib.qgtc_gcn_layer_batched.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_int] * 6 + [ctypes.c_uint, vp]
     rng = np.random.default_rng(17 + flags)
     act, wb, f_in, f_out = 2, 2, 64, 96
     batches = [(150, f_in), (333, f_in), (40, f_in)]
@@ -131,7 +120,6 @@ def test_chain_entry_with_raw_descriptors(lib, oracle, flags):
     and without QGTC_ZERO_JUMP - the descriptors carry no bitmaps, so every k-quad is visited) and as the two grouped
     launches of the popcount engine (flags 0)."""
     import torch
-    lib.qgtc_gcn_chain_batched.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_int] * 6 + [ctypes.c_uint, vp]
     rng = np.random.default_rng(23 + flags)
     act, wb, f1, f2 = 2, 2, 128, 96
     ns = [150, 333, 40]
@@ -182,9 +170,6 @@ def test_epoch_plan_fill_offsets_for_many_batch_counts(lib, count):
     pass keeps the table line and the handed-out pointers in registers, more than one re-reads them): every output where the host
     layout puts it, every chained operand the pointer of the stage it names. No product is launched (the operands are never read)."""
     import torch
-    lib.qgtc_epoch_pool_layout.restype = ctypes.c_size_t
-    lib.qgtc_epoch_pool_layout.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
-    lib.qgtc_epoch_plan_fill.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp]
     rng = np.random.default_rng(count)
     ns = [int(v) for v in rng.integers(1, 300, size=count)]
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -221,7 +206,6 @@ def test_epoch_plan_fill_offsets_for_many_batch_counts(lib, count):
     K = (got[:, :, 5] >> np.uint64(32)).astype(np.int64)
     assert (M == np.array(ns)[None, :]).all() and (K[1] == np.array(ns)).all() and (K[0] == F).all() and (K[2] == H).all()
     assert (np.diff(np.concatenate([O.reshape(-1), [pool_words]]).astype(np.int64)) >= 0).all()   # (stage, batch) order, nothing overlaps
-    lib.qgtc_last_batched_violation.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]
     assert lib.qgtc_last_batched_violation(None, None, st) == 0
 
 
@@ -231,12 +215,6 @@ def test_epoch_plan_filled_on_the_device_with_raw_pointers(lib, oracle):
     float32) filled by ONE launch from the per-batch table, QGTC_CHECK_DESCRIPTORS on every launch - against the oracle."""
     import torch
     assert ctypes.sizeof(QgtcBatch) == 96 and ctypes.sizeof(QgtcStage) == 44 and ctypes.sizeof(QgtcPackJob) == 48
-    lib.qgtc_val2bit_batched.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_epoch_pool_layout.restype = ctypes.c_size_t
-    lib.qgtc_epoch_pool_layout.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
-    lib.qgtc_epoch_plan_fill.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_size_t, vp, vp]
-    lib.qgtc_bitmm_batched.argtypes = [vp, ctypes.c_int] + [ctypes.c_int] * 3 + [ctypes.c_int] * 4 + [ctypes.c_uint, vp]
-    lib.qgtc_last_batched_violation.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]
     rng = np.random.default_rng(41)
     b, F, H, C = 2, 48, 64, 10
     ns = [150, 333, 40, 97]
@@ -310,7 +288,6 @@ def test_epoch_plan_filled_on_the_device_with_raw_pointers(lib, oracle):
     assert lib.qgtc_last_batched_violation(ctypes.byref(prob), ctypes.byref(field), st) == 0                                 # read once, then cleared
     assert lib.qgtc_bitmm_batched(descs.data_ptr(), count, mx, F, H - 1, b, b, b, 1, AUTO | CHECK, st) == 0                # N above max_N in every problem
     assert lib.qgtc_last_batched_violation(ctypes.byref(prob), ctypes.byref(field), st) == 1 and (prob.value, field.value) == (0, 3)
-    lib.qgtc_gcn_chain_batched.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.c_int] * 6 + [ctypes.c_uint, vp]
     # a "chain" whose second stage does not read the first one's output (stage 1 then stage 3)
     assert lib.qgtc_gcn_chain_batched(descs.data_ptr() + 72 * count, descs.data_ptr() + 72 * count * 3, count, mx, mx, H, C, 1, b, b, b, b, 2, CHECK, st) == 0
     assert lib.qgtc_last_batched_violation(ctypes.byref(prob), ctypes.byref(field), st) == 1 and field.value in (2, 5)
@@ -364,11 +341,6 @@ def test_chain_entries_with_raw_descriptors(lib, oracle, M, K, F, H, C, bitmaps,
     import torch
     if not _chain_covered(b, F, H, C):
         pytest.skip("outside the chain entries' range at this width (callers fall back to the grouped GEMMs)")
-    lib.qgtc_weight_codes_words.restype = lib.qgtc_chain_words.restype = lib.qgtc_occupancy_words.restype = ctypes.c_size_t
-    lib.qgtc_expand_weights.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_chain_transform.argtypes = [vp, ctypes.c_int] + [ctypes.c_int] * 5 + [vp, ctypes.c_uint, vp]
-    lib.qgtc_chain_aggregate.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 8 + [vp, ctypes.c_uint, vp]
-    lib.qgtc_tile_occupancy.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
     rng = np.random.default_rng(M + 3 * K + F)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P128 = lambda x: (x + 127) // 128 * 128   # noqa: E731
@@ -430,7 +402,6 @@ def test_chain_entries_with_raw_descriptors(lib, oracle, M, K, F, H, C, bitmaps,
             np.testing.assert_array_equal(o0.cpu().numpy().reshape(w0.shape), w0, err_msg=f"out_mode 0 after out_mode 1, batch {i}")
             o0.fill_(-7.0)
             o2.fill_(-7.0)
-    lib.qgtc_last_batched_violation.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]
     assert lib.qgtc_last_batched_violation(None, None, st) == 0
     # outside the entries' range: error codes (callers fall back to qgtc_gcn_chain_batched)
     assert lib.qgtc_chain_transform(d(0), count, K, 8193, H, b, b, c1.data_ptr(), 0, st) == 1         # K > 8192
@@ -475,11 +446,6 @@ def test_chain_entries_at_four_bits(lib, oracle, M, F, H, C, bitmaps, b):
     import torch
     if max(F, H, C) > (256 if b <= 4 else 128):
         pytest.skip("outside the chain entries' range at this width")
-    lib.qgtc_weight_codes_words.restype = lib.qgtc_chain_words.restype = lib.qgtc_occupancy_words.restype = ctypes.c_size_t
-    lib.qgtc_expand_weights.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_chain_from_cols.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.qgtc_chain_aggregate.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 8 + [vp, ctypes.c_uint, vp]
-    lib.qgtc_tile_occupancy.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
     rng = np.random.default_rng(M + F)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P128, P8 = (lambda x: (x + 127) // 128 * 128), (lambda x: (x + 7) // 8 * 8)   # noqa: E731
@@ -529,7 +495,6 @@ def test_chain_entries_at_four_bits(lib, oracle, M, F, H, C, bitmaps, b):
         for i, (o, w) in enumerate(want):
             np.testing.assert_array_equal(o.cpu().numpy().reshape(w.shape), w, err_msg=f"batch {i}")
             o.fill_(-7.0)
-    lib.qgtc_last_batched_violation.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]
     assert lib.qgtc_last_batched_violation(None, None, st) == 0
     # the second product's descriptors are checked too: a stage_xw entry for another batch size is a chaining violation (the entry only
     # takes `out` and N from it, so the product itself is unaffected)
@@ -559,14 +524,6 @@ def test_chain_entries_random_sweep(lib, oracle, seed):
     1 .. 4-bit chains with 129 .. 256 columns on at least one side."""
     import torch
     rng = np.random.default_rng(1000 + seed)
-    lib.qgtc_weight_codes_words.restype = lib.qgtc_chain_words.restype = lib.qgtc_occupancy_words.restype = ctypes.c_size_t
-    lib.qgtc_expand_weights.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_chain_from_cols.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.qgtc_chain_transform.argtypes = [vp, ctypes.c_int] + [ctypes.c_int] * 5 + [vp, ctypes.c_uint, vp]
-    lib.qgtc_chain_aggregate.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 8 + [vp, ctypes.c_uint, vp]
-    lib.qgtc_tile_occupancy.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.qgtc_adj_tiles_words.restype = ctypes.c_size_t
-    lib.qgtc_adj_tiles_from_rows.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P128 = lambda x: (x + 127) // 128 * 128   # noqa: E731
     tiles = seed % 2 == 1
@@ -649,7 +606,6 @@ def test_chain_entries_random_sweep(lib, oracle, seed):
     torch.cuda.synchronize()
     for i, (o, w) in enumerate(want):
         np.testing.assert_array_equal(o.cpu().numpy().reshape(w.shape), w, err_msg=f"seed {seed} b={b} xw={use_xw} F={F} H={H} C={C} m={ms[i]} k={ks[i]} density={density} bitmaps={bitmaps}")
-    lib.qgtc_last_batched_violation.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vp]
     assert lib.qgtc_last_batched_violation(None, None, st) == 0
 
 
@@ -659,10 +615,6 @@ def test_chain_aggregate_with_different_widths_inside_a_format_class(lib, oracle
     share a format class (1 / 2 bits, 3 / 4 bits, 5 .. 8 bits). T from the public cols layout (qgtc_chain_from_cols), then
     out = float32(requant(A . T) . W') (out_mode 2) against the oracle - the 5 .. 8-bit kernels skip zero top digits per operand."""
     import torch
-    lib.qgtc_weight_codes_words.restype = lib.qgtc_chain_words.restype = lib.qgtc_occupancy_words.restype = ctypes.c_size_t
-    lib.qgtc_expand_weights.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_chain_from_cols.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.qgtc_chain_aggregate.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 8 + [vp, ctypes.c_uint, vp]
     rng = np.random.default_rng(100 * t_bits + act_bits)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P128 = lambda x: (x + 127) // 128 * 128   # noqa: E731
@@ -696,10 +648,6 @@ def test_chain_aggregate_requantises_at_the_clamp_boundary(lib, oracle, b):
     values and read back through an identity W' (out_mode 2): float32(requant(A . T) . I) - against the oracle and the closed form.
     8 bits is the case a saturating byte conversion gets wrong (256 -> 255 instead of 0)."""
     import torch
-    lib.qgtc_weight_codes_words.restype = lib.qgtc_chain_words.restype = ctypes.c_size_t
-    lib.qgtc_expand_weights.argtypes = [vp, ctypes.c_int, vp]
-    lib.qgtc_chain_from_cols.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
-    lib.qgtc_chain_aggregate.argtypes = [vp, vp, ctypes.c_int] + [ctypes.c_int] * 8 + [vp, ctypes.c_uint, vp]
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P128 = lambda x: (x + 127) // 128 * 128   # noqa: E731
     m = k = 70

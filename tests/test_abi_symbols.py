@@ -15,11 +15,9 @@ def lib():
 
     path = qgtc_ppopp22_amd.lib_path()
     assert os.path.exists(path), "libqgtc_hip.so is not built (run __graft_entry__.build())"
-    L = ctypes.CDLL(path)
-    L.qgtc_rows_words.restype = ctypes.c_size_t
-    L.qgtc_cols_words.restype = ctypes.c_size_t
-    L.qgtc_strerror.restype = ctypes.c_char_p
-    return L
+    from qgtc_ppopp22_amd import cabi
+
+    return cabi.load()
 
 
 def declared_symbols():
@@ -101,9 +99,6 @@ def test_epoch_pool_layout_is_host_side(lib, oracle):
     helpers of the chain / tile formats."""
     from helpers import QgtcStage as Stage
 
-    lib.qgtc_epoch_pool_layout.restype = ctypes.c_size_t
-    lib.qgtc_epoch_pool_layout.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.qgtc_chain_words.restype = lib.qgtc_weight_codes_words.restype = ctypes.c_size_t
     ns = [1213, 599, 37, 8, 1]
     stages = (Stage * 4)(Stage(2, 16, 128, 128, 2, 2, 2, 1, 0, 0, 0), Stage(0, 32, -1, 128, 1, 2, 3, 0, 0, 1, 0), Stage(0, 33, -1, 10, 1, 2, 1, 2, 1, 1, 0),
                          Stage(2, 16, 128, 100, 2, 2, 2, 1, 0, 0, 1))
@@ -113,7 +108,7 @@ def test_epoch_pool_layout_is_host_side(lib, oracle):
     sizes = [oracle.cols_words(n, 128, 2, False) for n in ns] + [oracle.rows_words(n, 128, 3) for n in ns] + [(n * 10 + 3) // 4 * 4 for n in ns] \
         + [lib.qgtc_chain_words(n, 100, 2) for n in ns]                       # fmt 1: the chain format of qgtc_chain_*
     assert [lib.qgtc_chain_words(n, 100, 2) for n in ns] == [(n + 127) // 128 * 128 * 16 for n in ns]
-    lib.qgtc_adj_tiles_words.restype = ctypes.c_size_t                     # 512-byte tiles: [32-row block][k-quad][32 rows][4 words]
+    # 512-byte tiles: [32-row block][k-quad][32 rows][4 words]
     assert lib.qgtc_adj_tiles_words(1213, 1213) == 38 * 10 * 128 and lib.qgtc_adj_tiles_words(1, 129) == 2 * 128 and lib.qgtc_adj_tiles_words(0, 5) == 0
     assert lib.qgtc_weight_codes_words(128, 100, 2, 1) == 4 * 2 * 64 * 4 and lib.qgtc_weight_codes_words(64, 50, 4, 1) == 2 * 2 * 2 * 64 * 4
     assert lib.qgtc_weight_codes_words(128, 70, 3, 0) == 4 * 2 * 2 * 64 * 4      # three column blocks are kept as four (the fourth: zero codes)
@@ -132,7 +127,6 @@ def test_epoch_pool_layout_is_host_side(lib, oracle):
 def test_route_functions_name_the_kernel_behind_a_call(lib):
     """qgtc_bitmm_route / qgtc_bitmm_batched_route: host-only, the SAME rule functions the launchers switch on (qgtc_hip.hip:
     single_route / batched_route), so the routing table of DESIGN.md (tools/routing_table.py) cannot drift from the code."""
-    lib.qgtc_bitmm_route.restype = lib.qgtc_bitmm_batched_route.restype = ctypes.c_char_p
     POP, MFMA, AUTO, JUMP = 0x0, 0x8, 0x10, 0x4
     r = lambda *a: lib.qgtc_bitmm_route(*a).decode()             # noqa: E731
     g = lambda *a: lib.qgtc_bitmm_batched_route(*a).decode()     # noqa: E731
@@ -163,8 +157,6 @@ def test_route_functions_name_the_kernel_behind_a_call(lib):
 
 def test_the_library_alone_decides_the_loaders_route(lib, monkeypatch):
     """qgtc_load_work_words is the one decider (it reads QGTC_NO_LOAD_SORT on every call): 0 = the bitmap route, whatever was asked before."""
-    lib.qgtc_load_work_words.restype = ctypes.c_size_t
-    lib.qgtc_load_work_words.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64]
     assert lib.qgtc_load_work_words(3, 257, 1000) > 0
     monkeypatch.setenv("QGTC_NO_LOAD_SORT", "1")
     assert lib.qgtc_load_work_words(3, 257, 1000) == 0

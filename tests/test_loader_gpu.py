@@ -120,10 +120,8 @@ _LIB = None
 def _lib():
     global _LIB
     if _LIB is None:
-        import qgtc_ppopp22_amd
-        _LIB = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-        _LIB.qgtc_adj_tiles_words.restype = ctypes.c_size_t
-        _LIB.qgtc_chain_words.restype = ctypes.c_size_t
+        from qgtc_ppopp22_amd import cabi
+        _LIB = cabi.load()
     return _LIB
 
 
@@ -132,8 +130,6 @@ def _adj_tiles(qgtc, dA, n):
     lib = _lib()
     words = lib.qgtc_adj_tiles_words(n, n)
     out = torch.empty(words, dtype=torch.int32, device="cuda")
-    vp, sz = ctypes.c_void_p, ctypes.c_size_t
-    lib.qgtc_adj_tiles_from_rows.argtypes = [vp, sz, ctypes.c_int, ctypes.c_int, vp, sz, vp]
     assert lib.qgtc_adj_tiles_from_rows(dA.data_ptr(), dA.numel(), n, n, out.data_ptr(), words, torch.cuda.current_stream().cuda_stream) == 0
     return out
 
@@ -143,8 +139,6 @@ def _chain_from_cols(qgtc, dX, n, F, bits):
     lib = _lib()
     words = lib.qgtc_chain_words(n, F, bits)
     out = torch.empty(words, dtype=torch.int32, device="cuda")
-    vp, sz = ctypes.c_void_p, ctypes.c_size_t
-    lib.qgtc_chain_from_cols.argtypes = [vp, sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, sz, vp]
     assert lib.qgtc_chain_from_cols(dX.data_ptr(), dX.numel(), n, F, bits, out.data_ptr(), words, torch.cuda.current_stream().cuda_stream) == 0
     return out
 
@@ -198,7 +192,6 @@ def test_load_batches_through_the_raw_abi(oracle, with_work):
     from helpers import QgtcLoaderBatch as LoaderBatch
 
     assert ctypes.sizeof(LoaderBatch) == 88
-    lib.qgtc_rows_words.restype = lib.qgtc_cols_words.restype = ctypes.c_size_t
     rng = np.random.default_rng(11)
     sizes, F, bits = [70, 257, 5], 20, 2
     rows, cols, feats, ecounts = _batches(rng, sizes, F)
@@ -214,11 +207,6 @@ def test_load_batches_through_the_raw_abi(oracle, with_work):
                                  xp.data_ptr() + 4 * x0, None, None))
         e0, f0, a0, x0 = e0 + ne, f0 + n, a0 + aw, x0 + xw
     dev_table = torch.frombuffer(bytearray(bytes((LoaderBatch * len(sizes))(*table))), dtype=torch.uint8).cuda()
-    vp = ctypes.c_void_p
-    lib.qgtc_load_batches.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t,
-                                      vp, vp, ctypes.c_uint, vp, ctypes.c_size_t, vp]
-    lib.qgtc_load_work_words.restype = ctypes.c_size_t
-    lib.qgtc_load_work_words.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64]
     assert lib.qgtc_load_work_words(3, 257, sum(ecounts)) == 3 * (9 + 1) + sum(ecounts) + (sum(ecounts) & 1) + 3 * 9 and lib.qgtc_load_work_words(3, 5121, 10) == 0
     st = torch.cuda.current_stream().cuda_stream
     stats_ptr = zero.data_ptr() + 4 * sum(a_words)

@@ -1,6 +1,6 @@
 """C-ABI of the node reordering (include/qgtc.h, qgtc_reorder_*): exported, and bad arguments are refused before any device work (no
 GPU needed); and the rule itself, in its NumPy model (tests/reorder_model.py), brings a shuffled graph's tile count back to about
-what block-local ids give. The test keeps its own ctypes mirrors of the entry points."""
+what block-local ids give. The signatures come from the header (cabi.load())."""
 import ctypes
 
 import numpy as np
@@ -9,18 +9,13 @@ import pytest
 from reorder_model import mix32, reorder_model, shuffled_sbm, tile_count
 
 EINVAL = 1
-P, SZ, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_reorder_work_words.restype = SZ
-    L.qgtc_reorder_work_words.argtypes = [I, SZ]
-    L.qgtc_reorder_nodes.argtypes = [P, P, SZ, I, I, I, P, P, P, SZ, P, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

@@ -1,7 +1,6 @@
 """Node reordering on the device (QGTC.reorder_nodes, pack_edges_tiled(reorder=True), TiledAdjacency.to_new / to_old /
 to_old_packed, GCNConv_Qnt on a reordered adjacency): the permutation equals the NumPy model (tests/reorder_model.py) element for
 element, it makes shuffled graphs compact again, and the products and the module give the unreordered results after the gathers."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -186,13 +185,9 @@ def test_c_abi_work_buffer(qgtc):
     """The entry through ctypes with raw device pointers: the size it asks for, a smaller buffer refused, and rank optional."""
     import torch
 
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_reorder_work_words.restype = ctypes.c_size_t
-    L.qgtc_reorder_work_words.argtypes = [ctypes.c_int, ctypes.c_size_t]
-    P, SZ, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    L.qgtc_reorder_nodes.argtypes = [P, P, SZ, I, I, I, P, P, P, SZ, P, P]
+    L = cabi.load()
     src, dst, n = _graph("sbm1213")
     ds, dd = _dev(torch, src), _dev(torch, dst)
     e = src.size

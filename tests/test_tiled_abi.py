@@ -1,25 +1,17 @@
 """C-ABI of the tile-compressed adjacency (include/qgtc.h, qgtc_tiled_*): exported, and bad arguments are refused before any device
-work (no GPU needed). The test keeps its own ctypes mirrors of the entry points."""
+work (no GPU needed). The signatures come from the header (cabi.load())."""
 import ctypes
 
 import pytest
 
 EINVAL, ESIZE, EALIGN = 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiled_work_words.restype = SZ
-    L.qgtc_tiled_work_words.argtypes = [SZ]
-    L.qgtc_tiled_count.argtypes = [P, P, SZ, I, P, P, SZ, P, P]
-    L.qgtc_tiled_fill.argtypes = [SZ, I, I64, P, P, P, SZ, P]
-    L.qgtc_tiledmm2bit.argtypes = [P, P, P, I64, I, P, SZ, I, I, I, P, SZ, P]
-    L.qgtc_tiledmm2int.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

@@ -1,26 +1,19 @@
 """C-ABI of the attention tiled products (include/qgtc.h, "Attention tiled products": qgtc_tiledatt_f32 / _t, qgtc_tiledatt_grad_f32 / _t
 and qgtc_rowdot_f32): the five symbols are exported, the ABI version stays 11, and bad arguments are refused before any device work
-(no GPU needed). The test keeps its own ctypes mirrors of the entry points."""
+(no GPU needed). The signatures come from the header (cabi.load())."""
 import ctypes
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64, F = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 NAMES = ("qgtc_tiledatt_f32", "qgtc_tiledatt_f32_t", "qgtc_tiledatt_grad_f32", "qgtc_tiledatt_grad_f32_t", "qgtc_rowdot_f32")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledatt_f32.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_grad_f32.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_grad_f32_t.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_rowdot_f32.argtypes = [P, P, SZ, I, I, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

@@ -17,7 +17,6 @@ pytestmark = pytest.mark.gpu
 SWEEP_N = (1, 16, 17, 33, 65, 129, 257)
 SWEEP_n = (97, 333, 1000)                          # n % 32 and n % 128 are nonzero
 SWEEP = [(n, N) for N in SWEEP_N for n in SWEEP_n]
-P, SZ, I, I64, F = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 
 def _dev(torch, a):
@@ -331,14 +330,9 @@ def test_side_stream_and_graph_capture(qgtc):
 def test_the_c_entries_stay_within_their_outputs(qgtc, n, N):
     import torch
 
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledatt_f32.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_grad_f32.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledatt_grad_f32_t.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, P]
-    L.qgtc_rowdot_f32.argtypes = [P, P, SZ, I, I, P, SZ, P]
+    L = cabi.load()
     rng = np.random.default_rng(n)
     src, dst = random_edges(rng, n, 6 * n + 5)
     X, dY, p, q = _inputs(rng, n, N)

@@ -1,13 +1,12 @@
 """C-ABI of edge dropout (include/qgtc.h, "Edge dropout": qgtc_edge_kept and the eight _drop entries): the nine symbols are exported,
 the ABI version stays 11, and every _drop entry refuses what its parent refuses, in the parent's order, before any device work (no GPU
-needed). The test keeps its own ctypes mirrors of the entry points."""
+needed). The signatures come from the header (cabi.load())."""
 import ctypes
 import os
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64, F, U32, U64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint64
 NAMES = ("qgtc_edge_kept", "qgtc_tiledmm_f32_drop", "qgtc_tiledmm_f32_t_drop", "qgtc_tiledmax_f32_drop", "qgtc_tiledmax_f32_t_drop",
          "qgtc_tiledatt_f32_drop", "qgtc_tiledatt_f32_t_drop", "qgtc_tiledatt_grad_f32_drop", "qgtc_tiledatt_grad_f32_t_drop")
 MASK = (1 << 31, 0x0123456789ABCDEF)   # threshold, seed: any value of either is valid
@@ -15,19 +14,9 @@ MASK = (1 << 31, 0x0123456789ABCDEF)   # threshold, seed: any value of either is
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_edge_kept.argtypes = [U32, U32, U64, U32]
-    L.qgtc_tiledmm_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledmm_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledmax_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, U32, U64, P]
-    L.qgtc_tiledmax_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_grad_f32_drop.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_grad_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

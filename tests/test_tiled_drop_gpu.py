@@ -24,7 +24,6 @@ SWEEP_n = (97, 333, 1000)                          # n % 32 and n % 128 are nonz
 RATES = (0.0, 0.1, 0.6, 1.0 - 2.0 ** -32)          # thresholds 0, 429496729, 2576980377, 2^32 - 1
 # the grid N x n x both views x rate x seed, thinned: every (n, N) runs both views under one rate and one seed, which rotate
 SWEEP = [(n, N, RATES[(iN + i) % 4], dm.SEEDS[(2 * iN + i) % 4]) for iN, N in enumerate(SWEEP_N) for i, n in enumerate(SWEEP_n)]
-P, SZ, I, I64, F, U32, U64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint64
 
 
 def _dev(torch, a):
@@ -391,18 +390,9 @@ def test_side_stream_and_graph_capture(qgtc):
 def test_the_c_entries_stay_within_their_outputs(qgtc, n, N):
     import torch
 
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledmm_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledmm_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledmax_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, U32, U64, P]
-    L.qgtc_tiledmax_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_f32_drop.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_grad_f32_drop.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_tiledatt_grad_f32_t_drop.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ, U32, U64, P]
-    L.qgtc_rowdot_f32.argtypes = [P, P, SZ, I, I, P, SZ, P]
+    L = cabi.load()
     rate, seed = 0.6, 2 ** 64 - 1
     T = dm.threshold(rate)
     rng = np.random.default_rng(n)

@@ -2,7 +2,6 @@
 thresholds, the host function qgtc_edge_kept against the model, the statistics of the mask (kept fraction, independence of the
 transpose, of other seeds and of the row / column permutations a weaker combine would reduce a seed change to), the wrong rules, and
 masking = dropping in the models. No GPU."""
-import ctypes
 import itertools
 
 import numpy as np
@@ -47,12 +46,9 @@ def test_thresholds():
 
 @pytest.fixture(scope="module")
 def edge_kept():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    f = ctypes.CDLL(qgtc_ppopp22_amd.lib_path()).qgtc_edge_kept
-    f.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32]
-    f.restype = ctypes.c_int
-    return f
+    return cabi.load().qgtc_edge_kept
 
 
 def test_host_function_equals_the_model(edge_kept):

@@ -1,30 +1,21 @@
 """C-ABI of the edge values (include/qgtc.h, "Edge values": qgtc_tiled_value_index, qgtc_tiled_edge_slots, qgtc_tiled_edge_endpoints,
 qgtc_tiledmm_f32_edge / _t_edge and qgtc_tiled_sddmm_f32): the six symbols are exported, the ABI version stays 11, and bad arguments
-are refused before any device work, invalid before misaligned before short (no GPU needed). The test keeps its own ctypes mirrors of
-the entry points."""
+are refused before any device work, invalid before misaligned before short (no GPU needed). The signatures come from the header (cabi.load())."""
 import ctypes
 import os
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 NAMES = ("qgtc_tiled_value_index", "qgtc_tiled_edge_slots", "qgtc_tiled_edge_endpoints", "qgtc_tiledmm_f32_edge",
          "qgtc_tiledmm_f32_t_edge", "qgtc_tiled_sddmm_f32")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiled_value_index.argtypes = [P, I64, P, P, P]
-    L.qgtc_tiled_edge_slots.argtypes = [P, P, P, I64, I, P, P, P, P, SZ, P, P]
-    L.qgtc_tiled_edge_endpoints.argtypes = [P, P, P, I64, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledmm_f32_edge.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, SZ, P, P, P, SZ, P]
-    L.qgtc_tiledmm_f32_t_edge.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, SZ, P, P, P, SZ, P]
-    L.qgtc_tiled_sddmm_f32.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 @pytest.fixture(scope="module")

@@ -1,27 +1,21 @@
 """C-ABI of the edge softmax (include/qgtc.h, "Edge softmax": qgtc_tiled_edge_softmax_f32 / _t and qgtc_tiled_edge_softmax_grad_f32 /
 _t): the four symbols are exported and declared, the ABI version stays 11, and bad arguments are refused before any device work,
-invalid before misaligned (no GPU needed). The test keeps its own ctypes mirrors of the entry points."""
+invalid before misaligned (no GPU needed). The signatures come from the header (cabi.load())."""
 import ctypes
 import os
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 NAMES = ("qgtc_tiled_edge_softmax_f32", "qgtc_tiled_edge_softmax_f32_t", "qgtc_tiled_edge_softmax_grad_f32",
          "qgtc_tiled_edge_softmax_grad_f32_t")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiled_edge_softmax_f32.argtypes = [P, P, P, I64, I, P, P, P, P, SZ, P, P, P]
-    L.qgtc_tiled_edge_softmax_f32_t.argtypes = [P, P, P, P, I64, I, P, P, P, P, SZ, P, P, P]
-    L.qgtc_tiled_edge_softmax_grad_f32.argtypes = [P, P, P, I64, I, P, P, P, P, P, SZ, P]
-    L.qgtc_tiled_edge_softmax_grad_f32_t.argtypes = [P, P, P, P, I64, I, P, P, P, P, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 @pytest.fixture(scope="module")

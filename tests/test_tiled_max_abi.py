@@ -1,24 +1,18 @@
 """C-ABI of the extremum tiled products (include/qgtc.h, "Extremum tiled products": qgtc_tiledmax_f32 / _t and qgtc_tiledsel_f32 / _t):
-the four symbols are exported, the ABI version stays 11, and bad arguments are refused before any device work (no GPU needed). The test
-keeps its own ctypes mirrors of the entry points."""
+the four symbols are exported, the ABI version stays 11, and bad arguments are refused before any device work (no GPU needed).
+The signatures come from the header (cabi.load())."""
 import ctypes
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledmax_f32.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledmax_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledsel_f32.argtypes = [P, P, P, I64, I, P, SZ, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledsel_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, SZ, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

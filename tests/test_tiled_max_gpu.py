@@ -15,7 +15,6 @@ from tiled_model import random_edges, set_cells
 
 pytestmark = pytest.mark.gpu
 
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 SENTINEL = 0x5A5A5A5A                              # what `arg` holds before a C entry writes it
 OPS = ((MAX, "max"), (MIN, "min"))
 
@@ -38,14 +37,9 @@ def lib():
 
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledmax_f32.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledmax_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledsel_f32.argtypes = [P, P, P, I64, I, P, SZ, I, P, SZ, P, SZ, P]
-    L.qgtc_tiledsel_f32_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, SZ, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _index(adj, transposed, null=False):

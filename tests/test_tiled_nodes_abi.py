@@ -1,36 +1,23 @@
 """C-ABI and Python refusals of node masks (include/qgtc.h, "Node masks": qgtc_node_bitmap, qgtc_tiled_inv_degree and the eight _nodes
 entries): the symbols are exported, the ABI version stays 11, every _nodes entry refuses what its _drop twin refuses, in its order, then
 a short or misaligned mask, all before any device work; and the Python layer refuses bad masks on an adjacency of CPU tensors (no GPU
-needed). The test keeps its own ctypes mirrors of the entry points."""
-import ctypes
+needed). The signatures come from the header (cabi.load())."""
 import os
 
 import pytest
 
-from test_tiled_drop_abi import EALIGN, EINVAL, ESIZE, F, I, I64, P, SZ, _buf, _common_refusals
+from test_tiled_drop_abi import EALIGN, EINVAL, ESIZE, _buf, _common_refusals
 
 ENTRIES = ("qgtc_tiledmm_f32_nodes", "qgtc_tiledmm_f32_t_nodes", "qgtc_tiledmax_f32_nodes", "qgtc_tiledmax_f32_t_nodes",
            "qgtc_tiledatt_f32_nodes", "qgtc_tiledatt_f32_t_nodes", "qgtc_tiledatt_grad_f32_nodes", "qgtc_tiledatt_grad_f32_t_nodes")
 NAMES = ("qgtc_node_bitmap", "qgtc_tiled_inv_degree") + ENTRIES
-M3 = [P, P, SZ]   # row_mask, nbr_mask, mask_words
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_node_bitmap.argtypes = [P, I, P, SZ, P]
-    L.qgtc_tiled_inv_degree.argtypes = [P, I, P, P]
-    L.qgtc_tiledmm_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledmm_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledmax_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ] + M3 + [P]
-    L.qgtc_tiledmax_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_grad_f32_nodes.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_grad_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    return L
+    return cabi.load()
 
 
 def test_symbols_and_version(lib):

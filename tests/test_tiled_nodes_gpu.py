@@ -26,7 +26,6 @@ SWEEP_n = (97, 333, 1000)                          # n % 32 and n % 128 are nonz
 KINDS = ("both", "rows", "nbrs", "same")           # (random, random), (random, none), (none, random), one mask twice
 # the grid N x n x both views x mask pair, thinned as the edge-dropout sweep is: every (n, N) runs both views under one pair, which rotates
 SWEEP = [(n, N, KINDS[(iN + i) % 4]) for iN, N in enumerate(SWEEP_N) for i, n in enumerate(SWEEP_n)]
-P, SZ, I, I64, F = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 
 def _pair(rng, n, kind):
@@ -318,18 +317,9 @@ def test_the_c_entries_stay_within_their_outputs_and_ignore_pad_bits(qgtc, n, N)
     positions from n up) are all set: the outputs are the models' on the induced edges."""
     import torch
 
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    M3 = [P, P, SZ]
-    L.qgtc_tiledmm_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledmm_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledmax_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ] + M3 + [P]
-    L.qgtc_tiledmax_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_f32_nodes.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_grad_f32_nodes.argtypes = [P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
-    L.qgtc_tiledatt_grad_f32_t_nodes.argtypes = [P, P, P, P, I64, I, P, P, SZ, I, P, P, F, I, P, P, P, P, SZ] + M3 + [P]
+    L = cabi.load()
     rng = np.random.default_rng(n)
     src, dst = random_edges(rng, n, 6 * n + 5)
     X, dY, p, q, r, c = _inputs(rng, n, N)

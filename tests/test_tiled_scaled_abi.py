@@ -1,25 +1,18 @@
 """C-ABI of the scaled tiled products and the degrees (include/qgtc.h, "Scaled tiled products and degrees": qgtc_tiled_degrees,
 qgtc_tiledmm2bit_scaled / _int_scaled / _bit_t_scaled / _int_t_scaled): bad arguments are refused before any device work (no GPU
-needed). The test keeps its own ctypes mirrors of the entry points; test_abi_symbols checks that they are exported."""
+needed). The signatures come from the header (cabi.load()); test_abi_symbols checks that they are exported."""
 import ctypes
 
 import pytest
 
 EINVAL, ESIZE, EALIGN = 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiled_degrees.argtypes = [P, P, P, I64, I, P, P, P, P, P]
-    L.qgtc_tiledmm2bit_scaled.argtypes = [P, P, P, I64, I, P, SZ, I, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2int_scaled.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2bit_t_scaled.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2int_t_scaled.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

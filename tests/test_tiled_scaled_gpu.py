@@ -14,7 +14,6 @@ from tiled_scaled_model import degrees, expected_bits_scaled, mean_scale, scaled
 
 pytestmark = pytest.mark.gpu
 
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 CANARY = 64
 POISON_BITS = -0x5A5A5A5B                          # 0xA5A5A5A5 as int32
 NAN_WORD = 0x7FC00000                              # the float NaN torch.full writes
@@ -55,17 +54,9 @@ def lib():
 
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_rows_words.restype = SZ
-    L.qgtc_rows_words.argtypes = [I, I, I]
-    L.qgtc_tiled_degrees.argtypes = [P, P, P, I64, I, P, P, P, P, P]
-    L.qgtc_tiledmm2bit_scaled.argtypes = [P, P, P, I64, I, P, SZ, I, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2int_scaled.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2bit_t_scaled.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, I, P, P, SZ, P]
-    L.qgtc_tiledmm2int_t_scaled.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 # ---- 1. degrees ---------------------------------------------------------------------------------------------------------------------

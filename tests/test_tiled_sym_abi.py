@@ -1,24 +1,19 @@
 """C-ABI of the source-scaled float tiled products and the inverse square roots of the degrees (include/qgtc.h, "Source scale":
 qgtc_tiledmm_f32_src / qgtc_tiledmm_f32_t_src / qgtc_tiled_inv_sqrt_degree): the symbols are exported, the ABI version stays 11, bad
 arguments are refused before any device work, and the Python layer (QGTC.tiledMMFloat(src_scale=), QGTC.tiledAggregate) refuses what
-it must before it reaches the extension (no GPU needed). The test keeps its own ctypes mirrors of the entry points."""
+it must before it reaches the extension (no GPU needed). The signatures come from the header (cabi.load())."""
 import ctypes
 
 import pytest
 
 OK, EINVAL, ESIZE, EALIGN = 0, 1, 2, 3
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledmm_f32_src.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ, P]
-    L.qgtc_tiledmm_f32_t_src.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ, P]
-    L.qgtc_tiled_inv_sqrt_degree.argtypes = [P, I, P, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

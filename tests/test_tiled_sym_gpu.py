@@ -15,7 +15,6 @@ from tiled_sym_model import add_self_loops, aggregate_f32_src, error_bound, inv_
 
 pytestmark = pytest.mark.gpu
 
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 CANARY = 64
 NAN_WORD = 0x7FC00000                              # the float NaN torch.full writes
 NO_EDGES = (np.zeros(0, np.int64), np.zeros(0, np.int64))
@@ -50,13 +49,9 @@ def lib():
 
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiledmm_f32_src.argtypes = [P, P, P, I64, I, P, SZ, I, P, P, P, SZ, P]
-    L.qgtc_tiledmm_f32_t_src.argtypes = [P, P, P, P, I64, I, P, SZ, I, P, P, P, SZ, P]
-    L.qgtc_tiled_inv_sqrt_degree.argtypes = [P, I, P, P]
-    return L
+    return cabi.load()
 
 
 def _raw(torch, lib, adj, X, scale, src_scale, transposed):

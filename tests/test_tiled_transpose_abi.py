@@ -1,25 +1,18 @@
 """C-ABI of the transposed tiled adjacency (include/qgtc.h, "Transposed tiled adjacency": qgtc_tiled_colindex*, qgtc_tiledmm2*_t): bad
-arguments are refused before any device work (no GPU needed), and the work-size query keeps to its domain. The test keeps its own
-ctypes mirrors of the entry points; test_abi_symbols checks that they are exported."""
+arguments are refused before any device work (no GPU needed), and the work-size query keeps to its domain.
+The signatures come from the header (cabi.load()); test_abi_symbols checks that they are exported."""
 import ctypes
 
 import pytest
 
 EINVAL, ESIZE, EALIGN, ENODEVICE = 1, 2, 3, 5
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_tiled_colindex_work_words.restype = SZ
-    L.qgtc_tiled_colindex_work_words.argtypes = [I64]
-    L.qgtc_tiled_colindex.argtypes = [P, P, I64, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledmm2bit_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, I, P, SZ, P]
-    L.qgtc_tiledmm2int_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _buf(words):

@@ -14,7 +14,6 @@ from tiled_model import (FORWARD_VARIANTS, TRANSPOSED_VARIANTS, aggregate, expec
 
 pytestmark = pytest.mark.gpu
 
-P, SZ, I, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 # N over every variant boundary of both kernels (16 / 32 / 64 and the 128-column chunks); n, bit2 and ob rotate alongside
 SWEEP_N = [1, 15, 16, 17, 24, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 383]
@@ -76,19 +75,9 @@ def lib():
 
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    import qgtc_ppopp22_amd
+    from qgtc_ppopp22_amd import cabi
 
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    L.qgtc_rows_words.restype = SZ
-    L.qgtc_rows_words.argtypes = [I, I, I]
-    L.qgtc_tiled_colindex_work_words.restype = SZ
-    L.qgtc_tiled_colindex_work_words.argtypes = [I64]
-    L.qgtc_tiled_colindex.argtypes = [P, P, I64, I, P, P, P, P, SZ, P]
-    L.qgtc_tiledmm2bit.argtypes = [P, P, P, I64, I, P, SZ, I, I, I, P, SZ, P]
-    L.qgtc_tiledmm2int.argtypes = [P, P, P, I64, I, P, SZ, I, I, P, SZ, P]
-    L.qgtc_tiledmm2bit_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, I, P, SZ, P]
-    L.qgtc_tiledmm2int_t.argtypes = [P, P, P, P, I64, I, P, SZ, I, I, P, SZ, P]
-    return L
+    return cabi.load()
 
 
 def _ptr(t):

@@ -1,12 +1,11 @@
 """Single launches over plane counts and shapes on the default engine: time per launch and the kernel that served it (a scan for slow spots).
 usage: route_sweep.py [cols]"""
-import ctypes, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import QGTC as Q
-import qgtc_ppopp22_amd
-L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-L.qgtc_bitmm_route.restype = ctypes.c_char_p
+from qgtc_ppopp22_amd import cabi
+L = cabi.load()
 cols = len(sys.argv) > 1 and sys.argv[1] == "cols"
 for a, w in ((1, 1), (1, 4), (2, 2), (2, 8), (3, 3), (4, 4), (5, 5), (6, 2), (8, 1), (8, 8)):
     for M, K, N in ((599, 50, 64), (1213, 128, 128), (1213, 1213, 128), (1213, 1213, 10), (4096, 4096, 64), (4096, 4096, 256), (2048, 2048, 512)):

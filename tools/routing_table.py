@@ -3,24 +3,16 @@
 
     python tools/routing_table.py            # prints the table
 """
-import ctypes
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import qgtc_ppopp22_amd
+from qgtc_ppopp22_amd import cabi
 
 ENGINE = {"popcount": 0x0, "mfma": 0x8, "auto": 0x10}
 ZERO_JUMP = 0x4
 MODES = {0: "bits, rows", 1: "bits, cols", 2: "float32"}
-
-
-def lib():
-    L = ctypes.CDLL(qgtc_ppopp22_amd.lib_path())
-    for f in (L.qgtc_bitmm_route, L.qgtc_bitmm_batched_route):
-        f.restype = ctypes.c_char_p
-    return L
 
 
 SINGLE = [  # (what, M, K, N, a, w, ob, mode)
@@ -64,7 +56,7 @@ GROUPED = [  # (what, max_M, max_K, max_N, a, w, ob, mode, extra flags)
 
 
 def table():
-    L = lib()
+    L = cabi.load()
     out = ["| call shape (M x K x N, a x w -> ob, output) | engine `popcount` | engine `auto` (default) | engine `mfma` |", "|---|---|---|---|"]
     for what, M, K, N, a, w, ob, mode in SINGLE:
         r = [L.qgtc_bitmm_route(M, K, N, a, w, ob, mode, f).decode() for f in ENGINE.values()]
