@@ -98,6 +98,7 @@ int with_kernel(int a, int w, int K, int ob, int mode, long total_tiles, Plan *p
 // products of a --bit_width 9 .. 32 epoch - 1213 x 128 x 16 at 32 x 32 planes 27 -> 11-13 us. Measured level or behind the generic kernel
 // where the left operand has few planes (the 1 x 32-plane aggregations: 31 against 29 us) and on grouped launches (2850 tiles at 78 KB
 // of LDS each: 1.1 against 0.55 ms an epoch): those stay on k_bitmm<1, 0, 0>.
+// The decision is single_route's (qgtc_hip.hip: RT_POPCOUNT_PLANES), so that qgtc_bitmm_route names this kernel.
 inline bool planes_route(int a, int w, bool grouped) { (void)w; return a > 8 && !grouped && !getenv_flag("QGTC_NO_PLANES"); }
 template <bool BATCHED>
 int launch_planes(const qgtc_problem *prs, const qgtc_problem &pr1, int count, int max_M, int max_N, int a, int w, int ob, int mode, hipStream_t st) {
@@ -116,7 +117,6 @@ int launch_planes(const qgtc_problem *prs, const qgtc_problem &pr1, int count, i
 
 template <bool ZS>
 int dispatch_single(const qgtc_problem &pr, int K, int a, int w, int ob, int mode, hipStream_t st) {
-    if (ZS && planes_route(a, w, false)) return launch_planes<false>(nullptr, pr, 1, pr.M, pr.N, a, w, ob, mode, st);
     Plan pl;
     const long tiles = static_cast<long>((pr.M + TM - 1) / TM) * ((pr.N + TN - 1) / TN);
     return with_kernel<ZS>(a, w, K, ob, mode, tiles, &pl, [&](auto qw, auto na, auto nw) {

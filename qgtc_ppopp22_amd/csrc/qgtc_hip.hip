@@ -184,7 +184,7 @@ int qgtc_bit2val(const uint32_t *bits, size_t bits_words, int nbits, int H, int 
 }
 
 // ---- which kernel family a single launch takes (one rule set for the launchers and for qgtc_bitmm_route) ---------------
-enum SingleRoute { RT_FP4_NARROW = 0, RT_FP4_STREAM, RT_FP4_ROWS, RT_FP4_WIDE, RT_MFMA_128, RT_POPCOUNT };
+enum SingleRoute { RT_FP4_NARROW = 0, RT_FP4_STREAM, RT_FP4_ROWS, RT_FP4_WIDE, RT_MFMA_128, RT_POPCOUNT_PLANES, RT_POPCOUNT };
 static SingleRoute single_route(const qgtc_problem &pr, int a, int w, int ob, int mode, unsigned flags) {
     const bool mf = (flags & QGTC_ENGINE_MFMA) != 0u, au = (flags & QGTC_ENGINE_AUTO) != 0u;
     if (stream_ok(pr, a, w, ob, mode) && (mf || (au && auto_prefers_stream(pr.M, pr.K, pr.N)))) return RT_FP4_STREAM;
@@ -192,6 +192,8 @@ static SingleRoute single_route(const qgtc_problem &pr, int a, int w, int ob, in
     if (rows_single_ok(pr, a, w, ob, mode) && (mf || au)) return RT_FP4_ROWS;
     if (wide_ok(pr, a, w, ob, mode) && (mf || (au && auto_prefers_wide(pr.M, pr.K, pr.N, a, w, mode)))) return RT_FP4_WIDE;
     if ((mf && mfma_ok(a, w)) || (au && auto_prefers_mfma(pr.M, pr.K, pr.N, a, w))) return RT_MFMA_128;
+    // the census kernel skips planes that are all zero: with QGTC_NO_ZERO_SKIP the generic kernel runs, as it does for every other plane count
+    if (!(flags & QGTC_NO_ZERO_SKIP) && planes_route(a, w, false)) return RT_POPCOUNT_PLANES;
     return RT_POPCOUNT;
 }
 static int launch_single_route(const qgtc_problem &pr, int a, int w, int ob, int mode, unsigned flags, hipStream_t st) {
@@ -201,6 +203,7 @@ static int launch_single_route(const qgtc_problem &pr, int a, int w, int ob, int
         case RT_FP4_ROWS: return qgtc_launch_rows_single(pr, a, w, ob, mode, st);
         case RT_FP4_WIDE: return qgtc_launch_wide(pr, a, w, ob, mode, st);
         case RT_MFMA_128: return qgtc_launch_mfma(pr, a, w, ob, mode, st);
+        case RT_POPCOUNT_PLANES: return launch_planes<false>(nullptr, pr, 1, pr.M, pr.N, a, w, ob, mode, st);
         default: break;
     }
     if (flags & QGTC_NO_ZERO_SKIP) return dispatch_single<false>(pr, pr.K, a, w, ob, mode, st);
@@ -217,6 +220,7 @@ const char *qgtc_bitmm_route(int M, int K, int N, int bit1, int bit2, int output
         case RT_FP4_ROWS: return "k_bitmm_fp4_rows_single";
         case RT_FP4_WIDE: return "k_bitmm_fp4_wide";
         case RT_MFMA_128: return "k_bitmm_mfma";
+        case RT_POPCOUNT_PLANES: return "k_bitmm_planes";
         default: return "k_bitmm";
     }
 }

@@ -388,7 +388,7 @@ MM_FAMILIES = [
     ("skinny", (257, 9000, 40, 1, 1, 3), "auto", "k_bitmm_fp4_skinny"),
     ("wide", (1024, 1024, 1030, 1, 2, 2), "auto", "k_bitmm_fp4_wide"),
     ("int8", (77, 259, 40, 8, 8, 8), "mfma", "k_bitmm_mfma"),
-    ("planes", (20, 300, 40, 9, 12, 4), "auto", "k_bitmm"),
+    ("planes", (20, 300, 40, 9, 12, 4), "auto", "k_bitmm_planes"),
     ("popcount", (100, 1000, 64, 1, 1, 1), "popcount", "k_bitmm"),
 ]
 

@@ -139,7 +139,10 @@ def test_route_functions_name_the_kernel_behind_a_call(lib):
     assert r(32768, 32768, 64, 1, 2, 2, 0, AUTO) == "k_bitmm_fp4_skinny"           # more than one plane: K > 4096 stays there
     assert r(4096, 4096, 1024, 1, 1, 1, 0, AUTO) == "k_bitmm_fp4_wide"
     assert r(4096, 4096, 64, 8, 8, 8, 0, AUTO) == "k_bitmm_mfma"                   # 4096 * 255 * 255 >= 2^24: int8 form, int32 sums
-    assert r(512, 512, 64, 9, 2, 4, 0, MFMA) == "k_bitmm"                          # nine planes: AND + popcount only
+    # nine planes: AND + popcount only - the census kernel, and the generic one when zero-skip is off (the launchers switch on the same answer)
+    assert r(512, 512, 64, 9, 2, 4, 0, MFMA) == "k_bitmm_planes" and r(512, 512, 64, 9, 2, 4, 0, MFMA | 0x2) == "k_bitmm"
+    assert r(512, 512, 64, 9, 2, 4, 2, POP) == "k_bitmm_planes" and r(512, 512, 64, 8, 9, 4, 0, POP) == "k_bitmm"
+    assert g(512, 512, 64, 9, 2, 4, 0, MFMA) == "k_bitmm_batched"                  # (grouped launches stay on the generic kernel)
     assert r(0, 4, 4, 1, 1, 1, 0, AUTO) == "invalid" and r(4, 4, 4, 1, 1, 1, 3, AUTO) == "invalid"
     assert g(1213, 128, 128, 2, 2, 2, 1, AUTO) == "k_bitmm_fp4_xw_rows"
     assert g(1213, 1213, 128, 1, 2, 2, 0, AUTO | JUMP) == "k_bitmm_fp4_rows"
