@@ -10,6 +10,7 @@ import re
 from . import lib_path
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "qgtc.h")
+HEADS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_heads.h")   # the multi-head entries, declared beside qgtc.h until the two are folded
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
@@ -46,16 +47,19 @@ def signatures(text: str | None = None) -> dict:
 
 
 def load():
-    """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry. A declared entry the
-    library does not export is an error naming it."""
+    """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry - those of include/qgtc.h
+    and, through the same parser, those of include/qgtc_heads.h. A declared entry the library does not export is an error naming it."""
     global _lib
     if _lib is None:
         lib = ctypes.CDLL(lib_path())
-        for name, (restype, argtypes) in signatures().items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise ImportError(f"{lib_path()} does not export {name}, which include/qgtc.h declares") from None
-            fn.restype, fn.argtypes = restype, argtypes
+        with open(HEADS_HEADER) as f:
+            heads = signatures(f.read())
+        for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads)):
+            for name, (restype, argtypes) in table.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    raise ImportError(f"{lib_path()} does not export {name}, which include/{header} declares") from None
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib

@@ -327,7 +327,9 @@ class TransformerConv(torch.nn.Module):
     2021, without its skip connection): q = X . W_q, k = X . W_k, v = X . W_v, and per head the receiving node i takes
     ``sum over its neighbours j of softmax_j(q_i . k_j / sqrt(output_dim)) * v_j`` - ``tiled.tiledEdgeAttention(A, q_head, k_head,
     v_head)``: an SDDMM, the edge softmax and the weighted sum, every launch of forward and backward specified to the bit and without
-    atomics. The heads run one after the other and are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged
+    atomics. All heads share one call, ``tiledEdgeAttention(A, q, k, v, heads=heads)``: three launches forward and five backward for the
+    whole layer, reading q, k and v in place (head h is their columns h * output_dim ..), each head bit for bit what the single-head
+    call gives on its slice. The heads are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged
     ([n, output_dim]). Trainable in W_q, W_k and W_v. ``A`` is the view whose rows are the receiving nodes: ``adj`` attends over
     out-neighbours, ``adj.T`` over in-neighbours; on a reordered adjacency X moves to its numbering and the result back. A node without
     neighbours gives +0; self loops are the edge list's business (QGTC.add_self_loops).
@@ -350,12 +352,7 @@ class TransformerConv(torch.nn.Module):
 
         Xn = A.to_new(X)
         q, k, v = torch.mm(Xn, self.W_q), torch.mm(Xn, self.W_k), torch.mm(Xn, self.W_v)
-        outs = []
-        for i in range(self.heads):
-            cols = slice(i * self.output_dim, (i + 1) * self.output_dim)
-            outs.append(tiledEdgeAttention(A, q[:, cols].contiguous(), k[:, cols].contiguous(), v[:, cols].contiguous()))
-        if self.concat:
-            out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
-        else:
-            out = outs[0] if self.heads == 1 else torch.stack(outs).mean(dim=0)
+        out = tiledEdgeAttention(A, q, k, v, heads=self.heads)
+        if self.heads > 1 and not self.concat:   # the mean over the heads, in the layout and order of torch.stack(heads).mean(dim=0)
+            out = out.view(A.n, self.heads, self.output_dim).transpose(0, 1).contiguous().mean(dim=0)
         return A.to_old(out)

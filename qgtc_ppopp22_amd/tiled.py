@@ -67,6 +67,11 @@ exponential and the sum in ascending neighbour id, so forward and gradient are s
 logit masks its edge. :func:`tiledEdgeScores` is :func:`tiledSDDMM` under autograd (its two gradients are weighted products with the
 incoming gradient as the weights), and :func:`tiledEdgeAttention` composes the three into dot-product attention over the edges,
 ``softmax(scale * Q K^T restricted to the edges) . V``, differentiable in Q, K and V. ``conv.TransformerConv`` is the layer on top.
+
+All of that path takes HEADS without a loop (include/qgtc_heads.h): with ``heads=H`` the scores are float32 [nnz, H] (head-minor, the H
+values of a cell adjacent), the softmax accepts and returns [nnz, H] with [n, H] statistics, ``edge_weight`` accepts [nnz, H] for an X
+whose columns H divides, and ``tiledEdgeAttention(..., heads=H)`` is three launches forward and five backward for all heads - each head
+bit for bit what the single-head call gives on its contiguous slice of columns.
 """
 from __future__ import annotations
 
@@ -492,8 +497,10 @@ def _value_index(adj: TiledAdjacency):
     return base._val_index
 
 
-def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, nodes_kw=None, reduce: str = "sum", attn=None) -> None:
-    """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself."""
+def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, nodes_kw=None, reduce: str = "sum", attn=None,
+                       X=None) -> None:
+    """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself - float32 [nnz], or [nnz, H] with
+    H dividing the columns of ``X`` (one value per stored cell and head)."""
     for name, on in (("src_scale", src_scale is not None), ("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)),
                      (f'reduce="{reduce}"', reduce != "sum"), ("attn", attn is not None)):
         if on:
@@ -505,7 +512,10 @@ def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, no
     if values.device != adj.device:
         raise ValueError(f"edge_weight must be on the adjacency's device {adj.device}, not {values.device}")
     nnz = _value_index(adj)[2]
-    if values.dim() != 1 or values.numel() != nnz:
+    if values.dim() == 2 and values.size(0) == nnz and values.size(1) >= 2:   # [nnz, H]: a value per stored cell and head
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.size(1) % values.size(1) != 0:
+            raise ValueError(f"edge_weight has {values.size(1)} heads, which do not divide X's {X.size(1)} columns")
+    elif values.dim() != 1 or values.numel() != nnz:
         raise ValueError(f"edge_weight must have shape [{nnz}] (one value per stored cell), not {list(values.shape)}")
     if not values.is_contiguous():
         raise ValueError("edge_weight must be contiguous")
@@ -591,15 +601,52 @@ def edge_values(adj: TiledAdjacency, src: torch.Tensor, dst: torch.Tensor, weigh
     return values
 
 
-def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+def _check_heads(heads, width: int) -> int:
+    """``heads`` as an int: at least 1 and a divisor of ``width``, the columns of the node matrices. Another value is a ValueError,
+    another type a TypeError."""
+    if isinstance(heads, bool) or not isinstance(heads, int):
+        raise TypeError(f"heads must be an int, not {type(heads).__name__}")
+    if heads < 1 or width % heads != 0:
+        raise ValueError(f"heads must be at least 1 and divide the {width} columns, not {heads}")
+    return heads
+
+
+def _view_ptrs(adj: TiledAdjacency):
+    """What every multi-head entry takes first (include/qgtc_heads.h): the view's index pointers and tiles, then n_tiles and n - and
+    the pointers of the value index, which come later in the argument lists."""
+    base = _base(adj)
+    val_ptr, val_row, _ = _value_index(base)
+    T = base.n_tiles
+    view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles) if adj.transposed else (adj.row_ptr, adj.kquad, adj.tiles)
+    return tuple(t.data_ptr() if T else None for t in view) + (T, adj.n), (val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
+
+
+def _sddmm_heads(base: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
+    """float32 [nnz, heads] of qgtc_tiled_sddmm_heads_f32 on the untransposed adjacency (the caller has swapped the operands of the
+    other view): one launch on the current stream."""
+    val_ptr, val_row, nnz = _value_index(base)
+    out = torch.empty((nnz, heads), dtype=torch.float32, device=base.device)
+    if nnz:
+        _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_heads_f32, base.row_ptr.data_ptr(), base.kquad.data_ptr(), base.tiles.data_ptr(),
+                base.n_tiles, base.n, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), val_ptr.data_ptr(), val_row.data_ptr(),
+                out.data_ptr(), nnz, heads)
+    return out
+
+
+def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int = 1) -> torch.Tensor:
     """float32 [nnz] in slot order: ``out[slot(i, j)] = DOT(A[i], B[j])`` for every stored cell (i, j) of this view - on ``adj`` row i of A
     with row j of B; on ``adj.T`` the cell is the same one of ``adj`` and the operands swap, so the same kernel runs. DOT is the
     attention's (include/qgtc.h, "Attention tiled products"): 64 strided partial sums, then the xor butterfly, every step one float32
     operation, so the result is the same bits on every launch. Each slot is written once, without atomics. A and B are float32 [n, N],
     contiguous, on the adjacency's device, in the adjacency's numbering. It is the gradient of a weighted aggregate for its weights, a
-    link score, and the building block of dot-product attention."""
+    link score, and the building block of dot-product attention.
+
+    With ``heads=H`` > 1 (H dividing N; head h is the columns h d .. (h + 1) d - 1, d = N / H) the result is float32 [nnz, H],
+    ``out[slot, h]`` the DOT of head h's columns: one launch for all heads (include/qgtc_heads.h), each head bit for bit the single-head
+    call on its contiguous slice. ``heads=1`` is the call it always was. A ``heads`` that does not divide N is a ValueError."""
     _check(adj)
     _check_float_operand(adj, A)
+    heads = _check_heads(heads, A.size(1))
     if not isinstance(B, torch.Tensor) or B.dtype != torch.float32:
         raise TypeError("B must be a float32 torch.Tensor")
     if B.shape != A.shape or B.device != A.device or not B.is_contiguous():
@@ -608,6 +655,8 @@ def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.T
         A, B = B, A
     base = _base(adj)
     val_ptr, val_row, nnz = _value_index(base)
+    if heads > 1:
+        return _sddmm_heads(base, A, B, heads)
     out = torch.empty(nnz, dtype=torch.float32, device=base.device)
     if nnz:
         _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_f32, base.row_ptr.data_ptr(), base.kquad.data_ptr(), base.tiles.data_ptr(),
@@ -649,7 +698,7 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if edge_weight is not None:
-        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn)
+        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn, X)
         if return_arg or return_stats:
             raise ValueError("return_arg / return_stats cannot be combined with edge_weight: not built")
         mode = "weighted"
@@ -739,7 +788,13 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     ``values = c[col]`` (:func:`edge_endpoints`) gives ``src_scale=c`` on ``adj``. ``row_scale`` stays available. The values are a
     kernel argument read on the device: a captured graph follows their contents. Another dtype is a TypeError; another length or
     device or a non-contiguous vector a ValueError; ``edge_weight`` with ``src_scale``, ``edge_drop``, a node mask, ``reduce`` other than
-    "sum" or ``attn`` a ValueError (not built: fold a source scale into the weights with :func:`edge_endpoints`)."""
+    "sum" or ``attn`` a ValueError (not built: fold a source scale into the weights with :func:`edge_endpoints`).
+
+    ``edge_weight`` may also be float32 [nnz, H], contiguous, with H dividing N: a weight per stored cell and HEAD, head h being the
+    columns h d .. (h + 1) d - 1 of X and of the result (d = N / H). Column c takes ``values[slot, c // d]``; the operations and their
+    order are the same, so every head is bit for bit the 1-D call on its contiguous slice, in one launch (include/qgtc_heads.h).
+    H is at least 2: [nnz, 1] stays the ValueError it was (pass the 1-D vector). Whatever is refused with a 1-D ``edge_weight`` is
+    refused with this one in the same words; an H that does not divide N is a ValueError."""
     mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop,
                                     row_mask, nbr_mask, edge_weight)
     if mode == "sum":
@@ -752,8 +807,23 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     if mode == "attention":
         out, m, inv = _tiled_attention(adj, X, attn[0], attn[1], slope, mask_kw)
         return (out, m, inv) if return_stats else out
+    if edge_weight.dim() == 2:
+        return _weighted_heads(adj, X, row_scale, edge_weight)
     val_ptr, val_row, _ = _value_index(adj)   # "weighted"
     return _call(adj, "_tiled_mm_f32", X, row_scale, edge_values=(val_ptr, val_row, edge_weight))
+
+
+def _weighted_heads(adj: TiledAdjacency, X: torch.Tensor, row_scale, values: torch.Tensor) -> torch.Tensor:
+    """The weighted sum with a value per stored cell and head, qgtc_tiledmm_f32_edge_heads / _t_edge_heads: one launch on the current
+    stream, column c weighted by ``values[slot, c // (N / H)]``."""
+    out = torch.empty_like(X)
+    L = _c_abi()
+    head, (vp, vr) = _view_ptrs(adj)
+    nnz = values.size(0)
+    _c_call("tiledMMFloat", X, L.qgtc_tiledmm_f32_t_edge_heads if adj.transposed else L.qgtc_tiledmm_f32_edge_heads, *head, X.data_ptr(),
+            X.numel(), X.size(1), None if row_scale is None else row_scale.data_ptr(), out.data_ptr(), out.numel(), vp, vr,
+            values.data_ptr() if nnz else None, nnz, values.size(1))
+    return out
 
 
 def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
@@ -783,7 +853,8 @@ class _TiledAggregate(torch.autograd.Function):
 
 class _TiledWeighted(torch.autograd.Function):
     """Y = diag(r) . (A o W) . X with W the edge values: dX = (A o W)^T . diag(r) . dY, the weighted product on the other view, and
-    dW[slot(i, j)] = DOT(r[i] dY[i], X[j]), one SDDMM - each launched only when its gradient is needed."""
+    dW[slot(i, j)] = DOT(r[i] dY[i], X[j]), one SDDMM - each launched only when its gradient is needed. With values [nnz, H] both
+    are the entries with heads: still one launch each."""
 
     @staticmethod
     def forward(ctx, adj, X, row_scale, values):
@@ -803,7 +874,7 @@ class _TiledWeighted(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 dX = tiledMMFloat(ctx.adj.T, dY, edge_weight=values)
             if ctx.needs_input_grad[3]:
-                dV = tiledSDDMM(ctx.adj, dY, X)
+                dV = tiledSDDMM(ctx.adj, dY, X, values.size(1) if values.dim() == 2 else 1)
         return None, dX, None, dV
 
 
@@ -915,7 +986,7 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
 
 
 def _check_edge_vector(adj: TiledAdjacency, values, name: str) -> int:
-    """The checks of ``edge_weight`` on a per-edge vector of another name; returns nnz."""
+    """The checks of ``edge_weight`` on a per-edge vector of another name ([nnz], or [nnz, H] with a value per head); returns nnz."""
     if not isinstance(values, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor (float32 [nnz], in slot order)")
     if values.dtype != torch.float32:
@@ -923,8 +994,8 @@ def _check_edge_vector(adj: TiledAdjacency, values, name: str) -> int:
     if values.device != adj.device:
         raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {values.device}")
     nnz = _value_index(adj)[2]
-    if values.dim() != 1 or values.numel() != nnz:
-        raise ValueError(f"{name} must have shape [{nnz}] (one value per stored cell), not {list(values.shape)}")
+    if not (values.dim() == 2 and values.size(0) == nnz and values.size(1) >= 2) and (values.dim() != 1 or values.numel() != nnz):
+        raise ValueError(f"{name} must have shape [{nnz}] (one value per stored cell) or [{nnz}, H] with H >= 2, not {list(values.shape)}")
     if not values.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return nnz
@@ -945,8 +1016,36 @@ def _esoftmax_view(adj: TiledAdjacency, grad: bool):
     return fn, ptrs + (T, adj.n, val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
 
 
+def _edge_softmax_heads(adj: TiledAdjacency, logits: torch.Tensor):
+    """(alpha [nnz, H], m [n, H], inv [n, H]) of qgtc_tiled_edge_softmax_heads_f32 / _t: one launch on the current stream."""
+    nnz, H = logits.shape
+    alpha = torch.empty_like(logits)
+    m = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    inv = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    L = _c_abi()
+    head, idx = _view_ptrs(adj)
+    _c_call("tiledEdgeSoftmax", m, L.qgtc_tiled_edge_softmax_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_heads_f32, *head,
+            *idx, logits.data_ptr() if nnz else None, alpha.data_ptr() if nnz else None, nnz, m.data_ptr(), inv.data_ptr(), H)
+    return alpha, m, inv
+
+
+def _edge_softmax_grad_heads(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """out[slot, h] = alpha . (g - S[owner, h]) of qgtc_tiled_edge_softmax_grad_heads_f32 / _t: one launch on the current stream."""
+    nnz, H = alpha.shape
+    out = torch.empty_like(alpha)
+    if nnz:
+        L = _c_abi()
+        head, idx = _view_ptrs(adj)
+        _c_call("the gradient of tiledEdgeSoftmax", alpha,
+                L.qgtc_tiled_edge_softmax_grad_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_grad_heads_f32, *head, *idx,
+                alpha.data_ptr(), g.data_ptr(), out.data_ptr(), nnz, H)
+    return out
+
+
 def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
     """(alpha, m, inv) of qgtc_tiled_edge_softmax_f32 / _t: one launch on the current stream."""
+    if logits.dim() == 2:
+        return _edge_softmax_heads(adj, logits)
     nnz = logits.numel()
     alpha = torch.empty(nnz, dtype=torch.float32, device=adj.device)
     m = torch.empty(adj.n, dtype=torch.float32, device=adj.device)
@@ -959,6 +1058,8 @@ def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
 
 def _edge_softmax_grad(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """out[slot] = alpha . (g - S[owner]) of qgtc_tiled_edge_softmax_grad_f32 / _t: one launch on the current stream."""
+    if alpha.dim() == 2:
+        return _edge_softmax_grad_heads(adj, alpha, g)
     nnz = alpha.numel()
     out = torch.empty(nnz, dtype=torch.float32, device=adj.device)
     if nnz:
@@ -997,7 +1098,11 @@ def tiledEdgeSoftmax(adj: TiledAdjacency, logits: torch.Tensor, return_stats: bo
     bits on every launch; one kernel, no atomics. A ``-inf`` logit masks its edge. With ``return_stats`` the result is ``(alpha, m,
     inv)``, float32 [n] each (+0 and 0 for a node without cells). Differentiable in ``logits`` (one launch on the same view, specified
     to the bit too; no second derivative). ``logits`` is float32 [nnz], contiguous, on the adjacency's device: a wrong dtype is a
-    TypeError, a wrong shape, device or stride a ValueError."""
+    TypeError, a wrong shape, device or stride a ValueError.
+
+    ``logits`` may also be float32 [nnz, H], contiguous: H independent softmaxes in one launch (include/qgtc_heads.h), ``alpha`` then
+    [nnz, H] and the statistics [n, H], every head bit for bit the 1-D call on ``logits[:, h]`` - a ``-inf`` masks its edge in its head
+    only. H is at least 2: [nnz, 1] stays the ValueError it was (pass the 1-D vector)."""
     _check(adj)
     _check_edge_vector(adj, logits, "logits")
     alpha, m, inv = _TiledEdgeSoftmax.apply(adj, logits)
@@ -1009,10 +1114,10 @@ class _TiledEdgeScores(torch.autograd.Function):
     gradient as the weights - each launched only when its gradient is needed."""
 
     @staticmethod
-    def forward(ctx, adj, A, B):
+    def forward(ctx, adj, A, B, heads):
         ctx.adj = adj
         ctx.save_for_backward(A, B)
-        return tiledSDDMM(adj, A, B)
+        return tiledSDDMM(adj, A, B, heads)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1025,31 +1130,44 @@ class _TiledEdgeScores(torch.autograd.Function):
                 dA = tiledMMFloat(ctx.adj, B, edge_weight=g)
             if ctx.needs_input_grad[2]:
                 dB = tiledMMFloat(ctx.adj.T, A, edge_weight=g)
-        return None, dA, dB
+        return None, dA, dB, None
 
 
-def tiledEdgeScores(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+def tiledEdgeScores(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int = 1) -> torch.Tensor:
     """:func:`tiledSDDMM` under ``torch.autograd``: float32 [nnz] in slot order, ``out[slot(i, j)] = DOT(A[i], B[j])`` for the cells
     (i, j) of this view, differentiable in A and B. With g the incoming gradient, ``dA = tiledMMFloat(adj, B, edge_weight=g)`` and
     ``dB = tiledMMFloat(adj.T, A, edge_weight=g)``: one launch each, only when needed, both specified to the bit; no second
-    derivative."""
+    derivative. With ``heads=H`` > 1 the scores are [nnz, H] as in :func:`tiledSDDMM` and g is too: the same two launches, with a
+    weight per cell and head."""
     _check(adj)
     _check_float_operand(adj, A)
-    return _TiledEdgeScores.apply(adj, A, B)
+    heads = _check_heads(heads, A.size(1))
+    return _TiledEdgeScores.apply(adj, A, B, heads)
 
 
-def tiledEdgeAttention(adj: TiledAdjacency, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, scale: float | None = None) -> torch.Tensor:
+def tiledEdgeAttention(adj: TiledAdjacency, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, scale: float | None = None,
+                       heads: int = 1) -> torch.Tensor:
     """Dot-product attention over the graph's edges, float32 [n, N]: row i of the view receives
     ``sum over its neighbours j of softmax_j(scale * DOT(Q[i], K[j])) * V[j]`` - the composition
     ``tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, tiledEdgeScores(adj, Q, K) * scale))``: an SDDMM, one float32 torch
     multiply per slot, the edge softmax and the weighted sum. ``scale`` defaults to ``1 / sqrt(Q.size(1))``. Differentiable in Q, K and
     V; every launch of the forward and the backward is specified to the bit and none uses atomics. Q and K are float32 [n, d], V is
     float32 [n, N], in the adjacency's numbering; the rows of the view are the receiving nodes (``adj.T``: a node attends over its
-    in-neighbours)."""
+    in-neighbours).
+
+    With ``heads=H`` > 1 it is multi-head attention without a loop over the heads: head h is the columns h d .. (h + 1) d - 1 of Q and
+    K (d = Q.size(1) / H) and the columns h dv .. of V and of the result (dv = N / H), ``scale`` defaults to ``1 / sqrt(d)``, and the
+    same three launches carry all heads with [nnz, H] edge vectors in between (include/qgtc_heads.h); the backward is five launches
+    instead of five per head. Output and gradients are bit for bit those of the single-head call on every head's contiguous slices. H
+    must divide the widths of Q and of V: otherwise a ValueError."""
     _check(adj)
     _check_float_operand(adj, Q)
-    scale = 1.0 / math.sqrt(Q.size(1)) if scale is None else float(scale)
-    logits = tiledEdgeScores(adj, Q, K) * scale
+    heads = _check_heads(heads, Q.size(1))
+    if heads > 1:
+        _check_float_operand(adj, V)
+        _check_heads(heads, V.size(1))
+    scale = 1.0 / math.sqrt(Q.size(1) // heads) if scale is None else float(scale)
+    logits = tiledEdgeScores(adj, Q, K, heads) * scale
     return tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, logits))
 
 

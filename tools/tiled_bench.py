@@ -78,7 +78,14 @@ all three gradients against the edge-list route (index_select, a row dot, scatte
 autograd backward, which is not bit-reproducible). The attention is checked against the edge-list route before timing. Medians with
 their 10th and 90th percentiles.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax]
+`--leg heads` measures multi-head attention in one call (tiled.tiledEdgeAttention(heads=H)) against the loop over the
+heads it replaces - per head three `.contiguous()` column slices and the single-head call, concatenated -, on the reordered graphs
+(arxiv and reddit unless --graphs says otherwise), both directions, (H, d) in {(8, 8), (4, 16), (8, 32), (4, 64)} for Q, K and V alike.
+One alternating loop of four: forward and forward plus all three gradients, each way. Output and gradients of the two routes are
+checked bit for bit before timing. Medians with their 10th and 90th percentiles; `within_spread` says whether the one-call median is at
+most the loop's median plus the loop's own 10th-to-90th-percentile spread.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads]
 """
 from __future__ import annotations
 
@@ -767,12 +774,73 @@ def esoftmax_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+HEADS_SHAPES = ((8, 8), (4, 16), (8, 32), (4, 64))   # (heads, columns per head)
+
+
+def heads_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    def bits(x):
+        return x.contiguous().view(torch.int32)
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        nnz = int(tiled.edge_endpoints(adj)[0].numel())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": nnz, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {nnz}", flush=True)
+        xr = np.random.default_rng(1)
+        for H, d in HEADS_SHAPES:
+            Q, K, V, dY = (torch.from_numpy(xr.standard_normal((n, H * d)).astype(np.float32)).cuda() for _ in range(4))
+            Qg, Kg, Vg = (x.clone().requires_grad_(True) for x in (Q, K, V))
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                def loop(Ql, Kl, Vl):   # the layer's forward before the heads shared a call
+                    outs = []
+                    for h in range(H):
+                        c = slice(h * d, (h + 1) * d)
+                        outs.append(tiled.tiledEdgeAttention(a, Ql[:, c].contiguous(), Kl[:, c].contiguous(), Vl[:, c].contiguous()))
+                    return torch.cat(outs, dim=1)
+
+                def one_both():
+                    return torch.autograd.grad(tiled.tiledEdgeAttention(a, Qg, Kg, Vg, heads=H), (Qg, Kg, Vg), dY)
+
+                def loop_both():
+                    return torch.autograd.grad(loop(Qg, Kg, Vg), (Qg, Kg, Vg), dY)
+
+                assert torch.equal(bits(tiled.tiledEdgeAttention(a, Q, K, V, heads=H)), bits(loop(Q, K, V))), (H, d, direction)
+                for x, y in zip(one_both(), loop_both()):
+                    assert torch.equal(bits(x), bits(y)), (H, d, direction)
+                tof, tlf, tob, tlb = timed_alternating(torch, [lambda: tiled.tiledEdgeAttention(a, Q, K, V, heads=H), lambda: loop(Q, K, V),
+                                                               one_both, loop_both], reps)
+                ok_f, ok_b = tof[0] <= tlf[0] + (tlf[2] - tlf[1]), tob[0] <= tlb[0] + (tlb[2] - tlb[1])
+                rec["agg"].append({"heads": H, "d": d, "direction": direction, "one_call_forward_ms": tof, "loop_forward_ms": tlf,
+                                   "one_call_forward_backward_ms": tob, "loop_forward_backward_ms": tlb,
+                                   "loop_over_one_call_forward": round(tlf[0] / tof[0], 3),
+                                   "loop_over_one_call_forward_backward": round(tlb[0] / tob[0], 3),
+                                   "forward_within_spread": bool(ok_f), "forward_backward_within_spread": bool(ok_b)})
+                print(f"{name:9s} H={H} d={d:<3d} {direction:10s} forward: one call {tof[0]:8.4f} [{tof[1]:.4f}, {tof[2]:.4f}]  loop "
+                      f"{tlf[0]:8.4f} [{tlf[1]:.4f}, {tlf[2]:.4f}] ({tlf[0] / tof[0]:.2f}x)  forward + backward: one call {tob[0]:8.4f} "
+                      f"[{tob[1]:.4f}, {tob[2]:.4f}]  loop {tlb[0]:8.4f} [{tlb[1]:.4f}, {tlb[2]:.4f}] ({tlb[0] / tob[0]:.2f}x)"
+                      f"{'' if ok_f and ok_b else '  SLOWER THAN THE LOOP'}", flush=True)
+            del Q, K, V, dY, Qg, Kg, Vg
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads"))
     args = ap.parse_args()
 
     import torch
@@ -780,9 +848,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
