@@ -21,6 +21,9 @@ int qgtc_tiledmm_f32_t_edge_heads(const int64_t *col_ptr, const int64_t *col_til
                                   int64_t n_tiles, int n, const float *X, size_t x_elems, int N, const float *row_scale, float *out,
                                   size_t out_elems, const int64_t *val_ptr, const int16_t *val_row, const float *values,
                                   size_t n_values, int heads, void *stream) {
+    if (heads == 1)   // the single-head kernel (qgtc_tiled_float_t_edge.hip), with the same refusals
+        return qgtc_tiledmm_f32_t_edge(col_ptr, col_tile, col_rb, tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems, val_ptr,
+                                       val_row, values, n_values, stream);
     return tiled_mm_f32_heads_entry(TiledColIndex{col_ptr, col_tile, col_rb}, tiles, n_tiles, n, X, x_elems, N, row_scale, out, out_elems,
                                     val_ptr, val_row, values, n_values, heads, stream);
 }

@@ -31,7 +31,7 @@
 #include <utility>
 #include <vector>
 
-#include "qgtc.h"
+#include "qgtc_heads.h"
 
 namespace {
 
@@ -700,8 +700,9 @@ const float *tiled_src_scale(const c10::optional<torch::Tensor> &src_scale, cons
 }
 
 // Edge values (include/qgtc.h, "Edge values"): the optional keyword `edge_values` = (val_ptr, val_row, values) of the two sum overloads
-// sends the call to the entry's _edge twin; None, the default, is the call there always was. The three tensors are checked here:
-// val_ptr int64 [T + 1], val_row int16 [T, 32], values float32 [nnz], contiguous, on X's device.
+// sends the call to the entry's _edge_heads twin (include/qgtc_heads.h); None, the default, is the call there always was. The three
+// tensors are checked here: val_ptr int64 [T + 1], val_row int16 [T, 32], values float32 [nnz] (one head) or [nnz, H], contiguous, on
+// X's device.
 using EdgeValues = std::optional<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>;
 
 struct TiledEdgeView {
@@ -709,6 +710,7 @@ struct TiledEdgeView {
     const int16_t *val_row;
     const float *values;
     size_t n_values;
+    int heads;
 };
 TiledEdgeView tiled_edge_view(const EdgeValues &edge_values, const int64_t T, const torch::Tensor &X, const EdgeDrop &edge_drop,
                               const NodeMasks &node_masks) {
@@ -718,12 +720,14 @@ TiledEdgeView tiled_edge_view(const EdgeValues &edge_values, const int64_t T, co
                 "val_ptr must be a contiguous int64 tensor of T + 1 elements");
     TORCH_CHECK(vr.scalar_type() == torch::kInt16 && vr.numel() == T * 32 && vr.is_contiguous(),
                 "val_row must be a contiguous int16 tensor of [T, 32]");
-    TORCH_CHECK(vals.scalar_type() == torch::kFloat32 && vals.dim() == 1 && vals.is_contiguous(),
-                "the edge values must be a contiguous float32 vector");
+    TORCH_CHECK(vals.scalar_type() == torch::kFloat32 && (vals.dim() == 1 || vals.dim() == 2) && vals.is_contiguous(),
+                "the edge values must be a contiguous float32 vector, or [nnz, H] with a value per head");
+    const int64_t heads = vals.dim() == 2 ? vals.size(1) : 1;
+    TORCH_CHECK(heads >= 1 && heads <= INT32_MAX, "the edge values need at least one head");
     TORCH_CHECK(vp.device() == X.device() && vr.device() == X.device() && vals.device() == X.device(),
                 "the edge values and their index must be on the adjacency's device");
     return {vp.data_ptr<int64_t>(), T ? vr.data_ptr<int16_t>() : nullptr, vals.numel() ? vals.data_ptr<float>() : nullptr,
-            static_cast<size_t>(vals.numel())};
+            static_cast<size_t>(vals.size(0)), static_cast<int>(heads)};
 }
 
 // The sum on a view: plain, with a source scale, under a mask, or with edge values (which take no source scale and no mask)
@@ -741,8 +745,8 @@ torch::Tensor tiled_sum_on(const TiledView &v, const int64_t n, const torch::Ten
     if (edge_values) {
         const TiledEdgeView ev = tiled_edge_view(edge_values, v.T, X, edge_drop, node_masks);
         auto out = torch::empty({n, X.size(1)}, f32);
-        check_tiled_rc(on_view(v, qgtc_tiledmm_f32_edge, qgtc_tiledmm_f32_t_edge, nn, x, xn, N, sc, out.data_ptr<float>(),
-                               static_cast<size_t>(out.numel()), ev.val_ptr, ev.val_row, ev.values, ev.n_values, st),
+        check_tiled_rc(on_view(v, qgtc_tiledmm_f32_edge_heads, qgtc_tiledmm_f32_t_edge_heads, nn, x, xn, N, sc, out.data_ptr<float>(),
+                               static_cast<size_t>(out.numel()), ev.val_ptr, ev.val_row, ev.values, ev.n_values, ev.heads, st),
                        "tiledMMFloat", v, "edge values");
         return out;
     }

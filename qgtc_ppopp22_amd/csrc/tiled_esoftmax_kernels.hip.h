@@ -1,8 +1,9 @@
 // tiled_esoftmax_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_esoftmax.hip and qgtc_tiled_esoftmax_t.hip, after
-// tiled_float_kernels.hip.h, tiled_max_kernels.hip.h and tiled_attn_kernels.hip.h; the column view's unit defines
-// QGTC_TILED_ESOFTMAX_T and includes tiled_t_kernels.hip.h first): the softmax of a vector of per-edge logits over each node's
-// neighbourhood on the tile-compressed adjacency, and its gradient (include/qgtc.h, "Edge softmax"). Logits,
-// weights and gradients are float32 [n_values] in SLOT order (tiled_edge.hip.h), one array for both views.
+// tiled_float_kernels.hip.h, tiled_max_kernels.hip.h and tiled_attn_kernels.hip.h and before tiled_heads_esoftmax_kernels.hip.h,
+// which has the kernels for H heads and the host side of both; the column view's unit defines QGTC_TILED_ESOFTMAX_T and includes
+// tiled_t_kernels.hip.h first): the softmax of a vector of per-edge logits over each node's neighbourhood on the tile-compressed
+// adjacency, and its gradient (include/qgtc.h, "Edge softmax"). Logits, weights and gradients are float32
+// [n_values] in SLOT order (tiled_edge.hip.h), one array for both views.
 //
 // A lane owns one node - a row on the row view, a column on the column view - and visits that node's cells in ascending id of the other
 // end, so every fold is the in-order one of the contract and no lane reads what another produced:
@@ -329,29 +330,5 @@ __global__ __launch_bounds__(128) void k_tiled_esoftmax_grad_t(const int64_t *__
     tiled_esm_col_walk(col_tile, col_rb, tiles, n_tiles, n, val_ptr, val_row, w.b0, w.t1, w.j, w.live, n_values, lds, TiledEsmOutPass{st});
 }
 #endif
-
-// ---- the argument checks, made before any device work, and what the entries do without tiles or values ------------------------------------
-// invalid before misaligned; `index_ok` as in tiled_adj_malformed. vec: the float arrays of n_values elements (wanted when there are
-// values); m / inv are optional.
-template <size_t K>
-inline int tiled_esm_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row,
-                             size_t n_values, const float *const (&vec)[K], const float *m, const float *inv) {
-    int rc = QGTC_OK;
-    bool missing = false, off = false;
-    for (const float *v : vec) {
-        missing = missing || (n_values && !v);
-        off = off || !aligned4(v);
-    }
-    if (missing || tiled_adj_malformed(index_ok, tiles, n_tiles, n)) rc = QGTC_EINVAL;
-    else if (tiled_adj_misaligned(tiles) || off || !aligned4(m) || !aligned4(inv)) rc = QGTC_EALIGN;
-    return tiled_edge_rc(rc, tiled_edge_index_ok(val_ptr, val_row, n_tiles, n_values));
-}
-
-// m = +0 and inv = 0 for every node: an adjacency without tiles (or values) has no owner with cells
-inline int tiled_esm_no_cells(int n, float *m, float *inv, hipStream_t st) {
-    if (m) HIP_TRY(hipMemsetAsync(m, 0, static_cast<size_t>(n) * sizeof(float), st));
-    if (inv) HIP_TRY(hipMemsetAsync(inv, 0, static_cast<size_t>(n) * sizeof(float), st));
-    return QGTC_OK;
-}
 
 }  // namespace

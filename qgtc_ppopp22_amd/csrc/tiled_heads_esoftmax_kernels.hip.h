@@ -1,7 +1,8 @@
-// tiled_heads_esoftmax_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_esoftmax_heads.hip and
-// qgtc_tiled_esoftmax_heads_t.hip, after tiled_esoftmax_kernels.hip.h, whose walks and float helpers it uses as they are): the edge
-// softmax and its gradient for H heads in one launch (include/qgtc_heads.h). Logits, weights and gradients
-// are float32 [n_values, H], head-minor; the statistics are [n, H].
+// tiled_heads_esoftmax_kernels.hip.h — part of libqgtc_hip.so (included by qgtc_tiled_esoftmax.hip and qgtc_tiled_esoftmax_t.hip,
+// after tiled_esoftmax_kernels.hip.h, whose walks and float helpers it uses as they are): the edge softmax and its gradient for H
+// heads in one launch (include/qgtc_heads.h), and the host side of the softmax for any number of heads -
+// the argument checks and one entry body per operation, which sends one head to the single-head kernels. Logits, weights and
+// gradients are float32 [n_values, H], head-minor; the statistics are [n, H].
 //
 // A lane owns one node AND HC heads h0 .. h0 + HC - 1 of it, h0 = blockIdx.y * HC: the walks of the single-head kernels visit the
 // node's cells in the same order, and a pass reads the cell's HC adjacent values and keeps HC independent statistics, each folded by
@@ -212,16 +213,33 @@ __global__ __launch_bounds__(128) void k_tiled_esoftmax_grad_heads_t(const int64
 }
 #endif
 
-// ---- the host side both views share -------------------------------------------------------------------------------------------------
+// ---- the host side: one entry body per operation for both views and any number of heads -------------------------------------------------
 constexpr int TILED_ESM_HEADS_MAX = 65535;   // the heads ride the grid's y dimension (H / HC rows of it)
 
-// tiled_esm_args_ok with heads: QGTC_EINVAL for heads outside 1 .. TILED_ESM_HEADS_MAX before every other refusal's kind is weighed
+// the argument checks, made before any device work: invalid before misaligned; `index_ok` as in tiled_adj_malformed. vec: the float
+// arrays of n_values * heads elements (wanted when there are values); m / inv are optional. heads outside 1 .. TILED_ESM_HEADS_MAX is
+// QGTC_EINVAL before every other refusal's kind is weighed
 template <size_t K>
-inline int tiled_esm_heads_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const int64_t *val_ptr,
-                                   const int16_t *val_row, size_t n_values, const float *const (&vec)[K], const float *m, const float *inv,
-                                   int heads) {
-    const int rc = tiled_esm_args_ok(index_ok, tiles, n_tiles, n, val_ptr, val_row, n_values, vec, m, inv);
+inline int tiled_esm_args_ok(bool index_ok, const uint32_t *tiles, int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row,
+                             size_t n_values, const float *const (&vec)[K], const float *m, const float *inv, int heads) {
+    int rc = QGTC_OK;
+    bool missing = false, off = false;
+    for (const float *v : vec) {
+        missing = missing || (n_values && !v);
+        off = off || !aligned4(v);
+    }
+    if (missing || tiled_adj_malformed(index_ok, tiles, n_tiles, n)) rc = QGTC_EINVAL;
+    else if (tiled_adj_misaligned(tiles) || off || !aligned4(m) || !aligned4(inv)) rc = QGTC_EALIGN;
+    rc = tiled_edge_rc(rc, tiled_edge_index_ok(val_ptr, val_row, n_tiles, n_values));
     return heads < 1 || heads > TILED_ESM_HEADS_MAX ? QGTC_EINVAL : rc;
+}
+
+// m = +0 and inv = 0 for every (node, head): an adjacency without tiles (or values) has no owner with cells
+inline int tiled_esm_no_cells(int n, int H, float *m, float *inv, hipStream_t st) {
+    const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(H) * sizeof(float);
+    if (m) HIP_TRY(hipMemsetAsync(m, 0, bytes, st));
+    if (inv) HIP_TRY(hipMemsetAsync(inv, 0, bytes, st));
+    return QGTC_OK;
 }
 
 // launch(HC as an integral constant, grid y): the largest of 4, 2, 1 heads a lane that divides H
@@ -232,11 +250,86 @@ void tiled_esm_heads_switch(int H, F &&launch) {
     else launch(tiled_int<1>{}, H);
 }
 
-// m = +0 and inv = 0 for every (node, head): an adjacency without tiles (or values) has no owner with cells
-inline int tiled_esm_heads_no_cells(int n, int H, float *m, float *inv, hipStream_t st) {
-    const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(H) * sizeof(float);
-    if (m) HIP_TRY(hipMemsetAsync(m, 0, bytes, st));
-    if (inv) HIP_TRY(hipMemsetAsync(inv, 0, bytes, st));
+// the launches of this unit's view: one head is the single-head kernel, H heads the kernel of HC heads a lane over H / HC grid rows
+#ifndef QGTC_TILED_ESOFTMAX_T
+inline void tiled_esm_launch(const TiledRowIndex &ix, const uint32_t *tiles, uint64_t nt, int n, const int64_t *val_ptr, const int16_t *val_row,
+                             const float *logits, float *alpha, int nv, float *m, float *inv, int H, hipStream_t st) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (H > 1) {
+        tiled_esm_heads_switch(H, [&](auto hc, int gy) {
+            hipLaunchKernelGGL((k_tiled_esoftmax_heads<decltype(hc)::value>), dim3(grid.x, gy), block, 0, st, ix.row_ptr, ix.kquad, tiles, nt, n,
+                               val_ptr, val_row, logits, alpha, nv, m, inv, H);
+        });
+        return;
+    }
+    hipLaunchKernelGGL(k_tiled_esoftmax, grid, block, 0, st, ix.row_ptr, ix.kquad, tiles, nt, n, val_ptr, val_row, logits, alpha, nv, m, inv);
+}
+inline void tiled_esm_grad_launch(const TiledRowIndex &ix, const uint32_t *tiles, uint64_t nt, int n, const int64_t *val_ptr,
+                                  const int16_t *val_row, const float *alpha, const float *g, float *out, int nv, int H, hipStream_t st) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (H > 1) {
+        tiled_esm_heads_switch(H, [&](auto hc, int gy) {
+            hipLaunchKernelGGL((k_tiled_esoftmax_grad_heads<decltype(hc)::value>), dim3(grid.x, gy), block, 0, st, ix.row_ptr, ix.kquad, tiles, nt,
+                               n, val_ptr, val_row, alpha, g, out, nv, H);
+        });
+        return;
+    }
+    hipLaunchKernelGGL(k_tiled_esoftmax_grad, grid, block, 0, st, ix.row_ptr, ix.kquad, tiles, nt, n, val_ptr, val_row, alpha, g, out, nv);
+}
+#else
+inline void tiled_esm_launch(const TiledColIndex &ix, const uint32_t *tiles, uint64_t nt, int n, const int64_t *val_ptr, const int16_t *val_row,
+                             const float *logits, float *alpha, int nv, float *m, float *inv, int H, hipStream_t st) {
+    const dim3 grid(step128(n)), block(128);
+    if (H > 1) {
+        tiled_esm_heads_switch(H, [&](auto hc, int gy) {
+            hipLaunchKernelGGL((k_tiled_esoftmax_heads_t<decltype(hc)::value>), dim3(grid.x, gy), block, 0, st, ix.col_ptr, ix.col_tile, ix.col_rb,
+                               tiles, nt, n, val_ptr, val_row, logits, alpha, nv, m, inv, H);
+        });
+        return;
+    }
+    hipLaunchKernelGGL(k_tiled_esoftmax_t, grid, block, 0, st, ix.col_ptr, ix.col_tile, ix.col_rb, tiles, nt, n, val_ptr, val_row, logits,
+                       alpha, nv, m, inv);
+}
+inline void tiled_esm_grad_launch(const TiledColIndex &ix, const uint32_t *tiles, uint64_t nt, int n, const int64_t *val_ptr,
+                                  const int16_t *val_row, const float *alpha, const float *g, float *out, int nv, int H, hipStream_t st) {
+    const dim3 grid(step128(n)), block(128);
+    if (H > 1) {
+        tiled_esm_heads_switch(H, [&](auto hc, int gy) {
+            hipLaunchKernelGGL((k_tiled_esoftmax_grad_heads_t<decltype(hc)::value>), dim3(grid.x, gy), block, 0, st, ix.col_ptr, ix.col_tile,
+                               ix.col_rb, tiles, nt, n, val_ptr, val_row, alpha, g, out, nv, H);
+        });
+        return;
+    }
+    hipLaunchKernelGGL(k_tiled_esoftmax_grad_t, grid, block, 0, st, ix.col_ptr, ix.col_tile, ix.col_rb, tiles, nt, n, val_ptr, val_row,
+                       alpha, g, out, nv);
+}
+#endif
+
+// the forward's entry on either view: the refusals, the adjacency without cells, the launch
+template <class Index>
+int tiled_esm_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row,
+                    const float *logits, float *alpha, size_t n_values, float *m, float *inv, int heads, void *stream) {
+    const float *const vec[] = {logits, alpha};
+    const int rc = tiled_esm_args_ok(ix.ok(), tiles, n_tiles, n, val_ptr, val_row, n_values, vec, m, inv, heads);
+    if (rc != QGTC_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!n_tiles || !n_values) return tiled_esm_no_cells(n, heads, m, inv, st);
+    tiled_esm_launch(ix, tiles, static_cast<uint64_t>(n_tiles), n, val_ptr, val_row, logits, alpha, static_cast<int>(n_values), m, inv, heads, st);
+    HIP_TRY(hipGetLastError());
+    return QGTC_OK;
+}
+
+// the gradient's
+template <class Index>
+int tiled_esm_grad_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const int64_t *val_ptr, const int16_t *val_row,
+                         const float *alpha, const float *g, float *out, size_t n_values, int heads, void *stream) {
+    const float *const vec[] = {alpha, g, out};
+    const int rc = tiled_esm_args_ok(ix.ok(), tiles, n_tiles, n, val_ptr, val_row, n_values, vec, nullptr, nullptr, heads);
+    if (rc != QGTC_OK) return rc;
+    if (!n_tiles || !n_values) return QGTC_OK;
+    tiled_esm_grad_launch(ix, tiles, static_cast<uint64_t>(n_tiles), n, val_ptr, val_row, alpha, g, out, static_cast<int>(n_values), heads,
+                          static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
 

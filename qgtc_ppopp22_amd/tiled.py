@@ -497,28 +497,35 @@ def _value_index(adj: TiledAdjacency):
     return base._val_index
 
 
+def _check_edge_vector(adj: TiledAdjacency, values, name: str, X=None) -> None:
+    """The checks of a per-edge vector, ``edge_weight`` or one of another name: float32 [nnz] in slot order, or [nnz, H] with a value
+    per stored cell and head (H at least 2 and, for ``edge_weight``, a divisor of the columns of ``X``)."""
+    weight = name == "edge_weight"
+    if not isinstance(values, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor (float32 [nnz], " + ("tiled.edge_values) or None" if weight else "in slot order)"))
+    if values.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, not {values.dtype}")
+    if values.device != adj.device:
+        raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {values.device}")
+    nnz = _value_index(adj)[2]
+    if values.dim() == 2 and values.size(0) == nnz and values.size(1) >= 2:   # [nnz, H]: a value per stored cell and head
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.size(1) % values.size(1) != 0:
+            raise ValueError(f"{name} has {values.size(1)} heads, which do not divide X's {X.size(1)} columns")
+    elif values.dim() != 1 or values.numel() != nnz:
+        raise ValueError(f"{name} must have shape [{nnz}] (one value per stored cell)" + ("" if weight else f" or [{nnz}, H] with H >= 2") +
+                         f", not {list(values.shape)}")
+    if not values.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
 def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, nodes_kw=None, reduce: str = "sum", attn=None,
                        X=None) -> None:
-    """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself - float32 [nnz], or [nnz, H] with
-    H dividing the columns of ``X`` (one value per stored cell and head)."""
+    """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself."""
     for name, on in (("src_scale", src_scale is not None), ("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)),
                      (f'reduce="{reduce}"', reduce != "sum"), ("attn", attn is not None)):
         if on:
             raise ValueError(f"edge_weight cannot be combined with {name}: not built")
-    if not isinstance(values, torch.Tensor):
-        raise TypeError("edge_weight must be a torch.Tensor (float32 [nnz], tiled.edge_values) or None")
-    if values.dtype != torch.float32:
-        raise TypeError(f"edge_weight must be float32, not {values.dtype}")
-    if values.device != adj.device:
-        raise ValueError(f"edge_weight must be on the adjacency's device {adj.device}, not {values.device}")
-    nnz = _value_index(adj)[2]
-    if values.dim() == 2 and values.size(0) == nnz and values.size(1) >= 2:   # [nnz, H]: a value per stored cell and head
-        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.size(1) % values.size(1) != 0:
-            raise ValueError(f"edge_weight has {values.size(1)} heads, which do not divide X's {X.size(1)} columns")
-    elif values.dim() != 1 or values.numel() != nnz:
-        raise ValueError(f"edge_weight must have shape [{nnz}] (one value per stored cell), not {list(values.shape)}")
-    if not values.is_contiguous():
-        raise ValueError("edge_weight must be contiguous")
+    _check_edge_vector(adj, values, "edge_weight", X)
 
 
 def _base(adj: TiledAdjacency) -> TiledAdjacency:
@@ -612,8 +619,8 @@ def _check_heads(heads, width: int) -> int:
 
 
 def _view_ptrs(adj: TiledAdjacency):
-    """What every multi-head entry takes first (include/qgtc_heads.h): the view's index pointers and tiles, then n_tiles and n - and
-    the pointers of the value index, which come later in the argument lists."""
+    """What every entry of include/qgtc_heads.h takes first: the view's index pointers and tiles, then n_tiles and n - and the pointers
+    of the value index, which come later in the argument lists. The one place that turns a view into pointer arguments."""
     base = _base(adj)
     val_ptr, val_row, _ = _value_index(base)
     T = base.n_tiles
@@ -621,14 +628,14 @@ def _view_ptrs(adj: TiledAdjacency):
     return tuple(t.data_ptr() if T else None for t in view) + (T, adj.n), (val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
 
 
-def _sddmm_heads(base: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
+def _sddmm(base: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
     """float32 [nnz, heads] of qgtc_tiled_sddmm_heads_f32 on the untransposed adjacency (the caller has swapped the operands of the
-    other view): one launch on the current stream."""
-    val_ptr, val_row, nnz = _value_index(base)
+    other view): one launch on the current stream; one head is the single-head kernel."""
+    nnz = _value_index(base)[2]
     out = torch.empty((nnz, heads), dtype=torch.float32, device=base.device)
     if nnz:
-        _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_heads_f32, base.row_ptr.data_ptr(), base.kquad.data_ptr(), base.tiles.data_ptr(),
-                base.n_tiles, base.n, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), val_ptr.data_ptr(), val_row.data_ptr(),
+        head, idx = _view_ptrs(base)
+        _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_heads_f32, *head, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), *idx,
                 out.data_ptr(), nnz, heads)
     return out
 
@@ -653,16 +660,8 @@ def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int
         raise ValueError(f"B must be contiguous, on A's device and of A's shape {list(A.shape)}, not {list(B.shape)}")
     if adj.transposed:
         A, B = B, A
-    base = _base(adj)
-    val_ptr, val_row, nnz = _value_index(base)
-    if heads > 1:
-        return _sddmm_heads(base, A, B, heads)
-    out = torch.empty(nnz, dtype=torch.float32, device=base.device)
-    if nnz:
-        _c_call("tiledSDDMM", A, _c_abi().qgtc_tiled_sddmm_f32, base.row_ptr.data_ptr(), base.kquad.data_ptr(), base.tiles.data_ptr(),
-                base.n_tiles, base.n, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), val_ptr.data_ptr(), val_row.data_ptr(), out.data_ptr(),
-                nnz)
-    return out
+    out = _sddmm(_base(adj), A, B, heads)
+    return out if heads > 1 else out.view(-1)
 
 
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
@@ -807,23 +806,14 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     if mode == "attention":
         out, m, inv = _tiled_attention(adj, X, attn[0], attn[1], slope, mask_kw)
         return (out, m, inv) if return_stats else out
-    if edge_weight.dim() == 2:
-        return _weighted_heads(adj, X, row_scale, edge_weight)
-    val_ptr, val_row, _ = _value_index(adj)   # "weighted"
-    return _call(adj, "_tiled_mm_f32", X, row_scale, edge_values=(val_ptr, val_row, edge_weight))
+    return _weighted(adj, X, row_scale, edge_weight)
 
 
-def _weighted_heads(adj: TiledAdjacency, X: torch.Tensor, row_scale, values: torch.Tensor) -> torch.Tensor:
-    """The weighted sum with a value per stored cell and head, qgtc_tiledmm_f32_edge_heads / _t_edge_heads: one launch on the current
-    stream, column c weighted by ``values[slot, c // (N / H)]``."""
-    out = torch.empty_like(X)
-    L = _c_abi()
-    head, (vp, vr) = _view_ptrs(adj)
-    nnz = values.size(0)
-    _c_call("tiledMMFloat", X, L.qgtc_tiledmm_f32_t_edge_heads if adj.transposed else L.qgtc_tiledmm_f32_edge_heads, *head, X.data_ptr(),
-            X.numel(), X.size(1), None if row_scale is None else row_scale.data_ptr(), out.data_ptr(), out.numel(), vp, vr,
-            values.data_ptr() if nnz else None, nnz, values.size(1))
-    return out
+def _weighted(adj: TiledAdjacency, X: torch.Tensor, row_scale, values: torch.Tensor) -> torch.Tensor:
+    """The weighted sum, qgtc_tiledmm_f32_edge_heads / _t_edge_heads through the binding's ``edge_values`` keyword: one launch on the
+    current stream. ``values`` [nnz] is one head; [nnz, H] weighs column c by ``values[slot, c // (N / H)]``."""
+    val_ptr, val_row, _ = _value_index(adj)
+    return _call(adj, "_tiled_mm_f32", X, row_scale, edge_values=(val_ptr, val_row, values))
 
 
 def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
@@ -985,43 +975,13 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask)
 
 
-def _check_edge_vector(adj: TiledAdjacency, values, name: str) -> int:
-    """The checks of ``edge_weight`` on a per-edge vector of another name ([nnz], or [nnz, H] with a value per head); returns nnz."""
-    if not isinstance(values, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor (float32 [nnz], in slot order)")
-    if values.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, not {values.dtype}")
-    if values.device != adj.device:
-        raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {values.device}")
-    nnz = _value_index(adj)[2]
-    if not (values.dim() == 2 and values.size(0) == nnz and values.size(1) >= 2) and (values.dim() != 1 or values.numel() != nnz):
-        raise ValueError(f"{name} must have shape [{nnz}] (one value per stored cell) or [{nnz}, H] with H >= 2, not {list(values.shape)}")
-    if not values.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return nnz
-
-
-def _esoftmax_view(adj: TiledAdjacency, grad: bool):
-    """(entry, the view's index pointers and tiles, n_tiles, n, val_ptr, val_row) of the edge softmax or its gradient on this view."""
-    base, L = _base(adj), _c_abi()
-    val_ptr, val_row, _ = _value_index(base)
-    T = base.n_tiles
-    if adj.transposed:
-        fn = L.qgtc_tiled_edge_softmax_grad_f32_t if grad else L.qgtc_tiled_edge_softmax_f32_t
-        view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles)
-    else:
-        fn = L.qgtc_tiled_edge_softmax_grad_f32 if grad else L.qgtc_tiled_edge_softmax_f32
-        view = (adj.row_ptr, adj.kquad, adj.tiles)
-    ptrs = tuple(t.data_ptr() if T else None for t in view)
-    return fn, ptrs + (T, adj.n, val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
-
-
-def _edge_softmax_heads(adj: TiledAdjacency, logits: torch.Tensor):
-    """(alpha [nnz, H], m [n, H], inv [n, H]) of qgtc_tiled_edge_softmax_heads_f32 / _t: one launch on the current stream."""
-    nnz, H = logits.shape
+def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
+    """(alpha, m, inv) of qgtc_tiled_edge_softmax_heads_f32 / _t, one launch on the current stream: ``logits`` [nnz] is one head with
+    statistics [n]; [nnz, H] gives alpha [nnz, H] and statistics [n, H]."""
+    nnz, H = logits.size(0), logits.size(1) if logits.dim() == 2 else 1
     alpha = torch.empty_like(logits)
-    m = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
-    inv = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    m = torch.empty((adj.n, H) if logits.dim() == 2 else adj.n, dtype=torch.float32, device=adj.device)
+    inv = torch.empty_like(m)
     L = _c_abi()
     head, idx = _view_ptrs(adj)
     _c_call("tiledEdgeSoftmax", m, L.qgtc_tiled_edge_softmax_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_heads_f32, *head,
@@ -1029,9 +989,10 @@ def _edge_softmax_heads(adj: TiledAdjacency, logits: torch.Tensor):
     return alpha, m, inv
 
 
-def _edge_softmax_grad_heads(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    """out[slot, h] = alpha . (g - S[owner, h]) of qgtc_tiled_edge_softmax_grad_heads_f32 / _t: one launch on the current stream."""
-    nnz, H = alpha.shape
+def _edge_softmax_grad(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """out[slot] = alpha . (g - S[owner]) of qgtc_tiled_edge_softmax_grad_heads_f32 / _t, per head for [nnz, H] vectors: one launch on
+    the current stream."""
+    nnz, H = alpha.size(0), alpha.size(1) if alpha.dim() == 2 else 1
     out = torch.empty_like(alpha)
     if nnz:
         L = _c_abi()
@@ -1039,32 +1000,6 @@ def _edge_softmax_grad_heads(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.
         _c_call("the gradient of tiledEdgeSoftmax", alpha,
                 L.qgtc_tiled_edge_softmax_grad_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_grad_heads_f32, *head, *idx,
                 alpha.data_ptr(), g.data_ptr(), out.data_ptr(), nnz, H)
-    return out
-
-
-def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
-    """(alpha, m, inv) of qgtc_tiled_edge_softmax_f32 / _t: one launch on the current stream."""
-    if logits.dim() == 2:
-        return _edge_softmax_heads(adj, logits)
-    nnz = logits.numel()
-    alpha = torch.empty(nnz, dtype=torch.float32, device=adj.device)
-    m = torch.empty(adj.n, dtype=torch.float32, device=adj.device)
-    inv = torch.empty(adj.n, dtype=torch.float32, device=adj.device)
-    fn, head = _esoftmax_view(adj, False)
-    _c_call("tiledEdgeSoftmax", m, fn, *head, logits.data_ptr() if nnz else None, alpha.data_ptr() if nnz else None, nnz, m.data_ptr(),
-            inv.data_ptr())
-    return alpha, m, inv
-
-
-def _edge_softmax_grad(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    """out[slot] = alpha . (g - S[owner]) of qgtc_tiled_edge_softmax_grad_f32 / _t: one launch on the current stream."""
-    if alpha.dim() == 2:
-        return _edge_softmax_grad_heads(adj, alpha, g)
-    nnz = alpha.numel()
-    out = torch.empty(nnz, dtype=torch.float32, device=adj.device)
-    if nnz:
-        fn, head = _esoftmax_view(adj, True)
-        _c_call("the gradient of tiledEdgeSoftmax", alpha, fn, *head, alpha.data_ptr(), g.data_ptr(), out.data_ptr(), nnz)
     return out
 
 

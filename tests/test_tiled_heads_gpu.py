@@ -51,15 +51,15 @@ def test_the_per_edge_dot_equals_the_single_head_call_and_the_model(n, reorder, 
         rng = _rng(n, H, d)
         An, Bn = rng.normal(size=(n, H * d)).astype(np.float32), rng.normal(size=(n, H * d)).astype(np.float32)
         A, B = _dev(An), _dev(Bn)
-        # the entry itself, heads = 1 included (the public call routes one head to the single-head entry)
-        s = tiled._sddmm_heads(g.adj, B, A, H) if transposed else tiled._sddmm_heads(g.adj, A, B, H)
+        # the entry itself, heads = 1 included (there it launches the single-head kernel)
+        s = tiled._sddmm(g.adj, B, A, H) if transposed else tiled._sddmm(g.adj, A, B, H)
         assert s.shape == (g.nnz, H) and s.is_contiguous()
         identical(s, hm.sddmm_heads_f32(g.s, g.d, n, An, Bn, H, transposed), f"the model, H={H} d={d}")
         for h, (Ah, Bh) in enumerate(zip(_heads_of(A, H, d), _heads_of(B, H, d))):
             assert same_bits(_col(s, h), tiled.tiledSDDMM(a, Ah, Bh)), f"head {h} of H={H} d={d}"
         pub = tiled.tiledSDDMM(a, A, B, heads=H)
         assert pub.shape == ((g.nnz, H) if H > 1 else (g.nnz,)) and same_bits(pub.reshape(g.nnz, H), s)
-        assert same_bits(tiled._sddmm_heads(g.adj, B, A, H) if transposed else tiled._sddmm_heads(g.adj, A, B, H), s), "two launches"
+        assert same_bits(tiled._sddmm(g.adj, B, A, H) if transposed else tiled._sddmm(g.adj, A, B, H), s), "two launches"
     assert len(seen) == 7, "every lane mapping and register path"
 
 
@@ -75,13 +75,13 @@ def test_the_softmax_and_its_gradient_equal_the_single_head_call_and_the_model(n
         rng = _rng(n, H, 1)
         ln = (3 * rng.normal(size=(g.nnz, H))).astype(np.float32)
         gn = rng.normal(size=(g.nnz, H)).astype(np.float32)
-        alpha, m, inv = tiled._edge_softmax_heads(a, _dev(ln))
+        alpha, m, inv = tiled._edge_softmax(a, _dev(ln))
         assert alpha.shape == (g.nnz, H) and m.shape == (n, H) and inv.shape == (n, H)
         wa, wm, wi = hm.edge_softmax_heads_f32(g.s, g.d, n, ln, transposed)
         identical(alpha, wa, f"alpha, H={H}")
         identical(m, wm, f"m, H={H}")
         identical(inv, wi, f"inv, H={H}")
-        dl = tiled._edge_softmax_grad_heads(a, alpha, _dev(gn))
+        dl = tiled._edge_softmax_grad(a, alpha, _dev(gn))
         identical(dl, hm.edge_softmax_grad_heads_f32(g.s, g.d, n, wa, gn, transposed), f"dlogits, H={H}")
         for h in range(H):
             a1, m1, i1 = tiled.tiledEdgeSoftmax(a, _dev(ln[:, h]), return_stats=True)
@@ -111,7 +111,7 @@ def test_the_weighted_sum_equals_the_single_head_call_and_the_model(n, reorder, 
         rn = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
         X, v, r = _dev(Xn), _dev(vn), _dev(rn)
         for scale, sn in ((None, None), (r, rn)):
-            Y = tiled._weighted_heads(a, X, scale, v)
+            Y = tiled._weighted(a, X, scale, v)
             identical(Y, hm.weighted_heads_f32(g.s, g.d, n, Xn, vn, transposed, sn), f"the model, H={H} d={d}")
             for h, Xh in enumerate(_heads_of(X, H, d)):
                 assert same_bits(Y[:, h * d:(h + 1) * d], QGTC.tiledMMFloat(a, Xh, scale, edge_weight=_col(v, h))), f"head {h}, H={H} d={d}"
@@ -172,7 +172,7 @@ def test_special_logits_stay_with_their_head(transposed, H):
     owner_of_slot[slot] = owner
     rng = _rng(300, H, 4)
     ln = (3 * rng.normal(size=(g.nnz, H))).astype(np.float32)
-    clean = tiled._edge_softmax_heads(a, _dev(ln))
+    clean = tiled._edge_softmax(a, _dev(ln))
     # -inf in head 1 only: the first cell of every owner with two or more, the last one too where there are three or more
     big, big3 = np.flatnonzero(deg >= 2), np.flatnonzero(deg >= 3)
     masked = np.concatenate([slot[start[big]], slot[start[big3] + deg[big3] - 1]])
@@ -216,36 +216,36 @@ def test_a_gradient_not_required_is_not_launched(monkeypatch):
     g = graph(33)
     H, d = 3, 5
     calls = []
-    real = {name: getattr(tiled, name) for name in ("_weighted_heads", "_edge_softmax_grad_heads", "_sddmm_heads")}
+    real = {name: getattr(tiled, name) for name in ("_weighted", "_edge_softmax_grad", "_sddmm")}
     for name, fn in real.items():
         monkeypatch.setattr(tiled, name, lambda *a, _fn=fn, _name=name, **k: (calls.append(_name), _fn(*a, **k))[1])
     rng = _rng(33, 5)
     A, B = _dev(rng.normal(size=(33, H * d)).astype(np.float32)), _dev(rng.normal(size=(33, H * d)).astype(np.float32))
     gs = _dev(rng.normal(size=(g.nnz, H)).astype(np.float32))
     tiled.tiledEdgeScores(g.adj, A.clone().requires_grad_(True), B, heads=H).backward(gs)
-    assert calls == ["_sddmm_heads", "_weighted_heads"]
+    assert calls == ["_sddmm", "_weighted"]
     calls.clear()
     tiled.tiledEdgeScores(g.adj, A, B.clone().requires_grad_(True), heads=H).backward(gs)
-    assert calls == ["_sddmm_heads", "_weighted_heads"]
+    assert calls == ["_sddmm", "_weighted"]
     calls.clear()
     assert not tiled.tiledEdgeScores(g.adj, A, B, heads=H).requires_grad
     calls.clear()
     L = gs.clone().requires_grad_(True)
     tiled.tiledEdgeSoftmax(g.adj, L).backward(gs)
-    assert calls == ["_edge_softmax_grad_heads"]
+    assert calls == ["_edge_softmax_grad"]
     calls.clear()
     assert not tiled.tiledEdgeSoftmax(g.adj, gs).requires_grad
     # the weighted sum: X's gradient alone is one sum on the other view, the weights' alone one per-edge dot
     tiled.tiledAggregate(g.adj, A.clone().requires_grad_(True), edge_weight=gs).sum().backward()
-    assert calls == ["_weighted_heads", "_weighted_heads"]
+    assert calls == ["_weighted", "_weighted"]
     calls.clear()
     tiled.tiledAggregate(g.adj, A, edge_weight=gs.clone().requires_grad_(True)).sum().backward()
-    assert calls == ["_weighted_heads", "_sddmm_heads"]
+    assert calls == ["_weighted", "_sddmm"]
     calls.clear()
     # the attention with V alone: forward three launches, backward the sum on the other view only
     V = A.clone().requires_grad_(True)
     tiled.tiledEdgeAttention(g.adj, A, B, V, heads=H).sum().backward()
-    assert calls == ["_sddmm_heads", "_weighted_heads", "_weighted_heads"]
+    assert calls == ["_sddmm", "_weighted", "_weighted"]
     # and there is no second derivative
     import torch
 
@@ -253,6 +253,56 @@ def test_a_gradient_not_required_is_not_launched(monkeypatch):
     gx, = torch.autograd.grad(tiled.tiledAggregate(g.adj, X, edge_weight=gs), X, A, create_graph=True)
     with pytest.raises(RuntimeError):
         gx.sum().backward()
+
+
+@pytest.mark.parametrize("transposed", VIEWS)
+def test_one_head_through_a_heads_entry_is_the_single_head_entry(transposed):
+    """Every `*_heads*` entry of the C-ABI with heads = 1 against its single-head twin, bit for bit, on raw device pointers: the Python
+    route sends one head through the heads entries, whose heads = 1 branch launches the single-head kernels."""
+    torch = _torch()
+    from qgtc_ppopp22_amd import cabi, tiled
+
+    lib = cabi.load()
+    g = graph(129)
+    n, nnz = g.n, g.nnz
+    head, idx = tiled._view_ptrs(view(g, transposed))
+    rng = _rng(129, 8)
+
+    def pair(*shape):   # two outputs that differ wherever an entry writes nothing
+        return torch.zeros(shape, dtype=torch.float32, device="cuda"), torch.ones(shape, dtype=torch.float32, device="cuda")
+
+    def ok(rc):
+        assert rc == 0, lib.qgtc_strerror(rc).decode()
+
+    for N in (5, 70):
+        A, B = _dev(rng.normal(size=(n, N)).astype(np.float32)), _dev(rng.normal(size=(n, N)).astype(np.float32))
+        v, r = _dev(rng.normal(size=nnz).astype(np.float32)), _dev(rng.uniform(0.5, 2.0, size=n).astype(np.float32))
+        if not transposed:   # the per-edge dot has the row view only
+            one, many = pair(nnz)
+            ok(lib.qgtc_tiled_sddmm_f32(*head, A.data_ptr(), B.data_ptr(), A.numel(), N, *idx, one.data_ptr(), nnz, None))
+            ok(lib.qgtc_tiled_sddmm_heads_f32(*head, A.data_ptr(), B.data_ptr(), A.numel(), N, *idx, many.data_ptr(), nnz, 1, None))
+            assert same_bits(one, many), f"the per-edge dot, N={N}"
+        mm, mm_heads = ((lib.qgtc_tiledmm_f32_t_edge, lib.qgtc_tiledmm_f32_t_edge_heads) if transposed else
+                        (lib.qgtc_tiledmm_f32_edge, lib.qgtc_tiledmm_f32_edge_heads))
+        for scale in (None, r.data_ptr()):
+            one, many = pair(n, N)
+            ok(mm(*head, A.data_ptr(), A.numel(), N, scale, one.data_ptr(), one.numel(), *idx, v.data_ptr(), nnz, None))
+            ok(mm_heads(*head, A.data_ptr(), A.numel(), N, scale, many.data_ptr(), many.numel(), *idx, v.data_ptr(), nnz, 1, None))
+            assert same_bits(one, many), f"the weighted sum, N={N}, row_scale {scale is not None}"
+    ln = (3 * rng.normal(size=nnz)).astype(np.float32)
+    ln[nnz // 2] = -np.inf
+    L, G = _dev(ln), _dev(rng.normal(size=nnz).astype(np.float32))
+    sm1, sm_heads, gr, gr_heads = ((lib.qgtc_tiled_edge_softmax_f32_t, lib.qgtc_tiled_edge_softmax_heads_f32_t,
+                                    lib.qgtc_tiled_edge_softmax_grad_f32_t, lib.qgtc_tiled_edge_softmax_grad_heads_f32_t) if transposed else
+                                   (lib.qgtc_tiled_edge_softmax_f32, lib.qgtc_tiled_edge_softmax_heads_f32,
+                                    lib.qgtc_tiled_edge_softmax_grad_f32, lib.qgtc_tiled_edge_softmax_grad_heads_f32))
+    (a1, ah), (m1, mh), (i1, ih), (d1, dh) = pair(nnz), pair(n), pair(n), pair(nnz)
+    ok(sm1(*head, *idx, L.data_ptr(), a1.data_ptr(), nnz, m1.data_ptr(), i1.data_ptr(), None))
+    ok(sm_heads(*head, *idx, L.data_ptr(), ah.data_ptr(), nnz, mh.data_ptr(), ih.data_ptr(), 1, None))
+    assert same_bits(a1, ah) and same_bits(m1, mh) and same_bits(i1, ih), "the softmax and its statistics"
+    ok(gr(*head, *idx, a1.data_ptr(), G.data_ptr(), d1.data_ptr(), nnz, None))
+    ok(gr_heads(*head, *idx, a1.data_ptr(), G.data_ptr(), dh.data_ptr(), nnz, 1, None))
+    assert same_bits(d1, dh), "the softmax gradient"
 
 
 def _per_head_layer(layer, A, X):

@@ -10,6 +10,10 @@ pack element touches), EDGE_UNITS the edge-value units and BIT_UNITS the four un
 
 With --names every line is `unit hash name`, sorted by the kernel's mangled name: two checkouts whose outputs are equal instantiate the
 same kernels in every unit, under the same names, with the same instructions (a refactor of the host side must leave it so).
+
+A hash covers the disassembler's text of a kernel, and that text ends in a line `...` where zero bytes pad the kernel to the next one's
+256-byte boundary: the last kernel of a code object has no such line. With --code those lines and empty ones are left out, so a kernel
+that gains or loses a successor in its unit keeps its hash (compare two checkouts with the same setting).
 """
 import hashlib
 import os
@@ -29,7 +33,7 @@ WORDS = {"tiled": TILED_UNITS, "edge": EDGE_UNITS, "bit": BIT_UNITS}
 LLVM = "/opt/rocm/llvm/bin"
 
 
-def named_bodies(unit):
+def named_bodies(unit, code_only=False):
     """[(mangled name, hash of the body)] of the unit's kernels, in the code object's order"""
     obj = os.path.join(ROOT, "qgtc_ppopp22_amd", "build", unit + ".hip.o")
     with tempfile.TemporaryDirectory() as d:
@@ -46,26 +50,26 @@ def named_bodies(unit):
             if name:
                 out.append((name, hashlib.md5("\n".join(cur).encode()).hexdigest()))
             name, cur = m.group(1), []
-        elif name:
+        elif name and not (code_only and line.strip() in ("...", "")):
             cur.append(re.sub(r"//.*$", "", re.sub(r"<[^>]*>", "", line)).strip())
     if name:
         out.append((name, hashlib.md5("\n".join(cur).encode()).hexdigest()))
     return out
 
 
-def bodies(unit):
-    return sorted(h for _, h in named_bodies(unit))
+def bodies(unit, code_only=False):
+    return sorted(h for _, h in named_bodies(unit, code_only))
 
 
 if __name__ == "__main__":
-    names = "--names" in sys.argv[1:]
+    names, code = "--names" in sys.argv[1:], "--code" in sys.argv[1:]
     units = []
     for a in sys.argv[1:]:
-        units += [] if a == "--names" else list(WORDS.get(a, (a,)))
+        units += [] if a in ("--names", "--code") else list(WORDS.get(a, (a,)))
     for unit in units:
         if names:
-            for name, h in sorted(named_bodies(unit)):
+            for name, h in sorted(named_bodies(unit, code)):
                 print(unit, h, name)
         else:
-            for h in bodies(unit):
+            for h in bodies(unit, code):
                 print(unit, h)
