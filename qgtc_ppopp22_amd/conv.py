@@ -271,7 +271,8 @@ class GATConv(torch.nn.Module):
     heads are concatenated ([n, heads * output_dim]) or, with ``concat=False``, averaged ([n, output_dim]). Trainable in W, a_dst and
     a_src. ``A`` is the view whose rows are the receiving nodes: ``adj`` aggregates over out-neighbours, ``adj.T`` over in-neighbours;
     on a reordered adjacency X moves to its numbering and the result back. Self loops are the edge list's business
-    (QGTC.add_self_loops). One head is one launch sequence; all heads in one launch are not built.
+    (QGTC.add_self_loops). All heads share one ``tiledAggregate`` call with scores [n, heads] (include/qgtc_attn_heads.h): two launches
+    forward and five backward for the whole layer, each head bit for bit what the single-head call gives on its slice.
 
     ``edge_drop`` (a rate in [0, 1), default 0) is neighbourhood dropout: in training mode every head's softmax runs over one random
     subgraph, ``tiledAggregate(..., attn=, edge_drop=(edge_drop, seed))`` with one seed per forward for all heads - ``edge_seed`` of
@@ -310,15 +311,21 @@ class GATConv(torch.nn.Module):
                 raise NotImplementedError("nodes cannot be combined with an active edge_drop: not built")
             bm = _node_mask(A, nodes)
             mask = {"row_mask": bm, "nbr_mask": bm}
-        outs = []
+        his, ps, qs = [], [], []
         for i in range(self.heads):
             hi = h[:, i * self.output_dim:(i + 1) * self.output_dim].contiguous()
-            p, q = torch.mv(hi, self.a_dst[i]), torch.mv(hi, self.a_src[i])
-            outs.append(QGTC.tiledAggregate(A, hi, attn=(p, q), negative_slope=self.negative_slope, edge_drop=drop, **mask))
-        if self.concat:
-            out = outs[0] if self.heads == 1 else torch.cat(outs, dim=1)
-        else:
-            out = outs[0] if self.heads == 1 else torch.stack(outs).mean(dim=0)
+            his.append(hi)
+            ps.append(torch.mv(hi, self.a_dst[i]))
+            qs.append(torch.mv(hi, self.a_src[i]))
+        if self.heads == 1:
+            return A.to_old(QGTC.tiledAggregate(A, his[0], attn=(ps[0], qs[0]), negative_slope=self.negative_slope, edge_drop=drop, **mask))
+        # One call for all heads. The scores are stacked before the heads' slices are joined, and both after every torch.mv: autograd
+        # then hands a slice its three gradients in the order the loop over heads did - the aggregate's, a_src's, a_dst's - so the
+        # sums keep their association and the layer its bits.
+        P, Q = torch.stack(ps, dim=1), torch.stack(qs, dim=1)
+        out = QGTC.tiledAggregate(A, torch.cat(his, dim=1), attn=(P, Q), negative_slope=self.negative_slope, edge_drop=drop, **mask)
+        if not self.concat:   # the mean over the heads, in the layout and order of torch.stack(heads).mean(dim=0)
+            out = out.view(A.n, self.heads, self.output_dim).transpose(0, 1).contiguous().mean(dim=0)
         return A.to_old(out)
 
 

@@ -35,7 +35,10 @@ every launch.
 softmax-weighted sum of its neighbours' rows, the weight of edge (o, k) being the softmax over o's neighbours of
 ``leaky_relu(att_out[o] + att_nbr[k])``. No per-edge value is stored: the weight is rebuilt from the two per-node scores inside the tile
 walk, with an exponential that is a fixed sequence of float32 operations, so forward and all three gradients (X and both scores, each a
-fold in ascending id order on ``adj`` or ``adj.T``, no atomics) are specified to the bit. ``conv.GATConv`` is the layer on top.
+fold in ascending id order on ``adj`` or ``adj.T``, no atomics) are specified to the bit. ``conv.GATConv`` is the layer on top. With
+scores of shape [n, H] (head-minor; include/qgtc_attn_heads.h) the same launches carry H HEADS: head h is the columns h d .. (h + 1) d - 1
+of X and of the result, the statistics are [n, H], and every head is bit for bit what the single-head call gives on its contiguous
+slice - two launches forward and five backward for all heads, under ``edge_drop`` and node masks as for one head.
 
 ``edge_drop=(rate, seed)`` on both functions, in every mode, aggregates over a random subgraph instead (include/qgtc.h, "Edge dropout"):
 cell (i, j) of the adjacency survives when a fixed 32-bit hash of (i, j, seed) is at least ``floor(rate * 2^32)``, decided inside the tile
@@ -384,11 +387,34 @@ def _check_slope(negative_slope) -> float:
     return slope
 
 
-def _check_attn(adj: TiledAdjacency, attn) -> tuple[torch.Tensor, torch.Tensor]:
+def _attn_heads(adj: TiledAdjacency, score) -> int:
+    """H when ``score`` is a per-head score [n, H] with H at least 2, otherwise 0: the score is then checked as the vector [n] it
+    always had to be ([n, 1] included, which stays refused)."""
+    return score.size(1) if isinstance(score, torch.Tensor) and score.dim() == 2 and score.size(0) == adj.n and score.size(1) >= 2 else 0
+
+
+def _check_attn(adj: TiledAdjacency, attn, X=None) -> tuple[torch.Tensor, torch.Tensor]:
     if not isinstance(attn, (tuple, list)) or len(attn) != 2:
         raise TypeError("attn must be a pair (att_out, att_nbr) of float32 [n] tensors")
-    _check_scale(adj, attn[0], "att_out")
-    _check_scale(adj, attn[1], "att_nbr")
+    H = _attn_heads(adj, attn[0]) or _attn_heads(adj, attn[1])
+    if H == 0:
+        _check_scale(adj, attn[0], "att_out")
+        _check_scale(adj, attn[1], "att_nbr")
+        return attn[0], attn[1]
+    # scores per head: float32 [n, H], head-minor, both of one shape, H a divisor of X's columns
+    for name, t in (("att_out", attn[0]), ("att_nbr", attn[1])):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (float32 [n] or [n, H])")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, not {t.dtype}")
+        if tuple(t.shape) != (adj.n, H):
+            raise ValueError(f"att_out and att_nbr must have the same shape [{adj.n}, {H}], not {list(attn[0].shape)} and {list(attn[1].shape)}")
+        if t.device != adj.device:
+            raise ValueError(f"{name} must be on the adjacency's device {adj.device}, not {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if isinstance(X, torch.Tensor) and X.dim() == 2 and X.size(1) % H != 0:
+        raise ValueError(f"attn has {H} heads, which do not divide X's {X.size(1)} columns")
     return attn[0], attn[1]
 
 
@@ -673,8 +699,64 @@ def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor
     """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch. Under a mask
     (``mask_kw``, the checked keyword of the binding) both launches take it: M must be the maximum over the KEPT neighbours, or the
     weights' sum could fall below 1."""
+    if att_out.dim() == 2:   # a score per head: the same two launches carry all heads (include/qgtc_attn_heads.h)
+        M = _call(adj, "_tiled_mm_f32", att_nbr.detach(), reduce="max", return_arg=False, **mask_kw)[0]
+        return _att_heads_product(adj, X, att_out.detach(), att_nbr.detach(), slope, False, M, None, mask_kw)
     M = _call(adj, "_tiled_mm_f32", att_nbr.detach().unsqueeze(1), reduce="max", return_arg=False, **mask_kw)[0].reshape(adj.n)
     return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M, **mask_kw)
+
+
+def _att_heads_entry(adj: TiledAdjacency, stem: str, mask_kw: dict):
+    """(entry, view arguments, mask arguments) of an entry of include/qgtc_attn_heads.h on the view of ``adj`` under the checked mask
+    keyword of the binding: ``stem`` + "_t" on ``adj.T`` + "_drop" / "_nodes". The view's pointers come first, the mask's arguments
+    after ``heads``."""
+    T = adj.n_tiles
+    view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles) if adj.transposed else (adj.row_ptr, adj.kquad, adj.tiles)
+    name, tail = stem + ("_t" if adj.transposed else ""), ()
+    if "edge_drop" in mask_kw:
+        name, tail = name + "_drop", tuple(mask_kw["edge_drop"])
+    elif "node_masks" in mask_kw:
+        row_mask, nbr_mask = mask_kw["node_masks"]
+        name += "_nodes"
+        tail = (None if row_mask is None else row_mask.data_ptr(), None if nbr_mask is None else nbr_mask.data_ptr(),
+                (adj.n + 127) // 128 * 4)
+    return getattr(_c_abi(), name), tuple(t.data_ptr() if T else None for t in view) + (T, adj.n), tail
+
+
+def _att_heads_product(adj: TiledAdjacency, X: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float, backward: bool,
+                       shift: torch.Tensor, inv, mask_kw: dict):
+    """qgtc_tiledatt_heads_f32 and its twins, one launch on the current stream for all heads. Forward: ``shift`` is M [n, H] and the
+    result (out, m, inv) with the statistics [n, H]; backward: ``shift`` and ``inv`` are the forward's m and inv and the result (out,)."""
+    H = att_own.size(1)
+    out = torch.empty_like(X)
+    m = None if backward else torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    if not backward:
+        inv = torch.empty_like(m)
+    fn, view, tail = _att_heads_entry(adj, "qgtc_tiledatt_heads_f32", mask_kw)
+    _c_call("the attention product with heads", X, fn, *view, X.data_ptr(), X.numel(), X.size(1), att_own.data_ptr(), att_nbr.data_ptr(),
+            slope, int(backward), shift.data_ptr(), None if backward else m.data_ptr(), inv.data_ptr(), out.data_ptr(), out.numel(), H,
+            *tail)
+    return (out,) if backward else (out, m, inv)
+
+
+def _att_heads_grad(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float,
+                    nbr_owns: bool, m: torch.Tensor, inv: torch.Tensor, D: torch.Tensor, mask_kw: dict) -> torch.Tensor:
+    """float32 [n, H] of qgtc_tiledatt_grad_heads_f32 and its twins: the gradient of the out node's score (``nbr_owns`` False, on the
+    forward's view) or of the neighbour's (True, on the other view), one launch on the current stream for all heads."""
+    H = att_own.size(1)
+    out = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    fn, view, tail = _att_heads_entry(adj, "qgtc_tiledatt_grad_heads_f32", mask_kw)
+    _c_call("the score gradient with heads", A, fn, *view, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), att_own.data_ptr(),
+            att_nbr.data_ptr(), slope, int(nbr_owns), m.data_ptr(), inv.data_ptr(), D.data_ptr(), out.data_ptr(), out.numel(), H, *tail)
+    return out
+
+
+def _att_heads_rowdot(A: torch.Tensor, B: torch.Tensor, H: int) -> torch.Tensor:
+    """float32 [n, H] of qgtc_rowdot_heads_f32: DOT of every head's columns of A[o] and B[o], one launch on the current stream."""
+    out = torch.empty((A.size(0), H), dtype=torch.float32, device=A.device)
+    _c_call("the row dot with heads", A, _c_abi().qgtc_rowdot_heads_f32, A.data_ptr(), B.data_ptr(), A.numel(), A.size(0), A.size(1),
+            out.data_ptr(), out.numel(), H)
+    return out
 
 
 def _scale_name(row_scale) -> str:
@@ -710,7 +792,7 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
             raise ValueError("return_arg cannot be combined with attn: a weighted sum has no winning neighbour")
         slope = _check_slope(negative_slope)
         _check_float_operand(adj, X)
-        _check_attn(adj, attn)
+        _check_attn(adj, attn, X)
         return "attention", mask_kw, slope
     elif return_stats:
         raise ValueError("return_stats needs attn: only the attention product has softmax statistics")
@@ -760,6 +842,13 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     ``return_stats=True`` returns ``(out, m, inv)`` with inv float32 [n] the reciprocal of the weights' sum (0 without neighbours).
     ``attn`` with a scale, with ``reduce`` other than "sum" or with ``return_arg``, ``return_stats`` without ``attn`` and a slope
     outside [0, 1] are a ValueError. It is a max launch on the scores plus one product launch.
+
+    The scores may also be float32 [n, H] each, contiguous, of one shape, with H >= 2 dividing N: a score per node and HEAD, head h being
+    the columns h d .. (h + 1) d - 1 of X and of the result (d = N / H). Column c takes the softmax of head c // d; the operations and
+    their order are the same, so every head is bit for bit the 1-D call on its contiguous slice, in the same two launches
+    (include/qgtc_attn_heads.h). ``return_stats=True`` then gives m and inv as [n, H]. ``att_nbr[k, h] = -inf`` masks neighbour k in head
+    h only. ``edge_drop`` and the node masks below work as for one head. [n, 1] stays the ValueError it was (pass the 1-D vector); two
+    scores of different shapes and an H that does not divide N are a ValueError.
 
     ``edge_drop=(rate, seed)`` (rate a float in [0, 1), seed an int in [0, 2^64)), in every mode above, aggregates over a random subgraph
     (include/qgtc.h, "Edge dropout"): cell (i, j) of the adjacency - row i, column j, on ``adj.T`` still the cell of ``adj`` - is kept when
@@ -911,6 +1000,17 @@ class _TiledAttention(torch.autograd.Function):
         need_x, need_p, need_q = ctx.needs_input_grad[1:4]
         dY, kw = dY.contiguous(), ctx.drop_kw   # every gradient walks the forward's subgraph
         dX = dp = dq = None
+        if p.dim() == 2:   # scores per head: the same five launches carry all heads
+            H, here, there = p.size(1), {**kw, **ctx.kw_here}, {**kw, **ctx.kw_other}
+            if need_x:
+                dX = _att_heads_product(other, dY, q, p, slope, True, m, inv, there)[0]
+            if need_p or need_q:
+                D = _att_heads_rowdot(dY, Y, H)
+                if need_p:
+                    dp = _att_heads_grad(adj, dY, X, p, q, slope, False, m, inv, D, here)
+                if need_q:
+                    dq = _att_heads_grad(other, X, dY, q, p, slope, True, m, inv, D, there)
+            return None, dX, dp, dq, None, None, None, None
         if need_x:
             dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **ctx.kw_other)[0]
         if need_p or need_q:
@@ -942,7 +1042,9 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     differentiable in X, att_out and att_nbr: the gradient for X is one product launch on the other view, the two score gradients are
     a row dot and one launch each (att_out's on this view, att_nbr's on the other); a gradient nobody needs is not launched. All of
     them are specified to the bit (include/qgtc.h, "Attention tiled products") and there is no second derivative. ``attn`` with a
-    scale or with ``reduce`` other than "sum" is a ValueError.
+    scale or with ``reduce`` other than "sum" is a ValueError. With scores [n, H] (as in :func:`tiledMMFloat`) the gradients of the
+    scores are [n, H] and the backward is still at most five launches for all heads: the product on the other view, one row dot and
+    one launch per score gradient, each head bit for bit the single-head call's.
 
     With ``edge_drop=(rate, seed)`` (as in :func:`tiledMMFloat`, every mode) the forward runs on the random subgraph and every backward
     launch gets the same pair on the other view, where the mask is rebuilt from the same cells of the adjacency: the gradients are those

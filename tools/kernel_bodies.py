@@ -5,8 +5,8 @@ read from qgtc_ppopp22_amd/build/ (run build() first); gfx950 code objects are u
     python tools/kernel_bodies.py qgtc_tiled_float qgtc_tiled_max ... > bodies.txt     # in each checkout, then diff the two files
 
 TILED_UNITS lists the float, extremum and attention units of the tiled adjacency (the families whose shared templates a new trailing
-pack element touches), EDGE_UNITS the edge-value units and BIT_UNITS the four units of the quantised products; the word `tiled` /
-`edge` / `bit` on the command line stands for the list.
+pack element touches), EDGE_UNITS the edge-value units and BIT_UNITS the four units of the quantised products; ATTN_HEADS_UNITS the six units of the attention path with heads; the word
+`tiled` / `edge` / `bit` / `attn_heads` on the command line stands for the list.
 
 With --names every line is `unit hash name`, sorted by the kernel's mangled name: two checkouts whose outputs are equal instantiate the
 same kernels in every unit, under the same names, with the same instructions (a refactor of the host side must leave it so).
@@ -29,7 +29,9 @@ TILED_UNITS = ("qgtc_tiled_float", "qgtc_tiled_float_t", "qgtc_tiled_float_src",
                "qgtc_tiled_attn_t_drop", "qgtc_tiled_attn_nodes", "qgtc_tiled_attn_t_nodes")   # 263 kernels
 EDGE_UNITS = ("qgtc_tiled_float_edge", "qgtc_tiled_float_t_edge", "qgtc_tiled_sddmm")
 BIT_UNITS = ("qgtc_tiled", "qgtc_tiled_t", "qgtc_tiled_scaled", "qgtc_tiled_t_scaled")
-WORDS = {"tiled": TILED_UNITS, "edge": EDGE_UNITS, "bit": BIT_UNITS}
+ATTN_HEADS_UNITS = ("qgtc_tiled_attn_heads", "qgtc_tiled_attn_heads_t", "qgtc_tiled_attn_heads_drop", "qgtc_tiled_attn_heads_t_drop",
+                    "qgtc_tiled_attn_heads_nodes", "qgtc_tiled_attn_heads_t_nodes")
+WORDS = {"tiled": TILED_UNITS, "edge": EDGE_UNITS, "bit": BIT_UNITS, "attn_heads": ATTN_HEADS_UNITS}
 LLVM = "/opt/rocm/llvm/bin"
 
 

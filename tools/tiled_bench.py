@@ -85,7 +85,7 @@ One alternating loop of four: forward and forward plus all three gradients, each
 checked bit for bit before timing. Medians with their 10th and 90th percentiles; `within_spread` says whether the one-call median is at
 most the loop's median plus the loop's own 10th-to-90th-percentile spread.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads]
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads]
 """
 from __future__ import annotations
 
@@ -835,12 +835,71 @@ def heads_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def gatheads_leg(torch, QGTC, graphs, reps):
+    """The attention path (`attn=(p, q)`, the reducer of GAT) with scores [n, H] in ONE call against the loop over the heads of the same
+    tree - per head a `.contiguous()` column slice and the single-head call, concatenated -, on the heads leg's graphs, shapes and
+    rhythm: forward, and forward plus all three gradients, alternating in one loop. Outputs are checked bit for bit before timing."""
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    def bits(x):
+        return x.contiguous().view(torch.int32)
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles}", flush=True)
+        xr = np.random.default_rng(1)
+        for H, d in HEADS_SHAPES:
+            X, dY = (torch.from_numpy(xr.standard_normal((n, H * d)).astype(np.float32)).cuda() for _ in range(2))
+            P, Q = (torch.from_numpy(xr.uniform(-1, 1, (n, H)).astype(np.float32)).cuda() for _ in range(2))
+            Xg, Pg, Qg = (x.clone().requires_grad_(True) for x in (X, P, Q))
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                def loop(Xl, Pl, Ql):   # the layer's aggregation before the heads shared a call
+                    return torch.cat([QGTC.tiledAggregate(a, Xl[:, h * d:(h + 1) * d].contiguous(), attn=(Pl[:, h].contiguous(), Ql[:, h].contiguous()))
+                                      for h in range(H)], dim=1)
+
+                def one_both():
+                    return torch.autograd.grad(QGTC.tiledAggregate(a, Xg, attn=(Pg, Qg)), (Xg, Pg, Qg), dY)
+
+                def loop_both():
+                    return torch.autograd.grad(loop(Xg, Pg, Qg), (Xg, Pg, Qg), dY)
+
+                assert torch.equal(bits(QGTC.tiledAggregate(a, X, attn=(P, Q))), bits(loop(X, P, Q))), (H, d, direction)
+                for x, y in zip(one_both(), loop_both()):
+                    assert torch.equal(bits(x), bits(y)), (H, d, direction)
+                tof, tlf, tob, tlb = timed_alternating(torch, [lambda: QGTC.tiledAggregate(a, X, attn=(P, Q)), lambda: loop(X, P, Q),
+                                                               one_both, loop_both], reps)
+                # the expectation: the one call beats the loop by more than the loop's own 10th-90th spread
+                ok_f, ok_b = tof[0] < tlf[0] - (tlf[2] - tlf[1]), tob[0] < tlb[0] - (tlb[2] - tlb[1])
+                rec["agg"].append({"heads": H, "d": d, "direction": direction, "one_call_forward_ms": tof, "loop_forward_ms": tlf,
+                                   "one_call_forward_backward_ms": tob, "loop_forward_backward_ms": tlb,
+                                   "loop_over_one_call_forward": round(tlf[0] / tof[0], 3),
+                                   "loop_over_one_call_forward_backward": round(tlb[0] / tob[0], 3),
+                                   "forward_beats_the_loop_by_more_than_its_spread": bool(ok_f),
+                                   "forward_backward_beats_the_loop_by_more_than_its_spread": bool(ok_b)})
+                print(f"{name:9s} H={H} d={d:<3d} {direction:10s} forward: one call {tof[0]:8.4f} [{tof[1]:.4f}, {tof[2]:.4f}]  loop "
+                      f"{tlf[0]:8.4f} [{tlf[1]:.4f}, {tlf[2]:.4f}] ({tlf[0] / tof[0]:.2f}x)  forward + backward: one call {tob[0]:8.4f} "
+                      f"[{tob[1]:.4f}, {tob[2]:.4f}]  loop {tlb[0]:8.4f} [{tlb[1]:.4f}, {tlb[2]:.4f}] ({tlb[0] / tob[0]:.2f}x)"
+                      f"{'' if ok_f and ok_b else '  NOT AHEAD OF THE LOOP BY ITS SPREAD'}", flush=True)
+            del X, dY, P, Q, Xg, Pg, Qg
+        rows.append(rec)
+        del adj, t, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads"))
     args = ap.parse_args()
 
     import torch
@@ -848,9 +907,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
