@@ -12,6 +12,7 @@ from . import lib_path
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "qgtc.h")
 HEADS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_heads.h")   # the multi-head entries, declared beside qgtc.h until the two are folded
 ATTN_HEADS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_attn_heads.h")   # the multi-head entries of the attention path, likewise
+ADDSCORE_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_addscore.h")   # the additive edge score (GATv2) and its gradients, likewise
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
@@ -49,7 +50,7 @@ def signatures(text: str | None = None) -> dict:
 
 def load():
     """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry - those of include/qgtc.h
-    and, through the same parser, those of include/qgtc_heads.h and include/qgtc_attn_heads.h. A declared entry the library does not
+    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h and include/qgtc_addscore.h. A declared entry the library does not
     export is an error naming it."""
     global _lib
     if _lib is None:
@@ -58,7 +59,10 @@ def load():
             heads = signatures(f.read())
         with open(ATTN_HEADS_HEADER) as f:
             attn_heads = signatures(f.read())
-        for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads), ("qgtc_attn_heads.h", attn_heads)):
+        with open(ADDSCORE_HEADER) as f:
+            addscore = signatures(f.read())
+        for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads), ("qgtc_attn_heads.h", attn_heads),
+                              ("qgtc_addscore.h", addscore)):
             for name, (restype, argtypes) in table.items():
                 try:
                     fn = getattr(lib, name)

@@ -363,3 +363,47 @@ class TransformerConv(torch.nn.Module):
         if self.heads > 1 and not self.concat:   # the mean over the heads, in the layout and order of torch.stack(heads).mean(dim=0)
             out = out.view(A.n, self.heads, self.output_dim).transpose(0, 1).contiguous().mean(dim=0)
         return A.to_old(out)
+
+
+class GATv2Conv(torch.nn.Module):
+    """One GATv2 layer (Brody et al., 2022) on a whole graph's QGTC.TiledAdjacency: hl = X . W_l, hr = X . W_r, and per head the
+    receiving node o takes ``sum over its neighbours k of softmax_k(att . leaky_relu(hr_o + hl_k)) * hl_k`` -
+    ``tiled.tiledEdgeAdditiveAttention(A, hr, hl, hl, att, negative_slope, heads)``: the additive score (include/qgtc_addscore.h), the
+    edge softmax and the weighted sum, three launches forward and five backward for all heads, every one specified to the bit and
+    without atomics. Unlike GATConv's ``attn=(p, q)`` logit, the nonlinearity sits before the reduction with ``att``, so the ranking of
+    the neighbours depends on the receiving node ("dynamic" attention). With ``share_weights`` W_r is W_l. The heads are concatenated
+    ([n, heads * output_dim]) or, with ``concat=False``, averaged ([n, output_dim]), exactly as TransformerConv does. Trainable in W_l,
+    W_r and att ([heads, output_dim]). ``A`` is the view whose rows are the receiving nodes: ``adj`` attends over out-neighbours,
+    ``adj.T`` over in-neighbours; on a reordered adjacency X moves to its numbering and the result back. A node without neighbours
+    gives +0; self loops are the edge list's business (QGTC.add_self_loops).
+
+    There is no ``edge_drop`` and there are no ``nodes``: the aggregate takes the weights through ``edge_weight``, which accepts
+    neither."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, share_weights=False):
+        super().__init__()
+        if int(heads) < 1:
+            raise ValueError(f"heads must be at least 1, not {heads!r}")
+        slope = float(negative_slope)
+        if not 0.0 <= slope <= 1.0:
+            raise ValueError(f"negative_slope must lie in [0, 1], not {negative_slope!r}")
+        self.input_dim, self.output_dim, self.heads, self.concat = int(input_dim), int(output_dim), int(heads), bool(concat)
+        self.negative_slope, self.share_weights = slope, bool(share_weights)
+        self.W_l = torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
+        self.W_r = self.W_l if self.share_weights else torch.nn.Parameter(
+            torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
+        self.att = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
+
+    def forward(self, A, X):
+        if not isinstance(A, QGTC.TiledAdjacency):
+            raise NotImplementedError("GATv2Conv needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
+        assert A.n == X.size(0), "the adjacency and X must have the same number of nodes"
+        from .tiled import tiledEdgeAdditiveAttention
+
+        Xn = A.to_new(X)
+        hl = torch.mm(Xn, self.W_l)
+        hr = hl if self.share_weights else torch.mm(Xn, self.W_r)
+        out = tiledEdgeAdditiveAttention(A, hr, hl, hl, self.att, self.negative_slope, heads=self.heads)
+        if self.heads > 1 and not self.concat:   # the mean over the heads, in the layout and order of torch.stack(heads).mean(dim=0)
+            out = out.view(A.n, self.heads, self.output_dim).transpose(0, 1).contiguous().mean(dim=0)
+        return A.to_old(out)

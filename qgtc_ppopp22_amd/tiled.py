@@ -75,6 +75,12 @@ All of that path takes HEADS without a loop (include/qgtc_heads.h): with ``heads
 values of a cell adjacent), the softmax accepts and returns [nnz, H] with [n, H] statistics, ``edge_weight`` accepts [nnz, H] for an X
 whose columns H divides, and ``tiledEdgeAttention(..., heads=H)`` is three launches forward and five backward for all heads - each head
 bit for bit what the single-head call gives on its contiguous slice of columns.
+
+:func:`tiledEdgeAdditiveScores` is the ADDITIVE score of GATv2 on the same path (include/qgtc_addscore.h): per stored cell and head,
+``att . leaky_relu(own[o] + nbr[k])`` - the nonlinearity sits between the per-column add and the reduction, so it is neither a function
+of two per-node scalars (``attn=``) nor a dot product (:func:`tiledSDDMM`). One launch gives the [nnz, H] scores, two give its
+gradients, and :func:`tiledEdgeAdditiveAttention` composes it with the edge softmax and the weighted sum. ``conv.GATv2Conv`` is the
+layer on top.
 """
 from __future__ import annotations
 
@@ -115,7 +121,7 @@ def _inv_degree(deg: torch.Tensor) -> torch.Tensor:
 
 __all__ = ["TiledAdjacency", "pack_edges_tiled", "reorder_nodes", "tiledMM2Bit", "tiledMM2Int", "tiledMMFloat", "tiledAggregate",
            "add_self_loops", "node_bitmap", "edge_slots", "edge_endpoints", "edge_values", "tiledSDDMM", "tiledEdgeSoftmax",
-           "tiledEdgeScores", "tiledEdgeAttention"]
+           "tiledEdgeScores", "tiledEdgeAttention", "tiledEdgeAdditiveScores", "tiledEdgeAdditiveAttention"]
 
 
 class TiledAdjacency:
@@ -1206,6 +1212,114 @@ def tiledEdgeAttention(adj: TiledAdjacency, Q: torch.Tensor, K: torch.Tensor, V:
     scale = 1.0 / math.sqrt(Q.size(1) // heads) if scale is None else float(scale)
     logits = tiledEdgeScores(adj, Q, K, heads) * scale
     return tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, logits))
+
+
+def _addscore(base: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, att: torch.Tensor, slope: float, heads: int) -> torch.Tensor:
+    """float32 [nnz, heads] of qgtc_tiled_addscore_heads_f32 on the untransposed adjacency (the caller has swapped the operands of the
+    other view): one launch on the current stream."""
+    nnz = _value_index(base)[2]
+    out = torch.empty((nnz, heads), dtype=torch.float32, device=base.device)
+    if nnz:
+        head, idx = _view_ptrs(base)
+        _c_call("tiledEdgeAdditiveScores", A, _c_abi().qgtc_tiled_addscore_heads_f32, *head, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1),
+                att.data_ptr(), att.numel(), slope, *idx, out.data_ptr(), nnz, heads)
+    return out
+
+
+def _addscore_grad(adj: TiledAdjacency, own: torch.Tensor, nbr: torch.Tensor, att: torch.Tensor, slope: float, g: torch.Tensor, heads: int,
+                   want_own: bool, want_P: bool):
+    """(d_own, P) of qgtc_tiled_addscore_grad_heads_f32 / _t on this view, float32 [n, N] each or None where not wanted: one launch on
+    the current stream for both. ``g`` is the scores' gradient, [nnz] or [nnz, heads] in slot order."""
+    nnz = g.size(0)
+    if not nnz:   # no cell: every fold is its +0
+        return torch.zeros_like(own) if want_own else None, torch.zeros_like(own) if want_P else None
+    d_own = torch.empty_like(own) if want_own else None
+    P = torch.empty_like(own) if want_P else None
+    L = _c_abi()
+    head, idx = _view_ptrs(adj)
+    _c_call("the gradient of tiledEdgeAdditiveScores", own,
+            L.qgtc_tiled_addscore_grad_heads_f32_t if adj.transposed else L.qgtc_tiled_addscore_grad_heads_f32, *head, own.data_ptr(),
+            nbr.data_ptr(), own.numel(), own.size(1), att.data_ptr(), att.numel(), slope, d_own.data_ptr() if want_own else None,
+            P.data_ptr() if want_P else None, own.numel(), *idx, g.data_ptr(), nnz, heads)
+    return d_own, P
+
+
+class _TiledEdgeAdditiveScores(torch.autograd.Function):
+    """s[slot(o, k), h] = ADDSCORE(own[o], nbr[k]; att) on the view: d_own and P (whose column sum is datt) are one launch on the view,
+    d_nbr the same entry on the other view with the operands swapped - each launched only when a gradient it produces is needed."""
+
+    @staticmethod
+    def forward(ctx, adj, own, nbr, att, slope, heads):
+        ctx.adj, ctx.slope, ctx.heads = adj, slope, heads
+        ctx.save_for_backward(own, nbr, att)
+        A, B = (nbr, own) if adj.transposed else (own, nbr)   # fl(x + y) commutes: the row view's kernel serves both views
+        out = _addscore(_base(adj), A, B, att, slope, heads)
+        return out if heads > 1 else out.view(-1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        own, nbr, att = ctx.saved_tensors
+        d_own = d_nbr = d_att = None
+        need_own, need_nbr, need_att = ctx.needs_input_grad[1:4]
+        if need_own or need_nbr or need_att:
+            g = g.contiguous()
+            if need_own or need_att:
+                d_own, P = _addscore_grad(ctx.adj, own, nbr, att, ctx.slope, g, ctx.heads, need_own, need_att)
+                if need_att:
+                    d_att = P.sum(dim=0).view(att.shape)
+            if need_nbr:
+                d_nbr, _ = _addscore_grad(ctx.adj.T, nbr, own, att, ctx.slope, g, ctx.heads, True, False)
+        return None, d_own, d_nbr, d_att, None, None
+
+
+def _check_additive(adj: TiledAdjacency, own, nbr, att, negative_slope, heads):
+    """The checks of the additive score's operands; (slope, heads) as a float and an int."""
+    _check(adj)
+    _check_float_operand(adj, own)
+    heads = _check_heads(heads, own.size(1))
+    if not isinstance(nbr, torch.Tensor) or nbr.dtype != torch.float32:
+        raise TypeError("nbr must be a float32 torch.Tensor")
+    if nbr.shape != own.shape or nbr.device != own.device or not nbr.is_contiguous():
+        raise ValueError(f"nbr must be contiguous, on own's device and of own's shape {list(own.shape)}, not {list(nbr.shape)}")
+    if not isinstance(att, torch.Tensor) or att.dtype != torch.float32:
+        raise TypeError("att must be a float32 torch.Tensor")
+    N = own.size(1)
+    if tuple(att.shape) not in ((N,), (heads, N // heads)) or att.device != own.device or not att.is_contiguous():
+        raise ValueError(f"att must be contiguous, on own's device and of shape [{N}] or [{heads}, {N // heads}], not {list(att.shape)}")
+    return _check_slope(negative_slope), heads
+
+
+def tiledEdgeAdditiveScores(adj: TiledAdjacency, own: torch.Tensor, nbr: torch.Tensor, att: torch.Tensor, negative_slope: float = 0.2,
+                            heads: int = 1) -> torch.Tensor:
+    """The additive (GATv2) edge score, float32 [nnz] in slot order or [nnz, H] for ``heads=H`` > 1: for every stored cell of this view,
+    owner o and neighbour k, and every head h, ``att[h] . leaky_relu(own[o, head h] + nbr[k, head h])`` - ADDSCORE of
+    include/qgtc_addscore.h: one float32 add, the leaky relu, one multiply by att and one add per column, 64 strided partial sums and
+    the xor butterfly, never fused, so the result is the same bits on every launch; one launch for all heads, every (slot, head) written
+    once, no atomics. On ``adj.T`` the cell is the same one of ``adj`` with ``own`` and ``nbr`` swapped. ``own`` and ``nbr`` are float32
+    [n, N], contiguous, in the adjacency's numbering; ``att`` is float32 [N] or [H, N / H], contiguous; ``negative_slope`` lies in
+    [0, 1]. Differentiable in ``own``, ``nbr`` and ``att`` (no second derivative): ``own``'s gradient and P, whose column sum
+    (``torch.sum``) is ``att``'s, are one launch on this view, ``nbr``'s is the same entry on the other view - each launched only when
+    needed, both specified to the bit; the derivative of the leaky relu at 0 is the slope. A wrong dtype is a TypeError; a wrong
+    shape, device, stride, slope or ``heads`` a ValueError."""
+    slope, heads = _check_additive(adj, own, nbr, att, negative_slope, heads)
+    return _TiledEdgeAdditiveScores.apply(adj, own, nbr, att, slope, heads)
+
+
+def tiledEdgeAdditiveAttention(adj: TiledAdjacency, own: torch.Tensor, nbr: torch.Tensor, V: torch.Tensor, att: torch.Tensor,
+                               negative_slope: float = 0.2, heads: int = 1) -> torch.Tensor:
+    """GATv2 attention over the graph's edges, float32 [n, Nv]: row o of the view receives ``sum over its neighbours k of
+    softmax_k(att . leaky_relu(own[o] + nbr[k])) * V[k]`` - the composition ``tiledAggregate(adj, V,
+    edge_weight=tiledEdgeSoftmax(adj, tiledEdgeAdditiveScores(adj, own, nbr, att, negative_slope, heads)))``: three launches forward
+    and five backward for all heads, every one specified to the bit, none with atomics. Differentiable in ``own``, ``nbr``, ``V`` and
+    ``att``. With ``heads=H`` > 1 head h is the columns h d .. (h + 1) d - 1 of ``own`` / ``nbr`` and h dv .. of ``V`` and of the
+    result; H must divide both widths. A row without neighbours receives +0."""
+    slope, heads = _check_additive(adj, own, nbr, att, negative_slope, heads)
+    if heads > 1:
+        _check_float_operand(adj, V)
+        _check_heads(heads, V.size(1))
+    scores = _TiledEdgeAdditiveScores.apply(adj, own, nbr, att, slope, heads)
+    return tiledAggregate(adj, V, edge_weight=tiledEdgeSoftmax(adj, scores))
 
 
 def add_self_loops(src: torch.Tensor, dst: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Tensor]:

@@ -85,7 +85,14 @@ One alternating loop of four: forward and forward plus all three gradients, each
 checked bit for bit before timing. Medians with their 10th and 90th percentiles; `within_spread` says whether the one-call median is at
 most the loop's median plus the loop's own 10th-to-90th-percentile spread.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads]
+`--leg gatv2` measures the additive edge score of GATv2 (tiled.tiledEdgeAdditiveScores, tiled.tiledEdgeAdditiveAttention; DESIGN.md
+6.15k) on the heads leg's graphs and (H, d) cells, both directions. Three alternating loops: the score launch against the
+tiledSDDMM(heads=H) launch of the same shape; each gradient launch against the edge_weight weighted launch of the same shape and view;
+the attention's forward and forward plus all four gradients against the edge-list route in torch (edge_endpoints, index_select,
+leaky_relu, a scatter softmax, index_add_), against which it is checked before timing. Medians with their 10th and 90th percentiles; a
+cell slower than the edge-list route is reported as such.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2]
 """
 from __future__ import annotations
 
@@ -894,12 +901,100 @@ def gatheads_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def gatv2_leg(torch, QGTC, graphs, reps):
+    """The additive edge score of GATv2 (tiled.tiledEdgeAdditiveScores / tiledEdgeAdditiveAttention) on the heads leg's
+    graphs and shapes, both directions. Three alternating loops: (a) the score launch against the tiledSDDMM(heads=H) launch of the same
+    shape - the same walk and traffic, so the difference is the extra VALU work; (b) each gradient launch (d_own + P on the view, d_nbr
+    alone on the other view) against the edge_weight weighted launch of the same shape and view; (c) the attention's forward and
+    forward plus all four gradients against the edge-list route in torch (edge_endpoints, index_select, leaky_relu, a scatter softmax,
+    index_add_, with its autograd backward, which is not bit-reproducible). The attention is checked against the edge-list route
+    before timing. A cell slower than the edge-list route is printed as such."""
+    from qgtc_ppopp22_amd import tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    slope = 0.2
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        e_row, e_col = (v.long() for v in tiled.edge_endpoints(adj))
+        nnz = int(e_row.numel())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": nnz, "tiles": adj.n_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {nnz}", flush=True)
+        xr = np.random.default_rng(1)
+        for H, d in HEADS_SHAPES:
+            own, nbr, dY = (torch.from_numpy(xr.standard_normal((n, H * d)).astype(np.float32)).cuda() for _ in range(3))
+            att = torch.from_numpy((xr.standard_normal((H, d)) / math.sqrt(d)).astype(np.float32)).cuda()
+            gs = torch.from_numpy(xr.standard_normal((nnz, H)).astype(np.float32)).cuda()
+            leaves = [x.clone().requires_grad_(True) for x in (own, nbr, att)]
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                o, k = (e_col, e_row) if a.transposed else (e_row, e_col)
+
+                def edge_list(own_e, nbr_e, att_e):
+                    u = torch.nn.functional.leaky_relu(own_e.index_select(0, o) + nbr_e.index_select(0, k), slope)
+                    s = (u.view(nnz, H, d) * att_e).sum(dim=2)                                   # [nnz, H]
+                    top = torch.full((n, H), float("-inf"), device="cuda").scatter_reduce(0, o[:, None].expand(nnz, H), s.detach(), "amax")
+                    w = torch.exp(s - top.index_select(0, o))
+                    den = torch.zeros(n, H, device="cuda").index_add_(0, o, w)
+                    alpha = w / den.index_select(0, o)
+                    msg = alpha[:, :, None] * nbr_e.index_select(0, k).view(nnz, H, d)
+                    return torch.zeros(n, H * d, device="cuda").index_add_(0, o, msg.view(nnz, H * d))
+
+                def one(own_e, nbr_e, att_e):   # the layer's aggregation: V is the neighbour operand
+                    return tiled.tiledEdgeAdditiveAttention(a, own_e, nbr_e, nbr_e, att_e, slope, heads=H)
+
+                def one_both():
+                    return torch.autograd.grad(one(*leaves), leaves, dY)
+
+                def edge_both():
+                    return torch.autograd.grad(edge_list(*leaves), leaves, dY)
+
+                got, ref = one(own, nbr, att), edge_list(own, nbr, att)
+                assert torch.allclose(got, ref, rtol=1e-3, atol=1e-4), (H, d, direction, float((got - ref).abs().max()))
+                for gk, ge in zip(one_both(), edge_both()):
+                    assert torch.allclose(gk, ge, rtol=1e-3, atol=2e-3), (H, d, direction, float((gk - ge).abs().max()))
+                tsc, tsd = timed_alternating(torch, [lambda: tiled.tiledEdgeAdditiveScores(a, own, nbr, att, slope, heads=H),
+                                                     lambda: tiled.tiledSDDMM(a, own, nbr, heads=H)], reps)
+                tg2, tg1, tw, twt = timed_alternating(torch, [
+                    lambda: tiled._addscore_grad(a, own, nbr, att, slope, gs, H, True, True),
+                    lambda: tiled._addscore_grad(a.T, nbr, own, att, slope, gs, H, True, False),
+                    lambda: QGTC.tiledMMFloat(a, nbr, edge_weight=gs), lambda: QGTC.tiledMMFloat(a.T, own, edge_weight=gs)], reps)
+                tof, tob, tef, teb = timed_alternating(torch, [lambda: one(own, nbr, att), one_both, lambda: edge_list(own, nbr, att), edge_both],
+                                                       reps)
+                slower = [what for what, mine, theirs in (("forward", tof, tef), ("forward + backward", tob, teb)) if mine[0] > theirs[0]]
+                rec["agg"].append({"heads": H, "d": d, "direction": direction, "score_ms": tsc, "sddmm_ms": tsd,
+                                   "grad_own_P_ms": tg2, "grad_nbr_other_view_ms": tg1, "weighted_ms": tw, "weighted_other_view_ms": twt,
+                                   "attention_forward_ms": tof, "attention_forward_backward_ms": tob, "edge_list_forward_ms": tef,
+                                   "edge_list_forward_backward_ms": teb, "score_over_sddmm": round(tsc[0] / tsd[0], 3),
+                                   "grad_own_P_over_weighted": round(tg2[0] / tw[0], 3),
+                                   "grad_nbr_over_weighted_other_view": round(tg1[0] / twt[0], 3),
+                                   "edge_list_over_attention_forward": round(tef[0] / tof[0], 3),
+                                   "edge_list_over_attention_forward_backward": round(teb[0] / tob[0], 3),
+                                   "slower_than_the_edge_list": slower})
+                print(f"{name:9s} H={H} d={d:<3d} {direction:10s} score {tsc[0]:8.4f} [{tsc[1]:.4f}, {tsc[2]:.4f}]  sddmm {tsd[0]:8.4f} "
+                      f"[{tsd[1]:.4f}, {tsd[2]:.4f}] ({tsc[0] / tsd[0]:.3f}x)  d_own + P {tg2[0]:8.4f} [{tg2[1]:.4f}, {tg2[2]:.4f}]  weighted "
+                      f"{tw[0]:8.4f} [{tw[1]:.4f}, {tw[2]:.4f}] ({tg2[0] / tw[0]:.3f}x)  d_nbr {tg1[0]:8.4f} [{tg1[1]:.4f}, {tg1[2]:.4f}]  "
+                      f"weighted, other view {twt[0]:8.4f} [{twt[1]:.4f}, {twt[2]:.4f}] ({tg1[0] / twt[0]:.3f}x)  attention fwd {tof[0]:8.4f} "
+                      f"[{tof[1]:.4f}, {tof[2]:.4f}]  fwd + bwd {tob[0]:8.4f} [{tob[1]:.4f}, {tob[2]:.4f}]  edge list fwd {tef[0]:8.4f} "
+                      f"({tef[0] / tof[0]:.2f}x)  fwd + bwd {teb[0]:8.4f} ({teb[0] / tob[0]:.2f}x)"
+                      f"{'  SLOWER THAN THE EDGE LIST: ' + ', '.join(slower) if slower else ''}", flush=True)
+            del own, nbr, dY, att, gs, leaves
+        rows.append(rec)
+        del adj, t, dsrc, ddst, e_row, e_col
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2"))
     args = ap.parse_args()
 
     import torch
@@ -907,9 +1002,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
