@@ -14,6 +14,8 @@ HEADS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_heads.h")   # the mul
 ATTN_HEADS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_attn_heads.h")   # the multi-head entries of the attention path, likewise
 ADDSCORE_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_addscore.h")   # the additive edge score (GATv2) and its gradients, likewise
 
+FANOUT_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_fanout.h")   # fixed-fanout sampling: the selection launches and the _fanout twins, likewise
+
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
 _RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
@@ -50,7 +52,7 @@ def signatures(text: str | None = None) -> dict:
 
 def load():
     """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry - those of include/qgtc.h
-    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h and include/qgtc_addscore.h. A declared entry the library does not
+    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h, include/qgtc_addscore.h and include/qgtc_fanout.h. A declared entry the library does not
     export is an error naming it."""
     global _lib
     if _lib is None:
@@ -61,8 +63,10 @@ def load():
             attn_heads = signatures(f.read())
         with open(ADDSCORE_HEADER) as f:
             addscore = signatures(f.read())
+        with open(FANOUT_HEADER) as f:
+            fanout = signatures(f.read())
         for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads), ("qgtc_attn_heads.h", attn_heads),
-                              ("qgtc_addscore.h", addscore)):
+                              ("qgtc_addscore.h", addscore), ("qgtc_fanout.h", fanout)):
             for name, (restype, argtypes) in table.items():
                 try:
                     fn = getattr(lib, name)

@@ -81,6 +81,11 @@ bit for bit what the single-head call gives on its contiguous slice of columns.
 of two per-node scalars (``attn=``) nor a dot product (:func:`tiledSDDMM`). One launch gives the [nnz, H] scores, two give its
 gradients, and :func:`tiledEdgeAdditiveAttention` composes it with the edge softmax and the weighted sum. ``conv.GATv2Conv`` is the
 layer on top.
+
+``fanout=(k, seed)`` on :func:`tiledMMFloat` and :func:`tiledAggregate` aggregates over a fixed-fanout sample - at most k neighbours per
+output row, drawn inside the tile walk (include/qgtc_fanout.h): one selection launch gives a threshold per row, the aggregate then keeps
+a cell when its hash reaches its row's threshold, and a backward on the other view looks the thresholds up per neighbour. The module
+``fanout`` has the sample (``sample_fanout``, ``FanoutSample``), the ctypes calls and the allocations; ``sage.SAGEConv`` is the layer on top.
 """
 from __future__ import annotations
 
@@ -507,6 +512,20 @@ def _nodes_kw(adj: TiledAdjacency, row_mask, nbr_mask, key) -> dict:
     return {"node_masks": (row_mask, nbr_mask)}
 
 
+def _fanout_kw(adj: TiledAdjacency, fanout, key, nodes_kw, edge_weight, attn) -> dict:
+    """The keyword of a checked ``fanout=`` (a pair (k, seed) or a ``fanout.FanoutSample``; the module ``fanout`` has the checks, the
+    launches and the allocations), after the refusals of what is not built with it."""
+    from . import fanout as _fanout
+
+    _fanout.check_fanout(adj, fanout)
+    for name, on in (("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)), ("edge_weight", edge_weight is not None),
+                     ("[n, H] scores", isinstance(attn, (tuple, list)) and len(attn) == 2
+                      and bool(_attn_heads(adj, attn[0]) or _attn_heads(adj, attn[1])))):
+        if on:
+            raise ValueError(f"fanout cannot be combined with {name}: not built")
+    return {"fanout": fanout}
+
+
 def _value_index(adj: TiledAdjacency):
     """(val_ptr int64 [T + 1], val_row int16 [T, 32], nnz) of include/qgtc.h, "Edge values": one kernel for the tiles' bit counts and the
     in-tile row prefix, ``torch.cumsum`` for the scan, one host read for nnz. Built on first use and kept on the untransposed adjacency
@@ -771,7 +790,7 @@ def _scale_name(row_scale) -> str:
 
 
 def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop, row_mask,
-             nbr_mask, edge_weight):
+             nbr_mask, edge_weight, fanout=None):
     """(mode, mask_kw, slope) of a call of :func:`tiledMMFloat` / :func:`tiledAggregate`, or the refusal it earns. ``mode`` is
     "weighted" (``edge_weight``), "attention" (``attn``), "extremum" (``reduce`` "max" / "min") or "sum" (plain or scaled); ``mask_kw``
     the binding's keyword of the checked mask, ``edge_drop`` or ``node_masks`` - without a mask no keyword at all, which is the call the
@@ -782,6 +801,8 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
     key = _edge_drop_key(edge_drop)
     nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
     mask_kw = nodes_kw if key is None else _drop_kw(key)   # never both: _nodes_kw refuses a mask with edge_drop
+    if fanout is not None:
+        mask_kw = _fanout_kw(adj, fanout, key, nodes_kw, edge_weight, attn)
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if edge_weight is not None:
@@ -821,7 +842,7 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                  src_scale: torch.Tensor | None = None, reduce: str = "sum", return_arg: bool = False, attn=None,
                  negative_slope: float = 0.2, return_stats: bool = False, edge_drop=None, row_mask: torch.Tensor | None = None,
-                 nbr_mask: torch.Tensor | None = None, edge_weight: torch.Tensor | None = None):
+                 nbr_mask: torch.Tensor | None = None, edge_weight: torch.Tensor | None = None, fanout=None):
     """float32 [n, N] = A . X for a float32 ``X`` [n, N] (contiguous, on the adjacency's device, rows in the adjacency's numbering);
     on ``adj.T``, A^T . X. Every output row adds the rows of X of its neighbours in ASCENDING id order, starting from +0, one float32
     add each; with ``row_scale`` (as in :func:`tiledMM2Int`) the row is then multiplied by row_scale[r], one float32 multiply. The
@@ -888,9 +909,23 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     columns h d .. (h + 1) d - 1 of X and of the result (d = N / H). Column c takes ``values[slot, c // d]``; the operations and their
     order are the same, so every head is bit for bit the 1-D call on its contiguous slice, in one launch (include/qgtc_heads.h).
     H is at least 2: [nnz, 1] stays the ValueError it was (pass the 1-D vector). Whatever is refused with a 1-D ``edge_weight`` is
-    refused with this one in the same words; an H that does not divide N is a ValueError."""
+    refused with this one in the same words; an H that does not divide N is a ValueError.
+
+    ``fanout=(k, seed)`` (k an int >= 1, the seed as for ``edge_drop``) aggregates over a fixed-fanout sample instead
+    (include/qgtc_fanout.h): at most k neighbours per output row of the view passed, drawn by one selection launch - the k cells of the
+    row with the largest hashes H(i, j, seed), exactly min(deg, k) of them, a uniform draw without replacement - and then the result is
+    bit for bit the same call on ``pack_edges_tiled`` of the kept edges, as under ``edge_drop``. ``fanout`` may also be a
+    ``fanout.FanoutSample`` (``fanout.sample_fanout(view, k, seed)``): on the view it was taken on the thresholds are the output rows', on
+    the other view the neighbours' - the same kept cells, which is what a backward needs - and no selection is launched. Built for the sum
+    with either scale, ``reduce="max"`` / ``"min"`` with ``return_arg`` and one-head ``attn`` with ``return_stats``; k at least the largest
+    degree gives the plain call's bits. A k below 1 is a ValueError, a k that is no int a TypeError; a sample of another adjacency is a
+    ValueError; ``fanout`` with ``edge_drop``, a node mask, ``edge_weight`` or [n, H] scores a ValueError (not built)."""
     mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop,
-                                    row_mask, nbr_mask, edge_weight)
+                                    row_mask, nbr_mask, edge_weight, fanout)
+    if "fanout" in mask_kw:
+        from . import fanout as _fanout
+
+        return _fanout.forward(adj, mode, X, row_scale, src_scale, reduce, return_arg, attn, slope, return_stats, fanout)
     if mode == "sum":
         if src_scale is not None:
             return _call(adj, "_tiled_mm_f32_src", X, row_scale, src_scale, **mask_kw)
@@ -922,18 +957,18 @@ class _TiledAggregate(torch.autograd.Function):
     node masks swapped: a neighbour of the forward is an output row of the backward."""
 
     @staticmethod
-    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None, row_mask=None, nbr_mask=None):
+    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
         ctx.adj, ctx.row_scale, ctx.src_scale, ctx.edge_drop = adj, row_scale, src_scale, edge_drop
-        ctx.row_mask, ctx.nbr_mask = row_mask, nbr_mask
-        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask)
+        ctx.row_mask, ctx.nbr_mask, ctx.fanout = row_mask, nbr_mask, fanout   # fanout: the sample, taken once by tiledAggregate
+        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
 
     @staticmethod
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
             dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale, edge_drop=ctx.edge_drop,
-                              row_mask=ctx.nbr_mask, nbr_mask=ctx.row_mask)
-        return None, dX, None, None, None, None, None
+                              row_mask=ctx.nbr_mask, nbr_mask=ctx.row_mask, fanout=ctx.fanout)
+        return None, dX, None, None, None, None, None, None
 
 
 class _TiledWeighted(torch.autograd.Function):
@@ -967,8 +1002,9 @@ class _TiledExtremum(torch.autograd.Function):
     """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
 
     @staticmethod
-    def forward(ctx, adj, X, reduce, edge_drop=None, row_mask=None, nbr_mask=None):
-        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask)
+    def forward(ctx, adj, X, reduce, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
+        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask,
+                                fanout=fanout)
         ctx.adj, ctx.arg = adj, arg   # the select needs no mask: arg names kept (participating) neighbours only
         return out
 
@@ -978,7 +1014,7 @@ class _TiledExtremum(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[1]:
             dX = _tiled_select(ctx.adj.T, dY.contiguous(), ctx.arg)
-        return None, dX, None, None, None, None
+        return None, dX, None, None, None, None, None
 
 
 class _TiledAttention(torch.autograd.Function):
@@ -987,10 +1023,11 @@ class _TiledAttention(torch.autograd.Function):
     of edge (o, k) gets u = alpha[o, k] . (dY[o] . X[k] - D[o]) . L'(e), which dp folds over k on this view and dq over o on the other."""
 
     @staticmethod
-    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None, row_mask=None, nbr_mask=None):
+    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
         out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop,
-                                   row_mask=row_mask, nbr_mask=nbr_mask)
+                                   row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
         ctx.adj, ctx.slope, ctx.drop_kw = adj, slope, _drop_kw(_edge_drop_key(edge_drop))
+        ctx.fanout = fanout   # the sample, taken once by tiledAggregate: every gradient launch below reuses it
         # node masks: unchanged on this view (grad_own), swapped on the other (the backward product and grad_nbr)
         ctx.kw_here = ctx.kw_other = {}
         if row_mask is not None or nbr_mask is not None:
@@ -1016,7 +1053,20 @@ class _TiledAttention(torch.autograd.Function):
                     dp = _att_heads_grad(adj, dY, X, p, q, slope, False, m, inv, D, here)
                 if need_q:
                     dq = _att_heads_grad(other, X, dY, q, p, slope, True, m, inv, D, there)
-            return None, dX, dp, dq, None, None, None, None
+            return None, dX, dp, dq, None, None, None, None, None
+        if ctx.fanout is not None:   # one head over a fixed-fanout sample: the same five launches through the _fanout entries
+            from . import fanout as _fanout
+
+            q, p = q.contiguous(), p.contiguous()
+            if need_x:
+                dX = _fanout.att_product(other, dY, q, p, slope, True, m, inv, ctx.fanout)[0]
+            if need_p or need_q:
+                D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
+                if need_p:
+                    dp = _fanout.att_grad(adj, dY, X, p, q, slope, False, m, inv, D, ctx.fanout)
+                if need_q:
+                    dq = _fanout.att_grad(other, X, dY, q, p, slope, True, m, inv, D, ctx.fanout)
+            return None, dX, dp, dq, None, None, None, None, None
         if need_x:
             dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **ctx.kw_other)[0]
         if need_p or need_q:
@@ -1027,13 +1077,13 @@ class _TiledAttention(torch.autograd.Function):
             if need_q:
                 dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw,
                           **ctx.kw_other)[0]
-        return None, dX, dp, dq, None, None, None, None
+        return None, dX, dp, dq, None, None, None, None, None
 
 
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
                    src_scale: torch.Tensor | None = None, reduce: str = "sum", attn=None, negative_slope: float = 0.2,
                    edge_drop=None, row_mask: torch.Tensor | None = None, nbr_mask: torch.Tensor | None = None,
-                   edge_weight: torch.Tensor | None = None) -> torch.Tensor:
+                   edge_weight: torch.Tensor | None = None, fanout=None) -> torch.Tensor:
     """:func:`tiledMMFloat` under ``torch.autograd``: the forward is ``tiledMMFloat(adj, X, row_scale, src_scale)`` and the gradient
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
@@ -1067,9 +1117,17 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     ``dX = tiledMMFloat(other view, r[:, None] * dY, edge_weight=values)`` and ``dvalues = tiledSDDMM(adj, r[:, None] * dY, X)``, with r
     the ``row_scale`` (the elementwise pre-multiply is a torch operation and happens only when there is one). A gradient nobody needs
     is not launched; both are specified to the bit and there is no second derivative. The combinations :func:`tiledMMFloat` refuses are
-    refused here."""
-    mode, _, slope = _resolve(adj, X, row_scale, src_scale, reduce, False, attn, negative_slope, False, edge_drop, row_mask, nbr_mask,
-                              edge_weight)
+    refused here.
+
+    With ``fanout=(k, seed)`` or a ``fanout.FanoutSample`` (as in :func:`tiledMMFloat`: the sum, max / min, one-head ``attn``) the sample
+    is taken ONCE, in the forward - one selection launch for a pair, none for a sample - and every backward launch reuses it on the other
+    view in the neighbours' form: the gradients are those of the unmasked call on ``pack_edges_tiled`` of the kept edges, bit for bit."""
+    mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, False, attn, negative_slope, False, edge_drop, row_mask, nbr_mask,
+                                    edge_weight, fanout)
+    if "fanout" in mask_kw:
+        from . import fanout as _fanout
+
+        fanout = _fanout.as_sample(adj, fanout)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
             wrt = "X and edge_weight" if mode == "weighted" else "X"
@@ -1077,10 +1135,10 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     if mode == "weighted":
         return _TiledWeighted.apply(adj, X, row_scale, edge_weight)
     if mode == "attention":
-        return _TiledAttention.apply(adj, X, attn[0], attn[1], slope, edge_drop, row_mask, nbr_mask)
+        return _TiledAttention.apply(adj, X, attn[0], attn[1], slope, edge_drop, row_mask, nbr_mask, fanout)
     if mode == "extremum":
-        return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask)
-    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask)
+        return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask, fanout)
+    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask, fanout)
 
 
 def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):

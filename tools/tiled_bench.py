@@ -92,7 +92,13 @@ the attention's forward and forward plus all four gradients against the edge-lis
 leaky_relu, a scatter softmax, index_add_), against which it is checked before timing. Medians with their 10th and 90th percentiles; a
 cell slower than the edge-list route is reported as such.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2]
+`--leg fanout` measures fixed-fanout neighbour sampling inside the tile walk (``fanout=`` of QGTC.tiledMMFloat / QGTC.tiledAggregate,
+fanout.sample_fanout) on the reordered graphs, N in {64, 256}, k in {5, 10, 25}, both views: the selection launch, the
+sampled sum in the own form (a sample of the view) and in the nbr form (a sample of the other view), forward plus backward, against (a)
+the route without it - random keys on tiled.edge_endpoints, a per-row top-k in torch, pack_edges_tiled, the plain launch -, (b) the
+plain launch and (c) the ``edge_drop`` launch at the rate that keeps as many edges.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout]
 """
 from __future__ import annotations
 
@@ -989,12 +995,92 @@ def gatv2_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def fanout_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import fanout, tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    seed = 0x0123456789ABCDEF
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        e_row, e_col = (e.long() for e in tiled.edge_endpoints(adj))   # the set cells in slot order, the adjacency's numbering
+        cells = int(e_row.numel())
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": cells, "tiles": adj.n_tiles,
+               "max_out_degree": int(adj.degrees().max()), "max_in_degree": int(t.degrees().max()), "max_block_tiles": adj.max_block_tiles,
+               "max_col_tiles": t.max_block_tiles, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells}  largest degree out {rec['max_out_degree']} in {rec['max_in_degree']}", flush=True)
+        xr = np.random.default_rng(1)
+
+        def topk_repack(a, k):
+            """today's route: fresh keys, the k largest per node of the view's axis by one sort, a second adjacency, the plain launch"""
+            own = (e_col if a.transposed else e_row).to(torch.float64)
+            order = torch.argsort(own + torch.rand(cells, device="cuda", dtype=torch.float64))
+            first = torch.searchsorted(own[order], own[order])   # the first position of the node's run
+            keep = order[torch.arange(cells, device="cuda") - first < k]
+            return QGTC.pack_edges_tiled(e_row[keep], e_col[keep], n, False)
+
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            dY = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            Xg = X.clone().requires_grad_(True)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                for k in (5, 10, 25):
+                    own, other = fanout.sample_fanout(a, k, seed), fanout.sample_fanout(a.T, k, seed)
+                    kept = int(a.degrees().clamp(max=k).sum())
+                    got = QGTC.tiledMMFloat(a, torch.ones((n, 1), device="cuda"), fanout=own)
+                    assert int(got.sum()) == kept and torch.equal(got.view(-1).to(torch.int32), a.degrees().clamp(max=k)), (N, direction, k)
+                    rate = min(max(1.0 - kept / max(1, cells), 0.0), 1.0 - 2.0 ** -32)
+                    scale = tiled._inv_degree(a.degrees().clamp(max=k))
+
+                    def repack():
+                        sub = topk_repack(a, k)
+                        return QGTC.tiledMMFloat(sub.T if a.transposed else sub, X)
+
+                    def both(**kw):
+                        return lambda: torch.autograd.grad(QGTC.tiledAggregate(a, Xg, **kw), [Xg], dY)
+
+                    def repack_both():
+                        sub = topk_repack(a, k)
+                        return torch.autograd.grad(QGTC.tiledAggregate(sub.T if a.transposed else sub, Xg, scale), [Xg], dY)
+
+                    tsel, town, tnbr, tplain, tdrop, tpair = timed_alternating(torch, [
+                        lambda: fanout.sample_fanout(a, k, seed), lambda: QGTC.tiledMMFloat(a, X, fanout=own),
+                        lambda: QGTC.tiledMMFloat(a, X, fanout=other), lambda: QGTC.tiledMMFloat(a, X),
+                        lambda: QGTC.tiledMMFloat(a, X, edge_drop=(rate, seed)), lambda: QGTC.tiledMMFloat(a, X, fanout=(k, seed))], reps)
+                    (trepack,) = timed_alternating(torch, [repack], max(3, reps // 2))
+                    bf, bp, bd = timed_alternating(torch, [both(row_scale=scale, fanout=(k, seed)), both(row_scale=scale),
+                                                           both(row_scale=scale, edge_drop=(rate, seed))], reps)
+                    (br,) = timed_alternating(torch, [repack_both], max(3, reps // 2))
+                    rec["agg"].append({"N": N, "direction": direction, "k": k, "kept_cells": kept, "kept_fraction": round(kept / max(1, cells), 4),
+                                       "select_ms": tsel, "own_ms": town, "nbr_ms": tnbr, "plain_ms": tplain, "edge_drop_same_edges_ms": tdrop,
+                                       "select_plus_own_ms": tpair, "topk_repack_plain_ms": trepack, "fwd_bwd_fanout_ms": bf,
+                                       "fwd_bwd_plain_ms": bp, "fwd_bwd_edge_drop_ms": bd, "fwd_bwd_topk_repack_ms": br,
+                                       "repack_over_fanout": round(trepack[0] / tpair[0], 3), "own_over_plain": round(town[0] / tplain[0], 3),
+                                       "nbr_over_own": round(tnbr[0] / town[0], 3), "own_over_edge_drop": round(town[0] / tdrop[0], 3),
+                                       "fwd_bwd_repack_over_fanout": round(br[0] / bf[0], 3), "fwd_bwd_fanout_over_plain": round(bf[0] / bp[0], 3)})
+                    print(f"{name:9s} N={N:<4d} {direction:10s} k={k:<3d} kept {kept / max(1, cells):.3f}  select {tsel[0]:8.4f}  own {town[0]:8.4f}  "
+                          f"nbr {tnbr[0]:8.4f}  plain {tplain[0]:8.4f}  edge_drop {tdrop[0]:8.4f}  select+own {tpair[0]:8.4f}  top-k + pack + plain "
+                          f"{trepack[0]:8.4f} ({trepack[0] / tpair[0]:.2f}x)  fwd+bwd fanout {bf[0]:8.4f} plain {bp[0]:8.4f} edge_drop {bd[0]:8.4f} "
+                          f"top-k route {br[0]:8.4f} ({br[0] / bf[0]:.2f}x)", flush=True)
+                    del own, other
+            del X, dY, Xg
+        rows.append(rec)
+        del adj, t, dsrc, ddst, e_row, e_col
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout"))
     args = ap.parse_args()
 
     import torch
@@ -1002,9 +1088,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
