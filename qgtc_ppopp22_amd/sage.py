@@ -1,6 +1,7 @@
 """GraphSAGE on the tiled adjacency (Hamilton et al. 2017): ``lin_self(X) + lin_nbr(agg(X))`` with ``agg`` the mean or the maximum over
 the neighbours - all of them, or a fixed-fanout sample of at most ``fanout`` per node drawn fresh every training step inside the tile
-walk (``fanout=`` of ``tiled.tiledAggregate``; include/qgtc_fanout.h)."""
+walk (``fanout=`` of ``tiled.tiledAggregate``; include/qgtc_fanout.h), or the neighbours a mini-batch block keeps
+(``fanout.sample_blocks``; include/qgtc_blocks.h)."""
 from __future__ import annotations
 
 import torch
@@ -22,7 +23,13 @@ class SAGEConv(torch.nn.Module):
     With ``fanout=k`` and in ``train()`` every forward aggregates over a fresh sample of at most k neighbours per node:
     ``fanout=(k, seed)`` with ``seed`` the argument or, when None, 64 bits drawn from torch's CPU generator (as the layers of ``conv``
     draw their ``edge_drop`` seeds); the mean then divides by min(deg, k), the number of kept neighbours. One selection launch per
-    forward; the backward reuses the sample. In ``eval()``, and with ``fanout=None``, nothing is sampled and ``seed`` is ignored."""
+    forward; the backward reuses the sample. In ``eval()``, and with ``fanout=None``, nothing is sampled and ``seed`` is ignored.
+
+    With ``block=`` (a ``fanout.Block`` of ``fanout.sample_blocks``, on the view passed or the other) the layer runs one hop of a
+    mini-batch: the aggregate is taken over ``block.sample`` - the mean divides by the sample's own counts - and nothing is drawn, so the
+    layer's ``fanout``, ``seed`` and ``train()`` / ``eval()`` make no difference. Only the rows of ``block.rows`` are part of the batch:
+    every other row holds ``lin_self(X[o])`` plus the bias (its aggregate is +0), gets no gradient through the aggregate and is read by
+    no later block, because a layer's rows are a subset of the rows before it and the kept neighbours a subset of ``block.inputs``."""
 
     def __init__(self, in_features: int, out_features: int, aggr: str = "mean", fanout: int | None = None, bias: bool = True):
         super().__init__()
@@ -41,9 +48,21 @@ class SAGEConv(torch.nn.Module):
         """float32 [n]: 1 / min(deg, fanout), correctly rounded, 0 where the degree is 0 - the mean over a sample's kept neighbours."""
         return tiled._inv_degree(A.degrees().clamp(max=self.fanout))
 
-    def forward(self, A, X, seed=None):
+    def forward(self, A, X, seed=None, block=None):
         if not isinstance(A, tiled.TiledAdjacency):
             raise NotImplementedError("SAGEConv aggregates on a TiledAdjacency (QGTC.pack_edges_tiled)")
+        if block is not None:
+            from . import fanout as _fanout
+
+            if not isinstance(block, _fanout.Block):
+                raise TypeError(f"block must be a fanout.Block (fanout.sample_blocks), not {type(block).__name__}")
+            if not isinstance(block.sample, _fanout.FanoutSample) or block.sample.view is not A:   # counts belong to the sample's view
+                raise ValueError("block was sampled on another view than the one passed")
+            if self.aggr == "max":
+                agg = tiled.tiledAggregate(A, X, reduce="max", fanout=block.sample)
+            else:
+                agg = tiled.tiledAggregate(A, X, block.sample.mean_scale(), fanout=block.sample)
+            return self.lin_self(X) + self.lin_nbr(agg)
         kw = {}
         if self.training and self.fanout is not None:
             kw["fanout"] = (self.fanout, _draw_edge_seed() if seed is None else seed)

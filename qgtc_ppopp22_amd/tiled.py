@@ -86,6 +86,8 @@ layer on top.
 output row, drawn inside the tile walk (include/qgtc_fanout.h): one selection launch gives a threshold per row, the aggregate then keeps
 a cell when its hash reaches its row's threshold, and a backward on the other view looks the thresholds up per neighbour. The module
 ``fanout`` has the sample (``sample_fanout``, ``FanoutSample``), the ctypes calls and the allocations; ``sage.SAGEConv`` is the layer on top.
+A sample taken under node masks (``fanout.sample_fanout(view, k, seed, row_mask=, nbr_mask=)``; include/qgtc_blocks.h) carries them, and
+``fanout=`` then runs on the induced subgraph: mini-batch GraphSAGE (``fanout.frontier``, ``fanout.sample_blocks``, ``SAGEConv(block=)``).
 """
 from __future__ import annotations
 

@@ -98,7 +98,13 @@ sampled sum in the own form (a sample of the view) and in the nbr form (a sample
 the route without it - random keys on tiled.edge_endpoints, a per-row top-k in torch, pack_edges_tiled, the plain launch -, (b) the
 plain launch and (c) the ``edge_drop`` launch at the rate that keeps as many edges.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout]
+`--leg blocks` measures mini-batch sampling (fanout.sample_blocks, fanout.frontier, ``sample_fanout(..., row_mask=)``) on
+the reordered graphs, on adj, 1024 seed nodes, fanouts (25, 10), N in {64, 256}: (a) building the two blocks plus the two sampled mean
+aggregates against today's route for the same batch - per hop, filter the edge list by the row set, a per-row top-k in torch,
+pack_edges_tiled, the plain mean launch, the next row set by a scatter -, (b) the frontier launch against the three-launch route (the
+N = 1 sampled product of ones on the other view, a compare, node_bitmap) and (c) the masked selection against the unmasked one.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks]
 """
 from __future__ import annotations
 
@@ -1075,12 +1081,96 @@ def fanout_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def blocks_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd import fanout, tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    seed, fanouts, members = 0x0123456789ABCDEF, (25, 10), 1024
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T
+        e_row, e_col = (e.long() for e in tiled.edge_endpoints(adj))   # the set cells in slot order, the adjacency's numbering
+        cells = int(e_row.numel())
+        flags = torch.zeros(n, dtype=torch.bool, device="cuda")
+        flags[torch.from_numpy(np.random.default_rng(11).permutation(n)[:members]).cuda()] = True
+        seeds = tiled.node_bitmap(flags, n)
+        blocks = fanout.sample_blocks(adj, seeds, fanouts, seed)
+        sizes = [int(flags.sum())] + [_popcount(torch, b.inputs) for b in blocks[::-1]]
+        kept = [int(b.sample.counts.sum()) for b in blocks[::-1]]
+        rec = {"graph": name, "order": "reordered", "n": n, "set_cells": cells, "tiles": adj.n_tiles, "seeds": members, "fanouts": list(fanouts),
+               "rows_per_hop": sizes, "kept_cells_per_hop": kept, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {cells}  rows per hop (seeds first) {sizes}  kept cells per hop {kept}", flush=True)
+        xr = np.random.default_rng(1)
+
+        def today(X):
+            """per hop, last layer first: the edges of the row set, the k largest fresh keys per row by one sort, a second adjacency, the
+            plain mean launch, the next row set"""
+            rows_now, outs = flags, []
+            for k in fanouts[::-1]:
+                sel = rows_now[e_row]
+                er, ec = e_row[sel], e_col[sel]
+                own = er.to(torch.float64)
+                order = torch.argsort(own + torch.rand(er.numel(), device="cuda", dtype=torch.float64))
+                first = torch.searchsorted(own[order], own[order])
+                keep = order[torch.arange(er.numel(), device="cuda") - first < k]
+                sub = QGTC.pack_edges_tiled(er[keep], ec[keep], n, False)
+                outs.append(QGTC.tiledMMFloat(sub, X, sub.mean_scale()))
+                rows_now = rows_now.clone()
+                rows_now[ec[keep]] = True
+            return outs
+
+        def new(X):
+            return [QGTC.tiledMMFloat(adj, X, b.sample.mean_scale(), fanout=b.sample) for b in fanout.sample_blocks(adj, seeds, fanouts, seed)]
+
+        for N in (64, 256):
+            X = torch.from_numpy(xr.standard_normal((n, N)).astype(np.float32)).cuda()
+            tnew, tbuild = timed_alternating(torch, [lambda: new(X), lambda: fanout.sample_blocks(adj, seeds, fanouts, seed)], reps)
+            (ttoday,) = timed_alternating(torch, [lambda: today(X)], max(3, reps // 2))
+            rec["agg"].append({"what": "batch", "N": N, "blocks_plus_aggregates_ms": tnew, "blocks_alone_ms": tbuild, "today_ms": ttoday,
+                               "today_over_new": round(ttoday[0] / tnew[0], 3)})
+            print(f"{name:9s} (a) N={N:<4d} blocks + 2 aggregates {tnew[0]:8.4f} [{tnew[1]:.4f}, {tnew[2]:.4f}]  blocks alone {tbuild[0]:8.4f}  "
+                  f"today's route {ttoday[0]:8.4f} [{ttoday[1]:.4f}, {ttoday[2]:.4f}] ({ttoday[0] / tnew[0]:.2f}x)", flush=True)
+            del X
+        ones = torch.ones((n, 1), device="cuda")
+        for hop, b in zip(("seeds", "inputs"), blocks[::-1]):
+            s, k = b.sample, b.sample.k
+
+            def three():
+                return tiled.node_bitmap(QGTC.tiledMMFloat(adj.T, ones, fanout=s).view(n) > 0, n) | s.row_mask
+
+            assert torch.equal(three(), fanout.frontier(s, include=True)), hop
+            tfr, t3 = timed_alternating(torch, [lambda: fanout.frontier(s, include=True), three], reps)
+            tmask, tall = timed_alternating(torch, [lambda: fanout.sample_fanout(adj, k, seed, row_mask=s.row_mask),
+                                                    lambda: fanout.sample_fanout(adj, k, seed)], reps)
+            rec["agg"].append({"what": "hop", "hop": hop, "k": k, "frontier_ms": tfr, "three_launches_ms": t3, "masked_selection_ms": tmask,
+                               "unmasked_selection_ms": tall, "three_over_frontier": round(t3[0] / tfr[0], 3),
+                               "masked_over_unmasked": round(tmask[0] / tall[0], 3)})
+            print(f"{name:9s} (b) {hop:6s} k={k:<3d} frontier {tfr[0]:8.4f} [{tfr[1]:.4f}, {tfr[2]:.4f}]  three launches {t3[0]:8.4f} "
+                  f"[{t3[1]:.4f}, {t3[2]:.4f}] ({t3[0] / tfr[0]:.2f}x)   (c) masked selection {tmask[0]:8.4f} [{tmask[1]:.4f}, {tmask[2]:.4f}]  "
+                  f"unmasked {tall[0]:8.4f} [{tall[1]:.4f}, {tall[2]:.4f}] ({tmask[0] / tall[0]:.2f}x)", flush=True)
+        rows.append(rec)
+        del adj, dsrc, ddst, e_row, e_col, blocks
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _popcount(torch, bitmap):
+    """the set bits of an int32 bitmap"""
+    b = bitmap.to(torch.int64) & 0xFFFFFFFF
+    return int(sum(((b >> i) & 1).sum() for i in range(32)))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks"))
     args = ap.parse_args()
 
     import torch
@@ -1088,9 +1178,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
