@@ -954,22 +954,45 @@ def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> t
     return _call(adj, "_tiled_mm_f32", dY, reduce="select", arg=arg)[0]
 
 
+def _sample_key(sample):
+    """(what a context keeps of a ``fanout.FanoutSample`` as plain attributes, its tensors for ``save_for_backward``): the view, k and
+    the seed; thr, the two masks and counts (None where the sample has none). Every tensor a backward reads goes through
+    ``save_for_backward`` - a reference, nothing is copied -, so that autograd's version check sees an in-place edit between the
+    forward and the backward and raises instead of differentiating another graph."""
+    if sample is None:
+        return None, (None, None, None, None)
+    return (sample.view, sample.k, sample.seed), (sample.thr, sample.row_mask, sample.nbr_mask, sample.counts)
+
+
+def _sample_again(key, tensors):
+    """The forward's sample, rebuilt in a backward from the context's key and the saved (version-checked) tensors."""
+    if key is None:
+        return None
+    from .fanout import FanoutSample
+
+    return FanoutSample(*key, *tensors)
+
+
 class _TiledAggregate(torch.autograd.Function):
     """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped - and
-    node masks swapped: a neighbour of the forward is an output row of the backward."""
+    node masks swapped: a neighbour of the forward is an output row of the backward. The product is linear in X, so the backward is
+    this Function again, on the other view: it can be differentiated in turn, and the second derivative is the forward on the other
+    operand. Without a graph to build (``create_graph=False``) that is the one launch it always was."""
 
     @staticmethod
     def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
-        ctx.adj, ctx.row_scale, ctx.src_scale, ctx.edge_drop = adj, row_scale, src_scale, edge_drop
-        ctx.row_mask, ctx.nbr_mask, ctx.fanout = row_mask, nbr_mask, fanout   # fanout: the sample, taken once by tiledAggregate
+        ctx.adj, ctx.edge_drop = adj, edge_drop
+        ctx.sample, sample_tensors = _sample_key(fanout)   # fanout: the sample, taken once by tiledAggregate
+        ctx.save_for_backward(row_scale, src_scale, row_mask, nbr_mask, *sample_tensors)
         return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
 
     @staticmethod
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
-            dX = tiledMMFloat(ctx.adj.T, dY.contiguous(), row_scale=ctx.src_scale, src_scale=ctx.row_scale, edge_drop=ctx.edge_drop,
-                              row_mask=ctx.nbr_mask, nbr_mask=ctx.row_mask, fanout=ctx.fanout)
+            row_scale, src_scale, row_mask, nbr_mask, *sample_tensors = ctx.saved_tensors
+            dX = _TiledAggregate.apply(ctx.adj.T, dY.contiguous(), src_scale, row_scale, ctx.edge_drop, nbr_mask, row_mask,
+                                       _sample_again(ctx.sample, sample_tensors))
         return None, dX, None, None, None, None, None, None
 
 
@@ -980,19 +1003,19 @@ class _TiledWeighted(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adj, X, row_scale, values):
-        ctx.adj, ctx.row_scale = adj, row_scale
-        ctx.save_for_backward(X, values)
+        ctx.adj = adj
+        ctx.save_for_backward(X, values, row_scale)
         return tiledMMFloat(adj, X, row_scale, edge_weight=values)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dY):
-        X, values = ctx.saved_tensors
+        X, values, row_scale = ctx.saved_tensors
         dX = dV = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
             dY = dY.contiguous()
-            if ctx.row_scale is not None:
-                dY = ctx.row_scale[:, None] * dY
+            if row_scale is not None:
+                dY = row_scale[:, None] * dY
             if ctx.needs_input_grad[1]:
                 dX = tiledMMFloat(ctx.adj.T, dY, edge_weight=values)
             if ctx.needs_input_grad[3]:
@@ -1007,7 +1030,8 @@ class _TiledExtremum(torch.autograd.Function):
     def forward(ctx, adj, X, reduce, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
         out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask,
                                 fanout=fanout)
-        ctx.adj, ctx.arg = adj, arg   # the select needs no mask: arg names kept (participating) neighbours only
+        ctx.adj = adj
+        ctx.save_for_backward(arg)   # the select needs no mask: arg names kept (participating) neighbours only
         return out
 
     @staticmethod
@@ -1015,7 +1039,8 @@ class _TiledExtremum(torch.autograd.Function):
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
-            dX = _tiled_select(ctx.adj.T, dY.contiguous(), ctx.arg)
+            arg, = ctx.saved_tensors
+            dX = _tiled_select(ctx.adj.T, dY.contiguous(), arg)
         return None, dX, None, None, None, None, None
 
 
@@ -1029,24 +1054,25 @@ class _TiledAttention(torch.autograd.Function):
         out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop,
                                    row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
         ctx.adj, ctx.slope, ctx.drop_kw = adj, slope, _drop_kw(_edge_drop_key(edge_drop))
-        ctx.fanout = fanout   # the sample, taken once by tiledAggregate: every gradient launch below reuses it
-        # node masks: unchanged on this view (grad_own), swapped on the other (the backward product and grad_nbr)
-        ctx.kw_here = ctx.kw_other = {}
-        if row_mask is not None or nbr_mask is not None:
-            ctx.kw_here, ctx.kw_other = {"node_masks": (row_mask, nbr_mask)}, {"node_masks": (nbr_mask, row_mask)}
-        ctx.save_for_backward(X, att_out, att_nbr, out, m, inv)
+        ctx.sample, sample_tensors = _sample_key(fanout)   # the sample, taken once by tiledAggregate: every gradient launch reuses it
+        ctx.save_for_backward(X, att_out, att_nbr, out, m, inv, row_mask, nbr_mask, *sample_tensors)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dY):
-        X, p, q, Y, m, inv = ctx.saved_tensors
+        X, p, q, Y, m, inv, row_mask, nbr_mask, *sample_tensors = ctx.saved_tensors
         adj, other, slope = ctx.adj, ctx.adj.T, ctx.slope
         need_x, need_p, need_q = ctx.needs_input_grad[1:4]
         dY, kw = dY.contiguous(), ctx.drop_kw   # every gradient walks the forward's subgraph
+        # node masks: unchanged on this view (grad_own), swapped on the other (the backward product and grad_nbr)
+        kw_here = kw_other = {}
+        if row_mask is not None or nbr_mask is not None:
+            kw_here, kw_other = {"node_masks": (row_mask, nbr_mask)}, {"node_masks": (nbr_mask, row_mask)}
+        fanout = _sample_again(ctx.sample, sample_tensors)
         dX = dp = dq = None
         if p.dim() == 2:   # scores per head: the same five launches carry all heads
-            H, here, there = p.size(1), {**kw, **ctx.kw_here}, {**kw, **ctx.kw_other}
+            H, here, there = p.size(1), {**kw, **kw_here}, {**kw, **kw_other}
             if need_x:
                 dX = _att_heads_product(other, dY, q, p, slope, True, m, inv, there)[0]
             if need_p or need_q:
@@ -1056,29 +1082,29 @@ class _TiledAttention(torch.autograd.Function):
                 if need_q:
                     dq = _att_heads_grad(other, X, dY, q, p, slope, True, m, inv, D, there)
             return None, dX, dp, dq, None, None, None, None, None
-        if ctx.fanout is not None:   # one head over a fixed-fanout sample: the same five launches through the _fanout entries
+        if fanout is not None:   # one head over a fixed-fanout sample: the same five launches through the _fanout entries
             from . import fanout as _fanout
 
             q, p = q.contiguous(), p.contiguous()
             if need_x:
-                dX = _fanout.att_product(other, dY, q, p, slope, True, m, inv, ctx.fanout)[0]
+                dX = _fanout.att_product(other, dY, q, p, slope, True, m, inv, fanout)[0]
             if need_p or need_q:
                 D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
                 if need_p:
-                    dp = _fanout.att_grad(adj, dY, X, p, q, slope, False, m, inv, D, ctx.fanout)
+                    dp = _fanout.att_grad(adj, dY, X, p, q, slope, False, m, inv, D, fanout)
                 if need_q:
-                    dq = _fanout.att_grad(other, X, dY, q, p, slope, True, m, inv, D, ctx.fanout)
+                    dq = _fanout.att_grad(other, X, dY, q, p, slope, True, m, inv, D, fanout)
             return None, dX, dp, dq, None, None, None, None, None
         if need_x:
-            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **ctx.kw_other)[0]
+            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **kw_other)[0]
         if need_p or need_q:
             D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
             if need_p:
                 dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D, **kw,
-                          **ctx.kw_here)[0]
+                          **kw_here)[0]
             if need_q:
                 dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw,
-                          **ctx.kw_other)[0]
+                          **kw_other)[0]
         return None, dX, dp, dq, None, None, None, None, None
 
 
@@ -1090,6 +1116,17 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     for X is ``tiledMMFloat(adj.T, dY, row_scale=src_scale, src_scale=row_scale)`` - one launch each way, both specified to the bit.
     The scales get no gradient: one that requires it is a ValueError. It works on ``adj``, ``adj.T`` and reordered adjacencies
     (``to_new`` / ``to_old`` are ``index_select`` and differentiate by themselves).
+
+    The sum (plain, scaled, under ``edge_drop``, node masks or ``fanout``) is linear in X and has a SECOND derivative: its backward is
+    this differentiable call on the other view with the scales and masks swapped and the same sample, so under ``create_graph=True`` the
+    gradient carries a graph, and with ``dX = grad(Y, X, dY)`` the derivative of ``<dX, R>`` for dY is the forward on the other operand,
+    ``tiledMMFloat(adj, R, ...)`` with the forward's own scales, masks, key or sample, bit for bit. Every other mode below raises when
+    its backward is differentiated (``once_differentiable``).
+
+    Every tensor passed to a differentiable call - X, the scores, ``edge_weight``, the scales, the node bitmaps, a ``FanoutSample``'s
+    ``thr``, masks and ``counts`` - is kept for the backward by reference through ``save_for_backward``: it must not be edited in place
+    before the backward has run, and autograd raises ("modified by an inplace operation") if it was, instead of differentiating another
+    graph. The adjacency's own tensors and caches are constant by contract and not checked.
 
     With ``reduce="max"`` / ``"min"`` the forward is ``tiledMMFloat(adj, X, reduce=reduce)``; it keeps the winners, and the backward
     gives each element of dY to the neighbour that won it (under ties, all of it to the one ``arg`` names): one gather on the other
