@@ -16,6 +16,12 @@ class SAGEConv(torch.nn.Module):
     """``forward(A, X, seed=None) = lin_self(X) + lin_nbr(agg(X))`` for a ``TiledAdjacency`` A (either view; the neighbours are the
     view's) and float32 X [n, in_features]; ``lin_self`` carries the bias, ``lin_nbr`` has none.
 
+    X and the result are in the EDGE LIST'S numbering, as with every layer of ``conv``: on an adjacency of
+    ``pack_edges_tiled(..., reorder=True)`` the layer reads ``A.to_new(X)``, runs the aggregate and both linear maps there and returns
+    ``A.to_old`` of the sum; on any other adjacency the two are the identity and cost nothing. The sample, ``block.rows`` and
+    ``block.inputs`` stay in the ADJACENCY'S numbering (``fanout.sample_fanout``): the seed set of a mini-batch goes through
+    ``tiled.node_bitmap(A.to_new(flags), A.n)``, and the batch's rows of the result are ``out[flags]``.
+
     ``aggr="mean"`` is ``tiledAggregate(A, X, row_scale=s)`` with s the reciprocal of the number of terms, correctly rounded (the kernel
     of ``mean_scale``), 0 for a node without neighbours; ``aggr="max"`` is ``tiledAggregate(A, X, reduce="max")`` (+0 without
     neighbours).
@@ -58,19 +64,21 @@ class SAGEConv(torch.nn.Module):
                 raise TypeError(f"block must be a fanout.Block (fanout.sample_blocks), not {type(block).__name__}")
             if not isinstance(block.sample, _fanout.FanoutSample) or block.sample.view is not A:   # counts belong to the sample's view
                 raise ValueError("block was sampled on another view than the one passed")
+            Xn = A.to_new(X)
             if self.aggr == "max":
-                agg = tiled.tiledAggregate(A, X, reduce="max", fanout=block.sample)
+                agg = tiled.tiledAggregate(A, Xn, reduce="max", fanout=block.sample)
             else:
-                agg = tiled.tiledAggregate(A, X, block.sample.mean_scale(), fanout=block.sample)
-            return self.lin_self(X) + self.lin_nbr(agg)
+                agg = tiled.tiledAggregate(A, Xn, block.sample.mean_scale(), fanout=block.sample)
+            return A.to_old(self.lin_self(Xn) + self.lin_nbr(agg))
         kw = {}
         if self.training and self.fanout is not None:
             kw["fanout"] = (self.fanout, _draw_edge_seed() if seed is None else seed)
+        Xn = A.to_new(X)
         if self.aggr == "max":
-            agg = tiled.tiledAggregate(A, X, reduce="max", **kw)
+            agg = tiled.tiledAggregate(A, Xn, reduce="max", **kw)
         else:
-            agg = tiled.tiledAggregate(A, X, self.sampled_mean_scale(A) if kw else A.mean_scale(), **kw)
-        return self.lin_self(X) + self.lin_nbr(agg)
+            agg = tiled.tiledAggregate(A, Xn, self.sampled_mean_scale(A) if kw else A.mean_scale(), **kw)
+        return A.to_old(self.lin_self(Xn) + self.lin_nbr(agg))
 
     def extra_repr(self) -> str:
         return f"aggr={self.aggr}, fanout={self.fanout}"

@@ -3,6 +3,8 @@ Welling 2017; Velickovic et al. 2018) as plain torch on the CPU: an n x n matrix
 numbering, matrix products, a row softmax. No call into the library, no tiled format, no tiledAggregate. float64 is the reference;
 the same code in float32 only sizes the tolerance (:func:`tolerances`). Every function returns the output and, for a given dY, the
 gradient for X and for every parameter, worked out by hand (tests/test_layers_reference.py holds them against central differences of the forward).
+:func:`sage_layer` (sage.SAGEConv, Hamilton et al. 2017) takes its gradients from torch.autograd instead; its samples are those of
+tests/tiled_fanout_model.py and tests/tiled_blocks_model.py, NumPy models of the sampling rule that call nothing in the library either.
 
 ``WRONG`` names plausible mistakes; ``wrong=`` evaluates the definition with one of them. They are test aids: the CPU test shows
 that the inputs of the GPU test tell each mistake from the definition.
@@ -11,13 +13,16 @@ that the inputs of the GPU test tell each mistake from the definition.
 import numpy as np
 import torch
 
+import tiled_blocks_model
 import tiled_drop_model
+import tiled_fanout_model
 from tiled_model import random_edges
 
 N_NODES = 300                       # 10 row blocks of 32 and 3 k-quads of 128, the last of each partial
 F_IN, HIDDEN, CLASSES = 12, 20, 7
 GAT_OUT = 7
 DROP_RATE, DROP_SEED = 0.5, 0x0123456789ABCDEF
+BATCH, BATCH_SEED = 24, 41          # the seed nodes of a mini-batch chain: how many, and the generator that picks them
 
 WRONG = ("transposed",              # A of the other view
          "scores_swapped",          # e[i, j] = a_src . h_i + a_dst . h_j
@@ -29,7 +34,10 @@ WRONG = ("transposed",              # A of the other view
          "full_graph_degrees",      # nodes=: the degrees of the whole graph
          "no_keep_scale",           # edge_drop with aggr="sum": no 1 / (1 - rate)
          "mask_in_old_numbering",   # edge_drop under reorder: the edge list's ids are hashed
-         "weights_transposed")      # edge_weight of cell (j, i)
+         "weights_transposed",      # edge_weight of cell (j, i)
+         "mean_by_full_degree",     # sage: the sampled mean divided by deg instead of the kept count
+         "rows_not_moved",          # sage under reorder: X read, and the result left, in the adjacency's numbering
+         "batch_in_old_numbering")  # sage blocks under reorder: the seed flags handed over in the edge list's numbering
 
 
 # ---- the adjacency ------------------------------------------------------------------------------------------------------------------
@@ -263,6 +271,134 @@ def gat_layer(src, dst, n, X, W, a_dst, a_src, dY, view="adj", heads=1, concat=T
     return {"Y": Y, "dX": rec.mm("dX", dh, W.T), "dW": rec.mm("dW", X.T, dh), "da_dst": da_dst, "da_src": da_src}
 
 
+# ---- GraphSAGE ----------------------------------------------------------------------------------------------------------------------
+
+def batch_flags(n=N_NODES):
+    """bool [n]: the BATCH seed nodes of the chained cases, in the edge list's numbering."""
+    flags = np.zeros(n, dtype=bool)
+    flags[np.random.default_rng(BATCH_SEED).permutation(n)[:BATCH]] = True
+    return flags
+
+
+def sage_graph(src, dst, n, view, layers, fanout=None, batch=None, seed=DROP_SEED, rank=None, wrong=None):
+    """(kept, full, order): per layer the bool [n, n] matrix whose row i holds the neighbours node i aggregates over, the matrix of all
+    the view's cells, and the order in which a maximum lists tied neighbours - all three in the edge list's numbering.
+
+    ``fanout`` None: every layer sees the whole neighbourhood. An int k: tiled_fanout_model.kept_edges of fanout k under ``seed`` on the
+    view's axis. A tuple with ``batch`` (bool [n], the seed nodes): the chain of tiled_blocks_model.blocks, input layer first. A sample is
+    taken on the ids of the adjacency's numbering, (rank[s], rank[d]) for every cell, from the moved seed flags, and mapped back."""
+    a = cells(src, dst, n, wrong)
+    flip = (view == "adj.T") != (wrong == "transposed")
+    axis = "col" if flip else "row"
+    own = np.arange(n, dtype=np.int64)
+    new = own if rank is None else np.asarray(rank, dtype=np.int64)
+    if wrong in ("rows_not_moved", "batch_in_old_numbering"):
+        assert rank is not None, wrong
+    ids = own if wrong == "mask_in_old_numbering" else new
+    s, d = np.nonzero(a)
+    es, ed = ids[s], ids[d]                                    # every cell once, in the numbering the sample is taken in
+    if fanout is None:
+        assert batch is None
+        kept = [(es, ed)] * layers
+    elif batch is None:
+        assert layers == 1
+        kept = [tiled_fanout_model.kept_edges(es, ed, n, int(fanout), seed, axis)]
+    else:
+        assert len(fanout) == layers
+        moved = np.zeros(n, dtype=bool)
+        moved[ids] = np.asarray(batch, dtype=bool)             # flags[perm], what to_new gives
+        if wrong == "batch_in_old_numbering":
+            moved = np.asarray(batch, dtype=bool)
+        chain = tiled_blocks_model.blocks(es, ed, n, axis, moved, tuple(fanout), seed)
+        kept = [tiled_blocks_model.kept_edges(es, ed, n, b["k"], b["seed"], axis, b["rows"]) for b in chain]
+    back = own if wrong == "rows_not_moved" else ids           # not moved: the matrices stay in the adjacency's numbering
+
+    def matrix(ks, kd):
+        m = np.zeros((n, n), dtype=bool)
+        m[ks, kd] = True
+        m = m[back][:, back]
+        return np.ascontiguousarray(m.T if flip else m)
+
+    order = torch.arange(n) if wrong == "rows_not_moved" else torch.argsort(torch.from_numpy(new))
+    return [matrix(ks, kd) for ks, kd in kept], matrix(es, ed), order
+
+
+def sage_layer(src, dst, n, X, params, dY, view="adj", aggr="mean", fanout=None, batch=None, seed=DROP_SEED, rank=None,
+               dtype=torch.float64, wrong=None, record=None):
+    """``len(params)`` SAGEConv layers in a row and their gradients by torch.autograd. ``params`` is a list of (W_self [out, in], b [out],
+    W_nbr [out, in]); one layer is Y = X . W_self^T + b + agg(X) . W_nbr^T with agg the mean or (``aggr="max"``) the element-wise maximum
+    over the neighbours of :func:`sage_graph`, +0 for a node without any. The mean divides by the number of neighbours that matrix keeps:
+    deg, min(deg, k) under a fanout, the masked sample's own count in a block. Under a tie the maximum's gradient goes to the tied
+    neighbour with the lowest ``rank`` (the id in the adjacency's numbering; identity when None).
+
+    One layer (``batch`` None) returns {"Y", "dX", "dW_self", "db", "dW_nbr"} for the loss <Y, dY>. A chain (``fanout`` a tuple,
+    ``batch`` the seed flags) returns "Y" on the batch rows only, [batch.sum(), out], and the parameter gradients with the layer's index
+    appended, for the loss (h . dY)[batch].sum(). With ``record`` the backward is also walked by hand, so that every intermediate of
+    it is recorded with its bound; the entries named like a result hold what autograd must give."""
+    assert aggr in ("mean", "max")
+
+    def note(name, t, bound=None):          # the forward carries autograd's graph: the record gets detached values
+        if record is not None:
+            record.add(name, t.detach(), None if bound is None else bound.detach())
+        return t
+
+    def mm(name, a, b):
+        return note(name, a @ b, a.abs() @ b.abs() if record is not None else None)
+
+    L = len(params)
+    kept, full, order = sage_graph(src, dst, n, view, L, fanout, batch, seed, rank, wrong)
+    zero = torch.zeros((), dtype=dtype)
+    x = torch.as_tensor(np.asarray(X), dtype=dtype).clone().requires_grad_(True)
+    dY = torch.as_tensor(np.asarray(dY), dtype=dtype)
+    ps = [tuple(torch.as_tensor(np.asarray(p), dtype=dtype).clone().requires_grad_(True) for p in layer) for layer in params]
+    rows = None if batch is None else torch.from_numpy(np.asarray(batch, dtype=bool))
+    divisor = full.sum(axis=1) if wrong == "mean_by_full_degree" else None
+    if wrong == "mean_by_full_degree":
+        assert aggr == "mean" and fanout is not None
+
+    h, steps = x, []
+    for l, (Ws, b, Wn) in enumerate(ps):
+        m = torch.from_numpy(kept[l])
+        if aggr == "max":
+            win = _first_extremum(m, h.detach(), order, True)
+            agg = torch.where(win >= 0, torch.gather(h, 0, win.clamp(min=0)), zero)
+            steps.append((h, agg, win))
+        else:
+            s = _reciprocal(kept[l].sum(axis=1) if divisor is None else divisor, dtype, False)
+            M = m.to(dtype)
+            agg = note(f"agg{l}", _scaled(mm(f"agg{l} sum", M, h), s))
+            steps.append((h, agg, (M, s)))
+        own, nbr = mm(f"self{l}", h, Ws.T), mm(f"nbr{l}", agg, Wn.T)
+        h = note(f"h{l}", own + b + nbr, h.abs() @ Ws.abs().T + b.abs() + agg.abs() @ Wn.abs().T if record is not None else None)
+    if rows is None:
+        Y, dH = h, dY
+        Y.backward(dY)
+    else:
+        Y, dH = h[rows], torch.where(rows[:, None], dY, zero)
+        (h * dY)[rows].sum().backward()
+    tag = (lambda l: "") if rows is None else str
+    out = {"Y": Y.detach(), "dX": x.grad}
+    for l, (Ws, b, Wn) in enumerate(ps):
+        out.update({f"dW_self{tag(l)}": Ws.grad, f"db{tag(l)}": b.grad, f"dW_nbr{tag(l)}": Wn.grad})
+    if record is not None:
+        with torch.no_grad():
+            for l in range(L - 1, -1, -1):
+                (Ws, b, Wn), (hin, agg, how) = ps[l], steps[l]
+                record.mm(f"dW_self{tag(l)}", dH.T, hin)
+                record.add(f"db{tag(l)}", dH.sum(dim=0), dH.abs().sum(dim=0))
+                record.mm(f"dW_nbr{tag(l)}", dH.T, agg)
+                dagg = record.mm(f"dagg{l}", dH, Wn)
+                if aggr == "max":
+                    through = torch.zeros_like(hin).scatter_add_(0, how.clamp(min=0), torch.where(how >= 0, dagg, zero))
+                    through = record.add(f"dagg{l} scattered", through, torch.zeros_like(hin).scatter_add_(
+                        0, how.clamp(min=0), torch.where(how >= 0, dagg.abs(), zero)))
+                else:
+                    through = record.mm(f"dagg{l} spread", how[0].T, record.add(f"dagg{l} scaled", _scaled(dagg, how[1])))
+                direct = record.mm(f"dh{l} self", dH, Ws)
+                dH = record.add("dX" if l == 0 else f"dh{l}", direct + through, direct.abs() + through.abs())
+    return out
+
+
 # ---- graphs -------------------------------------------------------------------------------------------------------------------------
 
 def dyadic_graph(seed):
@@ -336,8 +472,16 @@ class Case:
 
     @property
     def uses_rank(self):
-        """The reference depends on the adjacency's numbering: the drop mask lives in it, and ties of max / min go by it."""
+        """The reference depends on the adjacency's numbering: the drop mask and the fanout sample live in it, and ties of max / min
+        go by it."""
+        if self.kind == "sage":
+            return self.options.get("fanout") is not None or self.options["aggr"] == "max"
         return self.options.get("drop", False) or self.options.get("aggr", "sum") != "sum"
+
+    @property
+    def chained(self):
+        """A sage case of two layers over the blocks of a mini-batch: ``fanout`` holds one k per layer."""
+        return self.kind == "sage" and isinstance(self.options.get("fanout"), tuple)
 
     def graph(self):
         return GRAPHS["dyadic" if self.exact else "random"]
@@ -359,6 +503,13 @@ class Case:
             if o.get("edge_weight"):
                 t["EW"] = weight(n, n) * cells(src, dst, n)
             return t
+        if self.kind == "sage":
+            dims = (F_IN, HIDDEN, CLASSES) if self.chained else (F_IN, HIDDEN)
+            t = {"X": draw(n, dims[0]), "dY": draw(n, dims[-1])}
+            for l, (fi, fo) in enumerate(zip(dims, dims[1:])):
+                for name, shape in (("W_self", (fo, fi)), ("b", (fo,)), ("W_nbr", (fo, fi))):   # scaled as torch.nn.Linear scales them
+                    t[f"{name}{l}"] = weight(*shape) if self.exact else rng.uniform(-1.0, 1.0, size=shape) / fi ** 0.5
+            return t
         heads, width = o["heads"], o["heads"] * GAT_OUT
         t = {"X": draw(n, F_IN), "W": weight(F_IN, width), "dY": draw(n, width if o["concat"] else GAT_OUT)}
         if self.exact:
@@ -368,10 +519,18 @@ class Case:
             t["a_dst"], t["a_src"] = rng.standard_normal((heads, GAT_OUT)) / GAT_OUT ** 0.5, rng.standard_normal((heads, GAT_OUT)) / GAT_OUT ** 0.5
         return t
 
+    def sage_params(self, t):
+        """[(W_self, b, W_nbr)] of the layers of a sage case, from its inputs ``t``."""
+        return [(t[f"W_self{l}"], t[f"b{l}"], t[f"W_nbr{l}"]) for l in range(2 if self.chained else 1)]
+
     def reference(self, view, dtype=torch.float64, rank=None, wrong=None, record=None):
         """The dense definition on this case: dict of tensors, "Y" and the gradients."""
         src, dst, nodes = self.graph()
         t, o = self.inputs(), self.options
+        if self.kind == "sage":
+            return sage_layer(src, dst, N_NODES, t["X"], self.sage_params(t), t["dY"], view=view, aggr=o["aggr"], fanout=o.get("fanout"),
+                              batch=batch_flags() if self.chained else None, seed=DROP_SEED, rank=rank, dtype=dtype, wrong=wrong,
+                              record=record)
         common = dict(view=view, nodes=nodes if o.get("nodes") else None, dtype=dtype, wrong=wrong, record=record,
                       edge_drop=(DROP_RATE, DROP_SEED, rank) if o.get("drop") else None)
         if self.kind == "gcn":
@@ -415,8 +574,27 @@ def _cases():
     return out
 
 
+def _sage_cases():
+    """The cases of kind "sage", after every other so that no earlier case's inputs move. Exact: fanouts 4 and (4, 2) keep 0, 1, 2 or 4
+    of a node's 0, 1, 4 or 16 neighbours, so every mean divides by a power of two - 1/16 over a whole neighbourhood, 1/4 under k = 4,
+    1/4 . 1/2 through the chain."""
+    moved, sampled, mean = ("rows_not_moved",), _DROP + ("rows_not_moved",), ("mean_by_full_degree",)
+    chain = ("batch_in_old_numbering",)
+    return [Case("sage-mean", "sage", True, _BASE, 16, aggr="mean"),
+            Case("sage-max", "sage", True, _BASE + moved, 1, aggr="max", eval=True),
+            Case("sage-mean-fanout", "sage", True, _BASE + sampled + mean, 4, aggr="mean", fanout=4),
+            Case("sage-max-fanout", "sage", True, _BASE + sampled, 1, aggr="max", fanout=4),
+            Case("sage-mean-blocks", "sage", True, _BASE + sampled + mean + chain, 8, aggr="mean", fanout=(4, 2)),
+            Case("sage-max-blocks", "sage", True, _BASE + sampled + chain, 1, aggr="max", fanout=(4, 2)),
+            Case("sage-mean-random", "sage", False, _BASE, aggr="mean"),
+            Case("sage-mean-fanout-random", "sage", False, _BASE + sampled + mean, aggr="mean", fanout=3),
+            Case("sage-mean-blocks-random", "sage", False, _BASE + sampled + mean + chain, aggr="mean", fanout=(3, 2)),
+            Case("sage-max-blocks-random", "sage", False, _BASE + sampled + chain, aggr="max", fanout=(3, 2))]
+
+
 CASES = []
 CASES.extend(_cases())
+CASES.extend(_sage_cases())
 EXACT_CASES = [c for c in CASES if c.exact]
 TOLERANCE_CASES = [c for c in CASES if not c.exact]
 VIEWS = ("adj", "adj.T")

@@ -1,5 +1,5 @@
-"""conv.GCNConv and conv.GATConv on the device against the dense float64 definitions of tests/layers_reference.py, gradients
-included. Every case runs the real layer on ``adj``, on ``adj.T`` and on both views of ``pack_edges_tiled(..., reorder=True)`` of the
+"""conv.GCNConv, conv.GATConv and sage.SAGEConv (whole neighbourhoods, fixed-fanout samples, two layers over the blocks of a mini-batch)
+on the device against the dense float64 definitions of tests/layers_reference.py, gradients included. Every case runs the real layer on ``adj``, on ``adj.T`` and on both views of ``pack_edges_tiled(..., reorder=True)`` of the
 same edge list, with the parameters the reference used; X and the result are in the edge list's numbering and every element is
 compared. On the dyadic graph with integer data all arithmetic is exact (tests/test_layers_reference.py proves it for these inputs), so
 the four forms give the reference's bits; on the random graph every tensor lies within the tolerance the reference computes for it,
@@ -55,6 +55,9 @@ def _run(torch, qgtc, case, a, train=True, dense=None):
     from qgtc_ppopp22_amd.conv import GATConv, GCNConv
     from qgtc_ppopp22_amd.tiled import edge_slots, edge_values
 
+    if case.kind == "sage":
+        assert dense is None and train
+        return _run_sage(torch, case, a)
     t, o = case.inputs(), case.options
     src, dst, nodes = case.graph()
     X = _dev(torch, t["X"], torch.float32).requires_grad_(True)
@@ -91,6 +94,49 @@ def _run(torch, qgtc, case, a, train=True, dense=None):
         assert slots.min() >= 0 and np.unique(slots).size == slots.size == ew.numel()
         got["dEW"] = np.zeros((N_NODES, N_NODES), dtype=np.float32)
         got["dEW"][r, c] = ew.grad.cpu().numpy()[slots]
+    for v in got.values():
+        assert v.dtype == np.float32
+    return got
+
+
+def _run_sage(torch, case, a):
+    """{name: float32 numpy}: the real sage.SAGEConv on the adjacency (view) ``a`` with the case's parameters - one layer, or two over
+    fanout.sample_blocks of the view with the batch loss. X, dY and the batch flags are in the edge list's numbering, and so is every
+    result; the seed flags are moved as a user must move them, ``node_bitmap(a.to_new(flags), n)``."""
+    from qgtc_ppopp22_amd import fanout as fo
+    from qgtc_ppopp22_amd.sage import SAGEConv
+    from qgtc_ppopp22_amd.tiled import node_bitmap
+
+    t, o = case.inputs(), case.options
+    k = o.get("fanout")
+    layers = []
+    for l, (Ws, b, Wn) in enumerate(case.sage_params(t)):
+        # a block's layer draws nothing, and a layer of the whole neighbourhood has no fanout or is in eval()
+        layer = SAGEConv(Ws.shape[1], Ws.shape[0], aggr=o["aggr"], fanout=k if isinstance(k, int) else 4 if o.get("eval") else None).cuda()
+        with torch.no_grad():
+            for prm, value in ((layer.lin_self.weight, Ws), (layer.lin_self.bias, b), (layer.lin_nbr.weight, Wn)):
+                assert prm.shape == value.shape
+                prm.copy_(_dev(torch, value, torch.float32))
+        layers.append(layer.train(not o.get("eval")))
+    X = _dev(torch, t["X"], torch.float32).requires_grad_(True)
+    dY = _dev(torch, t["dY"], torch.float32)
+    if case.chained:
+        flags = _dev(torch, R.batch_flags())
+        blocks = fo.sample_blocks(a, node_bitmap(a.to_new(flags), N_NODES), k, DROP_SEED)
+        h = X
+        for layer, block in zip(layers, blocks):
+            h = layer(a, h, block=block)
+        (h * dY)[flags].sum().backward()
+        out = {"Y": h[flags], "dX": X.grad}
+        tags = ("0", "1")
+    else:
+        Y = layers[0](a, X, seed=DROP_SEED)
+        Y.backward(dY)
+        out = {"Y": Y, "dX": X.grad}
+        tags = ("",)
+    for tag, layer in zip(tags, layers):
+        out.update({f"dW_self{tag}": layer.lin_self.weight.grad, f"db{tag}": layer.lin_self.bias.grad, f"dW_nbr{tag}": layer.lin_nbr.weight.grad})
+    got = {name: v.detach().cpu().numpy() for name, v in out.items()}
     for v in got.values():
         assert v.dtype == np.float32
     return got

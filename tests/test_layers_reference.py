@@ -1,18 +1,22 @@
 """The dense layer definitions of tests/layers_reference.py checked on the CPU, on the very inputs tests/test_layers_dense_gpu.py
 hands the real layers: the hand-written gradients are the derivatives of the forward, the dyadic cases are exact in float32 (with the
 guard that makes them so), and every WRONG variant is told from the definition - by an element in the exact cases, by 100 times the
-tolerance in the others. No GPU, no call into the library."""
+tolerance in the others. For the SAGE cases also what their samples rest on: kept degrees that are powers of two, nodes with more
+neighbours than the fanout, a kept set that changes with the numbering, chains with a real frontier. No GPU, no call into the library."""
 import numpy as np
 import pytest
 import torch
 
 import layers_reference as R
+import tiled_blocks_model as bm
+import tiled_fanout_model as fm
 from layers_reference import CASES, EXACT_CASES, N_NODES, TOLERANCE_CASES, VIEWS, WRONG
 
 # a numbering other than the edge list's, for the cases whose reference depends on it (the GPU test takes the adjacency's own)
 RANK = np.random.default_rng(5).permutation(N_NODES)
 DEGREES = {0, 1, 4, 16}
 SEPARATION = 100.0
+NEED_A_NUMBERING = ("mask_in_old_numbering", "rows_not_moved", "batch_in_old_numbering")   # they show under a non-identity rank only
 
 
 def _ranks(case):
@@ -117,6 +121,105 @@ def test_gat_gradients_are_the_derivatives(options, view):
     _directional(run, t, {"X": "dX", "W": "dW", "a_dst": "da_dst", "a_src": "da_src"}, dY, 1e-6)
 
 
+@pytest.mark.parametrize("view", VIEWS)
+@pytest.mark.parametrize("options", [dict(aggr="mean"), dict(aggr="max"), dict(aggr="mean", fanout=3), dict(aggr="max", fanout=3),
+                                     dict(aggr="mean", fanout=(3, 2)), dict(aggr="max", fanout=(3, 2))], ids=str)
+def test_sage_gradients_are_the_derivatives(options, view):
+    """torch.autograd's gradients of the dense SAGE definition against central differences, for one layer and for the chain with the
+    batch loss; standard-normal data, so no maximum is tied."""
+    src, dst, _ = R.random_graph(7)
+    n, rng = N_NODES, np.random.default_rng(6)
+    chained = isinstance(options.get("fanout"), tuple)
+    dims = (5, 6, 3) if chained else (5, 6)
+    t = {"X": rng.standard_normal((n, dims[0]))}
+    grads = {"X": "dX"}
+    for l, (fi, fo) in enumerate(zip(dims, dims[1:])):
+        tag = str(l) if chained else ""
+        t[f"W_self{l}"], t[f"b{l}"], t[f"W_nbr{l}"] = rng.standard_normal((fo, fi)), rng.standard_normal(fo), rng.standard_normal((fo, fi))
+        grads.update({f"W_self{l}": f"dW_self{tag}", f"b{l}": f"db{tag}", f"W_nbr{l}": f"dW_nbr{tag}"})
+    dY = rng.standard_normal((n, dims[-1]))
+    batch = R.batch_flags() if chained else None
+
+    def run(v):
+        params = [(v[f"W_self{l}"], v[f"b{l}"], v[f"W_nbr{l}"]) for l in range(len(dims) - 1)]
+        return R.sage_layer(src, dst, n, v["X"], params, dY, view=view, aggr=options["aggr"], fanout=options.get("fanout"), batch=batch,
+                            seed=11, rank=RANK)
+
+    assert run(t)["Y"].shape == ((int(batch.sum()) if chained else n), dims[-1])
+    _directional(run, t, grads, dY[batch] if chained else dY, 1e-6)      # a chain's Y holds the batch rows only
+
+
+def _kept_degrees(src, dst, ids, k, axis, seed=R.DROP_SEED):
+    """(kept cells as a set of (s, d) in the edge list's numbering, the kept degrees of the axis) of the fanout-k sample taken on ids"""
+    s, d = np.nonzero(R.cells(src, dst, N_NODES))
+    ks, kd = fm.kept_edges(ids[s], ids[d], N_NODES, k, seed, axis)
+    inv = np.argsort(ids)
+    return set(zip(inv[ks].tolist(), inv[kd].tolist())), np.bincount(ks if axis == "row" else kd, minlength=N_NODES)
+
+
+@pytest.mark.parametrize("axis", fm.AXES)
+def test_sage_samples_are_dyadic_and_depend_on_the_numbering(axis):
+    """What the exact sampled cases rest on: under k = 4 and k = 2 every kept degree of the dyadic graph is 0, 1, 2 or 4, some node has
+    more than k neighbours (on the random graph under k = 3 too), and a sample taken in another numbering keeps other cells."""
+    own = np.arange(N_NODES)
+    for graph, k, degrees in (("dyadic", 4, {0, 1, 4}), ("dyadic", 2, {0, 1, 2}), ("random", 3, None)):
+        src, dst, _ = R.GRAPHS[graph]
+        a = R.cells(src, dst, N_NODES)
+        deg = a.sum(axis=1 if axis == "row" else 0)
+        assert int((deg > k).sum()) >= 50, "the sample drops something"
+        here, kept_deg = _kept_degrees(src, dst, own, k, axis)
+        there, moved_deg = _kept_degrees(src, dst, RANK, k, axis)
+        assert np.array_equal(kept_deg, np.minimum(deg, k)) and np.array_equal(np.sort(moved_deg), np.sort(kept_deg))
+        assert degrees is None or set(kept_deg.tolist()) == degrees
+        assert len(here) == len(there) == int(np.minimum(deg, k).sum()) < int(a.sum())
+        print(f"{graph} k={k} {axis}: {len(here)} of {int(a.sum())} cells kept, {len(here ^ there)} differ under the relabelling")
+        assert len(here ^ there) > (600 if graph == "dyadic" else len(here) // 4)
+
+
+@pytest.mark.parametrize("axis", fm.AXES)
+@pytest.mark.parametrize("graph, fanouts", [("dyadic", (4, 2)), ("random", (3, 2))])
+def test_sage_chains_have_a_real_frontier(graph, fanouts, axis):
+    """The chained cases: the batch is BATCH nodes, the last block's rows are the batch and the first block has rows outside it and
+    inputs beyond its rows; on the dyadic graph the kept counts are {0, 1, 4} then {0, 1, 2}, in either numbering."""
+    src, dst, _ = R.GRAPHS[graph]
+    batch = R.batch_flags()
+    assert int(batch.sum()) == R.BATCH == 24
+    s, d = np.nonzero(R.cells(src, dst, N_NODES))
+    kept = {}
+    for name, ids in (("own", np.arange(N_NODES)), ("other", RANK)):
+        moved = np.zeros(N_NODES, dtype=bool)
+        moved[ids] = batch
+        first, last = bm.blocks(ids[s], ids[d], N_NODES, axis, moved, fanouts, R.DROP_SEED)
+        assert np.array_equal(last["rows"], moved) and np.array_equal(first["rows"], last["inputs"])
+        rows, inputs = int(first["rows"].sum()), int(first["inputs"].sum())
+        print(f"{graph} {fanouts} {axis} {name} numbering: {rows} rows and {inputs} inputs in the first block")
+        assert R.BATCH < rows < inputs < N_NODES
+        assert int((first["kept"] > 0).sum()) > R.BATCH and int((last["kept"] > 0).sum()) > 0
+        if graph == "dyadic":
+            assert set(first["kept"].tolist()) == {0, 1, 4} and set(last["kept"].tolist()) == {0, 1, 2}
+        inv = np.argsort(ids)
+        kept[name] = [set(zip(*(inv[e].tolist() for e in bm.kept_edges(ids[s], ids[d], N_NODES, b["k"], b["seed"], axis, b["rows"]))))
+                      for b in (first, last)]
+    assert kept["own"][0] != kept["other"][0] and kept["own"][1] != kept["other"][1]
+
+
+def test_sage_cases_are_as_the_gpu_test_needs_them():
+    sage = [c for c in CASES if c.kind == "sage"]
+    assert [c.name for c in sage] == ["sage-mean", "sage-max", "sage-mean-fanout", "sage-max-fanout", "sage-mean-blocks", "sage-max-blocks",
+                                      "sage-mean-random", "sage-mean-fanout-random", "sage-mean-blocks-random", "sage-max-blocks-random"]
+    for c in sage:
+        sampled = c.options.get("fanout") is not None
+        assert c.uses_rank == (sampled or c.options["aggr"] == "max")
+        assert ("rows_not_moved" in c.wrong) == c.uses_rank and ("mask_in_old_numbering" in c.wrong) == sampled
+        assert ("batch_in_old_numbering" in c.wrong) == c.chained and ("mean_by_full_degree" in c.wrong) == (sampled and c.options["aggr"] == "mean")
+        assert c.exact == (not c.name.endswith("-random")) and {"transposed", "multiplicity_kept"} <= set(c.wrong)
+    assert {c.name: c.denominator for c in sage if c.exact} == {"sage-mean": 16, "sage-max": 1, "sage-mean-fanout": 4, "sage-max-fanout": 1,
+                                                                "sage-mean-blocks": 8, "sage-max-blocks": 1}
+    assert {c.name: c.options["fanout"] for c in sage if c.options.get("fanout")} == {
+        "sage-mean-fanout": 4, "sage-max-fanout": 4, "sage-mean-blocks": (4, 2), "sage-max-blocks": (4, 2), "sage-mean-fanout-random": 3,
+        "sage-mean-blocks-random": (3, 2), "sage-max-blocks-random": (3, 2)}
+
+
 def test_leaky_relu_has_the_slope_at_zero():
     """With all scores 0 every logit is exactly 0: the gradient for a_src is the slope times what the identity would give."""
     case = next(c for c in EXACT_CASES if c.name == "gat-zero-h2-concat")
@@ -145,6 +248,11 @@ def test_exact_cases_are_exact_in_float32(case, view):
         # the guard: every intermediate is a multiple of 1 / denominator, and every partial sum behind it, in any order, is below 2^24
         # of those units, so float32 holds each of them exactly
         assert len(rec.items) >= 8
+        if case.kind == "sage":     # autograd's gradients are the ones the record walked by hand, so its bounds cover them
+            walked = {name: value for name, value, _ in rec.items if name in ref64}
+            assert set(walked) == set(ref64) - {"Y"}
+            for name, value in walked.items():
+                assert torch.equal(value, ref64[name]), name
         for name, value, bound in rec.items:
             scaled = value * case.denominator
             assert torch.equal(scaled, scaled.round()), (name, "not a multiple of 1 /", case.denominator)
@@ -161,7 +269,7 @@ def separations(case, view, rank):
     tol = None if case.exact else R.tolerances(right, case.reference(view, torch.float32, rank=rank))
     out = {}
     for wrong in case.wrong:
-        if wrong == "mask_in_old_numbering" and rank is None:
+        if wrong in NEED_A_NUMBERING and rank is None:
             continue
         got = case.reference(view, torch.float64, rank=rank, wrong=wrong)
         if case.exact:
