@@ -84,19 +84,16 @@ class GCNConv_Qnt(torch.nn.Module):
         # edge-list adjacencies: True checks the indices on the device and reads the flag back (one host sync per
         # forward); callers that build their own induced edge lists (sampler.ClusterIter) can switch it off
         self.validate_edges = True
-        self.bit_W_in = None
+        self.bit_W_in = None    # what the last forward packed (kept for callers that read them); never read back by a forward
         self.bit_W_out = None
-        self._packed_from = None   # (device, version of W_in, version of W_out) the packed weights were made from
-
-    def _weights_key(self):
-        return (self.W_in.device, self.W_in._version, self.W_out._version, self.w_bit)
 
     def weight_Qnt(self):
-        """Pack the weights (cols layout: they are right operands). forward() calls this again whenever the
-        parameters moved to another device or were modified in place (optimizer step, load_state_dict)."""
+        """Pack the weights (cols layout: they are right operands): two val2bit launches, on [input_dim, hidden_dim] and
+        [hidden_dim, output_dim]. forward() calls this EVERY time: torch's version counter misses ``p.data.copy_()``, ``p.data = t``,
+        ``vector_to_parameters``, ``half().float()`` and ``load_state_dict(assign=True)``, so nothing short of reading the weights can
+        tell that they moved. val2bit runs on the current stream and is capturable: a captured forward follows the weights' contents."""
         self.bit_W_in = QGTC.val2bit(self.W_in.detach().contiguous(), self.w_bit, True, False)
         self.bit_W_out = QGTC.val2bit(self.W_out.detach().contiguous(), self.w_bit, True, False)
-        self._packed_from = self._weights_key()
 
     def A_Qnt(self, A):
         """A: dense float [n, n], or a (src, dst, n) edge list (packed without the dense detour)."""
@@ -111,8 +108,9 @@ class GCNConv_Qnt(torch.nn.Module):
     def forward(self, A, X):
         """X: node embeddings [n_nodes, n_dim]; A: the subgraph's adjacency (dense or edge list), or a whole graph's
         QGTC.TiledAdjacency (QGTC.pack_edges_tiled)."""
-        if self.bit_W_in is None or self._packed_from != self._weights_key():
-            self.weight_Qnt()
+        if self.aggr not in ("sum", "mean"):   # read at every forward: the constructor's refusal holds for a reassigned value too
+            raise ValueError(f'aggr must be "sum" or "mean", not {self.aggr!r}')
+        self.weight_Qnt()
         assert X.device == self.W_in.device, "inputs and weights must be on the same device"
         n = X.size(0)
         if isinstance(A, QGTC.TiledAdjacency):
@@ -161,7 +159,9 @@ class GCNConv(torch.nn.Module):
 
     ``aggr`` is the reducer of both aggregates: "sum" (the default, under ``norm``), or "max" / "min", the element-wise extremum over
     the neighbours (``tiledAggregate(reduce=)``; the gradient goes to the neighbour that won). An extremum has no normalisation, so
-    "max" / "min" with a ``norm`` is a ValueError, and it needs a QGTC.TiledAdjacency.
+    "max" / "min" with a ``norm`` is a ValueError, and it needs a QGTC.TiledAdjacency. ``norm``, ``aggr`` and ``edge_drop`` are read at
+    every forward and may be reassigned on a live layer; the same refusals hold then (``edge_drop`` where it is assigned, the other two
+    at the next forward).
 
     ``edge_drop`` (a rate in [0, 1), default 0) is DropEdge on a QGTC.TiledAdjacency: in training mode both aggregates of a forward run
     on one random subgraph, ``tiledAggregate(..., edge_drop=(edge_drop, seed))`` with one seed per forward - ``edge_seed`` of
@@ -185,21 +185,39 @@ class GCNConv(torch.nn.Module):
 
     def __init__(self, input_dim, hidden_dim, output_dim, num_layers=2, norm=None, aggr="sum", edge_drop=0.0):
         super().__init__()
-        self.edge_drop = _check_drop_rate(edge_drop)
-        self.keep_scale = float(torch.tensor(1.0 / (1.0 - self.edge_drop), dtype=torch.float64).to(torch.float32))
-        self._keep_vector = None   # norm=None under the mask: keep_scale on every row, per (n, device)
-        if norm not in (None, "mean", "sym"):
-            raise ValueError(f'norm must be None, "mean" or "sym", not {norm!r}')
-        if aggr not in ("sum", "max", "min"):
-            raise ValueError(f'aggr must be "sum", "max" or "min", not {aggr!r}')
-        if aggr != "sum" and norm is not None:
-            raise ValueError(f'aggr="{aggr}" takes no norm (norm={norm!r}): an extremum is not scaled')
+        self.edge_drop = edge_drop
+        self._keep_vector = None   # norm=None under the mask: (keep_scale, the vector holding it on every row), per (n, device, keep_scale)
         self.norm = norm
         self.aggr = aggr
+        self._check_config()
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
 
+    @property
+    def edge_drop(self) -> float:
+        return self._edge_drop
+
+    @edge_drop.setter
+    def edge_drop(self, rate):
+        """``layer.edge_drop = r`` anneals DropEdge: the rate is checked here, and ``keep_scale`` is computed from it."""
+        self._edge_drop = _check_drop_rate(rate)
+
+    @property
+    def keep_scale(self) -> float:
+        """The float32 nearest 1 / (1 - edge_drop), as a Python float: always of the rate the layer holds now."""
+        return float(torch.tensor(1.0 / (1.0 - self._edge_drop), dtype=torch.float64).to(torch.float32))
+
+    def _check_config(self):
+        """``norm`` and ``aggr`` are read at every forward and may be reassigned: the constructor's refusals hold there too."""
+        if self.norm not in (None, "mean", "sym"):
+            raise ValueError(f'norm must be None, "mean" or "sym", not {self.norm!r}')
+        if self.aggr not in ("sum", "max", "min"):
+            raise ValueError(f'aggr must be "sum", "max" or "min", not {self.aggr!r}')
+        if self.aggr != "sum" and self.norm is not None:
+            raise ValueError(f'aggr="{self.aggr}" takes no norm (norm={self.norm!r}): an extremum is not scaled')
+
     def forward(self, A, X, edge_seed=None, nodes=None, edge_weight=None):
+        self._check_config()
         if isinstance(A, QGTC.TiledAdjacency):
             if edge_weight is not None:
                 return self._forward_weighted(A, X, edge_weight, nodes)
@@ -218,12 +236,13 @@ class GCNConv(torch.nn.Module):
 
     def _keep_row_scale(self, A, row):
         """``row`` times keep_scale (one float32 multiply an element); for norm=None the constant vector, cached."""
+        keep = self.keep_scale
         if row is not None:
-            return row * self.keep_scale
-        v = self._keep_vector
-        if v is None or v.numel() != A.n or v.device != A.device:
-            v = self._keep_vector = torch.full((A.n,), self.keep_scale, dtype=torch.float32, device=A.device)
-        return v
+            return row * keep
+        cached = self._keep_vector
+        if cached is None or cached[0] != keep or cached[1].numel() != A.n or cached[1].device != A.device:
+            cached = self._keep_vector = (keep, torch.full((A.n,), keep, dtype=torch.float32, device=A.device))
+        return cached[1]
 
     def _forward_weighted(self, A, X, edge_weight, nodes=None):
         """agg(agg(X . W_in) . W_out) with agg = tiledAggregate(edge_weight=): the plain weighted sum, nothing else."""
@@ -371,7 +390,8 @@ class GATv2Conv(torch.nn.Module):
     ``tiled.tiledEdgeAdditiveAttention(A, hr, hl, hl, att, negative_slope, heads)``: the additive score (include/qgtc_addscore.h), the
     edge softmax and the weighted sum, three launches forward and five backward for all heads, every one specified to the bit and
     without atomics. Unlike GATConv's ``attn=(p, q)`` logit, the nonlinearity sits before the reduction with ``att``, so the ranking of
-    the neighbours depends on the receiving node ("dynamic" attention). With ``share_weights`` W_r is W_l. The heads are concatenated
+    the neighbours depends on the receiving node ("dynamic" attention). With ``share_weights`` W_r is W_l: the matrix is registered once,
+    as ``W_l`` (``state_dict()`` has no "W_r"), and ``layer.W_r`` reads it. The heads are concatenated
     ([n, heads * output_dim]) or, with ``concat=False``, averaged ([n, output_dim]), exactly as TransformerConv does. Trainable in W_l,
     W_r and att ([heads, output_dim]). ``A`` is the view whose rows are the receiving nodes: ``adj`` attends over out-neighbours,
     ``adj.T`` over in-neighbours; on a reordered adjacency X moves to its numbering and the result back. A node without neighbours
@@ -390,9 +410,27 @@ class GATv2Conv(torch.nn.Module):
         self.input_dim, self.output_dim, self.heads, self.concat = int(input_dim), int(output_dim), int(heads), bool(concat)
         self.negative_slope, self.share_weights = slope, bool(share_weights)
         self.W_l = torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
-        self.W_r = self.W_l if self.share_weights else torch.nn.Parameter(
-            torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
+        if not self.share_weights:   # shared: ONE registered name, so a state dict has one tensor for it (see __getattr__)
+            self.W_r = torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
         self.att = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
+
+    def __getattr__(self, name):
+        # With share_weights W_r is whatever W_l is now - also after load_state_dict(assign=True) replaced it. A second registered
+        # name for the one Parameter would give state_dict() two keys, and loading two differing tensors would keep the last silently.
+        if name == "W_r" and self.__dict__.get("share_weights"):
+            return self.W_l
+        return super().__getattr__(name)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A shared layer takes a "W_r" entry only when it equals "W_l" (checkpoints of shared layers from before carried both keys);
+        two differing tensors for the one matrix are an error, never a silent choice."""
+        if self.share_weights and prefix + "W_r" in state_dict:
+            left, right = state_dict.get(prefix + "W_l"), state_dict[prefix + "W_r"]
+            if left is not None and left.shape == right.shape and torch.equal(left.to(right.device), right):
+                state_dict.pop(prefix + "W_r")   # load_state_dict works on its own shallow copy of the caller's dict
+            else:
+                error_msgs.append(f'"{prefix}W_r" differs from "{prefix}W_l", and this layer has share_weights=True: it holds one matrix')
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
     def forward(self, A, X):
         if not isinstance(A, QGTC.TiledAdjacency):
