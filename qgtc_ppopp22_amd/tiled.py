@@ -85,17 +85,18 @@ layer on top.
 ``fanout=(k, seed)`` on :func:`tiledMMFloat` and :func:`tiledAggregate` aggregates over a fixed-fanout sample - at most k neighbours per
 output row, drawn inside the tile walk (include/qgtc_fanout.h): one selection launch gives a threshold per row, the aggregate then keeps
 a cell when its hash reaches its row's threshold, and a backward on the other view looks the thresholds up per neighbour. The module
-``fanout`` has the sample (``sample_fanout``, ``FanoutSample``), the ctypes calls and the allocations; ``sage.SAGEConv`` is the layer on top.
+``fanout`` re-exports the sample (``sample_fanout``, ``FanoutSample``, defined here beside the other subgraphs of a call) and has the mini-batch
+chain; the launches and their allocations are the family launchers' below. ``sage.SAGEConv`` is the layer on top.
 A sample taken under node masks (``fanout.sample_fanout(view, k, seed, row_mask=, nbr_mask=)``; include/qgtc_blocks.h) carries them, and
 ``fanout=`` then runs on the induced subgraph: mini-batch GraphSAGE (``fanout.frontier``, ``fanout.sample_blocks``, ``SAGEConv(block=)``).
 """
 from __future__ import annotations
 
+import ctypes
 import math
+from typing import NamedTuple
 
 import torch
-
-import ctypes
 
 from . import cabi, load_ext
 
@@ -152,6 +153,7 @@ class TiledAdjacency:
     def __init__(self, n: int, row_ptr: torch.Tensor, kquad: torch.Tensor, tiles: torch.Tensor, perm: torch.Tensor | None = None,
                  rank: torch.Tensor | None = None):
         self.n = int(n)
+        self.mask_words = _mask_words(self.n)   # the int32 words of a node bitmap of this graph
         self.row_ptr, self.kquad, self.tiles = row_ptr, kquad, tiles
         self.perm, self.rank = perm, rank
         self.transposed = False
@@ -197,7 +199,7 @@ class TiledAdjacency:
         return self._max_block_tiles
 
     def _degree_tensors(self):
-        base = self._other if self.transposed else self
+        base = _base(self)
         if base._degrees is None:
             base._degrees = _ext._tiled_degrees(base.row_ptr, base.kquad, base.tiles, base.n)
         return base._degrees
@@ -237,7 +239,7 @@ class TiledAdjacency:
         ``nbr_mask`` the masked graph's (as in :meth:`degrees`; not cached; the same inverse-square-root kernel)."""
         if row_mask is not None or nbr_mask is not None:
             return _ext._tiled_inv_sqrt_degree(self._masked_degrees(row_mask, nbr_mask))
-        base = self._other if self.transposed else self
+        base = _base(self)
         if base._sym is None:
             deg = self._degree_tensors()
             base._sym = [_ext._tiled_inv_sqrt_degree(deg[0]), _ext._tiled_inv_sqrt_degree(deg[1])]
@@ -247,7 +249,7 @@ class TiledAdjacency:
         """The dense rows-layout words [PAD8(n), S128(n)*4] (what ``pack_edges(src, dst, n, n, 1)`` returns; transposed, what
         ``pack_edges(dst, src, n, n, 1)`` returns). A test aid for small n."""
         if self.transposed:
-            n, p8, w = self.n, (self.n + 7) // 8 * 8, (self.n + 127) // 128 * 4
+            n, p8, w = self.n, (self.n + 7) // 8 * 8, self.mask_words
             shifts = 31 - torch.arange(32, device=self.device, dtype=torch.int64)
             bits = (self._other.to_rows().to(torch.int64)[:, :, None] >> shifts) & 1            # [P8, W, 32]
             dense = torch.zeros((p8, w * 32), dtype=torch.int64, device=self.device)
@@ -294,6 +296,23 @@ class TiledAdjacency:
                 f"transposed={self.transposed})")
 
 
+def _base(adj: TiledAdjacency) -> TiledAdjacency:
+    """The untransposed adjacency of either view: the owner of what both views share."""
+    return adj._other if adj.transposed else adj
+
+
+def _mask_words(n: int) -> int:
+    """S128(n) * 4: the int32 words of a node bitmap, and of one row of the dense rows layout."""
+    return (n + 127) // 128 * 4
+
+
+def _to_new_ids(rank: torch.Tensor, n: int, src: torch.Tensor, dst: torch.Tensor):
+    """(src, dst) of an edge list moved to the numbering of ``rank``; out-of-range ids stay out of range (the packer and the slot search
+    skip them)."""
+    ok_s, ok_d = (src >= 0) & (src < n), (dst >= 0) & (dst < n)
+    return torch.where(ok_s, rank.index_select(0, src.clamp(0, n - 1)), src), torch.where(ok_d, rank.index_select(0, dst.clamp(0, n - 1)), dst)
+
+
 def reorder_nodes(src: torch.Tensor, dst: torch.Tensor, n: int, sweeps: int = 20, cap: int = 128, validate: bool = True) -> torch.Tensor:
     """perm (int64 [n] on the edges' device, perm[new] = old): a numbering under which neighbours have nearby ids, from size-capped
     label propagation on the symmetrised graph (``sweeps`` 0 .. 64, communities of about ``cap`` nodes; include/qgtc.h,
@@ -312,10 +331,7 @@ def pack_edges_tiled(src: torch.Tensor, dst: torch.Tensor, n: int, validate: boo
         return TiledAdjacency(n, row_ptr, kquad, tiles)
     perm, rank = _ext._reorder_nodes(src, dst, int(n), 20, 128, bool(validate))
     if src.numel():
-        # out-of-range indices stay out of range (the packer skips them); the others move to their new ids
-        ok_s, ok_d = (src >= 0) & (src < n), (dst >= 0) & (dst < n)
-        src = torch.where(ok_s, rank.index_select(0, src.clamp(0, n - 1)), src)
-        dst = torch.where(ok_d, rank.index_select(0, dst.clamp(0, n - 1)), dst)
+        src, dst = _to_new_ids(rank, n, src, dst)
     row_ptr, kquad, tiles = _ext._tiled_pack(src.contiguous(), dst.contiguous(), int(n), False)
     return TiledAdjacency(n, row_ptr, kquad, tiles, perm, rank)
 
@@ -452,11 +468,6 @@ def _edge_drop_key(edge_drop):
     return int(math.floor(rate * 4294967296.0)), seed
 
 
-def _drop_kw(key) -> dict:
-    """The binding's keyword for a checked key; without a mask no keyword at all, which is the call the binding always took."""
-    return {} if key is None else {"edge_drop": key}
-
-
 def node_bitmap(nodes: torch.Tensor, n: int) -> torch.Tensor:
     """int32 [S128(n) * 4]: the bitmap of a node set (include/qgtc.h, "Node masks"; node i at word i >> 5, bit 31 - (i & 31), pad bits
     zero), on the device of ``nodes`` (a GPU), built by one small kernel on the current stream (the C entry qgtc_node_bitmap, called
@@ -482,7 +493,7 @@ def node_bitmap(nodes: torch.Tensor, n: int) -> torch.Tensor:
         flags[nodes] = True   # duplicates write the same value
     else:
         raise TypeError(f"nodes must be bool or int64, not {nodes.dtype}")
-    out = torch.empty((n + 127) // 128 * 4, dtype=torch.int32, device=flags.device)
+    out = torch.empty(_mask_words(n), dtype=torch.int32, device=flags.device)
     _c_call("node_bitmap", flags, _c_abi().qgtc_node_bitmap, flags.data_ptr(), n, out.data_ptr(), out.numel())
     return out
 
@@ -492,7 +503,7 @@ def _check_mask(adj: TiledAdjacency, mask, name: str) -> None:
         raise TypeError(f"{name} must be a torch.Tensor (the int32 bitmap of tiled.node_bitmap) or None")
     if mask.dtype != torch.int32:
         raise TypeError(f"{name} must be int32 (tiled.node_bitmap), not {mask.dtype}")
-    words = (adj.n + 127) // 128 * 4
+    words = adj.mask_words
     if mask.dim() != 1 or mask.numel() != words:
         raise ValueError(f"{name} must have shape [{words}] (S128(n) * 4 words), not {list(mask.shape)}")
     if mask.device != adj.device:
@@ -501,38 +512,230 @@ def _check_mask(adj: TiledAdjacency, mask, name: str) -> None:
         raise ValueError(f"{name} must be contiguous")
 
 
-def _nodes_kw(adj: TiledAdjacency, row_mask, nbr_mask, key) -> dict:
-    """The binding's keyword for checked masks; without a mask no keyword at all, which is the call the binding always took."""
+def _check_k_seed(k, seed) -> None:
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"fanout's k must be an int >= 1, not {type(k).__name__}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"fanout's seed must be an int in [0, 2^64), not {type(seed).__name__}")
+    if k < 1:
+        raise ValueError(f"fanout's k must be at least 1, not {k!r}")
+    if not 0 <= seed < (1 << 64):
+        raise ValueError(f"fanout's seed must lie in [0, 2^64), not {seed!r}")
+
+
+class FanoutSample:
+    """A fixed-fanout sample: the view it was taken on (``view``: ``adj`` samples the rows of A, ``adj.T`` its columns), ``k``, ``seed``
+    and ``thr`` (int32 storage of the uint32 thresholds, [n], on the adjacency's device). Cell (i, j) of A is kept when
+    ``H(i, j, seed) >= thr[u]`` with u the cell's coordinate on the sampled axis: exactly min(deg, k) cells per node of that axis.
+
+    A MASKED sample (``sample_fanout(..., row_mask=, nbr_mask=)``) also carries the two bitmaps, relative to ``view`` (either may be None:
+    all nodes), and ``counts`` int32 [n], the kept neighbours per node: min(deg_m, k) inside ``row_mask``, 0 outside. A cell is then kept
+    when its sampled end is in ``row_mask``, its other end in ``nbr_mask`` and the hash test holds."""
+
+    def __init__(self, view: TiledAdjacency, k: int, seed: int, thr: torch.Tensor, row_mask: torch.Tensor | None = None,
+                 nbr_mask: torch.Tensor | None = None, counts: torch.Tensor | None = None):
+        self.view, self.k, self.seed, self.thr = view, k, seed, thr
+        self.row_mask, self.nbr_mask, self.counts = row_mask, nbr_mask, counts
+
+    def mean_scale(self) -> torch.Tensor:
+        """float32 [n]: the reciprocal of the number of kept neighbours, correctly rounded, 0 where there are none - ``row_scale`` of the
+        mean over the sample on ``view``. Unmasked that is 1 / min(deg, k)."""
+        if self.counts is not None:
+            return _inv_degree(self.counts)
+        if _masked(self):
+            raise ValueError("a masked FanoutSample needs its counts for the mean (sample_fanout returns them)")
+        return _inv_degree(self.view.degrees().clamp(max=min(self.k, (1 << 31) - 1)))
+
+    def __repr__(self) -> str:
+        masks = "".join(f", {name}" for name, m in (("row_mask", self.row_mask), ("nbr_mask", self.nbr_mask)) if m is not None)
+        return (f"FanoutSample(k={self.k}, seed={self.seed:#x}, axis={'columns' if self.view.transposed else 'rows'}, "
+                f"n={self.view.n}{masks})")
+
+
+def check_fanout(adj: TiledAdjacency, fanout) -> None:
+    """The refusals of ``fanout=`` itself: a pair (k, seed) with k an int >= 1 and the seed under ``edge_drop``'s rules, or a
+    :class:`FanoutSample` of this adjacency (either view). Anything else is a TypeError; a sample of another adjacency a ValueError."""
+    if isinstance(fanout, FanoutSample):
+        if not isinstance(fanout.view, TiledAdjacency) or _base(fanout.view) is not _base(adj):
+            raise ValueError("fanout is a sample of another adjacency")
+        _check_k_seed(fanout.k, fanout.seed)
+        # the C entries take no length for thr and the kernels index it by node id: this is the only guard of a hand-built sample
+        thr = fanout.thr
+        if not isinstance(thr, torch.Tensor):
+            raise TypeError(f"a FanoutSample's thr must be a torch.Tensor (int32 [{adj.n}]), not {type(thr).__name__}")
+        if thr.dtype != torch.int32:
+            raise TypeError(f"a FanoutSample's thr must be int32 (the uint32 thresholds' words), not {thr.dtype}")
+        if thr.dim() != 1 or thr.numel() != adj.n:
+            raise ValueError(f"a FanoutSample's thr must have shape [{adj.n}], not {list(thr.shape)}")
+        if thr.device != adj.device:
+            raise ValueError(f"a FanoutSample's thr must be on the adjacency's device {adj.device}, not {thr.device}")
+        if not thr.is_contiguous():
+            raise ValueError("a FanoutSample's thr must be contiguous")
+        for name in ("row_mask", "nbr_mask"):   # bitmaps relative to the sample's view; both views have the adjacency's n and device
+            if getattr(fanout, name) is not None:
+                _check_mask(adj, getattr(fanout, name), f"a FanoutSample's {name}")
+        counts = fanout.counts
+        if counts is not None:
+            if not isinstance(counts, torch.Tensor):
+                raise TypeError(f"a FanoutSample's counts must be a torch.Tensor (int32 [{adj.n}]), not {type(counts).__name__}")
+            if counts.dtype != torch.int32:
+                raise TypeError(f"a FanoutSample's counts must be int32, not {counts.dtype}")
+            if counts.dim() != 1 or counts.numel() != adj.n:
+                raise ValueError(f"a FanoutSample's counts must have shape [{adj.n}], not {list(counts.shape)}")
+            if counts.device != adj.device:
+                raise ValueError(f"a FanoutSample's counts must be on the adjacency's device {adj.device}, not {counts.device}")
+            if not counts.is_contiguous():
+                raise ValueError("a FanoutSample's counts must be contiguous")
+        return
+    if not isinstance(fanout, (tuple, list)) or len(fanout) != 2:
+        raise TypeError("fanout must be a pair (k, seed), a FanoutSample or None")
+    _check_k_seed(*fanout)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _masked(of) -> bool:
+    """Whether a subgraph, or a sample, carries a node bitmap."""
+    return of.row_mask is not None or of.nbr_mask is not None
+
+
+_NO_KW: dict = {}   # read only: ``**`` copies it, and ``_call`` hands pybind11 no dictionary when it is empty
+
+
+class _Subgraph(NamedTuple):
+    """The subgraph one call aggregates over, of exactly one kind: ALL nodes and edges (the one
+    instance ``_ALL``: a plain call constructs nothing), edge dropout (``key``, the checked (threshold, seed)), node masks (``row_mask`` /
+    ``nbr_mask``, relative to the view of the call, either may be None) or a :class:`FanoutSample` (which carries its own masks, relative
+    to the view it was taken on). ``_resolve`` builds it once, through :meth:`of`; the launchers, the C tails and the backwards ask it,
+    and nobody else tells the kinds apart. ``kw`` is what the extension's bindings take for it - no keyword, ``edge_drop=`` or
+    ``node_masks=`` -, or None: a sample has no binding route; ``suffix`` is what the name of a C entry ends in for it. (Fields, not
+    methods: every launch reads one of them.)"""
+    key: tuple | None = None
+    row_mask: torch.Tensor | None = None
+    nbr_mask: torch.Tensor | None = None
+    sample: FanoutSample | None = None
+    kw: dict | None = _NO_KW
+    suffix: str = ""
+
+    @classmethod
+    def of(cls, key=None, row_mask=None, nbr_mask=None, sample=None) -> "_Subgraph":
+        """The subgraph of checked arguments, at most one kind of which is set; the one place that writes ``kw`` and ``suffix``. (The
+        fields are passed by position: a NamedTuple takes keywords at half again the cost, on every masked call.)"""
+        if sample is not None:
+            return cls(None, None, None, sample, None, "_fanout_nodes" if _masked(sample) else "_fanout")
+        if key is not None:
+            return cls(key, None, None, None, {"edge_drop": key}, "_drop")
+        if row_mask is None and nbr_mask is None:
+            return _ALL
+        return cls(None, row_mask, nbr_mask, None, {"node_masks": (row_mask, nbr_mask)}, "_nodes")
+
+    def c_tail(self, adj: TiledAdjacency) -> tuple:
+        """The trailing arguments of a C entry on the view of ``adj``. A key is (threshold, seed); node masks are (row_mask, nbr_mask,
+        mask_words). A sample is (thr, thr_of_nbr, seed): OWN (0) on the view it was taken on, NBR (1) on the other - check_fanout has made
+        sure that both views belong to one adjacency, so their direction alone tells them apart - and a masked sample adds its bitmaps
+        relative to the view walked: its own on its own view, the two swapped on the other."""
+        if self is _ALL:
+            return ()
+        if self.key is not None:
+            return tuple(self.key)
+        s = self.sample
+        if s is None:
+            return _ptr(self.row_mask), _ptr(self.nbr_mask), adj.mask_words
+        nbr = int(s.view.transposed != adj.transposed)
+        tail = (s.thr.data_ptr(), nbr, s.seed)
+        if _masked(s):
+            row, other = (s.nbr_mask, s.row_mask) if nbr else (s.row_mask, s.nbr_mask)
+            tail += (_ptr(row), _ptr(other), adj.mask_words)
+        return tail
+
+    def other(self) -> "_Subgraph":
+        """Itself as the other view sees it - what every backward needs: node masks swapped (a neighbour there is an output row
+        here); a key and a sample unchanged (both name cells of the adjacency, and ``c_tail`` reads a sample per view)."""
+        if self.row_mask is None and self.nbr_mask is None:
+            return self
+        return self.of(row_mask=self.nbr_mask, nbr_mask=self.row_mask)
+
+    def tensors(self) -> tuple:
+        """Its tensors, for ``save_for_backward`` (None where it has none): every tensor a backward reads goes through there - a
+        reference, nothing is copied -, so that autograd's version check sees an in-place edit between the forward and the backward and
+        raises instead of differentiating another graph."""
+        s = self.sample
+        return (self.row_mask, self.nbr_mask) if s is None else (s.thr, s.row_mask, s.nbr_mask, s.counts)
+
+    def rebuilt(self, tensors) -> "_Subgraph":
+        """Itself in a backward, from the saved (version-checked) ``tensors()``."""
+        s = self.sample
+        if s is not None:
+            return self.of(sample=FanoutSample(s.view, s.k, s.seed, *tensors))
+        if self.row_mask is None and self.nbr_mask is None:
+            return self
+        return self.of(row_mask=tensors[0], nbr_mask=tensors[1])
+
+
+_ALL = _Subgraph()
+
+
+def _view_args(adj: TiledAdjacency) -> tuple:
+    """(the view's index pointers, tiles, n_tiles, n) as every C entry takes them first; an adjacency without tiles passes NULL
+    pointers. The one place that turns a view into pointer arguments."""
+    T = adj.n_tiles
+    view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles) if adj.transposed else (adj.row_ptr, adj.kquad, adj.tiles)
+    return tuple(t.data_ptr() if T else None for t in view) + (T, adj.n)
+
+
+def _c_name(stem: str, heads, transposed: bool, sub: _Subgraph = _ALL) -> str:
+    """The name of the C entry of a family: ``stem`` (the plain single-head entry of the row view, ending in ``_f32`` where it has
+    heads), ``_heads`` before that ending for the entry with heads, ``_t`` on ``adj.T``, then the subgraph's suffix. The one place
+    that composes a name; it opens no library."""
+    if heads:
+        stem = stem[:-len("_f32")] + "_heads_f32"
+    return stem + ("_t" if transposed else "") + sub.suffix
+
+
+def _c_entry(stem: str, heads, adj: TiledAdjacency, sub: _Subgraph = _ALL):
+    return getattr(_c_abi(), _c_name(stem, heads, adj.transposed, sub))
+
+
+def sample_fanout(adj_view: TiledAdjacency, k: int, seed: int, row_mask: torch.Tensor | None = None,
+                  nbr_mask: torch.Tensor | None = None) -> FanoutSample:
+    """The sample of fanout ``k`` under ``seed`` on the view passed (``adj``: at most k out-neighbours per row of A; ``adj.T``: at most k
+    in-neighbours per column): one selection launch on the current stream, no host read. The sample is in the adjacency's own numbering
+    (the new ids on a reordered adjacency).
+
+    With ``row_mask`` and / or ``nbr_mask`` (bitmaps of ``tiled.node_bitmap``, relative to the view passed) the sample is taken on the
+    induced subgraph: only the nodes of ``row_mask`` are sampled, among their neighbours in ``nbr_mask``; a node outside ``row_mask``
+    keeps nothing and none of its tiles is read. Still one launch; the sample carries the masks and ``counts``. It is, word for word, the
+    unmasked sample of ``pack_edges_tiled`` of the edges between the two sets."""
+    _check(adj_view)
+    _check_k_seed(k, seed)
+    thr = torch.empty(adj_view.n, dtype=torch.int32, device=adj_view.device)
     if row_mask is None and nbr_mask is None:
-        return {}
-    if row_mask is not None:
-        _check_mask(adj, row_mask, "row_mask")
-    if nbr_mask is not None:
-        _check_mask(adj, nbr_mask, "nbr_mask")
-    if key is not None:
-        raise ValueError("row_mask / nbr_mask cannot be combined with edge_drop: not built")
-    return {"node_masks": (row_mask, nbr_mask)}
+        _c_call("the fanout selection", thr, _c_entry("qgtc_tiled_fanout_thr", False, adj_view), *_view_args(adj_view),
+                min(k, (1 << 31) - 1), seed, thr.data_ptr(), thr.numel())
+        return FanoutSample(adj_view, k, seed, thr)
+    for name, mask in (("row_mask", row_mask), ("nbr_mask", nbr_mask)):
+        if mask is not None:
+            _check_mask(adj_view, mask, name)
+    masks = _Subgraph.of(row_mask=row_mask, nbr_mask=nbr_mask)
+    counts = torch.empty(adj_view.n, dtype=torch.int32, device=adj_view.device)
+    _c_call("the masked fanout selection", thr, _c_entry("qgtc_tiled_fanout_thr", False, adj_view, masks), *_view_args(adj_view),
+            min(k, (1 << 31) - 1), seed, thr.data_ptr(), thr.numel(), counts.data_ptr(), counts.numel(), *masks.c_tail(adj_view))
+    return FanoutSample(adj_view, k, seed, thr, row_mask, nbr_mask, counts)
 
 
-def _fanout_kw(adj: TiledAdjacency, fanout, key, nodes_kw, edge_weight, attn) -> dict:
-    """The keyword of a checked ``fanout=`` (a pair (k, seed) or a ``fanout.FanoutSample``; the module ``fanout`` has the checks, the
-    launches and the allocations), after the refusals of what is not built with it."""
-    from . import fanout as _fanout
-
-    _fanout.check_fanout(adj, fanout)
-    for name, on in (("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)), ("edge_weight", edge_weight is not None),
-                     ("[n, H] scores", isinstance(attn, (tuple, list)) and len(attn) == 2
-                      and bool(_attn_heads(adj, attn[0]) or _attn_heads(adj, attn[1])))):
-        if on:
-            raise ValueError(f"fanout cannot be combined with {name}: not built")
-    return {"fanout": fanout}
+def as_sample(adj: TiledAdjacency, fanout) -> FanoutSample:
+    """The checked ``fanout=`` as a sample: a pair is drawn on the view passed (one selection launch), a sample is itself."""
+    check_fanout(adj, fanout)
+    return fanout if isinstance(fanout, FanoutSample) else sample_fanout(adj, int(fanout[0]), int(fanout[1]))
 
 
 def _value_index(adj: TiledAdjacency):
     """(val_ptr int64 [T + 1], val_row int16 [T, 32], nnz) of include/qgtc.h, "Edge values": one kernel for the tiles' bit counts and the
     in-tile row prefix, ``torch.cumsum`` for the scan, one host read for nnz. Built on first use and kept on the untransposed adjacency
     for both views."""
-    base = adj._other if adj.transposed else adj
+    base = _base(adj)
     if base._val_index is None:
         T = base.n_tiles
         counts = torch.empty(T, dtype=torch.int64, device=base.device)
@@ -571,18 +774,14 @@ def _check_edge_vector(adj: TiledAdjacency, values, name: str, X=None) -> None:
         raise ValueError(f"{name} must be contiguous")
 
 
-def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, nodes_kw=None, reduce: str = "sum", attn=None,
+def _check_edge_weight(adj: TiledAdjacency, values, src_scale=None, key=None, masked: bool = False, reduce: str = "sum", attn=None,
                        X=None) -> None:
     """The refusals of ``edge_weight``: the combinations that are not built, then the vector itself."""
-    for name, on in (("src_scale", src_scale is not None), ("edge_drop", key is not None), ("row_mask / nbr_mask", bool(nodes_kw)),
+    for name, on in (("src_scale", src_scale is not None), ("edge_drop", key is not None), ("row_mask / nbr_mask", masked),
                      (f'reduce="{reduce}"', reduce != "sum"), ("attn", attn is not None)):
         if on:
             raise ValueError(f"edge_weight cannot be combined with {name}: not built")
     _check_edge_vector(adj, values, "edge_weight", X)
-
-
-def _base(adj: TiledAdjacency) -> TiledAdjacency:
-    return adj._other if adj.transposed else adj
 
 
 def edge_slots(adj: TiledAdjacency, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
@@ -601,9 +800,7 @@ def edge_slots(adj: TiledAdjacency, src: torch.Tensor, dst: torch.Tensor) -> tor
         raise ValueError("src and dst must have the same length")
     n = base.n
     if base.rank is not None and src.numel():
-        ok_s, ok_d = (src >= 0) & (src < n), (dst >= 0) & (dst < n)
-        src = torch.where(ok_s, base.rank.index_select(0, src.clamp(0, n - 1)), src)
-        dst = torch.where(ok_d, base.rank.index_select(0, dst.clamp(0, n - 1)), dst)
+        src, dst = _to_new_ids(base.rank, n, src, dst)
     src, dst = src.contiguous(), dst.contiguous()
     val_ptr, val_row, _ = _value_index(base)
     out = torch.empty(src.numel(), dtype=torch.int64, device=base.device)
@@ -672,13 +869,11 @@ def _check_heads(heads, width: int) -> int:
 
 
 def _view_ptrs(adj: TiledAdjacency):
-    """What every entry of include/qgtc_heads.h takes first: the view's index pointers and tiles, then n_tiles and n - and the pointers
-    of the value index, which come later in the argument lists. The one place that turns a view into pointer arguments."""
-    base = _base(adj)
-    val_ptr, val_row, _ = _value_index(base)
-    T = base.n_tiles
-    view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles) if adj.transposed else (adj.row_ptr, adj.kquad, adj.tiles)
-    return tuple(t.data_ptr() if T else None for t in view) + (T, adj.n), (val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
+    """What every entry of include/qgtc_heads.h takes: ``_view_args`` first - and the pointers of the value index, which come later in
+    the argument lists."""
+    val_ptr, val_row, _ = _value_index(adj)
+    T = adj.n_tiles
+    return _view_args(adj), (val_ptr.data_ptr() if T else None, val_row.data_ptr() if T else None)
 
 
 def _sddmm(base: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
@@ -717,73 +912,125 @@ def tiledSDDMM(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int
     return out if heads > 1 else out.view(-1)
 
 
+# ---- one launcher per family: (adj, operands..., subgraph) -> freshly allocated outputs --------------------
+def _c_route(heads, sub: _Subgraph) -> bool:
+    """The route of one launch, chosen here for every family. False: the extension's binding, which takes one head under no mask,
+    edge dropout or node masks. True: the C entry through ctypes, which takes heads and samples. Heads over a sample are not built:
+    ``_resolve`` refuses them first, so that ValueError is never reached through a public call."""
+    if sub.kw is not None:
+        return bool(heads)
+    if heads:
+        raise ValueError("fanout cannot be combined with [n, H] scores: not built")
+    return True
+
+
+def _c_launch(what: str, on: torch.Tensor, stem: str, heads, adj: TiledAdjacency, sub: _Subgraph, *args) -> None:
+    """One launch of the C entry of (``stem``, heads, the view, the subgraph): the view's arguments, the operands, ``heads`` where the
+    entry has them, the subgraph's tail."""
+    _c_call(f"the {what} with heads" if heads else f"the sampled {what}", on, getattr(_c_abi(), _c_name(stem, heads, adj.transposed, sub)),
+            *_view_args(adj), *args, *((heads,) if heads else ()), *sub.c_tail(adj))
+
+
+def _sum(adj: TiledAdjacency, X: torch.Tensor, row_scale, src_scale, sub: _Subgraph) -> torch.Tensor:
+    """diag(row_scale) . A . diag(src_scale) . X over the subgraph, either scale optional: one launch."""
+    if sub.kw is not None:   # _c_route(0, sub), inline: every plain call comes through here
+        if src_scale is not None:
+            return _call(adj, "_tiled_mm_f32_src", X, row_scale, src_scale, **sub.kw)
+        return _call(adj, "_tiled_mm_f32", X, row_scale, **sub.kw)
+    out = torch.empty_like(X)
+    _c_launch("sum", X, "qgtc_tiledmm_f32", 0, adj, sub, X.data_ptr(), X.numel(), X.size(1), _ptr(row_scale), _ptr(src_scale),
+              out.data_ptr(), out.numel())
+    return out
+
+
+def _extremum(adj: TiledAdjacency, X: torch.Tensor, reduce: str, return_arg: bool, sub: _Subgraph):
+    """(out, arg or None): the element-wise "max" / "min" over the subgraph's neighbours and the winners; one launch."""
+    if sub.kw is not None:   # _c_route(0, sub), inline
+        res = _call(adj, "_tiled_mm_f32", X, reduce=reduce, return_arg=return_arg, **sub.kw)
+        return res[0], res[1] if return_arg else None
+    out = torch.empty_like(X)
+    arg = torch.empty(X.shape, dtype=torch.int32, device=X.device) if return_arg else None
+    _c_launch("extremum", X, "qgtc_tiledmax_f32", 0, adj, sub, X.data_ptr(), X.numel(), X.size(1), 0 if reduce == "max" else 1,
+              out.data_ptr(), out.numel(), _ptr(arg), 0 if arg is None else arg.numel())
+    return out, arg
+
+
 def _att(adj: TiledAdjacency, X: torch.Tensor, **kw):
     """The ``att_mode`` keyword overload of the binding on this view (include/qgtc.h, "Attention tiled products")."""
     return _call(adj, "_tiled_mm_f32", X, **kw)
 
 
-def _tiled_attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, mask_kw: dict):
-    """(out, m, inv): the N = 1 max launch gives M, the largest neighbour score of every row, then one product launch. Under a mask
-    (``mask_kw``, the checked keyword of the binding) both launches take it: M must be the maximum over the KEPT neighbours, or the
-    weights' sum could fall below 1."""
-    if att_out.dim() == 2:   # a score per head: the same two launches carry all heads (include/qgtc_attn_heads.h)
-        M = _call(adj, "_tiled_mm_f32", att_nbr.detach(), reduce="max", return_arg=False, **mask_kw)[0]
-        return _att_heads_product(adj, X, att_out.detach(), att_nbr.detach(), slope, False, M, None, mask_kw)
-    M = _call(adj, "_tiled_mm_f32", att_nbr.detach().unsqueeze(1), reduce="max", return_arg=False, **mask_kw)[0].reshape(adj.n)
-    return _att(adj, X, att_mode="forward", att_own=att_out.detach(), att_nbr=att_nbr.detach(), negative_slope=slope, shift=M, **mask_kw)
-
-
-def _att_heads_entry(adj: TiledAdjacency, stem: str, mask_kw: dict):
-    """(entry, view arguments, mask arguments) of an entry of include/qgtc_attn_heads.h on the view of ``adj`` under the checked mask
-    keyword of the binding: ``stem`` + "_t" on ``adj.T`` + "_drop" / "_nodes". The view's pointers come first, the mask's arguments
-    after ``heads``."""
-    T = adj.n_tiles
-    view = (adj.col_ptr, adj.col_tile, adj.col_rb, adj.tiles) if adj.transposed else (adj.row_ptr, adj.kquad, adj.tiles)
-    name, tail = stem + ("_t" if adj.transposed else ""), ()
-    if "edge_drop" in mask_kw:
-        name, tail = name + "_drop", tuple(mask_kw["edge_drop"])
-    elif "node_masks" in mask_kw:
-        row_mask, nbr_mask = mask_kw["node_masks"]
-        name += "_nodes"
-        tail = (None if row_mask is None else row_mask.data_ptr(), None if nbr_mask is None else nbr_mask.data_ptr(),
-                (adj.n + 127) // 128 * 4)
-    return getattr(_c_abi(), name), tuple(t.data_ptr() if T else None for t in view) + (T, adj.n), tail
-
-
 def _att_heads_product(adj: TiledAdjacency, X: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float, backward: bool,
-                       shift: torch.Tensor, inv, mask_kw: dict):
-    """qgtc_tiledatt_heads_f32 and its twins, one launch on the current stream for all heads. Forward: ``shift`` is M [n, H] and the
-    result (out, m, inv) with the statistics [n, H]; backward: ``shift`` and ``inv`` are the forward's m and inv and the result (out,)."""
-    H = att_own.size(1)
+                       shift: torch.Tensor, inv, sub: _Subgraph):
+    """The C-entry route of :func:`_att_product` - qgtc_tiledatt_heads_f32 and its twins for scores [n, H], qgtc_tiledatt_f32_fanout and
+    its twins for one head over a sample -, one launch on the current stream for all heads. The statistics have the scores' shape."""
     out = torch.empty_like(X)
-    m = None if backward else torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
+    m = None if backward else torch.empty(att_own.shape, dtype=torch.float32, device=adj.device)
     if not backward:
         inv = torch.empty_like(m)
-    fn, view, tail = _att_heads_entry(adj, "qgtc_tiledatt_heads_f32", mask_kw)
-    _c_call("the attention product with heads", X, fn, *view, X.data_ptr(), X.numel(), X.size(1), att_own.data_ptr(), att_nbr.data_ptr(),
-            slope, int(backward), shift.data_ptr(), None if backward else m.data_ptr(), inv.data_ptr(), out.data_ptr(), out.numel(), H,
-            *tail)
+    _c_launch("attention product", X, "qgtc_tiledatt_f32", att_own.size(1) if att_own.dim() == 2 else 0, adj, sub, X.data_ptr(), X.numel(),
+              X.size(1), att_own.data_ptr(), att_nbr.data_ptr(), slope, int(backward), shift.data_ptr(), None if backward else m.data_ptr(),
+              inv.data_ptr(), out.data_ptr(), out.numel())
     return (out,) if backward else (out, m, inv)
 
 
+def _att_product(adj: TiledAdjacency, X: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float, backward: bool,
+                 shift: torch.Tensor, inv, sub: _Subgraph):
+    """The softmax-weighted product over the subgraph, one launch. Forward: ``shift`` is M, the largest neighbour score of every row
+    (and head), and the result (out, m, inv); backward (on the other view, the scores swapped): ``shift`` and ``inv`` are the forward's
+    m and inv and the result (out,)."""
+    if _c_route(att_own.dim() == 2, sub):
+        return _att_heads_product(adj, X, att_own, att_nbr, slope, backward, shift, inv, sub)
+    if backward:
+        return _att(adj, X, att_mode="backward", att_own=att_own, att_nbr=att_nbr, negative_slope=slope, shift=shift, inv=inv,
+                    **sub.kw)
+    return _att(adj, X, att_mode="forward", att_own=att_own, att_nbr=att_nbr, negative_slope=slope, shift=shift, **sub.kw)
+
+
 def _att_heads_grad(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float,
-                    nbr_owns: bool, m: torch.Tensor, inv: torch.Tensor, D: torch.Tensor, mask_kw: dict) -> torch.Tensor:
-    """float32 [n, H] of qgtc_tiledatt_grad_heads_f32 and its twins: the gradient of the out node's score (``nbr_owns`` False, on the
-    forward's view) or of the neighbour's (True, on the other view), one launch on the current stream for all heads."""
-    H = att_own.size(1)
-    out = torch.empty((adj.n, H), dtype=torch.float32, device=adj.device)
-    fn, view, tail = _att_heads_entry(adj, "qgtc_tiledatt_grad_heads_f32", mask_kw)
-    _c_call("the score gradient with heads", A, fn, *view, A.data_ptr(), B.data_ptr(), A.numel(), A.size(1), att_own.data_ptr(),
-            att_nbr.data_ptr(), slope, int(nbr_owns), m.data_ptr(), inv.data_ptr(), D.data_ptr(), out.data_ptr(), out.numel(), H, *tail)
+                    nbr_owns: bool, m: torch.Tensor, inv: torch.Tensor, D: torch.Tensor, sub: _Subgraph) -> torch.Tensor:
+    """The C-entry route of :func:`_att_grad`: qgtc_tiledatt_grad_heads_f32 and its twins, qgtc_tiledatt_grad_f32_fanout and its twins;
+    one launch on the current stream for all heads. The gradient has the scores' shape."""
+    out = torch.empty(att_own.shape, dtype=torch.float32, device=adj.device)
+    _c_launch("score gradient", A, "qgtc_tiledatt_grad_f32", att_own.size(1) if att_own.dim() == 2 else 0, adj, sub, A.data_ptr(),
+              B.data_ptr(), A.numel(), A.size(1), att_own.data_ptr(), att_nbr.data_ptr(), slope, int(nbr_owns), m.data_ptr(), inv.data_ptr(),
+              D.data_ptr(), out.data_ptr(), out.numel())
     return out
+
+
+def _att_grad(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, att_own: torch.Tensor, att_nbr: torch.Tensor, slope: float,
+              nbr_owns: bool, m: torch.Tensor, inv: torch.Tensor, D: torch.Tensor, sub: _Subgraph) -> torch.Tensor:
+    """The gradient of a score over the subgraph, one launch: the out node's (``nbr_owns`` False, on the forward's view, A = dY and
+    B = X) or the neighbour's (True, on the other view, A = X and B = dY, the scores swapped)."""
+    if _c_route(att_own.dim() == 2, sub):
+        return _att_heads_grad(adj, A, B, att_own, att_nbr, slope, nbr_owns, m, inv, D, sub)
+    return _att(adj, A, att_mode="grad_nbr" if nbr_owns else "grad_own", att_own=att_own, att_nbr=att_nbr, negative_slope=slope, shift=m,
+                inv=inv, other=B, D=D, **sub.kw)[0]
 
 
 def _att_heads_rowdot(A: torch.Tensor, B: torch.Tensor, H: int) -> torch.Tensor:
     """float32 [n, H] of qgtc_rowdot_heads_f32: DOT of every head's columns of A[o] and B[o], one launch on the current stream."""
     out = torch.empty((A.size(0), H), dtype=torch.float32, device=A.device)
-    _c_call("the row dot with heads", A, _c_abi().qgtc_rowdot_heads_f32, A.data_ptr(), B.data_ptr(), A.numel(), A.size(0), A.size(1),
-            out.data_ptr(), out.numel(), H)
+    _c_call("the row dot with heads", A, getattr(_c_abi(), _c_name("qgtc_rowdot_f32", H, False)), A.data_ptr(), B.data_ptr(), A.numel(),
+            A.size(0), A.size(1), out.data_ptr(), out.numel(), H)
     return out
+
+
+def _rowdot(adj: TiledAdjacency, A: torch.Tensor, B: torch.Tensor, heads: int) -> torch.Tensor:
+    """DOT(A[o], B[o]) of every row, per head with ``heads``: one launch. It walks no tile, so it has no subgraph; the binding takes it
+    through the view's ``att_mode`` overload all the same."""
+    return _att_heads_rowdot(A, B, heads) if _c_route(heads, _ALL) else _att(adj, A, att_mode="rowdot", other=B)[0]
+
+
+def _attention(adj: TiledAdjacency, X: torch.Tensor, att_out: torch.Tensor, att_nbr: torch.Tensor, slope: float, sub: _Subgraph):
+    """(out, m, inv): the max launch on the neighbours' scores gives M, the largest neighbour score of every row (and head), then one
+    product launch. Both run over the subgraph: M must be the maximum over the KEPT neighbours, or the weights' sum could fall below 1."""
+    p, q = att_out.detach(), att_nbr.detach()
+    if q.dim() == 2:   # a score per head: the same two launches carry all heads (include/qgtc_attn_heads.h)
+        M = _extremum(adj, q, "max", False, sub)[0]
+    else:
+        M = _extremum(adj, q.unsqueeze(1), "max", False, sub)[0].reshape(adj.n)
+    return _att_product(adj, X, p, q, slope, False, M, None, sub)
 
 
 def _scale_name(row_scale) -> str:
@@ -793,22 +1040,33 @@ def _scale_name(row_scale) -> str:
 
 def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop, row_mask,
              nbr_mask, edge_weight, fanout=None):
-    """(mode, mask_kw, slope) of a call of :func:`tiledMMFloat` / :func:`tiledAggregate`, or the refusal it earns. ``mode`` is
-    "weighted" (``edge_weight``), "attention" (``attn``), "extremum" (``reduce`` "max" / "min") or "sum" (plain or scaled); ``mask_kw``
-    the binding's keyword of the checked mask, ``edge_drop`` or ``node_masks`` - without a mask no keyword at all, which is the call the
-    binding always took -; ``slope`` the checked ``negative_slope`` of the attention. This is the one table of what may be combined, in
-    the order the refusals are made: the masks, ``reduce``, then per mode what it does not take and its operands. A new variant adds its
-    row here."""
+    """(mode, subgraph, slope) of a call of :func:`tiledMMFloat` / :func:`tiledAggregate`, or the refusal it earns. ``mode`` is
+    "weighted" (``edge_weight``), "attention" (``attn``), "extremum" (``reduce`` "max" / "min") or "sum" (plain or scaled); ``subgraph``
+    the :class:`_Subgraph` of the checked ``edge_drop``, node masks or ``fanout`` - ``_ALL`` without any, and a pair (k, seed) is drawn
+    here, by one selection launch after every refusal -; ``slope`` the checked ``negative_slope`` of the attention. This is the one table
+    of what may be combined, in the order the refusals are made: the masks, ``reduce``, then per mode what it does not take and its
+    operands. A new variant adds its row here."""
     _check(adj)
-    key = _edge_drop_key(edge_drop)
-    nodes_kw = _nodes_kw(adj, row_mask, nbr_mask, key)
-    mask_kw = nodes_kw if key is None else _drop_kw(key)   # never both: _nodes_kw refuses a mask with edge_drop
+    key, slope = _edge_drop_key(edge_drop), None
+    masked = row_mask is not None or nbr_mask is not None
+    if masked:
+        if row_mask is not None:
+            _check_mask(adj, row_mask, "row_mask")
+        if nbr_mask is not None:
+            _check_mask(adj, nbr_mask, "nbr_mask")
+        if key is not None:
+            raise ValueError("row_mask / nbr_mask cannot be combined with edge_drop: not built")
     if fanout is not None:
-        mask_kw = _fanout_kw(adj, fanout, key, nodes_kw, edge_weight, attn)
+        check_fanout(adj, fanout)
+        for name, on in (("edge_drop", key is not None), ("row_mask / nbr_mask", masked), ("edge_weight", edge_weight is not None),
+                         ("[n, H] scores", isinstance(attn, (tuple, list)) and len(attn) == 2
+                          and bool(_attn_heads(adj, attn[0]) or _attn_heads(adj, attn[1])))):
+            if on:
+                raise ValueError(f"fanout cannot be combined with {name}: not built")
     if reduce not in ("sum", "max", "min"):
         raise ValueError(f'reduce must be "sum", "max" or "min", not {reduce!r}')
     if edge_weight is not None:
-        _check_edge_weight(adj, edge_weight, src_scale, key, nodes_kw, reduce, attn, X)
+        _check_edge_weight(adj, edge_weight, src_scale, key, masked, reduce, attn, X)
         if return_arg or return_stats:
             raise ValueError("return_arg / return_stats cannot be combined with edge_weight: not built")
         mode = "weighted"
@@ -822,7 +1080,7 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
         slope = _check_slope(negative_slope)
         _check_float_operand(adj, X)
         _check_attn(adj, attn, X)
-        return "attention", mask_kw, slope
+        mode = "attention"
     elif return_stats:
         raise ValueError("return_stats needs attn: only the attention product has softmax statistics")
     elif reduce == "sum":
@@ -833,12 +1091,16 @@ def _resolve(adj: TiledAdjacency, X, row_scale, src_scale, reduce, return_arg, a
         if row_scale is not None or src_scale is not None:
             raise ValueError(f'{_scale_name(row_scale)} cannot be combined with reduce="{reduce}"')
         mode = "extremum"
-    _check_float_operand(adj, X)
-    if row_scale is not None:
-        _check_scale(adj, row_scale)
-    if src_scale is not None:
-        _check_scale(adj, src_scale, "src_scale")
-    return mode, mask_kw, None
+    if mode != "attention":   # which has checked its operands, and takes no scale
+        _check_float_operand(adj, X)
+        if row_scale is not None:
+            _check_scale(adj, row_scale)
+        if src_scale is not None:
+            _check_scale(adj, src_scale, "src_scale")
+    # after every refusal: the common call constructs nothing, and a pair (k, seed) is drawn here
+    if key is None and not masked and fanout is None:
+        return mode, _ALL, slope
+    return mode, _Subgraph.of(key, row_mask, nbr_mask, None if fanout is None else as_sample(adj, fanout)), slope
 
 
 def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
@@ -922,21 +1184,15 @@ def tiledMMFloat(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor |
     with either scale, ``reduce="max"`` / ``"min"`` with ``return_arg`` and one-head ``attn`` with ``return_stats``; k at least the largest
     degree gives the plain call's bits. A k below 1 is a ValueError, a k that is no int a TypeError; a sample of another adjacency is a
     ValueError; ``fanout`` with ``edge_drop``, a node mask, ``edge_weight`` or [n, H] scores a ValueError (not built)."""
-    mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop,
-                                    row_mask, nbr_mask, edge_weight, fanout)
-    if "fanout" in mask_kw:
-        from . import fanout as _fanout
-
-        return _fanout.forward(adj, mode, X, row_scale, src_scale, reduce, return_arg, attn, slope, return_stats, fanout)
+    mode, sub, slope = _resolve(adj, X, row_scale, src_scale, reduce, return_arg, attn, negative_slope, return_stats, edge_drop,
+                                row_mask, nbr_mask, edge_weight, fanout)
     if mode == "sum":
-        if src_scale is not None:
-            return _call(adj, "_tiled_mm_f32_src", X, row_scale, src_scale, **mask_kw)
-        return _call(adj, "_tiled_mm_f32", X, row_scale, **mask_kw)
+        return _sum(adj, X, row_scale, src_scale, sub)
     if mode == "extremum":
-        res = _call(adj, "_tiled_mm_f32", X, reduce=reduce, return_arg=bool(return_arg), **mask_kw)
-        return (res[0], res[1]) if return_arg else res[0]
+        out, arg = _extremum(adj, X, reduce, bool(return_arg), sub)
+        return (out, arg) if return_arg else out
     if mode == "attention":
-        out, m, inv = _tiled_attention(adj, X, attn[0], attn[1], slope, mask_kw)
+        out, m, inv = _attention(adj, X, attn[0], attn[1], slope, sub)
         return (out, m, inv) if return_stats else out
     return _weighted(adj, X, row_scale, edge_weight)
 
@@ -954,25 +1210,6 @@ def _tiled_select(adj: TiledAdjacency, dY: torch.Tensor, arg: torch.Tensor) -> t
     return _call(adj, "_tiled_mm_f32", dY, reduce="select", arg=arg)[0]
 
 
-def _sample_key(sample):
-    """(what a context keeps of a ``fanout.FanoutSample`` as plain attributes, its tensors for ``save_for_backward``): the view, k and
-    the seed; thr, the two masks and counts (None where the sample has none). Every tensor a backward reads goes through
-    ``save_for_backward`` - a reference, nothing is copied -, so that autograd's version check sees an in-place edit between the
-    forward and the backward and raises instead of differentiating another graph."""
-    if sample is None:
-        return None, (None, None, None, None)
-    return (sample.view, sample.k, sample.seed), (sample.thr, sample.row_mask, sample.nbr_mask, sample.counts)
-
-
-def _sample_again(key, tensors):
-    """The forward's sample, rebuilt in a backward from the context's key and the saved (version-checked) tensors."""
-    if key is None:
-        return None
-    from .fanout import FanoutSample
-
-    return FanoutSample(*key, *tensors)
-
-
 class _TiledAggregate(torch.autograd.Function):
     """Y = diag(r) . A . diag(c) . X, so dX = diag(c) . A^T . diag(r) . dY: the same product on the other view, scales swapped - and
     node masks swapped: a neighbour of the forward is an output row of the backward. The product is linear in X, so the backward is
@@ -980,20 +1217,18 @@ class _TiledAggregate(torch.autograd.Function):
     operand. Without a graph to build (``create_graph=False``) that is the one launch it always was."""
 
     @staticmethod
-    def forward(ctx, adj, X, row_scale, src_scale, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
-        ctx.adj, ctx.edge_drop = adj, edge_drop
-        ctx.sample, sample_tensors = _sample_key(fanout)   # fanout: the sample, taken once by tiledAggregate
-        ctx.save_for_backward(row_scale, src_scale, row_mask, nbr_mask, *sample_tensors)
-        return tiledMMFloat(adj, X, row_scale, src_scale, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
+    def forward(ctx, adj, X, row_scale, src_scale, sub=_ALL):
+        ctx.adj, ctx.sub = adj, sub   # a sample was taken once, by _resolve
+        ctx.save_for_backward(row_scale, src_scale, *sub.tensors())
+        return _sum(adj, X, row_scale, src_scale, sub)
 
     @staticmethod
     def backward(ctx, dY):
         dX = None
         if ctx.needs_input_grad[1]:
-            row_scale, src_scale, row_mask, nbr_mask, *sample_tensors = ctx.saved_tensors
-            dX = _TiledAggregate.apply(ctx.adj.T, dY.contiguous(), src_scale, row_scale, ctx.edge_drop, nbr_mask, row_mask,
-                                       _sample_again(ctx.sample, sample_tensors))
-        return None, dX, None, None, None, None, None, None
+            row_scale, src_scale, *mine = ctx.saved_tensors
+            dX = _TiledAggregate.apply(ctx.adj.T, dY.contiguous(), src_scale, row_scale, ctx.sub.rebuilt(mine).other())
+        return None, dX, None, None, None
 
 
 class _TiledWeighted(torch.autograd.Function):
@@ -1027,9 +1262,8 @@ class _TiledExtremum(torch.autograd.Function):
     """Y[r] = X[arg[r]] element by element, so dX[v] = the sum of dY[r] over the rows r that chose v: the select on the other view."""
 
     @staticmethod
-    def forward(ctx, adj, X, reduce, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
-        out, arg = tiledMMFloat(adj, X, reduce=reduce, return_arg=True, edge_drop=edge_drop, row_mask=row_mask, nbr_mask=nbr_mask,
-                                fanout=fanout)
+    def forward(ctx, adj, X, reduce, sub=_ALL):
+        out, arg = _extremum(adj, X, reduce, True, sub)
         ctx.adj = adj
         ctx.save_for_backward(arg)   # the select needs no mask: arg names kept (participating) neighbours only
         return out
@@ -1041,7 +1275,7 @@ class _TiledExtremum(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             arg, = ctx.saved_tensors
             dX = _tiled_select(ctx.adj.T, dY.contiguous(), arg)
-        return None, dX, None, None, None, None, None
+        return None, dX, None, None
 
 
 class _TiledAttention(torch.autograd.Function):
@@ -1050,62 +1284,32 @@ class _TiledAttention(torch.autograd.Function):
     of edge (o, k) gets u = alpha[o, k] . (dY[o] . X[k] - D[o]) . L'(e), which dp folds over k on this view and dq over o on the other."""
 
     @staticmethod
-    def forward(ctx, adj, X, att_out, att_nbr, slope, edge_drop=None, row_mask=None, nbr_mask=None, fanout=None):
-        out, m, inv = tiledMMFloat(adj, X, attn=(att_out, att_nbr), negative_slope=slope, return_stats=True, edge_drop=edge_drop,
-                                   row_mask=row_mask, nbr_mask=nbr_mask, fanout=fanout)
-        ctx.adj, ctx.slope, ctx.drop_kw = adj, slope, _drop_kw(_edge_drop_key(edge_drop))
-        ctx.sample, sample_tensors = _sample_key(fanout)   # the sample, taken once by tiledAggregate: every gradient launch reuses it
-        ctx.save_for_backward(X, att_out, att_nbr, out, m, inv, row_mask, nbr_mask, *sample_tensors)
+    def forward(ctx, adj, X, att_out, att_nbr, slope, sub=_ALL):
+        out, m, inv = _attention(adj, X, att_out, att_nbr, slope, sub)
+        ctx.adj, ctx.slope, ctx.sub = adj, slope, sub   # a sample was taken once, by _resolve: every gradient launch reuses it
+        ctx.save_for_backward(X, att_out, att_nbr, out, m, inv, *sub.tensors())
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dY):
-        X, p, q, Y, m, inv, row_mask, nbr_mask, *sample_tensors = ctx.saved_tensors
+        X, p, q, Y, m, inv, *mine = ctx.saved_tensors
         adj, other, slope = ctx.adj, ctx.adj.T, ctx.slope
         need_x, need_p, need_q = ctx.needs_input_grad[1:4]
-        dY, kw = dY.contiguous(), ctx.drop_kw   # every gradient walks the forward's subgraph
-        # node masks: unchanged on this view (grad_own), swapped on the other (the backward product and grad_nbr)
-        kw_here = kw_other = {}
-        if row_mask is not None or nbr_mask is not None:
-            kw_here, kw_other = {"node_masks": (row_mask, nbr_mask)}, {"node_masks": (nbr_mask, row_mask)}
-        fanout = _sample_again(ctx.sample, sample_tensors)
+        dY = dY.contiguous()
+        # every gradient walks the forward's subgraph: as it is on this view (dp), as the other view sees it there (dX and dq)
+        here = ctx.sub.rebuilt(mine)
+        there = here.other()
         dX = dp = dq = None
-        if p.dim() == 2:   # scores per head: the same five launches carry all heads
-            H, here, there = p.size(1), {**kw, **kw_here}, {**kw, **kw_other}
-            if need_x:
-                dX = _att_heads_product(other, dY, q, p, slope, True, m, inv, there)[0]
-            if need_p or need_q:
-                D = _att_heads_rowdot(dY, Y, H)
-                if need_p:
-                    dp = _att_heads_grad(adj, dY, X, p, q, slope, False, m, inv, D, here)
-                if need_q:
-                    dq = _att_heads_grad(other, X, dY, q, p, slope, True, m, inv, D, there)
-            return None, dX, dp, dq, None, None, None, None, None
-        if fanout is not None:   # one head over a fixed-fanout sample: the same five launches through the _fanout entries
-            from . import fanout as _fanout
-
-            q, p = q.contiguous(), p.contiguous()
-            if need_x:
-                dX = _fanout.att_product(other, dY, q, p, slope, True, m, inv, fanout)[0]
-            if need_p or need_q:
-                D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
-                if need_p:
-                    dp = _fanout.att_grad(adj, dY, X, p, q, slope, False, m, inv, D, fanout)
-                if need_q:
-                    dq = _fanout.att_grad(other, X, dY, q, p, slope, True, m, inv, D, fanout)
-            return None, dX, dp, dq, None, None, None, None, None
         if need_x:
-            dX = _att(other, dY, att_mode="backward", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, **kw, **kw_other)[0]
+            dX = _att_product(other, dY, q, p, slope, True, m, inv, there)[0]
         if need_p or need_q:
-            D = _att(adj, dY, att_mode="rowdot", other=Y)[0]
+            D = _rowdot(adj, dY, Y, p.size(1) if p.dim() == 2 else 0)
             if need_p:
-                dp = _att(adj, dY, att_mode="grad_own", att_own=p, att_nbr=q, negative_slope=slope, shift=m, inv=inv, other=X, D=D, **kw,
-                          **kw_here)[0]
+                dp = _att_grad(adj, dY, X, p, q, slope, False, m, inv, D, here)
             if need_q:
-                dq = _att(other, X, att_mode="grad_nbr", att_own=q, att_nbr=p, negative_slope=slope, shift=m, inv=inv, other=dY, D=D, **kw,
-                          **kw_other)[0]
-        return None, dX, dp, dq, None, None, None, None, None
+                dq = _att_grad(other, X, dY, q, p, slope, True, m, inv, D, there)
+        return None, dX, dp, dq, None, None
 
 
 def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor | None = None,
@@ -1161,12 +1365,8 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     With ``fanout=(k, seed)`` or a ``fanout.FanoutSample`` (as in :func:`tiledMMFloat`: the sum, max / min, one-head ``attn``) the sample
     is taken ONCE, in the forward - one selection launch for a pair, none for a sample - and every backward launch reuses it on the other
     view in the neighbours' form: the gradients are those of the unmasked call on ``pack_edges_tiled`` of the kept edges, bit for bit."""
-    mode, mask_kw, slope = _resolve(adj, X, row_scale, src_scale, reduce, False, attn, negative_slope, False, edge_drop, row_mask, nbr_mask,
-                                    edge_weight, fanout)
-    if "fanout" in mask_kw:
-        from . import fanout as _fanout
-
-        fanout = _fanout.as_sample(adj, fanout)
+    mode, sub, slope = _resolve(adj, X, row_scale, src_scale, reduce, False, attn, negative_slope, False, edge_drop, row_mask, nbr_mask,
+                                edge_weight, fanout)
     for name, sc in (("row_scale", row_scale), ("src_scale", src_scale)):
         if isinstance(sc, torch.Tensor) and sc.requires_grad:
             wrt = "X and edge_weight" if mode == "weighted" else "X"
@@ -1174,10 +1374,10 @@ def tiledAggregate(adj: TiledAdjacency, X: torch.Tensor, row_scale: torch.Tensor
     if mode == "weighted":
         return _TiledWeighted.apply(adj, X, row_scale, edge_weight)
     if mode == "attention":
-        return _TiledAttention.apply(adj, X, attn[0], attn[1], slope, edge_drop, row_mask, nbr_mask, fanout)
+        return _TiledAttention.apply(adj, X, attn[0], attn[1], slope, sub)
     if mode == "extremum":
-        return _TiledExtremum.apply(adj, X, reduce, edge_drop, row_mask, nbr_mask, fanout)
-    return _TiledAggregate.apply(adj, X, row_scale, src_scale, edge_drop, row_mask, nbr_mask, fanout)
+        return _TiledExtremum.apply(adj, X, reduce, sub)
+    return _TiledAggregate.apply(adj, X, row_scale, src_scale, sub)
 
 
 def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
@@ -1187,10 +1387,8 @@ def _edge_softmax(adj: TiledAdjacency, logits: torch.Tensor):
     alpha = torch.empty_like(logits)
     m = torch.empty((adj.n, H) if logits.dim() == 2 else adj.n, dtype=torch.float32, device=adj.device)
     inv = torch.empty_like(m)
-    L = _c_abi()
     head, idx = _view_ptrs(adj)
-    _c_call("tiledEdgeSoftmax", m, L.qgtc_tiled_edge_softmax_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_heads_f32, *head,
-            *idx, logits.data_ptr() if nnz else None, alpha.data_ptr() if nnz else None, nnz, m.data_ptr(), inv.data_ptr(), H)
+    _c_call("tiledEdgeSoftmax", m, _c_entry("qgtc_tiled_edge_softmax_heads_f32", False, adj), *head, *idx, logits.data_ptr() if nnz else None, alpha.data_ptr() if nnz else None, nnz, m.data_ptr(), inv.data_ptr(), H)
     return alpha, m, inv
 
 
@@ -1200,10 +1398,8 @@ def _edge_softmax_grad(adj: TiledAdjacency, alpha: torch.Tensor, g: torch.Tensor
     nnz, H = alpha.size(0), alpha.size(1) if alpha.dim() == 2 else 1
     out = torch.empty_like(alpha)
     if nnz:
-        L = _c_abi()
         head, idx = _view_ptrs(adj)
-        _c_call("the gradient of tiledEdgeSoftmax", alpha,
-                L.qgtc_tiled_edge_softmax_grad_heads_f32_t if adj.transposed else L.qgtc_tiled_edge_softmax_grad_heads_f32, *head, *idx,
+        _c_call("the gradient of tiledEdgeSoftmax", alpha, _c_entry("qgtc_tiled_edge_softmax_grad_heads_f32", False, adj), *head, *idx,
                 alpha.data_ptr(), g.data_ptr(), out.data_ptr(), nnz, H)
     return out
 
@@ -1332,10 +1528,8 @@ def _addscore_grad(adj: TiledAdjacency, own: torch.Tensor, nbr: torch.Tensor, at
         return torch.zeros_like(own) if want_own else None, torch.zeros_like(own) if want_P else None
     d_own = torch.empty_like(own) if want_own else None
     P = torch.empty_like(own) if want_P else None
-    L = _c_abi()
     head, idx = _view_ptrs(adj)
-    _c_call("the gradient of tiledEdgeAdditiveScores", own,
-            L.qgtc_tiled_addscore_grad_heads_f32_t if adj.transposed else L.qgtc_tiled_addscore_grad_heads_f32, *head, own.data_ptr(),
+    _c_call("the gradient of tiledEdgeAdditiveScores", own, _c_entry("qgtc_tiled_addscore_grad_heads_f32", False, adj), *head, own.data_ptr(),
             nbr.data_ptr(), own.numel(), own.size(1), att.data_ptr(), att.numel(), slope, d_own.data_ptr() if want_own else None,
             P.data_ptr() if want_P else None, own.numel(), *idx, g.data_ptr(), nnz, heads)
     return d_own, P

@@ -1,7 +1,7 @@
 """The ledger of uninitialised allocations ("Dirty memory").
 
 Every ``torch::empty`` / ``empty_like`` of the binding (``csrc/qgtc_torch.cpp``) and every ``torch.empty`` / ``empty_like`` / ``new_empty`` of
-``tiled.py``, ``sampler.py``, ``driver.py`` and ``dist.py`` hands out memory whose words are UNDEFINED: the caching allocator returns
+``tiled.py``, ``fanout.py``, ``sampler.py``, ``driver.py`` and ``dist.py`` hands out memory whose words are UNDEFINED: the caching allocator returns
 whatever the block held last. :data:`LEDGER` names, for each such site, what defines every element before anything reads it:
 
 ``written whole by X``            entry (or host code) X stores every element, pad rows and pad words included, on every path
@@ -19,7 +19,7 @@ from collections import Counter
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 PKG = ROOT / "qgtc_ppopp22_amd"
-FILES = {"qgtc_torch.cpp": PKG / "csrc" / "qgtc_torch.cpp", "tiled.py": PKG / "tiled.py", "sampler.py": PKG / "sampler.py",
+FILES = {"qgtc_torch.cpp": PKG / "csrc" / "qgtc_torch.cpp", "tiled.py": PKG / "tiled.py", "fanout.py": PKG / "fanout.py", "sampler.py": PKG / "sampler.py",
          "driver.py": PKG / "driver.py", "dist.py": PKG / "dist.py"}
 
 VERDICTS = ("written whole by ", "cleared by ", "host-filled")
@@ -102,7 +102,7 @@ def all_sites() -> Counter:
 
 
 W, C, H = "written whole by ", "cleared by ", "host-filled"
-CPP, TILED, DIST = "qgtc_torch.cpp", "tiled.py", "dist.py"
+CPP, TILED, FANOUT, DIST = "qgtc_torch.cpp", "tiled.py", "fanout.py", "dist.py"
 
 # (file, function or struct, tensor) -> one verdict per site of that name, in source order. What follows the verdict's opening words names
 # the entry (include/qgtc.h) or the host code that defines every element before anything reads it, and the path that was read for it.
@@ -195,10 +195,27 @@ LEDGER = {
     (TILED, "edge_endpoints", "row"): [W + "qgtc_tiled_edge_endpoints: one store per stored cell; [0] without a cell, where the entry is not called"],
     (TILED, "edge_endpoints", "col"): [W + "qgtc_tiled_edge_endpoints: one store per stored cell; [0] without a cell"],
     (TILED, "_sddmm", "out"): [W + "qgtc_tiled_sddmm_heads_f32: one store per (slot, head); [0, heads] without a cell, where the entry is not called"],
-    (TILED, "_att_heads_product", "out"): [W + "qgtc_tiledatt_heads_f32 and twins: every row and head, +0 without a (kept) neighbour"],
-    (TILED, "_att_heads_product", "m"): [W + "qgtc_tiledatt_heads_f32 and twins, forward: every (row, head)"],
-    (TILED, "_att_heads_product", "inv"): [W + "qgtc_tiledatt_heads_f32 and twins, forward: 0 without a (kept) neighbour"],
-    (TILED, "_att_heads_grad", "out"): [W + "qgtc_tiledatt_grad_heads_f32 and twins: every (row, head), +0 without a cell"],
+    (TILED, "sample_fanout", "thr"): [W + "qgtc_tiled_fanout_thr / _t / _nodes / _t_nodes: k_tiled_fanout_thr and k_tiled_fanout_thr_nodes run one wave per "
+                                      "node below n (grid (n + 3) / 4 of four waves) and lane 0 stores thr[u] last, 0 where nothing is selected or walked"],
+    (TILED, "sample_fanout", "counts"): [W + "qgtc_tiled_fanout_thr_nodes / _t_nodes: k_tiled_fanout_thr_nodes stores kept[u] beside thr[u] for every node "
+                                         "below n, 0 outside row_mask (deg is 0 without a walk)"],
+    (TILED, "_sum", "out"): [W + "qgtc_tiledmm_f32_fanout / _fanout_nodes and their _t twins: the entry bodies (qgtc_tiled_float*_fanout*.hip) call "
+                             "tiled_mm_f32_masked, the launcher of qgtc_tiledmm_f32 (tiled_sum_on above), with the sample as the pack's mask: every row, "
+                             "+0 for a row that keeps no neighbour"],
+    (TILED, "_extremum", "out"): [W + "qgtc_tiledmax_f32_fanout / _fanout_nodes and their _t twins: the entry bodies (qgtc_tiled_max_fanout*.hip) call "
+                                  "tiled_extremum_run, the launcher of qgtc_tiledmax_f32 (tiled_red_on above): every row, +0 without a kept neighbour"],
+    (TILED, "_extremum", "arg"): [W + "qgtc_tiledmax_f32_fanout / _fanout_nodes and their _t twins, the same launch: every element, -1 without a kept "
+                                  "neighbour; absent (NULL, 0 elements) without return_arg"],
+    (TILED, "_att_heads_product", "out"): [W + "qgtc_tiledatt_heads_f32 and twins: every row and head, +0 without a (kept) neighbour; one head over a sample: "
+                                           "qgtc_tiledatt_f32_fanout / _fanout_nodes and their _t twins, whose bodies (qgtc_tiled_attn*_fanout*.hip) call "
+                                           "tiled_att_f32_run, the launcher of qgtc_tiledatt_f32 (tiled_att_on above)"],
+    (TILED, "_att_heads_product", "m"): [W + "qgtc_tiledatt_heads_f32 and twins, forward: every (row, head); over a sample the same tiled_att_f32_run: "
+                                         "L(att_own + M) for every row"],
+    (TILED, "_att_heads_product", "inv"): [W + "qgtc_tiledatt_heads_f32 and twins, forward: 0 without a (kept) neighbour; over a sample the same "
+                                           "tiled_att_f32_run"],
+    (TILED, "_att_heads_grad", "out"): [W + "qgtc_tiledatt_grad_heads_f32 and twins: every (row, head), +0 without a cell; one head over a sample: "
+                                        "qgtc_tiledatt_grad_f32_fanout / _fanout_nodes and their _t twins, whose bodies call tiled_att_grad_run, the "
+                                        "launcher of qgtc_tiledatt_grad_f32 (tiled_att_on above)"],
     (TILED, "_att_heads_rowdot", "out"): [W + "qgtc_rowdot_heads_f32: one DOT per (row, head)"],
     (TILED, "_edge_softmax", "alpha"): [W + "qgtc_tiled_edge_softmax_heads_f32 / _t: one store per (slot, head); empty without a cell"],
     (TILED, "_edge_softmax", "m"): [W + "qgtc_tiled_edge_softmax_heads_f32 / _t: every (node, head); the entry's own clear (tiled_esm_no_cells) without a cell"],
@@ -207,6 +224,10 @@ LEDGER = {
     (TILED, "_addscore", "out"): [W + "qgtc_tiled_addscore_heads_f32: one store per (slot, head); [0, heads] without a cell, not called"],
     (TILED, "_addscore_grad", "d_own"): [W + "qgtc_tiled_addscore_grad_heads_f32 / _t: every owner's fold, +0 without a cell (torch.zeros_like when nnz is 0)"],
     (TILED, "_addscore_grad", "P"): [W + "qgtc_tiled_addscore_grad_heads_f32 / _t: every owner's fold, +0 without a cell"],
+    # ---- fanout.py ---------------------------------------------------------------------------------------------------------------
+    (FANOUT, "frontier", "out"): [W + "qgtc_tiled_fanout_frontier / _t: k_tiled_fanout_frontier (grid S128(n), threads 0 .. 3 store the k-quad's four "
+                                  "words) and k_tiled_fanout_frontier_t (grid S128(n) * 4, thread 0 stores the block's word) store every word after the "
+                                  "barrier, also without a tile; pad bits cleared by tiled_blocks_valid"],
     # ---- dist.py (multi-GPU: in the ledger only) ----------------------------------------------------------------------------------
     (DIST, "gather_batch_summaries", "out"): [W + "dist.all_gather_into_tensor: world equal shards"],
     (DIST, "gather_replica_summaries", "out"): [W + "dist.all_gather_into_tensor: world equal shards"],

@@ -335,7 +335,9 @@ def test_tiledaggregate_gradients_under_a_masked_sample(qgtc, mode, monkeypatch)
     fo = _fo()
     launches = []
     real = fo.sample_fanout
-    monkeypatch.setattr(fo, "sample_fanout", lambda *a, **kw: (launches.append(a[1:]), real(*a, **kw))[1])
+    counted = lambda *a, **kw: (launches.append(a[1:]), real(*a, **kw))[1]
+    monkeypatch.setattr(fo, "sample_fanout", counted)
+    monkeypatch.setattr(fo.tiled, "sample_fanout", counted)   # where fanout=(k, seed) of the aggregates draws: fanout re-exports it
     for axis, taken_on in _views(adj):
         kadj = _pack(torch, qgtc, *bm.kept_edges(src, dst, n, k, seed, axis, row, nbr), n)
         sample = fo.sample_fanout(taken_on, k, seed, row_mask=_bits(torch, row), nbr_mask=_bits(torch, nbr))

@@ -252,7 +252,9 @@ def test_backward_equals_the_unmasked_composition_on_the_repacked_adjacency(qgtc
     fo = _fanout()
     launches = []
     real = fo.sample_fanout
-    monkeypatch.setattr(fo, "sample_fanout", lambda *a, **kw: (launches.append(a[1:]), real(*a, **kw))[1])
+    counted = lambda *a, **kw: (launches.append(a[1:]), real(*a, **kw))[1]
+    monkeypatch.setattr(fo, "sample_fanout", counted)
+    monkeypatch.setattr(fo.tiled, "sample_fanout", counted)   # where fanout=(k, seed) of the aggregates draws: fanout re-exports it
     subsets = [(bool(m & 1), bool(m & 2), bool(m & 4)) for m in range(1, 8)] if mode == "attn" else [(True, False, False)]
     for transposed in (False, True):
         a = adj.T if transposed else adj
