@@ -1,4 +1,5 @@
-"""Helpers and cases of the stream tests (tests/test_streams_gpu.py, tests/test_stream_abi_gpu.py, tests/test_multistream_gpu.py).
+"""Helpers and cases of the stream tests (tests/test_streams_gpu.py, tests/test_stream_abi_gpu.py, tests/test_multistream_gpu.py, and
+the stream test of every later tiled operator, which builds its own LIVE object next to the test).
 
 A CASE names the entries of tests/stream_contract.py it exercises and builds a LIVE object on the GPU: static device buffers, four
 seeded CONTENTS for them (pinned host tensors), the EXPECTED results of every content from the CPU oracle or the NumPy models, and
@@ -10,7 +11,8 @@ seeded CONTENTS for them (pinned host tensors), the EXPECTED results of every co
                        gives content 0's result: "ran ahead of its stream".
 ``capture_and_replay`` one warm-up call on a side stream, one call captured into a graph, three replays with contents 1, 2, 3 copied into
                        the buffers before each: every replay gives that content's result and the bits of an eager call. A launch that
-                       was not captured raises at capture time or leaves a stale result.
+                       was not captured raises at capture time or leaves a stale result. Outputs a case lists in ``refill`` are
+                       filled with -1 before each replay.
 
 Everything is compared bit for bit. Importing this module needs neither a GPU nor the built extension (test_stream_contract.py reads
 CASES on the CPU).
@@ -145,12 +147,14 @@ def check(got, want, what, old=None, old_means="ran ahead of its stream"):
 class Live:
     """bufs: static device tensors; contents[k]: one host array per buffer; expected[k]: one array per output; run(): the operator on
     bufs -> list of output tensors (or a callable giving them: outputs that only exist once a capture has ended). engine / zero_skip:
-    the switches the case runs under. raw(stream_ptr) -> rc, for the C entries: writes into `outs`."""
+    the switches the case runs under. raw(stream_ptr) -> rc, for the C entries: writes into `outs`. refill: indices of outputs that do
+    not depend on the contents (a sample's thresholds); they are filled with -1 before every replay, so a replay that did not write them
+    shows."""
 
-    def __init__(self, torch, bufs, contents, expected, run=None, raw=None, outs=None, engine="auto", zero_skip=True, keep=None):
+    def __init__(self, torch, bufs, contents, expected, run=None, raw=None, outs=None, engine="auto", zero_skip=True, keep=None, refill=()):
         assert len(contents) == len(expected) == 4 and all(len(c) == len(bufs) for c in contents)
         self.torch, self.bufs, self.expected, self.run, self.raw, self.outs = torch, bufs, expected, run, raw, outs
-        self.engine, self.zero_skip, self.keep = engine, zero_skip, keep
+        self.engine, self.zero_skip, self.keep, self.refill = engine, zero_skip, keep, tuple(refill)
         self.contents = []
         for c in contents:
             row = []
@@ -173,6 +177,18 @@ class Live:
 
     def outputs(self, r):
         return list(r() if callable(r) else r)
+
+
+def eager_results(torch, bufs, contents, run):
+    """The `expected` of a case whose reference is the operator's own eager result: run() on every content in turn, on the current
+    (default) stream before any probe, as CPU tensors."""
+    want = []
+    for c in contents:
+        with torch.no_grad():
+            for b, h in zip(bufs, c):
+                b.copy_(torch.from_numpy(np.ascontiguousarray(h)))
+        want.append([o.detach().cpu() for o in run()])
+    return want
 
 
 @contextlib.contextmanager
@@ -250,13 +266,15 @@ def capture_and_replay(torch, qgtc, live, what, replays=(1, 2, 3)):
             call()
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        captured = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(captured):
             r = call()
         outs = live.outputs(r)
         for k in replays:
             live.load(k)
-            graph.replay()
+            for i in live.refill:
+                outs[i].fill_(-1)
+            captured.replay()
             got = [o.clone() for o in outs]
             torch.cuda.synchronize(dev)
             check([g.cpu() for g in got], live.expected[k], f"{what}, replay with content {k}", old=live.expected[k - 1],
@@ -264,7 +282,7 @@ def capture_and_replay(torch, qgtc, live, what, replays=(1, 2, 3)):
             eager = live.outputs(call())
             torch.cuda.synchronize(dev)
             check([e.cpu() for e in eager], [g.cpu() for g in got], f"{what}, eager call on content {k} against the replay")
-        del graph
+        del captured
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -298,12 +316,12 @@ def env_of(qgtc, oracle, torch, device="cuda:0"):
     return types.SimpleNamespace(Q=qgtc, O=oracle, torch=torch, dev=torch.device(device), ext=qgtc_ppopp22_amd.load_ext())
 
 
-def _empty(env, shape, dtype):
+def empty(env, shape, dtype):
     return env.torch.empty(shape, dtype=dtype, device=env.dev)
 
 
 def _i32(env, shape):
-    return _empty(env, shape, env.torch.int32)
+    return empty(env, shape, env.torch.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -325,7 +343,7 @@ def _val2bit_inputs(H, W, nbits, seed):
 def _val2bit_case(name, H, W, nbits, cm, ol, seed):
     def build(env):
         xs = _val2bit_inputs(H, W, nbits, seed)
-        buf = _empty(env, (H, W), env.torch.float32)
+        buf = empty(env, (H, W), env.torch.float32)
         fn = getattr(env.Q, name)
         return Live(env.torch, [buf], [[x] for x in xs], [[env.O.val2bit(x, nbits, cm, ol)] for x in xs],
                     run=lambda: [fn(buf, nbits, cm, ol)])
@@ -351,7 +369,7 @@ def _bit2val(env):
 def _val2bit_many(env):
     shapes, nbits, cm, ol = [(50, 64), (64, 64), (64, 10), (64, 10)], 2, [True, True, True, False], [False, False, True, False]
     xs = [[edge_floats(np.random.default_rng(50 + 4 * k + i), h, w, nbits) for i, (h, w) in enumerate(shapes)] for k in range(4)]
-    bufs = [_empty(env, s, env.torch.float32) for s in shapes]
+    bufs = [empty(env, s, env.torch.float32) for s in shapes]
     return Live(env.torch, bufs, xs, [[env.O.val2bit(x, nbits, c, o) for x, c, o in zip(row, cm, ol)] for row in xs],
                 run=lambda: env.Q.val2bit_many(bufs, nbits, cm, ol))
 
@@ -362,7 +380,7 @@ def _i8gemm(env):
 
     M, K, N = 100, 256, 48
     ab = [[np.random.default_rng(60 + k).integers(-128, 128, size=s, dtype=np.int8) for s in ((M, K), (N, K))] for k in range(4)]
-    bufs = [_empty(env, (M, K), env.torch.int8), _empty(env, (N, K), env.torch.int8)]
+    bufs = [empty(env, (M, K), env.torch.int8), empty(env, (N, K), env.torch.int8)]
     return Live(env.torch, bufs, ab, [[np_i8gemm(a, b)] for a, b in ab], run=lambda: [env.Q.i8gemm(bufs[0], bufs[1])])
 
 
@@ -531,13 +549,13 @@ for _dims in ENQUEUE_BIG + ENQUEUE_SMALL:          # the graphs `bench.py --issu
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the tiled products on a warmed adjacency
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _graph(n, seed):
+def graph(n, seed):
     from tiled_model import random_edges
 
     return random_edges(np.random.default_rng(seed), n, 4 * n)
 
 
-def _warm_adjacency(env, src, dst, n, reorder=False):
+def warm_adjacency(env, src, dst, n, reorder=False):
     t = env.torch
     adj = env.Q.pack_edges_tiled(t.from_numpy(src).to(env.dev), t.from_numpy(dst).to(env.dev), n, reorder=reorder)
     adj.T, adj.mean_scale(), adj.sym_scale(), adj.T.sym_scale()        # every lazy cache, before any probe or capture
@@ -567,8 +585,8 @@ def _tiled_bits_case(to_float, transposed, scaled, N, bit2, ob, seed):
         from tiled_scaled_model import expected_bits_scaled, scaled as scale_rows
 
         n = 600
-        src, dst = _graph(n, seed)
-        adj = _warm_adjacency(env, src, dst, n)
+        src, dst = graph(n, seed)
+        adj = warm_adjacency(env, src, dst, n)
         view = adj.T if transposed else adj
         r, _ = _scales(src, dst, n, transposed, "mean" if scaled else None)
         dr = view.mean_scale() if scaled else None
@@ -605,8 +623,8 @@ def _tiled_float_case(transposed, kind, N, seed, aggregate_op=False):
         from tiled_sym_model import aggregate_f32_src
 
         n = 600
-        src, dst = _graph(n, seed)
-        adj = _warm_adjacency(env, src, dst, n)
+        src, dst = graph(n, seed)
+        adj = warm_adjacency(env, src, dst, n)
         view = adj.T if transposed else adj
         r, c = _scales(src, dst, n, transposed, kind)
         dr, dc = _dev_scales(view, kind)
@@ -624,13 +642,13 @@ def _tiled_float_case(transposed, kind, N, seed, aggregate_op=False):
                 contents.append([X])
                 want.append([y])
         if aggregate_op:
-            bufs = [_empty(env, (n, N), torch.float32).requires_grad_(True), _empty(env, (n, N), torch.float32)]
+            bufs = [empty(env, (n, N), torch.float32).requires_grad_(True), empty(env, (n, N), torch.float32)]
 
             def run():
                 y = env.Q.tiledAggregate(view, bufs[0], dr, dc)
                 return [y.detach(), torch.autograd.grad(y, bufs[0], bufs[1])[0]]
         else:
-            bufs = [_empty(env, (n, N), torch.float32)]
+            bufs = [empty(env, (n, N), torch.float32)]
             run = lambda: [env.Q.tiledMMFloat(view, bufs[0], dr, dc)]            # noqa: E731
         return Live(torch, bufs, contents, want, run=run, keep=adj)
     return build
@@ -655,8 +673,8 @@ def _reordered(env):
     from tiled_model import aggregate, expected_bits
 
     n, N, bit2, ob = 600, 24, 2, 4
-    src, dst = _graph(n, 77)
-    adj = _warm_adjacency(env, src, dst, n, reorder=True)
+    src, dst = graph(n, 77)
+    adj = warm_adjacency(env, src, dst, n, reorder=True)
     assert adj.perm is not None
     contents, want = [], []
     for k in range(4):
@@ -665,7 +683,7 @@ def _reordered(env):
         C = aggregate(src, dst, n, Xq)
         contents.append([Xq.astype(np.float32)])
         want.append([C.astype(np.float32), expected_bits(env.O, C, ob)])
-    buf = _empty(env, (n, N), env.torch.float32)
+    buf = empty(env, (n, N), env.torch.float32)
 
     def run():
         Xn = adj.to_new(buf)
@@ -709,7 +727,7 @@ def cache_graphs():
 def _adjacency_buffers(env, graphs):
     t = env.torch
     rp, kq, tl = graphs[0][2]
-    return [_empty(env, rp.shape, t.int64), _i32(env, kq.shape), _i32(env, tl.shape)]
+    return [empty(env, rp.shape, t.int64), _i32(env, kq.shape), _i32(env, tl.shape)]
 
 
 @case("ext._tiled_colindex", ["ext._tiled_colindex"])
@@ -770,7 +788,7 @@ def cache_run(Q, adj, X):
 def _lazy(env):
     """A FRESH TiledAdjacency over the static buffers in every call: each call builds every cache again, on the stream it runs on."""
     gs = cache_graphs()
-    bufs = _adjacency_buffers(env, gs) + [_empty(env, (CACHE_N, 24), env.torch.float32)]
+    bufs = _adjacency_buffers(env, gs) + [empty(env, (CACHE_N, 24), env.torch.float32)]
     Xs = [np.random.default_rng(85 + k).normal(size=(CACHE_N, 24)).astype(np.float32) for k in range(4)]
     return Live(env.torch, bufs, [list(g[2]) + [x] for g, x in zip(gs, Xs)], [cache_expected(g[0], g[1], x) for g, x in zip(gs, Xs)],
                 run=lambda: cache_run(env.Q, env.Q.TiledAdjacency(CACHE_N, bufs[0], bufs[1], bufs[2]), bufs[3]))
@@ -938,7 +956,7 @@ def raw_case(id, entry):
 @raw_case("qgtc_val2bit-rows", "qgtc_val2bit")
 def _raw_val2bit(env, H=37, W=130, nbits=3, cm=0):
     L, xs = cabi.load(), _val2bit_inputs(37, 130, 3, 201)
-    buf, out = _empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_rows_words(H, W, nbits)), env.torch.int32)
+    buf, out = empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_rows_words(H, W, nbits)), env.torch.int32)
     return Live(env.torch, [buf], [[x] for x in xs], [[env.O.val2bit(x, nbits, False, False)] for x in xs], outs=[out],
                 raw=lambda st: L.qgtc_val2bit(buf.data_ptr(), H, W, nbits, 0, 0, out.data_ptr(), out.numel(), st))
 
@@ -947,7 +965,7 @@ def _raw_val2bit(env, H=37, W=130, nbits=3, cm=0):
 def _raw_val2bit_cols(env):
     H, W, nbits = 130, 37, 2
     L, xs = cabi.load(), _val2bit_inputs(H, W, nbits, 202)
-    buf, out = _empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_cols_words(H, W, nbits, 0)), env.torch.int32)
+    buf, out = empty(env, (H, W), env.torch.float32), _out(env, int(L.qgtc_cols_words(H, W, nbits, 0)), env.torch.int32)
     return Live(env.torch, [buf], [[x] for x in xs], [[env.O.val2bit(x, nbits, True, False)] for x in xs], outs=[out],
                 raw=lambda st: L.qgtc_val2bit(buf.data_ptr(), H, W, nbits, 1, 0, out.data_ptr(), out.numel(), st))
 
@@ -993,7 +1011,7 @@ def _raw_pack_edges(env):
         counts = rng.integers(1, 10, size=n_cells).astype(np.int32)
         contents.append([cells, counts])
         want.append([np_pack_edges(np.repeat(cells // W, counts), np.repeat(cells % W, counts), H, W, nbits)])
-    bufs = [_empty(env, (n_cells,), env.torch.int64), _i32(env, (n_cells,))]
+    bufs = [empty(env, (n_cells,), env.torch.int64), _i32(env, (n_cells,))]
     out = _out(env, int(L.qgtc_rows_words(H, W, nbits)), env.torch.int32)
     return Live(env.torch, bufs, contents, want, outs=[out],
                 raw=lambda st: L.qgtc_pack_edges(bufs[0].data_ptr(), bufs[1].data_ptr(), n_cells, H, W, nbits, out.data_ptr(), out.numel(), st))
@@ -1014,7 +1032,7 @@ def _raw_pack_edge_list(env):
         contents.append([r, c])
         want.append([np_pack_edges(r, c, H, W, 1)])
     words = int(L.qgtc_rows_words(H, W, 1))
-    bufs = [_empty(env, (n_edges,), env.torch.int64), _empty(env, (n_edges,), env.torch.int64)]
+    bufs = [empty(env, (n_edges,), env.torch.int64), empty(env, (n_edges,), env.torch.int64)]
     out, scratch = _out(env, words, env.torch.int32), _i32(env, (2 * words,))
     return Live(env.torch, bufs, contents, want, outs=[out], keep=scratch,
                 raw=lambda st: L.qgtc_pack_edge_list(bufs[0].data_ptr(), bufs[1].data_ptr(), n_edges, H, W, out.data_ptr(), words, scratch.data_ptr(),
@@ -1078,7 +1096,7 @@ def _raw_tiled_product(entry):
                 X = rng.normal(size=(n, N)).astype(np.float32)
                 contents.append(index + [tl, X, r, c])
                 want.append([aggregate_f32_src(s, d, n, X, transposed, r, c)])
-        index_bufs = [_empty(env, (n // 128 + 1,), t.int64), _empty(env, (T,), t.int64), _i32(env, (T,))] if transposed else adj[:2]
+        index_bufs = [empty(env, (n // 128 + 1,), t.int64), empty(env, (T,), t.int64), _i32(env, (T,))] if transposed else adj[:2]
         if entry == "qgtc_tiledmm2bit_t":
             X = _i32(env, cols_shape(n, N, bit2))
             out = _out(env, want[0][0].size, t.int32)
@@ -1086,7 +1104,7 @@ def _raw_tiled_product(entry):
             raw = lambda st: L.qgtc_tiledmm2bit_t(*[b.data_ptr() for b in index_bufs], adj[2].data_ptr(), T, n, X.data_ptr(), X.numel(), N, bit2, ob,   # noqa: E731
                                                   out.data_ptr(), out.numel(), st)
         else:
-            X, r, c = _empty(env, (n, N), t.float32), _empty(env, (n,), t.float32), _empty(env, (n,), t.float32)
+            X, r, c = empty(env, (n, N), t.float32), empty(env, (n,), t.float32), empty(env, (n,), t.float32)
             out = _out(env, n * N, t.float32)
             bufs = index_bufs + [adj[2], X, r, c]
             fn = getattr(L, entry)
@@ -1154,8 +1172,8 @@ def _raw_load_batches(with_work):
                 np.add.at(A, (r, c), 1.0)
                 dense.append(O.val2bit(A, 1))
             want.append([np.concatenate(dense), np.concatenate([O.val2bit(x, bits, True) for x in feats])])
-        src, dst = _empty(env, (sum(ecounts),), t.int64), _empty(env, (sum(ecounts),), t.int64)
-        X = _empty(env, (sum(sizes), F), t.float32)
+        src, dst = empty(env, (sum(ecounts),), t.int64), empty(env, (sum(ecounts),), t.int64)
+        X = empty(env, (sum(sizes), F), t.float32)
         # [A of every batch | stats (4 words) | scratch]: the first sum(a_words) words are the output, the rest is the entry's own
         zero = _i32(env, (3 * sum(a_words) + 4,))
         out_a = zero[: sum(a_words)]

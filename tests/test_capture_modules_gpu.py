@@ -60,7 +60,7 @@ def test_gcnconv_qnt_under_capture(env, adjacency, aggr, float_out):
     from tiled_model import set_cells
 
     torch, n = env.torch, N_NODES
-    src, dst = sc._graph(n, 41)
+    src, dst = sc.graph(n, 41)
     cells = set_cells(src, dst, n)
     s1, d1 = cells // n, cells % n            # the quantised adjacency's own edge list: the dense matrix below holds exactly these
     model = GCNConv_Qnt(F, H, C, w_bit=WB, act_bit=AB, aggr=aggr, float_out=float_out).to(env.dev)

@@ -99,7 +99,7 @@ def test_backward_builds_the_transposed_view_on_the_stream_it_runs_on(env, turn)
 
     torch, Q = env.torch, env.Q
     n, N = 600, 24
-    src, dst = sc._graph(n, 31)
+    src, dst = sc.graph(n, 31)
     adj = Q.pack_edges_tiled(torch.from_numpy(src).to(env.dev), torch.from_numpy(dst).to(env.dev), n)
     assert adj._other is None
     rng = np.random.default_rng(32)

@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from stream_cases import Live, capture_and_replay, eager_results, empty, env_of, ordering_probe, warm_adjacency
 from test_tiled_float_gpu import CANARY, NAN_WORD, NO_EDGES, assert_floats_identical
 from tiled_attn_model import (ATT_FORWARD_VARIANTS, ATT_GRAD_VARIANTS, ATT_TRANSPOSED_VARIANTS, att_chunks, att_grad_variant, att_variant,
                               attention_f32, attention_grads_f32, lrelu_f32)
@@ -280,49 +281,37 @@ def test_two_launches_give_identical_bits(qgtc):
 
 
 # ---- 6. streams and graph capture -----------------------------------------------------------------------------------------------------------
-def test_side_stream_and_graph_capture(qgtc):
-    """After one warm-up (it builds adj.T), forward and all three gradients on a side stream and captured into a graph; three replays
-    on new inputs equal the eager results."""
-    import torch
-
+def _live(env, transposed):
+    """Forward and all three gradients as a ``Live`` case of tests/stream_cases.py; the reference is the eager result on the default
+    stream."""
+    torch = env.torch
     n, N = 600, 40
     rng = np.random.default_rng(41)
     src, dst = random_edges(rng, n, 6 * n + 5)
-    adj = qgtc.pack_edges_tiled(_dev(torch, src), _dev(torch, dst), n)
-    data = [tuple(_dev(torch, t) for t in _inputs(rng, n, N)) for _ in range(4)]      # (X, dY, p, q)
+    adj = warm_adjacency(env, src, dst, n)
+    a = adj.T if transposed else adj
+    data = [_inputs(rng, n, N) for _ in range(4)]      # (X, dY, p, q)
+    X, dY, p, q = bufs = [empty(env, t.shape, torch.float32) for t in data[0]]
+    for t in (X, p, q):
+        t.requires_grad_(True)
 
-    def both_ways(a, X, dY, p, q):
-        Y = qgtc.tiledAggregate(a, X, attn=(p, q))
-        return (Y,) + torch.autograd.grad(Y, (X, p, q), dY)
+    def run():
+        Y = env.Q.tiledAggregate(a, X, attn=(p, q))
+        return [Y.detach(), *torch.autograd.grad(Y, (X, p, q), dY)]
 
-    for a in (adj, adj.T):
-        eager = []
-        for X, dY, p, q in data:                   # the first of these is the warm-up
-            res = both_ways(a, X.clone().requires_grad_(True), dY, p.clone().requires_grad_(True), q.clone().requires_grad_(True))
-            eager.append([t.detach().clone() for t in res])
-        torch.cuda.synchronize()
-        Xs, ps, qs = (data[0][i].clone().requires_grad_(True) for i in (0, 2, 3))
-        dYs = data[0][1].clone()
-        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            res = both_ways(a, Xs, dYs, ps, qs)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        assert all(_same(torch, r, e) for r, e in zip(res, eager[0])), a.transposed
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            res = both_ways(a, Xs, dYs, ps, qs)
-        for k in (1, 2, 3):
-            with torch.no_grad():
-                Xs.copy_(data[k][0])
-                dYs.copy_(data[k][1])
-                ps.copy_(data[k][2])
-                qs.copy_(data[k][3])
-            graph.replay()
-            torch.cuda.synchronize()
-            assert all(_same(torch, r, e) for r, e in zip(res, eager[k])), (a.transposed, k)
-            assert not torch.equal(eager[k][0], eager[0][0])
+    return Live(torch, bufs, data, eager_results(torch, bufs, data, run), run=run, keep=adj)
+
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["adj", "adjT"])
+def test_side_stream_and_graph_capture(qgtc, oracle, transposed):
+    """Forward and all three gradients behind a timed head start on three fresh side streams (``ordering_probe``) and captured into a
+    graph; three replays on new inputs equal the eager results (``capture_and_replay``)."""
+    import torch
+
+    live = _live(env_of(qgtc, oracle, torch), transposed)
+    what = f"attention, {'adj.T' if transposed else 'adj'}"
+    ordering_probe(torch, qgtc, live, what)
+    capture_and_replay(torch, qgtc, live, what)
 
 
 # ---- 7. the C entries write what they own and nothing else --------------------------------------------------------------------------------------

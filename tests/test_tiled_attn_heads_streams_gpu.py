@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import tiled_attn_heads_model as hm
-from stream_cases import Live, _empty, _graph, _warm_adjacency, capture_and_replay, env_of, ordering_probe
+from stream_cases import Live, empty, graph, warm_adjacency, capture_and_replay, env_of, ordering_probe
 
 pytestmark = pytest.mark.gpu
 
@@ -17,8 +17,8 @@ N_NODES, H, D = 600, 4, 6
 def _live(env, transposed, backward):
     torch = env.torch
     n = N_NODES
-    src, dst = _graph(n, 77)
-    adj = _warm_adjacency(env, src, dst, n)
+    src, dst = graph(n, 77)
+    adj = warm_adjacency(env, src, dst, n)
     view = adj.T if transposed else adj
     contents, want = [], []
     for k in range(4):
@@ -31,8 +31,8 @@ def _live(env, transposed, backward):
             want.append([Y, *hm.attention_grads_heads_f32(src, dst, n, X, p, q, G, Y, m, inv, 0.2, transposed)[:3]])
         else:
             want.append([Y, m, inv])
-    bufs = [_empty(env, (n, H * D), torch.float32), _empty(env, (n, H), torch.float32), _empty(env, (n, H), torch.float32),
-            _empty(env, (n, H * D), torch.float32)]
+    bufs = [empty(env, (n, H * D), torch.float32), empty(env, (n, H), torch.float32), empty(env, (n, H), torch.float32),
+            empty(env, (n, H * D), torch.float32)]
     if backward:
         for b in bufs[:3]:
             b.requires_grad_(True)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import tiled_drop_model as dm
+from stream_cases import Live, capture_and_replay, eager_results, empty, env_of, ordering_probe, same, warm_adjacency
 from test_tiled_float_gpu import CANARY, NAN_WORD, NO_EDGES, assert_floats_identical
 from tiled_attn_model import (ATT_FORWARD_VARIANTS, ATT_GRAD_VARIANTS, ATT_TRANSPOSED_VARIANTS, att_grad_variant, att_variant, attention_f32,
                               attention_grads_f32, lrelu_f32)
@@ -335,54 +336,49 @@ def test_two_launches_agree_and_two_seeds_differ(qgtc):
             assert (f.view(np.uint32) != o.view(np.uint32)).any(), name
 
 
-def test_side_stream_and_graph_capture(qgtc):
-    """After one warm-up (it builds adj.T), masked forward and backward of all three modes on a side stream and captured into a graph;
-    three replays on new inputs equal the eager results under the captured seed: a captured graph replays ONE mask."""
-    import torch
-
+def _live(env, transposed):
+    """Masked forward and backward of all three modes as a ``Live`` case of tests/stream_cases.py: X, dY, p and q are the contents, ONE
+    pair of scales and ONE seed stay (a captured graph replays one mask); the reference is the eager result on the default stream.
+    ``live.both_ways(edge_drop)`` runs the same on the buffers under another pair."""
+    torch, qgtc = env.torch, env.Q
     n, N, drop = 600, 40, (0.5, 0x0123456789ABCDEF)
     rng = np.random.default_rng(41)
     src, dst = random_edges(rng, n, 6 * n + 5)
-    adj = qgtc.pack_edges_tiled(_dev(torch, src), _dev(torch, dst), n)
-    data = [tuple(_dev(torch, t) for t in _inputs(rng, n, N)) for _ in range(4)]      # (X, dY, p, q, r, c)
+    adj = warm_adjacency(env, src, dst, n)
+    a = adj.T if transposed else adj
+    data = [_inputs(rng, n, N) for _ in range(4)]      # (X, dY, p, q, r, c)
+    r, c = _dev(torch, data[0][4]), _dev(torch, data[0][5])
+    contents = [d[:4] for d in data]
+    X, dY, p, q = bufs = [empty(env, t.shape, torch.float32) for t in contents[0]]
+    for t in (X, p, q):
+        t.requires_grad_(True)
 
-    def both_ways(a, X, dY, p, q, r, c, edge_drop=drop):
+    def both_ways(edge_drop=drop):
         Ys = qgtc.tiledAggregate(a, X, r, c, edge_drop=edge_drop)
         Ym = qgtc.tiledAggregate(a, X, reduce="max", edge_drop=edge_drop)
         Ya = qgtc.tiledAggregate(a, X, attn=(p, q), edge_drop=edge_drop)
-        return (Ys, Ym, Ya) + torch.autograd.grad(Ys, X, dY) + torch.autograd.grad(Ym, X, dY) + torch.autograd.grad(Ya, (X, p, q), dY)
+        grads = torch.autograd.grad(Ys, X, dY) + torch.autograd.grad(Ym, X, dY) + torch.autograd.grad(Ya, (X, p, q), dY)
+        return [Ys.detach(), Ym.detach(), Ya.detach(), *grads]
 
-    def leaves(d):
-        """X, p, q as leaves, dY, and ONE pair of scales: the graph's inputs are X, dY, p and q"""
-        X, dY, p, q = d[:4]
-        return X.clone().requires_grad_(True), dY.clone(), p.clone().requires_grad_(True), q.clone().requires_grad_(True), data[0][4], data[0][5]
+    live = Live(torch, bufs, contents, eager_results(torch, bufs, contents, both_ways), run=both_ways, keep=adj)
+    live.both_ways = both_ways
+    return live
 
-    for a in (adj, adj.T):
-        eager = [[t.detach().clone() for t in both_ways(a, *leaves(d))] for d in data]   # the first of these is the warm-up
-        torch.cuda.synchronize()
-        Xs, dYs, ps, qs, r, c = leaves(data[0])
-        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            res = both_ways(a, Xs, dYs, ps, qs, r, c)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        assert all(_same(torch, x, e) for x, e in zip(res, eager[0])), a.transposed
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            res = both_ways(a, Xs, dYs, ps, qs, r, c)
-        for k in (1, 2, 3):
-            with torch.no_grad():
-                Xs.copy_(data[k][0])
-                dYs.copy_(data[k][1])
-                ps.copy_(data[k][2])
-                qs.copy_(data[k][3])
-            graph.replay()
-            torch.cuda.synchronize()
-            assert all(_same(torch, x, e) for x, e in zip(res, eager[k])), (a.transposed, k)
-            assert not torch.equal(eager[k][0], eager[0][0])
-        other = both_ways(a, *leaves(data[3]), edge_drop=(0.5, 7))
-        assert not any(_same(torch, x, e) for x, e in zip(other[:3], eager[3][:3]))
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["adj", "adjT"])
+def test_side_stream_and_graph_capture(qgtc, oracle, transposed):
+    """Masked forward and backward of all three modes behind a timed head start on three fresh side streams (``ordering_probe``) and
+    captured into a graph; three replays on new inputs equal the eager results under the captured seed (``capture_and_replay``).
+    Another seed gives other results."""
+    import torch
+
+    live = _live(env_of(qgtc, oracle, torch), transposed)
+    what = f"edge dropout, {'adj.T' if transposed else 'adj'}"
+    ordering_probe(torch, qgtc, live, what)
+    capture_and_replay(torch, qgtc, live, what)
+    live.load(3)
+    other = [t.cpu() for t in live.both_ways(edge_drop=(0.5, 7))]
+    assert not any(same(x, e) for x, e in zip(other[:3], live.expected[3][:3]))
 
 
 # ---- 5. the C entries write what they own and nothing else -----------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from stream_cases import Live, capture_and_replay, eager_results, empty, env_of, ordering_probe, warm_adjacency
 from test_tiled_float_gpu import CANARY, NAN_WORD, NO_EDGES, SWEEP, assert_floats_identical
 from tiled_float_model import neighbour_lists
 from tiled_max_model import (MAX, MAX_FORWARD_VARIANTS, MAX_TRANSPOSED_VARIANTS, MIN, SELECT_FORWARD_VARIANTS, SELECT_TRANSPOSED_VARIANTS,
@@ -364,48 +365,35 @@ def test_two_launches_give_identical_bits(qgtc):
 
 
 # ---- 8. streams and graph capture ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["max", "min"])
-def test_side_stream_and_graph_capture(qgtc, name):
-    """After one warm-up (it builds adj.T), forward and backward on a side stream and captured into a graph; three replays on new
-    inputs equal the eager results."""
-    import torch
-
+def _live(env, transposed, name):
+    """Forward and backward as a ``Live`` case of tests/stream_cases.py; the reference is the eager result on the default stream."""
+    torch = env.torch
     n, N = 600, 40
     rng = np.random.default_rng(41)
     src, dst = random_edges(rng, n, 6 * n + 5)
-    adj = qgtc.pack_edges_tiled(_dev(torch, src), _dev(torch, dst), n)
-    data = [(_dev(torch, _tied(rng, n, N)), _dev(torch, rng.standard_normal((n, N)).astype(np.float32))) for _ in range(4)]
+    adj = warm_adjacency(env, src, dst, n)
+    a = adj.T if transposed else adj
+    data = [(_tied(rng, n, N), rng.standard_normal((n, N)).astype(np.float32)) for _ in range(4)]      # (X, dY)
+    X, dY = bufs = [empty(env, (n, N), torch.float32).requires_grad_(True), empty(env, (n, N), torch.float32)]
 
-    def both_ways(a, X, dY):
-        Y = qgtc.tiledAggregate(a, X, reduce=name)
-        return Y, torch.autograd.grad(Y, X, dY)[0]
+    def run():
+        Y = env.Q.tiledAggregate(a, X, reduce=name)
+        return [Y.detach(), torch.autograd.grad(Y, X, dY)[0]]
 
-    for a in (adj, adj.T):
-        eager = []
-        for X, dY in data:                         # the first of these is the warm-up
-            Y, g = both_ways(a, X.clone().requires_grad_(True), dY)
-            eager.append((Y.detach().clone(), g.clone()))
-        torch.cuda.synchronize()
-        Xs, dYs = data[0][0].clone().requires_grad_(True), data[0][1].clone()
-        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            Y, g = both_ways(a, Xs, dYs)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        assert torch.equal(Y.detach().view(torch.int32), eager[0][0].view(torch.int32)) and torch.equal(g.view(torch.int32), eager[0][1].view(torch.int32))
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            Y, g = both_ways(a, Xs, dYs)
-        for k in (1, 2, 3):
-            with torch.no_grad():
-                Xs.copy_(data[k][0])
-                dYs.copy_(data[k][1])
-            graph.replay()
-            torch.cuda.synchronize()
-            assert torch.equal(Y.detach().view(torch.int32), eager[k][0].view(torch.int32)), (a.transposed, k)
-            assert torch.equal(g.view(torch.int32), eager[k][1].view(torch.int32)), (a.transposed, k)
-            assert not torch.equal(eager[k][0], eager[0][0])
+    return Live(torch, bufs, data, eager_results(torch, bufs, data, run), run=run, keep=adj)
+
+
+@pytest.mark.parametrize("name", ["max", "min"])
+@pytest.mark.parametrize("transposed", [False, True], ids=["adj", "adjT"])
+def test_side_stream_and_graph_capture(qgtc, oracle, transposed, name):
+    """Forward and backward behind a timed head start on three fresh side streams (``ordering_probe``) and captured into a graph; three
+    replays on new inputs equal the eager results (``capture_and_replay``)."""
+    import torch
+
+    live = _live(env_of(qgtc, oracle, torch), transposed, name)
+    what = f"{name}, {'adj.T' if transposed else 'adj'}"
+    ordering_probe(torch, qgtc, live, what)
+    capture_and_replay(torch, qgtc, live, what)
 
 
 # ---- 9. refusals --------------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import pytest
 
 import tiled_nodes_model as nm
 from qgtc_ppopp22_amd.tiled import node_bitmap
+from stream_cases import Live, capture_and_replay, eager_results, empty, env_of, ordering_probe, warm_adjacency
 from test_tiled_drop_gpu import NAMES, _assert_all, _dev, _forwards, _grads, _inputs, _models, _np, _same
 from test_tiled_float_gpu import CANARY, NAN_WORD, NO_EDGES, assert_floats_identical
 from tiled_attn_model import (ATT_FORWARD_VARIANTS, ATT_GRAD_VARIANTS, ATT_TRANSPOSED_VARIANTS, att_grad_variant, att_variant, attention_f32,
@@ -260,54 +261,44 @@ def test_two_launches_agree_and_two_masks_differ(qgtc):
                 assert (f.view(np.uint32) != o.view(np.uint32)).any(), name
 
 
-def test_side_stream_and_graph_capture(qgtc):
-    """After one warm-up (it builds adj.T), masked forward and backward of all three modes on a side stream and captured into a graph;
-    three replays on new inputs equal the eager results. The bitmaps are read on the device: a replay follows their contents."""
-    import torch
-
+def _live(env, transposed):
+    """Masked forward and backward of all three modes as a ``Live`` case of tests/stream_cases.py: X, dY, p and q are the contents, one
+    pair of scales and one pair of bitmaps stay; the reference is the eager result on the default stream."""
+    torch, qgtc = env.torch, env.Q
     n, N = 600, 40
     rng = np.random.default_rng(41)
     src, dst = random_edges(rng, n, 6 * n + 5)
-    adj = qgtc.pack_edges_tiled(_dev(torch, src), _dev(torch, dst), n)
-    data = [tuple(_dev(torch, t) for t in _inputs(rng, n, N)) for _ in range(4)]      # (X, dY, p, q, r, c)
+    adj = warm_adjacency(env, src, dst, n)
+    a = adj.T if transposed else adj
+    data = [_inputs(rng, n, N) for _ in range(4)]      # (X, dY, p, q, r, c)
     Rf, Sf = rng.random(n) < 0.5, rng.random(n) < 0.5
-    rm, sm = _bm(torch, qgtc, Rf, n), _bm(torch, qgtc, Sf, n)
+    kw = {"row_mask": _bm(torch, qgtc, Rf, n), "nbr_mask": _bm(torch, qgtc, Sf, n)}
+    r, c = _dev(torch, data[0][4]), _dev(torch, data[0][5])
+    contents = [d[:4] for d in data]
+    X, dY, p, q = bufs = [empty(env, t.shape, torch.float32) for t in contents[0]]
+    for t in (X, p, q):
+        t.requires_grad_(True)
 
-    def both_ways(a, X, dY, p, q, r, c):
-        kw = {"row_mask": rm, "nbr_mask": sm}
+    def run():
         Ys = qgtc.tiledAggregate(a, X, r, c, **kw)
         Ym = qgtc.tiledAggregate(a, X, reduce="max", **kw)
         Ya = qgtc.tiledAggregate(a, X, attn=(p, q), **kw)
-        return (Ys, Ym, Ya) + torch.autograd.grad(Ys, X, dY) + torch.autograd.grad(Ym, X, dY) + torch.autograd.grad(Ya, (X, p, q), dY)
+        grads = torch.autograd.grad(Ys, X, dY) + torch.autograd.grad(Ym, X, dY) + torch.autograd.grad(Ya, (X, p, q), dY)
+        return [Ys.detach(), Ym.detach(), Ya.detach(), *grads]
 
-    def leaves(d):
-        X, dY, p, q = d[:4]
-        return X.clone().requires_grad_(True), dY.clone(), p.clone().requires_grad_(True), q.clone().requires_grad_(True), data[0][4], data[0][5]
+    return Live(torch, bufs, contents, eager_results(torch, bufs, contents, run), run=run, keep=(adj, kw))
 
-    for a in (adj, adj.T):
-        eager = [[t.detach().clone() for t in both_ways(a, *leaves(d))] for d in data]   # the first of these is the warm-up
-        torch.cuda.synchronize()
-        Xs, dYs, ps, qs, r, c = leaves(data[0])
-        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            res = both_ways(a, Xs, dYs, ps, qs, r, c)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        assert all(_same(torch, x, e) for x, e in zip(res, eager[0])), a.transposed
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            res = both_ways(a, Xs, dYs, ps, qs, r, c)
-        for k in (1, 2, 3):
-            with torch.no_grad():
-                Xs.copy_(data[k][0])
-                dYs.copy_(data[k][1])
-                ps.copy_(data[k][2])
-                qs.copy_(data[k][3])
-            graph.replay()
-            torch.cuda.synchronize()
-            assert all(_same(torch, x, e) for x, e in zip(res, eager[k])), (a.transposed, k)
-            assert not torch.equal(eager[k][0], eager[0][0])
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["adj", "adjT"])
+def test_side_stream_and_graph_capture(qgtc, oracle, transposed):
+    """Masked forward and backward of all three modes behind a timed head start on three fresh side streams (``ordering_probe``) and
+    captured into a graph; three replays on new inputs equal the eager results (``capture_and_replay``)."""
+    import torch
+
+    live = _live(env_of(qgtc, oracle, torch), transposed)
+    what = f"node masks, {'adj.T' if transposed else 'adj'}"
+    ordering_probe(torch, qgtc, live, what)
+    capture_and_replay(torch, qgtc, live, what)
 
 
 # ---- 4. the C entries write what they own and nothing else, and ignore pad bits ----------------------------------------------------------------
@@ -506,20 +497,14 @@ def test_node_bitmap(qgtc, n):
         node_bitmap(torch.tensor([-1], device="cuda"), n)
 
 
-def test_node_bitmap_and_masked_scales_follow_the_current_stream(qgtc):
-    """tiled.node_bitmap (from flags) and the masked mean_scale / sym_scale reach their C entries through ctypes with the handle of
-    torch's current stream: behind a head start of plain torch work on a side stream they see the flags copied in on that stream, and a
-    captured graph replays them on new flags."""
-    import torch
-
+def _bitmap_live(env):
+    torch = env.torch
     n = 1000
     rng = np.random.default_rng(77)
     src, dst = random_edges(rng, n, 6 * n + 5)
-    adj = qgtc.pack_edges_tiled(_dev(torch, src), _dev(torch, dst), n)
-    adj.T                                          # the column index, before any capture
+    adj = warm_adjacency(env, src, dst, n)
     flags = [rng.random(n) < 0.5 for _ in range(4)]
-    pinned = [torch.from_numpy(f).pin_memory() for f in flags]
-    buf = torch.zeros(n, dtype=torch.bool, device="cuda")
+    buf = empty(env, (n,), torch.bool)
 
     def run():
         bm = node_bitmap(buf, n)
@@ -529,32 +514,18 @@ def test_node_bitmap_and_masked_scales_follow_the_current_stream(qgtc):
         ks, kd = nm.induced_edges(src, dst, n, f, f, False)
         return [nm.bitmap(f).view(np.int32), mean_scale(neighbour_lists(ks, kd, n, False)[2]), inv_sqrt_degree(neighbour_lists(ks, kd, n, True)[2])]
 
-    def same(got, f, what):
-        for g, w in zip(got, want(f)):
-            assert (_np(g).view(np.uint32) == np.ascontiguousarray(w).view(np.uint32)).all(), what
+    return Live(torch, [buf], [[f] for f in flags], [want(f) for f in flags], run=run, keep=adj)
 
-    buf.copy_(pinned[0])
-    same(run(), flags[0], "eager")
-    torch.cuda.synchronize()
-    filler_a, filler_b = torch.rand(4096, 4096, device="cuda"), torch.rand(4096, 4096, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(8):
-            filler_a = torch.mm(filler_a, filler_b).clamp_(0, 1)       # the head start: work queued ahead on the side stream
-        buf.copy_(pinned[1], non_blocking=True)
-        got = run()
-    side.synchronize()
-    same(got, flags[1], "side stream: a launch on another stream would have read the previous flags")
-    torch.cuda.current_stream().wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        got = run()
-    for k in (2, 3, 1):
-        buf.copy_(pinned[k])
-        graph.replay()
-        torch.cuda.synchronize()
-        same(got, flags[k], f"replay on flags {k}")
+
+def test_node_bitmap_and_masked_scales_follow_the_current_stream(qgtc, oracle):
+    """tiled.node_bitmap (from flags) and the masked mean_scale / sym_scale reach their C entries through ctypes with the handle of
+    torch's current stream: behind a timed head start on three fresh side streams they see the flags copied in on that stream
+    (``ordering_probe`` of tests/stream_cases.py), and a captured graph replays them on new flags (``capture_and_replay``)."""
+    import torch
+
+    live = _bitmap_live(env_of(qgtc, oracle, torch))
+    ordering_probe(torch, qgtc, live, "node bitmap and masked scales")
+    capture_and_replay(torch, qgtc, live, "node bitmap and masked scales")
 
 
 def test_masked_degrees_and_scales(qgtc):
