@@ -60,7 +60,8 @@ struct TiledClamp {
     explicit TiledClamp(int ob) : maxv(std::ldexp(1.0f, ob)), maxm1(maxv - 1.0f) {}
 };
 
-// The launchers of the two kernels, at the foot of tiled_kernels.hip.h and tiled_t_kernels.hip.h: `scale` is () or (row_scale).
+// The launchers of the two kernels, at the foot of tiled_kernels.hip.h and tiled_t_kernels.hip.h: `scale` is () or (row_scale), and
+// either with the node masks (a TiledNodes of tiled_nodes.hip.h) behind it.
 template <int MODE, class... Scale>
 int tiled_mm_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N,
                     int bit2, int ob, void *out, hipStream_t st, Scale... scale);

@@ -12,6 +12,7 @@
 #pragma once
 
 #include "tiled_args.hip.h"
+#include "tiled_nodes.hip.h"
 
 namespace {
 
@@ -108,16 +109,26 @@ __global__ void k_tiled_fill(const uint64_t *__restrict__ cells, const uint64_t 
 // thread's R rows (row < n only) and forms y = float(sum) * row_scale[row], one IEEE single multiply; MODE 2 stores y, MODE 0 runs
 // the value quantiser quant1 on y in place of requant. `Scale` is empty - the unscaled kernel, with the arguments and the code it
 // always had - or one `const float *`, row_scale, behind `out`.
+//
+// NODES (include/qgtc_bitnodes.h): the pack ends in a TiledNodes, the two node bitmaps (either may be null: all
+// nodes). The block's rows are the one word row_mask[rb]: zero, and the workgroup reads no index, no tile and no X and runs the epilogue on
+// zero sums. Per tile the four words nbr_mask[4q .. 4q + 3] are one uniform 16-byte read (a scalar load): all zero, and the tile is skipped
+// before X's planes are loaded; otherwise they are ANDed into every tile row ahead of the non-zero test, and a row outside row_mask counts
+// as an empty tile row. Without a TiledNodes every `if constexpr (NODES)` is discarded and the kernels are the ones that existed.
 __device__ __forceinline__ const float *tiled_scale_ptr() { return nullptr; }
 __device__ __forceinline__ const float *tiled_scale_ptr(const float *p) { return p; }
+__device__ __forceinline__ const float *tiled_scale_ptr(const TiledNodes &) { return nullptr; }
+__device__ __forceinline__ const float *tiled_scale_ptr(const float *p, const TiledNodes &) { return p; }
 
 template <int R, int MODE, typename... Scale>
 __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                   const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                   const uint32_t *__restrict__ X, uint64_t x_words, int N, int bit2, int ob,
                                                   float maxv, float maxm1, void *__restrict__ out, Scale... scale) {
-    constexpr bool SCALED = sizeof...(Scale) > 0;
+    constexpr bool NODES = tiled_has_nodes<Scale...>();
+    constexpr bool SCALED = sizeof...(Scale) > (NODES ? 1 : 0);
     [[maybe_unused]] const float *__restrict__ row_scale = tiled_scale_ptr(scale...);
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(scale...);
     constexpr int RS = 32 / R, CW = 256 / RS;   // row groups per block, columns per workgroup
     const int rb = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
     const int rs = CW >= 64 ? __builtin_amdgcn_readfirstlane(tid / CW) : tid / CW;
@@ -129,11 +140,23 @@ __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ ro
 #pragma unroll
     for (int i = 0; i < R; ++i) acc[i] = 0;
 
-    uint64_t t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
+    // with masks: the row bitmap's word of this block, and this thread's R rows of it from bit 31 down
+    [[maybe_unused]] uint32_t rword = 0xffffffffu, rlive = 0xffffffffu;
+    if constexpr (NODES) {
+        rword = tiled_nodes_word(nodes.row, rb);
+        rlive = rword << (rs * R);
+    }
+    const bool live = tiled_nodes_and<NODES>(true, rword != 0);   // a dead block reads no row_ptr: its tile range is empty
+    uint64_t t1 = live ? static_cast<uint64_t>(row_ptr[rb + 1]) : 0;
     t1 = t1 < n_tiles ? t1 : n_tiles;
-    for (uint64_t t = static_cast<uint64_t>(row_ptr[rb]); t < t1; ++t) {
+    for (uint64_t t = live ? static_cast<uint64_t>(row_ptr[rb]) : 0; t < t1; ++t) {
         const int q = kquad[t];
         if (static_cast<unsigned>(q) >= static_cast<unsigned>(nq)) continue;
+        [[maybe_unused]] uint4 nb;
+        if constexpr (NODES) {
+            nb = tiled_nodes_quad(nodes.nbr, q);
+            if (!(nb.x | nb.y | nb.z | nb.w)) continue;   // no neighbour of this k-quad takes part: X's planes stay unread
+        }
         uint4 x[8];
 #pragma unroll
         for (int p = 0; p < 8; ++p)
@@ -141,8 +164,9 @@ __global__ __launch_bounds__(256) void k_tiled_mm(const int64_t *__restrict__ ro
         const uint4 *a = reinterpret_cast<const uint4 *>(tiles + t * 128) + rs * R;
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const uint4 ai = a[i];
-            if (ai.x | ai.y | ai.z | ai.w) {
+            uint4 ai = a[i];
+            if constexpr (NODES) ai = make_uint4(ai.x & nb.x, ai.y & nb.y, ai.z & nb.z, ai.w & nb.w);
+            if (tiled_nodes_and<NODES>((ai.x | ai.y | ai.z | ai.w) != 0, tiled_nodes_bit(rlive, i))) {
                 int s = 0;
 #pragma unroll
                 for (int p = 0; p < 8; ++p)
@@ -213,8 +237,8 @@ void tiled_mm_rows_switch(int N, F &&launch) {
     }
 }
 
-// It ends in the kernel's own trailing pack and forwards it: empty is the plain kernel, (row_scale) the scaled one
-// (DESIGN.md section 6.15f).
+// It ends in the kernel's own trailing pack and forwards it: empty is the plain kernel, (row_scale) the scaled one, and either
+// with a TiledNodes behind it the masked one (DESIGN.md sections 6.15f, 6.15n).
 template <int MODE, class... Scale>
 int tiled_mm_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N,
                     int bit2, int ob, void *out, hipStream_t st, Scale... scale) {

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "tiled_args.hip.h"
+#include "tiled_nodes.hip.h"
 
 namespace {
 
@@ -82,16 +83,26 @@ __device__ __forceinline__ void tiled_t_transpose(uint32_t (&v)[4], int lane) {
 
 // SCALED: as in k_tiled_mm - y = float(sum) * row_scale[row] in the epilogue (row < n only), stored (MODE 2) or quantised by quant1
 // in place of requant (MODE 0). `Scale` is empty (the unscaled kernel, arguments and code as they always were) or one `const float *`.
+//
+// NODES (include/qgtc_bitnodes.h): the pack ends in a TiledNodes. The k-quad's output rows are the four words
+// row_mask[4q .. 4q + 3], one uniform 16-byte read: all zero, and the workgroup reads no col_ptr, no tile and no X. A masked-out output
+// row's column mask is cleared as it is staged, so the multiply's non-zero test (uniform from R = 32 up) skips it as it skips an empty
+// column. A staged tile's neighbours are A's rows 32 rb .., the one word nbr_mask[rb], in the bit order of the column masks and of X's line
+// word: zero, and the tile is skipped before X's words are loaded; otherwise it is ANDed into X's bit2 words once per tile.
 __device__ __forceinline__ const float *tiled_t_scale_ptr() { return nullptr; }
 __device__ __forceinline__ const float *tiled_t_scale_ptr(const float *p) { return p; }
+__device__ __forceinline__ const float *tiled_t_scale_ptr(const TiledNodes &) { return nullptr; }
+__device__ __forceinline__ const float *tiled_t_scale_ptr(const float *p, const TiledNodes &) { return p; }
 
 template <int R, int MODE, typename... Scale>
 __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                     const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                     uint64_t n_tiles, int n, const uint32_t *__restrict__ X, uint64_t x_words, int N,
                                                     int bit2, int ob, float maxv, float maxm1, void *__restrict__ out, Scale... scale) {
-    constexpr bool SCALED = sizeof...(Scale) > 0;
+    constexpr bool NODES = tiled_has_nodes<Scale...>();
+    constexpr bool SCALED = sizeof...(Scale) > (NODES ? 1 : 0);
     [[maybe_unused]] const float *__restrict__ row_scale = tiled_t_scale_ptr(scale...);
+    [[maybe_unused]] const TiledNodes nodes = tiled_nodes_of(scale...);
     constexpr int RS = 128 / R, CW = 256 / RS;   // row groups per k-quad, columns per workgroup
     constexpr int TS = TILED_T_TS;
     const int q = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
@@ -109,9 +120,13 @@ __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ 
 
     // transposer role: half-wave s of the workgroup stages tile base + s
     const int lane = tid & 31, s_own = tid >> 5;
-    uint64_t t1 = static_cast<uint64_t>(col_ptr[q + 1]);
+    // with masks: the row bitmap's four words of this k-quad's 128 output rows
+    [[maybe_unused]] uint4 rq = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if constexpr (NODES) rq = tiled_nodes_quad(nodes.row, q);
+    const bool live = tiled_nodes_and<NODES>(true, (rq.x | rq.y | rq.z | rq.w) != 0);   // a dead k-quad reads no col_ptr: its list is empty
+    uint64_t t1 = live ? static_cast<uint64_t>(col_ptr[q + 1]) : 0;
     t1 = t1 < n_tiles ? t1 : n_tiles;
-    for (uint64_t base = static_cast<uint64_t>(col_ptr[q]); base < t1; base += TS) {
+    for (uint64_t base = live ? static_cast<uint64_t>(col_ptr[q]) : 0; base < t1; base += TS) {
         {
             const uint64_t i = base + s_own;
             uint4 w = make_uint4(0, 0, 0, 0);
@@ -124,6 +139,11 @@ __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ 
             }
             uint32_t v[4] = {w.x, w.y, w.z, w.w};
             tiled_t_transpose(v, lane);
+            if constexpr (NODES) {   // v[k] is output row 32 k + 31 - lane of the k-quad: bit `lane` of its word
+                const uint32_t rw[4] = {rq.x, rq.y, rq.z, rq.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = ((rw[k] >> lane) & 1u) ? v[k] : 0u;
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) mk[s_own * 128 + k * 32 + 31 - lane] = v[k];
             if (lane == 0) srb[s_own] = rb;
@@ -133,9 +153,18 @@ __global__ __launch_bounds__(256) void k_tiled_mm_t(const int64_t *__restrict__ 
         for (int s = 0; s < ns; ++s) {
             const int rb = srb[s];
             if (static_cast<unsigned>(rb) >= static_cast<unsigned>(nrb)) continue;
+            [[maybe_unused]] uint32_t nbw = 0xffffffffu;
+            if constexpr (NODES) {
+                nbw = tiled_nodes_word(nodes.nbr, rb);
+                if (!nbw) continue;   // none of the tile's 32 neighbours takes part: X's words stay unread
+            }
             uint32_t x[8];
 #pragma unroll
             for (int p = 0; p < 8; ++p) x[p] = (cv && p < bit2) ? ldw(X, x_words, p * plane + xcol + static_cast<uint64_t>(rb)) : 0u;
+            if constexpr (NODES) {
+#pragma unroll
+                for (int p = 0; p < 8; ++p) x[p] &= nbw;
+            }
             const uint4 *mrow = reinterpret_cast<const uint4 *>(mk + s * 128 + rs * R);
 #pragma unroll
             for (int i4 = 0; i4 < R / 4; ++i4) {
@@ -227,7 +256,7 @@ void tiled_mm_t_rows_switch(int N, F &&launch) {
     }
 }
 
-// the column view's overload of tiled_kernels.hip.h's launcher: the pack is empty or (row_scale)
+// the column view's overload of tiled_kernels.hip.h's launcher: the pack is empty or (row_scale), and either with a TiledNodes behind it
 template <int MODE, class... Scale>
 int tiled_mm_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint32_t *X, size_t x_words, int N,
                     int bit2, int ob, void *out, hipStream_t st, Scale... scale) {

@@ -104,7 +104,15 @@ aggregates against today's route for the same batch - per hop, filter the edge l
 pack_edges_tiled, the plain mean launch, the next row set by a scatter -, (b) the frontier launch against the three-launch route (the
 N = 1 sampled product of ones on the other view, a compare, node_bitmap) and (c) the masked selection against the unmasked one.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks]
+`--leg bitnodes` measures node masks on the quantised products (``row_mask=`` / ``nbr_mask=`` of QGTC.tiledMM2Bit) on
+the reordered graphs (pass --graphs arxiv,reddit), both directions, N = 64, 1 and 2 feature bits (output bits alike), under the node sets
+of `--leg nodes`: a contiguous eighth, a community-aligned eighth and a random eighth, each as both masks, and a random half as the row
+mask alone. Two alternating loops: first the plain launch, the four masked launches and the masked launch with all-ones bitmaps; second
+the route each masked launch replaces - filter the edge list, pack_edges_tiled, (on adj.T: build the column index,) plain launch. Every
+masked product is checked equal to the plain launch on the re-packed adjacency before timing. Medians with their 10th and 90th
+percentiles, the share of live workgroups, and the ratios masked / plain and masked / re-pack.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes]
 """
 from __future__ import annotations
 
@@ -649,6 +657,80 @@ def nodes_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def bitnodes_leg(torch, QGTC, graphs, reps):
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+    from qgtc_ppopp22_amd.tiled import node_bitmap
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        t = adj.T
+        # the set cells as an edge list in the adjacency's numbering (multiplicity 2 is unset, as the packer quantises it)
+        keys, counts = torch.unique(adj.rank.index_select(0, dsrc) * n + adj.rank.index_select(0, ddst), return_counts=True)
+        keys = keys[counts != 2]
+        e_row, e_col = (keys // n).contiguous(), (keys % n).contiguous()
+        mr = np.random.default_rng(11)
+        ids = np.arange(n)
+        quads = (n + 127) // 128
+        sets = {"contiguous_eighth": ids < n // 8,
+                "community_eighth": np.isin(ids // 128, mr.permutation(quads)[: max(1, quads // 8)]),
+                "random_eighth": mr.random(n) < 0.125,
+                "rows_half": mr.random(n) < 0.5}
+        ones = node_bitmap(torch.ones(n, dtype=torch.bool, device="cuda"), n)
+        masks = {}
+        for kind, f in sets.items():
+            fl = torch.from_numpy(f).cuda()
+            bm = node_bitmap(fl, n)
+            masks[kind] = (fl, None, bm, None) if kind == "rows_half" else (fl, fl, bm, bm)
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": int(keys.numel()), "tiles": adj.n_tiles,
+               "node_share": {k: round(float(f.mean()), 4) for k, f in sets.items()}, "agg": []}
+        print(f"{name:9s} T={adj.n_tiles} set cells {int(keys.numel())}", flush=True)
+        xr = np.random.default_rng(1)
+        N = 64
+        for w in (1, 2):
+            X = QGTC.val2bit(torch.from_numpy(xr.integers(0, 2 ** w, size=(n, N)).astype(np.float32)).cuda(), w, True, False)
+            for a, direction in ((adj, "forward"), (t, "transposed")):
+                e_out, e_nbr = (e_col, e_row) if a.transposed else (e_row, e_col)
+
+                def induced(kind):
+                    R, S = masks[kind][:2]
+                    k = R[e_out] if S is None else R[e_out] & S[e_nbr]
+                    sub = QGTC.pack_edges_tiled(e_row[k], e_col[k], n, False)
+                    return sub.T if a.transposed else sub
+
+                def masked(kind):
+                    return lambda: QGTC.tiledMM2Bit(a, X, N, w, w, row_mask=masks[kind][2], nbr_mask=masks[kind][3])
+
+                out = {"N": N, "w": w, "direction": direction}
+                for kind in sets:
+                    assert torch.equal(masked(kind)(), QGTC.tiledMM2Bit(induced(kind), X, N, w, w)), (w, direction, kind)
+                    # one workgroup a k-quad on adj.T, a 32-row block on adj
+                    words = masks[kind][2].view(-1, 4) if a.transposed else masks[kind][2][: (n + 31) // 32].view(-1, 1)
+                    out[f"live_workgroups_{kind}"] = round(float((words != 0).any(dim=1).float().mean()), 4)
+                assert torch.equal(QGTC.tiledMM2Bit(a, X, N, w, w, row_mask=ones, nbr_mask=ones), QGTC.tiledMM2Bit(a, X, N, w, w))
+                kinds = list(sets)
+                ta, *tm, to = timed_alternating(torch, [lambda: QGTC.tiledMM2Bit(a, X, N, w, w)] + [masked(k) for k in kinds]
+                                                + [lambda: QGTC.tiledMM2Bit(a, X, N, w, w, row_mask=ones, nbr_mask=ones)], reps)
+                tr = timed_alternating(torch, [(lambda k=k: QGTC.tiledMM2Bit(induced(k), X, N, w, w)) for k in kinds], reps)
+                out.update({"plain_ms": ta, "all_ones_masked_ms": to, "all_ones_over_plain": round(to[0] / ta[0], 3)})
+                line = f"{name:9s} N={N:<4d} w={w} {direction:10s} plain {ta[0]:.4f} [{ta[1]:.4f}, {ta[2]:.4f}]  all ones {to[0]:.4f} ({to[0] / ta[0]:.3f}x)"
+                for i, k in enumerate(kinds):
+                    out.update({f"masked_{k}_ms": tm[i], f"filter_repack_plain_{k}_ms": tr[i], f"masked_{k}_over_plain": round(tm[i][0] / ta[0], 3),
+                                f"masked_{k}_over_repack": round(tm[i][0] / tr[i][0], 3)})
+                    line += f"  {k} {tm[i][0]:.4f} [{tm[i][1]:.4f}, {tm[i][2]:.4f}] ({tm[i][0] / ta[0]:.3f}x plain, {tm[i][0] / tr[i][0]:.3f}x repack {tr[i][0]:.4f})"
+                rec["agg"].append(out)
+                print(line, flush=True)
+            del X
+        rows.append(rec)
+        del adj, t, dsrc, ddst, keys, e_row, e_col, masks
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1170,7 +1252,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes"))
     args = ap.parse_args()
 
     import torch
@@ -1178,9 +1260,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
