@@ -112,7 +112,11 @@ the route each masked launch replaces - filter the edge list, pack_edges_tiled, 
 masked product is checked equal to the plain launch on the re-packed adjacency before timing. Medians with their 10th and 90th
 percentiles, the share of live workgroups, and the ratios masked / plain and masked / re-pack.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes]
+`--leg affine` measures affine quantisation (qgtc_ppopp22_amd/affine.py) on the reordered graphs at N = 64: the range
+launch, ``val2bit_affine`` in both layouts at 2 / 4 / 8 bits beside ``QGTC.val2bit`` at the same shape, ``dequant``, ``aggregate`` beside
+``tiledMM2Int`` alone and ``tiledMMFloat``, the layer's forward beside ``conv.GCNConv``'s and its relative error against the float layer.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine]
 """
 from __future__ import annotations
 
@@ -731,6 +735,88 @@ def bitnodes_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def affine_leg(torch, QGTC, graphs, reps):
+    """Affine quantisation (qgtc_ppopp22_amd/affine.py) on the reordered graphs at N = 64: the range launch, the fused
+    quantise + pack beside QGTC.val2bit at the same shape, the dequantising epilogue, affine.aggregate beside tiledMM2Int alone and beside
+    tiledMMFloat, the layer's forward beside conv.GCNConv's, and the layer's relative error against the float layer. No pass mark."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    N, dims = 64, (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T, adj.mean_scale()
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "tiles": adj.n_tiles, "N": N, "dims": list(dims), "agg": []}
+        xr = np.random.default_rng(1)
+        X = torch.from_numpy(xr.normal(size=(n, N)).astype(np.float32)).cuda()
+        Xpos = (X.abs() * 2.0).contiguous()      # what the parent's quantiser is meaningful on: values in [0, 2^b]
+        x_bytes = n * N * 4
+        qt, qc = timed_alternating(torch, [lambda: affine.qparams(X, 8), lambda: affine.qparams(X, 8, per_column=True)], reps)
+        rec["qparams_ms"], rec["qparams_per_column_ms"] = qt, qc
+        rec["qparams_GBps"] = round(x_bytes / qt[0] / 1e6, 1)
+        print(f"{name:9s} n={n} N={N} qparams {qt[0]:.4f} ms ({rec['qparams_GBps']} GB/s of x)  per column {qc[0]:.4f} ms", flush=True)
+        for bits in (2, 4, 8):
+            qp = affine.qparams(X, bits)
+            out = {"bits": bits}
+            for cm, layout in ((False, "rows"), (True, "cols")):
+                new, new_sums, old = timed_alternating(torch, [lambda: affine.val2bit_affine(X, bits, qp, cm, False),
+                                                               lambda: affine.val2bit_affine(X, bits, qp, cm, True),
+                                                               lambda: QGTC.val2bit(Xpos, bits, cm, False)], reps)
+                out.update({f"val2bit_affine_{layout}_ms": new, f"val2bit_affine_{layout}_sums_ms": new_sums, f"val2bit_{layout}_ms": old,
+                            f"affine_over_val2bit_{layout}": round(new[0] / old[0], 3), f"sums_launch_{layout}_ms": round(new_sums[0] - new[0], 4)})
+                print(f"{name:9s} {bits} bits {layout}: val2bit_affine {new[0]:.4f} [{new[1]:.4f}, {new[2]:.4f}] ms, with sums {new_sums[0]:.4f}, "
+                      f"val2bit {old[0]:.4f} [{old[1]:.4f}, {old[2]:.4f}] ms, ratio {new[0] / old[0]:.3f}", flush=True)
+            bit_T, _ = affine.val2bit_affine(X, bits, qp, True, False)
+            acc = QGTC.tiledMM2Int(adj, bit_T, N, bits)
+            ident = affine._identity_qparams(X.device)
+            degs = adj.degrees()
+            want = affine.aggregate(adj, X, bits)
+            exact = QGTC.tiledMMFloat(adj, X)
+            out["aggregate_rel_error"] = round(float((want - exact).norm() / exact.norm()), 5)
+            dq, agg, mm, fl = timed_alternating(torch, [lambda: affine.dequant(acc, n, ident, degs, qp, None),
+                                                        lambda: affine.aggregate(adj, X, bits),
+                                                        lambda: QGTC.tiledMM2Int(adj, bit_T, N, bits),
+                                                        lambda: QGTC.tiledMMFloat(adj, X)], reps)
+            out.update({"dequant_ms": dq, "aggregate_ms": agg, "tiledMM2Int_ms": mm, "tiledMMFloat_ms": fl,
+                        "aggregate_over_mm2int": round(agg[0] / mm[0], 3), "aggregate_over_float": round(agg[0] / fl[0], 3)})
+            print(f"{name:9s} {bits} bits: dequant {dq[0]:.4f} ms  aggregate {agg[0]:.4f} [{agg[1]:.4f}, {agg[2]:.4f}] ms  tiledMM2Int alone {mm[0]:.4f} ms  "
+                  f"tiledMMFloat {fl[0]:.4f} ms  rel. error {out['aggregate_rel_error']}", flush=True)
+            rec["agg"].append(out)
+            del bit_T, acc, want, exact
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, norm="mean").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(xr.normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        with torch.no_grad():
+            want = ref(adj, F)
+        layer = {}
+        for w_bit, act_bit in ((4, 4), (4, 8), (8, 8)):
+            q = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit)
+            got = q(adj, F)
+            err = float((got - want).norm() / want.norm())
+
+            def float_forward():
+                with torch.no_grad():
+                    return ref(adj, F)
+
+            tq, tf = timed_alternating(torch, [lambda: q(adj, F), float_forward], reps)
+            layer[f"w{w_bit}a{act_bit}"] = {"forward_ms": tq, "float_forward_ms": tf, "over_float": round(tq[0] / tf[0], 3), "rel_error": round(err, 5)}
+            print(f"{name:9s} layer {dims} w{w_bit} a{act_bit}: forward {tq[0]:.4f} [{tq[1]:.4f}, {tq[2]:.4f}] ms  conv.GCNConv {tf[0]:.4f} ms  "
+                  f"({tq[0] / tf[0]:.2f}x)  rel. error against the float layer {err:.5f}", flush=True)
+        rec["layer"] = layer
+        rows.append(rec)
+        del adj, dsrc, ddst, X, Xpos, F, want
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1252,7 +1338,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine"))
     args = ap.parse_args()
 
     import torch
@@ -1260,9 +1346,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
