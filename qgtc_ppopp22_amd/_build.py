@@ -39,7 +39,7 @@ def _run(cmd: list[str]) -> None:
     subprocess.run(cmd, check=True)
 
 
-HIP_UNITS = ("qgtc_hip.hip", "qgtc_mfma.hip", "qgtc_fp4.hip", "qgtc_wide.hip", "qgtc_epoch.hip", "qgtc_chainx.hip", "qgtc_stream.hip", "qgtc_tiled.hip", "qgtc_tiled_t.hip", "qgtc_tiled_scaled.hip", "qgtc_tiled_t_scaled.hip", "qgtc_tiled_float.hip", "qgtc_tiled_float_t.hip", "qgtc_tiled_float_src.hip", "qgtc_tiled_float_t_src.hip", "qgtc_tiled_max.hip", "qgtc_tiled_max_t.hip", "qgtc_tiled_attn.hip", "qgtc_tiled_attn_t.hip", "qgtc_tiled_float_drop.hip", "qgtc_tiled_float_t_drop.hip", "qgtc_tiled_max_drop.hip", "qgtc_tiled_attn_drop.hip", "qgtc_tiled_attn_t_drop.hip", "qgtc_tiled_float_nodes.hip", "qgtc_tiled_float_t_nodes.hip", "qgtc_tiled_max_nodes.hip", "qgtc_tiled_attn_nodes.hip", "qgtc_tiled_attn_t_nodes.hip", "qgtc_tiled_float_edge.hip", "qgtc_tiled_float_t_edge.hip", "qgtc_tiled_sddmm.hip", "qgtc_tiled_esoftmax.hip", "qgtc_tiled_esoftmax_t.hip", "qgtc_tiled_float_edge_heads.hip", "qgtc_tiled_float_t_edge_heads.hip", "qgtc_tiled_attn_heads.hip", "qgtc_tiled_attn_heads_t.hip", "qgtc_tiled_attn_heads_drop.hip", "qgtc_tiled_attn_heads_t_drop.hip", "qgtc_tiled_attn_heads_nodes.hip", "qgtc_tiled_attn_heads_t_nodes.hip", "qgtc_tiled_addscore.hip", "qgtc_tiled_addscore_grad.hip", "qgtc_tiled_addscore_grad_t.hip", "qgtc_tiled_fanout.hip", "qgtc_tiled_float_fanout.hip", "qgtc_tiled_float_t_fanout.hip", "qgtc_tiled_max_fanout.hip", "qgtc_tiled_attn_fanout.hip", "qgtc_tiled_attn_t_fanout.hip", "qgtc_tiled_blocks.hip", "qgtc_tiled_float_fanout_nodes.hip", "qgtc_tiled_float_t_fanout_nodes.hip", "qgtc_tiled_max_fanout_nodes.hip", "qgtc_tiled_attn_fanout_nodes.hip", "qgtc_tiled_attn_t_fanout_nodes.hip", "qgtc_tiled_bit_nodes.hip", "qgtc_tiled_bit_t_nodes.hip", "qgtc_affine.hip", "qgtc_reorder.hip")   # translation units of libqgtc_hip.so, compiled in parallel
+HIP_UNITS = ("qgtc_hip.hip", "qgtc_mfma.hip", "qgtc_fp4.hip", "qgtc_wide.hip", "qgtc_epoch.hip", "qgtc_chainx.hip", "qgtc_stream.hip", "qgtc_tiled.hip", "qgtc_tiled_t.hip", "qgtc_tiled_scaled.hip", "qgtc_tiled_t_scaled.hip", "qgtc_tiled_float.hip", "qgtc_tiled_float_t.hip", "qgtc_tiled_float_src.hip", "qgtc_tiled_float_t_src.hip", "qgtc_tiled_max.hip", "qgtc_tiled_max_t.hip", "qgtc_tiled_attn.hip", "qgtc_tiled_attn_t.hip", "qgtc_tiled_float_drop.hip", "qgtc_tiled_float_t_drop.hip", "qgtc_tiled_max_drop.hip", "qgtc_tiled_attn_drop.hip", "qgtc_tiled_attn_t_drop.hip", "qgtc_tiled_float_nodes.hip", "qgtc_tiled_float_t_nodes.hip", "qgtc_tiled_max_nodes.hip", "qgtc_tiled_attn_nodes.hip", "qgtc_tiled_attn_t_nodes.hip", "qgtc_tiled_float_edge.hip", "qgtc_tiled_float_t_edge.hip", "qgtc_tiled_sddmm.hip", "qgtc_tiled_esoftmax.hip", "qgtc_tiled_esoftmax_t.hip", "qgtc_tiled_float_edge_heads.hip", "qgtc_tiled_float_t_edge_heads.hip", "qgtc_tiled_attn_heads.hip", "qgtc_tiled_attn_heads_t.hip", "qgtc_tiled_attn_heads_drop.hip", "qgtc_tiled_attn_heads_t_drop.hip", "qgtc_tiled_attn_heads_nodes.hip", "qgtc_tiled_attn_heads_t_nodes.hip", "qgtc_tiled_addscore.hip", "qgtc_tiled_addscore_grad.hip", "qgtc_tiled_addscore_grad_t.hip", "qgtc_tiled_fanout.hip", "qgtc_tiled_float_fanout.hip", "qgtc_tiled_float_t_fanout.hip", "qgtc_tiled_max_fanout.hip", "qgtc_tiled_attn_fanout.hip", "qgtc_tiled_attn_t_fanout.hip", "qgtc_tiled_blocks.hip", "qgtc_tiled_float_fanout_nodes.hip", "qgtc_tiled_float_t_fanout_nodes.hip", "qgtc_tiled_max_fanout_nodes.hip", "qgtc_tiled_attn_fanout_nodes.hip", "qgtc_tiled_attn_t_fanout_nodes.hip", "qgtc_tiled_bit_nodes.hip", "qgtc_tiled_bit_t_nodes.hip", "qgtc_affine.hip", "qgtc_tiled_codes.hip", "qgtc_tiled_codes_t.hip", "qgtc_reorder.hip")   # translation units of libqgtc_hip.so, compiled in parallel
 
 
 OBJ_DIR = os.path.join(PKG, "build")    # objects + dependency files of the translation units (git- and gpurun-ignored)

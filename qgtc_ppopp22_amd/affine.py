@@ -7,10 +7,13 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     y = affine.dequant(acc, K, qa, row_sums, qb, col_sums)
     y = affine.linear(X, W, 8, 4)                         # ~ X @ W
     y = affine.aggregate(adj, T, 8)                       # ~ A . T on a QGTC.TiledAdjacency view
+    y = affine.aggregate(adj, T, 8, route="bytes")        # the same bits from one walk over byte codes (include/qgtc_codes.h)
+    q = affine.codes(x, bits, qp)                         # uint8 [H, W], one byte a code, rows PAD4(W) bytes apart
+    acc = affine.tiledMMCodes(adj, q)                     # int32 [n, N]: the exact neighbour sum of the codes
     layer = affine.GCNConv_Affine.from_float(trained_gcnconv, 4, 8)
 
-The four C entries are reached through ctypes on torch's current stream (the extension binds no name for them): every call enqueues,
-reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h) are reached through ctypes on torch's current stream (the
+extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
 requires grad. The accumulators are float32 holding integers: ``linear`` refuses a K at which K * qmax_a * qmax_w could pass 2^24."""
 from __future__ import annotations
@@ -22,7 +25,9 @@ import QGTC  # the HIP extension; there is no fallback
 from . import conv, tiled
 from .tiled import _c_abi, _ptr
 
-__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine"]
+__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes"]
+
+ROUTES = ("planes", "bytes")   # how ``aggregate`` sums the codes: eight bit planes through tiledMM2Int, or one gather of byte codes
 
 _identity = {}   # per device: the qparams row (1, 0, 1, 0) of an operand that is its own code; a constant, built outside captures
 
@@ -178,12 +183,101 @@ def _identity_qparams(device: torch.device) -> torch.Tensor:
     return t
 
 
-def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_scale=None, row_mask=None, nbr_mask=None) -> torch.Tensor:
+def _check_route(route) -> str:
+    if route not in ROUTES:
+        raise ValueError(f'route must be "planes" or "bytes", not {route!r}')
+    return route
+
+
+def _pad4(W: int) -> int:
+    return (W + 3) // 4 * 4
+
+
+def codes(x: torch.Tensor, bits: int, qp: torch.Tensor) -> torch.Tensor:
+    """uint8 [H, W]: x quantised with ``qp`` ([1, 4]: per tensor; [W, 4]: per column) by the rule of :func:`val2bit_affine`, one byte a
+    code - a view of a [H, PAD4(W)] buffer (row stride PAD4(W)), whose bytes W .. PAD4(W) - 1 of every row are written 0. One launch."""
+    bits = _check_bits(bits)
+    _check_f32(x, "x")
+    H, W = x.shape
+    groups = _check_qparams(qp, "qp", (1, W), x)
+    ld = _pad4(W)
+    buf = torch.empty((H, ld), dtype=torch.uint8, device=x.device)
+    _c_call("affine.codes", x, _c_abi().qgtc_affine_codes, x.data_ptr(), H, W, bits, qp.data_ptr(), groups, buf.data_ptr(), ld, buf.numel())
+    return buf[:, :W]
+
+
+def _check_codes(adj_view, Q) -> torch.Tensor:
+    """Q as the C entries take it: any 2-D uint8 with unit column stride; a row stride or a base address off the 4-byte rule of a code
+    matrix (include/qgtc_codes.h) gets a padded copy."""
+    if not isinstance(Q, torch.Tensor):
+        raise TypeError(f"Q must be a torch.Tensor, not {type(Q).__name__}")
+    if Q.dtype != torch.uint8:
+        raise TypeError(f"Q must be uint8, not {Q.dtype}")
+    if not Q.is_cuda:
+        raise ValueError(f"Q must be on a GPU, not on {Q.device}")
+    if Q.dim() != 2:
+        raise ValueError(f"Q must have 2 dimensions, not shape {list(Q.shape)}")
+    if Q.numel() == 0:
+        raise ValueError(f"Q must not be empty (shape {list(Q.shape)})")
+    if Q.size(0) != adj_view.n or Q.device != adj_view.device:
+        raise ValueError(f"Q must have shape [{adj_view.n}, N] on {adj_view.device}, not {list(Q.shape)} on {Q.device}")
+    if Q.stride(1) != 1 and Q.size(1) > 1:
+        raise ValueError(f"Q must have unit column stride, not strides {list(Q.stride())}")
+    n, N = Q.shape
+    ld = _codes_ld(Q)
+    if ld < N or ld % 4 or Q.data_ptr() % 4 or Q.stride(1) != 1 or _codes_bytes(Q) < (n - 1) * ld + _pad4(N):
+        buf = torch.empty((n, _pad4(N)), dtype=torch.uint8, device=Q.device)   # (the pad bytes may hold anything)
+        buf[:, :N] = Q
+        Q = buf[:, :N]
+    return Q
+
+
+def _codes_ld(Q: torch.Tensor) -> int:
+    """The row stride in bytes; a single row, whose stride torch leaves arbitrary, counts as PAD4(N) apart."""
+    return Q.stride(0) if Q.size(0) > 1 else _pad4(Q.size(1))
+
+
+def _codes_bytes(Q: torch.Tensor) -> int:
+    """The bytes the storage holds from Q's first byte on."""
+    return Q.untyped_storage().nbytes() - Q.storage_offset()
+
+
+def _check_masks(adj_view, row_mask, nbr_mask) -> None:
+    for m, name in ((row_mask, "row_mask"), (nbr_mask, "nbr_mask")):
+        if m is not None:
+            tiled._check_mask(adj_view, m, name)
+
+
+def _u8_call(what: str, stem: str, adj_view, Q: torch.Tensor, out: torch.Tensor, row_mask, nbr_mask, *extra) -> torch.Tensor:
+    fn = getattr(_c_abi(), stem + ("_t" if adj_view.transposed else "") + ("_affine" if extra else ""))
+    _c_call(what, Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), Q.size(1), *extra, out.data_ptr(),
+            out.numel(), _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+    return out
+
+
+def tiledMMCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, row_mask=None, nbr_mask=None) -> torch.Tensor:
+    """int32 [n, N]: the exact sum of the code rows Q[k] (uint8 [n, N], in the adjacency's numbering) over the neighbours k of every row
+    of the view ``adj_view`` (``adj`` or ``adj.T``), under the node masks of :func:`QGTC.tiledMM2Int` - what ``tiledMM2Int`` gives on the
+    packed planes of the same codes, from one walk that gathers one dword of four codes per neighbour. One launch."""
+    tiled._check(adj_view)
+    Q = _check_codes(adj_view, Q)
+    _check_masks(adj_view, row_mask, nbr_mask)
+    out = torch.empty((adj_view.n, Q.size(1)), dtype=torch.int32, device=Q.device)
+    return _u8_call("affine.tiledMMCodes", "qgtc_tiledmm_u8", adj_view, Q, out, row_mask, nbr_mask)
+
+
+def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_scale=None, row_mask=None, nbr_mask=None,
+              route: str = "planes") -> torch.Tensor:
     """float32 [n, N] ~ A . T on the view ``adj_view`` (``adj`` or ``adj.T``; T in the adjacency's numbering): T quantised per tensor to
     ``bits`` into the cols layout, ``QGTC.tiledMM2Int`` on the codes (the exact neighbour sum), then :func:`dequant` with the view's
     degrees under the masks as the row sums of A, and ``row_scale`` (float32 [n], say ``adj_view.mean_scale()``) applied there. Row i is
-    within deg_i * scale / 2 of the exact sum; a row without live neighbours, or outside ``row_mask``, comes back +0."""
+    within deg_i * scale / 2 of the exact sum; a row without live neighbours, or outside ``row_mask``, comes back +0.
+
+    ``route="bytes"`` gives the same bits from byte codes (include/qgtc_codes.h): :func:`qparams`, :func:`codes`,
+    then one launch that gathers the neighbours' codes, counts the terms of every row and dequantises in its epilogue - four launches, no
+    degree launch and no integer intermediate."""
     tiled._check(adj_view)
+    route = _check_route(route)
     bits = _check_bits(bits)
     _check_f32(T, "T")
     n, N = T.shape
@@ -192,6 +286,11 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     if row_scale is not None:
         tiled._check_scale(adj_view, row_scale)
     qt = qparams(T, bits)
+    if route == "bytes":
+        _check_masks(adj_view, row_mask, nbr_mask)
+        out = torch.empty((n, N), dtype=torch.float32, device=T.device)
+        return _u8_call("affine.aggregate", "qgtc_tiledmm_u8", adj_view, codes(T, bits, qt), out, row_mask, nbr_mask, qt.data_ptr(),
+                        _ptr(row_scale))
     bit_T, _ = val2bit_affine(T, bits, qt, True, False)
     acc = QGTC.tiledMM2Int(adj_view, bit_T, N, bits, None, row_mask=row_mask, nbr_mask=nbr_mask)
     deg = adj_view.degrees(row_mask=row_mask, nbr_mask=nbr_mask)
@@ -206,12 +305,14 @@ class GCNConv_Affine(torch.nn.Module):
     (D^-1/2 . A . D^-1/2: ``A.T.sym_scale()`` as the row scale of ``linear``, so the source factor is applied before the neighbour sum is
     quantised, and ``A.sym_scale()`` on the aggregate). ``A`` is a QGTC.TiledAdjacency view; X moves to its numbering and the result
     back. ``nodes`` (bool [n] in X's numbering) runs the pair on the induced subgraph: one bitmap as both masks, with the masked degrees
-    and scales; rows outside come back +0. Inference only: forward runs without grad."""
+    and scales; rows outside come back +0. ``route`` ("planes" or "bytes") is the route of both aggregates (:func:`aggregate`; the same
+    bits either way); ``linear`` stays on the bit-GEMM. Inference only: forward runs without grad."""
 
-    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None):
+    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None, route="planes"):
         super().__init__()
         self.w_bit, self.act_bit = _check_bits(w_bit, "w_bit"), _check_bits(act_bit, "act_bit")
         self.norm = norm
+        self.route = route
         self._check_config()
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
@@ -221,9 +322,10 @@ class GCNConv_Affine(torch.nn.Module):
             raise ValueError(f'norm must be None, "mean" or "sym", not {self.norm!r}')
         _check_bits(self.w_bit, "w_bit")
         _check_bits(self.act_bit, "act_bit")
+        _check_route(self.route)
 
     @classmethod
-    def from_float(cls, layer: "conv.GCNConv", w_bit: int = 4, act_bit: int = 8) -> "GCNConv_Affine":
+    def from_float(cls, layer: "conv.GCNConv", w_bit: int = 4, act_bit: int = 8, route: str = "planes") -> "GCNConv_Affine":
         """The quantised twin of a (trained) float ``conv.GCNConv``: its two weights (copied) and its norm."""
         if not isinstance(layer, conv.GCNConv):
             raise TypeError(f"layer must be a conv.GCNConv, not {type(layer).__name__}")
@@ -231,7 +333,7 @@ class GCNConv_Affine(torch.nn.Module):
             raise ValueError(f'aggr="{layer.aggr}" has no quantised twin: only aggr="sum" is built')
         if layer.edge_drop > 0.0:
             raise ValueError(f"edge_drop={layer.edge_drop} has no quantised twin: the layer is inference only")
-        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm)
+        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm, route)
         with torch.no_grad():
             new.W_in.copy_(layer.W_in)
             new.W_out.copy_(layer.W_out)
@@ -255,5 +357,6 @@ class GCNConv_Affine(torch.nn.Module):
         elif self.norm == "sym":
             row, src = A.sym_scale(**mask), A.T.sym_scale(**mask)
         W_in, W_out = self.W_in.detach().contiguous(), self.W_out.detach().contiguous()
-        h = aggregate(A, linear(A.to_new(X).contiguous(), W_in, self.act_bit, self.w_bit, True, src), self.act_bit, row, **mask)
-        return A.to_old(aggregate(A, linear(h, W_out, self.act_bit, self.w_bit, True, src), self.act_bit, row, **mask))
+        h = aggregate(A, linear(A.to_new(X).contiguous(), W_in, self.act_bit, self.w_bit, True, src), self.act_bit, row, route=self.route,
+                      **mask)
+        return A.to_old(aggregate(A, linear(h, W_out, self.act_bit, self.w_bit, True, src), self.act_bit, row, route=self.route, **mask))

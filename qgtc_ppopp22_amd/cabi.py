@@ -18,6 +18,7 @@ FANOUT_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_fanout.h")   # fixed
 BLOCKS_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_blocks.h")   # mini-batch sampling: masked selection, frontier and the _fanout_nodes twins, likewise
 BITNODES_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_bitnodes.h")   # node masks on the bit products: the four _nodes entries, likewise
 AFFINE_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_affine.h")   # affine quantisation: range, quantise + pack, dequantising epilogue, likewise
+CODES_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_codes.h")   # the byte-code route: quantise to bytes, the uint8 gather on both views and its fused epilogue, likewise
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
@@ -55,7 +56,7 @@ def signatures(text: str | None = None) -> dict:
 
 def load():
     """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry - those of include/qgtc.h
-    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h, include/qgtc_addscore.h, include/qgtc_fanout.h, include/qgtc_blocks.h, include/qgtc_bitnodes.h and include/qgtc_affine.h. A declared entry the library does not
+    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h, include/qgtc_addscore.h, include/qgtc_fanout.h, include/qgtc_blocks.h, include/qgtc_bitnodes.h, include/qgtc_affine.h and include/qgtc_codes.h. A declared entry the library does not
     export is an error naming it."""
     global _lib
     if _lib is None:
@@ -74,9 +75,11 @@ def load():
             bitnodes = signatures(f.read())
         with open(AFFINE_HEADER) as f:
             affine = signatures(f.read())
+        with open(CODES_HEADER) as f:
+            codes = signatures(f.read())
         for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads), ("qgtc_attn_heads.h", attn_heads),
                               ("qgtc_addscore.h", addscore), ("qgtc_fanout.h", fanout), ("qgtc_blocks.h", blocks),
-                              ("qgtc_bitnodes.h", bitnodes), ("qgtc_affine.h", affine)):
+                              ("qgtc_bitnodes.h", bitnodes), ("qgtc_affine.h", affine), ("qgtc_codes.h", codes)):
             for name, (restype, argtypes) in table.items():
                 try:
                     fn = getattr(lib, name)

@@ -116,7 +116,12 @@ percentiles, the share of live workgroups, and the ratios masked / plain and mas
 launch, ``val2bit_affine`` in both layouts at 2 / 4 / 8 bits beside ``QGTC.val2bit`` at the same shape, ``dequant``, ``aggregate`` beside
 ``tiledMM2Int`` alone and ``tiledMMFloat``, the layer's forward beside ``conv.GCNConv``'s and its relative error against the float layer.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine]
+`--leg codes` measures the byte-code route (include/qgtc_codes.h) on the reordered graphs at N = 64 and 256, on adj and
+adj.T: ``affine.codes`` beside ``val2bit_affine`` (cols, 8 bits), ``tiledMMCodes``, ``aggregate`` on both routes at 2 / 4 / 8 bits in the
+same alternating rounds beside ``tiledMMFloat``, and the layer on both routes beside ``conv.GCNConv``. A cell passes (4 and 8 bits only)
+when the bytes route's 90th percentile lies under the planes route's 10th.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes]
 """
 from __future__ import annotations
 
@@ -817,6 +822,83 @@ def affine_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def _separated(a, b):
+    """whether timing a = (median, p10, p90) lies wholly below timing b: a's 90th percentile under b's 10th"""
+    return a[2] < b[1]
+
+
+def codes_leg(torch, QGTC, graphs, reps):
+    """The byte-code route of affine quantisation (include/qgtc_codes.h) on the reordered graphs, Gaussian float32
+    [n, 64] and [n, 256], adj and adj.T: affine.codes beside val2bit_affine in the cols layout at 8 bits, tiledMMCodes, aggregate on
+    both routes at 2 / 4 / 8 bits in the same alternating rounds beside tiledMMFloat, and the layer at 128 / 64 / 40 dims with norm
+    "mean" on both routes beside conv.GCNConv. Pass mark (4 and 8 bits only): the bytes route's 90th percentile lies under the planes
+    route's 10th."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    dims = (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T, adj.mean_scale()
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "tiles": adj.n_tiles, "dims": list(dims), "agg": []}
+        xr = np.random.default_rng(1)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.normal(size=(n, N)).astype(np.float32)).cuda()
+            qp = affine.qparams(X, 8)
+            cd, pk = timed_alternating(torch, [lambda: affine.codes(X, 8, qp), lambda: affine.val2bit_affine(X, 8, qp, True, False)], reps)
+            rec[f"codes_N{N}_ms"], rec[f"val2bit_affine_cols_N{N}_ms"] = cd, pk
+            print(f"{name:9s} N={N}: codes {cd[0]:.4f} [{cd[1]:.4f}, {cd[2]:.4f}] ms  val2bit_affine cols 8 bits {pk[0]:.4f} [{pk[1]:.4f}, {pk[2]:.4f}] ms",
+                  flush=True)
+            Q = affine.codes(X, 8, qp)
+            for view, a in (("adj", adj), ("adjT", adj.T)):
+                assert torch.equal(affine.aggregate(a, X, 8, route="bytes").view(torch.int32), affine.aggregate(a, X, 8).view(torch.int32))
+                mmc, fl = timed_alternating(torch, [lambda: affine.tiledMMCodes(a, Q), lambda: QGTC.tiledMMFloat(a, X)], reps)
+                for bits in (2, 4, 8):
+                    by, pl, f2 = timed_alternating(torch, [lambda: affine.aggregate(a, X, bits, route="bytes"),
+                                                           lambda: affine.aggregate(a, X, bits, route="planes"),
+                                                           lambda: QGTC.tiledMMFloat(a, X)], reps)
+                    out = {"N": N, "view": view, "bits": bits, "bytes_ms": by, "planes_ms": pl, "tiledMMFloat_ms": f2,
+                           "bytes_over_planes": round(by[0] / pl[0], 3), "bytes_over_float": round(by[0] / f2[0], 3),
+                           "tiledMMCodes_ms": mmc, "tiledMMCodes_over_float": round(mmc[0] / fl[0], 3)}
+                    if bits in (4, 8):
+                        out["pass"] = _separated(by, pl)
+                    rec["agg"].append(out)
+                    print(f"{name:9s} N={N} {view:4s} {bits} bits: bytes {by[0]:.4f} [{by[1]:.4f}, {by[2]:.4f}] ms  planes {pl[0]:.4f} [{pl[1]:.4f}, {pl[2]:.4f}] ms  "
+                          f"ratio {by[0] / pl[0]:.3f}  tiledMMFloat {f2[0]:.4f} ms  tiledMMCodes {mmc[0]:.4f} ms  pass {out.get('pass', '-')}", flush=True)
+            del X, Q
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, norm="mean").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(xr.normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        layer = {}
+        for w_bit, act_bit in ((4, 4), (4, 8)):
+            qb = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit, route="bytes")
+            qpl = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit)
+            assert torch.equal(qb(adj, F).view(torch.int32), qpl(adj, F).view(torch.int32))
+
+            def float_forward():
+                with torch.no_grad():
+                    return ref(adj, F)
+
+            tb, tp, tf = timed_alternating(torch, [lambda: qb(adj, F), lambda: qpl(adj, F), float_forward], reps)
+            layer[f"w{w_bit}a{act_bit}"] = {"bytes_ms": tb, "planes_ms": tp, "float_ms": tf, "bytes_over_planes": round(tb[0] / tp[0], 3),
+                                            "bytes_over_float": round(tb[0] / tf[0], 3), "pass": _separated(tb, tp)}
+            print(f"{name:9s} layer {dims} w{w_bit} a{act_bit}: bytes {tb[0]:.4f} [{tb[1]:.4f}, {tb[2]:.4f}] ms  planes {tp[0]:.4f} [{tp[1]:.4f}, {tp[2]:.4f}] ms  "
+                  f"conv.GCNConv {tf[0]:.4f} ms", flush=True)
+        rec["layer"] = layer
+        rows.append(rec)
+        del adj, dsrc, ddst, F
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1338,7 +1420,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes"))
     args = ap.parse_args()
 
     import torch
@@ -1346,9 +1428,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
