@@ -39,8 +39,11 @@ def _run(cmd: list[str]) -> None:
     subprocess.run(cmd, check=True)
 
 
-HIP_UNITS = ("qgtc_hip.hip", "qgtc_mfma.hip", "qgtc_fp4.hip", "qgtc_wide.hip", "qgtc_epoch.hip", "qgtc_chainx.hip", "qgtc_stream.hip", "qgtc_tiled.hip", "qgtc_tiled_t.hip", "qgtc_tiled_scaled.hip", "qgtc_tiled_t_scaled.hip", "qgtc_tiled_float.hip", "qgtc_tiled_float_t.hip", "qgtc_tiled_float_src.hip", "qgtc_tiled_float_t_src.hip", "qgtc_tiled_max.hip", "qgtc_tiled_max_t.hip", "qgtc_tiled_attn.hip", "qgtc_tiled_attn_t.hip", "qgtc_tiled_float_drop.hip", "qgtc_tiled_float_t_drop.hip", "qgtc_tiled_max_drop.hip", "qgtc_tiled_attn_drop.hip", "qgtc_tiled_attn_t_drop.hip", "qgtc_tiled_float_nodes.hip", "qgtc_tiled_float_t_nodes.hip", "qgtc_tiled_max_nodes.hip", "qgtc_tiled_attn_nodes.hip", "qgtc_tiled_attn_t_nodes.hip", "qgtc_tiled_float_edge.hip", "qgtc_tiled_float_t_edge.hip", "qgtc_tiled_sddmm.hip", "qgtc_tiled_esoftmax.hip", "qgtc_tiled_esoftmax_t.hip", "qgtc_tiled_float_edge_heads.hip", "qgtc_tiled_float_t_edge_heads.hip", "qgtc_tiled_attn_heads.hip", "qgtc_tiled_attn_heads_t.hip", "qgtc_tiled_attn_heads_drop.hip", "qgtc_tiled_attn_heads_t_drop.hip", "qgtc_tiled_attn_heads_nodes.hip", "qgtc_tiled_attn_heads_t_nodes.hip", "qgtc_tiled_addscore.hip", "qgtc_tiled_addscore_grad.hip", "qgtc_tiled_addscore_grad_t.hip", "qgtc_tiled_fanout.hip", "qgtc_tiled_float_fanout.hip", "qgtc_tiled_float_t_fanout.hip", "qgtc_tiled_max_fanout.hip", "qgtc_tiled_attn_fanout.hip", "qgtc_tiled_attn_t_fanout.hip", "qgtc_tiled_blocks.hip", "qgtc_tiled_float_fanout_nodes.hip", "qgtc_tiled_float_t_fanout_nodes.hip", "qgtc_tiled_max_fanout_nodes.hip", "qgtc_tiled_attn_fanout_nodes.hip", "qgtc_tiled_attn_t_fanout_nodes.hip", "qgtc_tiled_bit_nodes.hip", "qgtc_tiled_bit_t_nodes.hip", "qgtc_affine.hip", "qgtc_tiled_codes.hip", "qgtc_tiled_codes_t.hip", "qgtc_reorder.hip")   # translation units of libqgtc_hip.so, compiled in parallel
+HIP_UNITS = ("qgtc_hip.hip", "qgtc_mfma.hip", "qgtc_fp4.hip", "qgtc_wide.hip", "qgtc_epoch.hip", "qgtc_chainx.hip", "qgtc_stream.hip", "qgtc_tiled.hip", "qgtc_tiled_t.hip", "qgtc_tiled_scaled.hip", "qgtc_tiled_t_scaled.hip", "qgtc_tiled_float.hip", "qgtc_tiled_float_t.hip", "qgtc_tiled_float_src.hip", "qgtc_tiled_float_t_src.hip", "qgtc_tiled_max.hip", "qgtc_tiled_max_t.hip", "qgtc_tiled_attn.hip", "qgtc_tiled_attn_t.hip", "qgtc_tiled_float_drop.hip", "qgtc_tiled_float_t_drop.hip", "qgtc_tiled_max_drop.hip", "qgtc_tiled_attn_drop.hip", "qgtc_tiled_attn_t_drop.hip", "qgtc_tiled_float_nodes.hip", "qgtc_tiled_float_t_nodes.hip", "qgtc_tiled_max_nodes.hip", "qgtc_tiled_attn_nodes.hip", "qgtc_tiled_attn_t_nodes.hip", "qgtc_tiled_float_edge.hip", "qgtc_tiled_float_t_edge.hip", "qgtc_tiled_sddmm.hip", "qgtc_tiled_esoftmax.hip", "qgtc_tiled_esoftmax_t.hip", "qgtc_tiled_float_edge_heads.hip", "qgtc_tiled_float_t_edge_heads.hip", "qgtc_tiled_attn_heads.hip", "qgtc_tiled_attn_heads_t.hip", "qgtc_tiled_attn_heads_drop.hip", "qgtc_tiled_attn_heads_t_drop.hip", "qgtc_tiled_attn_heads_nodes.hip", "qgtc_tiled_attn_heads_t_nodes.hip", "qgtc_tiled_addscore.hip", "qgtc_tiled_addscore_grad.hip", "qgtc_tiled_addscore_grad_t.hip", "qgtc_tiled_fanout.hip", "qgtc_tiled_float_fanout.hip", "qgtc_tiled_float_t_fanout.hip", "qgtc_tiled_max_fanout.hip", "qgtc_tiled_attn_fanout.hip", "qgtc_tiled_attn_t_fanout.hip", "qgtc_tiled_blocks.hip", "qgtc_tiled_float_fanout_nodes.hip", "qgtc_tiled_float_t_fanout_nodes.hip", "qgtc_tiled_max_fanout_nodes.hip", "qgtc_tiled_attn_fanout_nodes.hip", "qgtc_tiled_attn_t_fanout_nodes.hip", "qgtc_tiled_bit_nodes.hip", "qgtc_tiled_bit_t_nodes.hip", "qgtc_affine.hip", "qgtc_tiled_codes.hip", "qgtc_tiled_codes_t.hip", "qgtc_affine_linear.hip", "qgtc_reorder.hip")   # translation units of libqgtc_hip.so, compiled in parallel
 
+
+# extra hipcc flags of single units: the float path of the fused affine linear kernel is kept on scalar fp32 instructions
+UNIT_FLAGS = {"qgtc_affine_linear.hip": ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")}
 
 OBJ_DIR = os.path.join(PKG, "build")    # objects + dependency files of the translation units (git- and gpurun-ignored)
 
@@ -68,7 +71,7 @@ def build_hip(force: bool = False) -> str:
             continue
         # kernels with scalar arguments get them preloaded into SGPRs (no s_load round trip at the head of the kernel)
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-Wno-unused-value", "-Wno-pass-failed",
-               "-mllvm", "-amdgpu-kernarg-preload-count=16", f"-I{INC}", "-MD", "-MF", dep, "-o", obj, u]
+               "-mllvm", "-amdgpu-kernarg-preload-count=16", *UNIT_FLAGS.get(os.path.basename(u), ()), f"-I{INC}", "-MD", "-MF", dep, "-o", obj, u]
         print("[qgtc build]", " ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))
     for cmd, pr in procs:

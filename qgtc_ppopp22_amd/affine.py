@@ -6,16 +6,19 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     words, sums = affine.val2bit_affine(x, bits, qp)      # the layouts of QGTC.val2bit(x, bits, col_major, False), and the code sums
     y = affine.dequant(acc, K, qa, row_sums, qb, col_sums)
     y = affine.linear(X, W, 8, 4)                         # ~ X @ W
+    y = affine.linear(X, W, 8, 4, route="bytes")          # the same bits from one int8 MFMA launch on byte codes (include/qgtc_linear.h)
+    wt, qw, sums = affine.pack_weight(W, 4)               # W's codes transposed (uint8 [N, PAD16(K)]), its qparams rows and column sums
     y = affine.aggregate(adj, T, 8)                       # ~ A . T on a QGTC.TiledAdjacency view
     y = affine.aggregate(adj, T, 8, route="bytes")        # the same bits from one walk over byte codes (include/qgtc_codes.h)
     q = affine.codes(x, bits, qp)                         # uint8 [H, W], one byte a code, rows PAD4(W) bytes apart
     acc = affine.tiledMMCodes(adj, q)                     # int32 [n, N]: the exact neighbour sum of the codes
     layer = affine.GCNConv_Affine.from_float(trained_gcnconv, 4, 8)
 
-The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h) are reached through ctypes on torch's current stream (the
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h) are reached through ctypes on torch's current stream (the
 extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
-requires grad. The accumulators are float32 holding integers: ``linear`` refuses a K at which K * qmax_a * qmax_w could pass 2^24."""
+requires grad. The accumulators of the planes route are float32 holding integers: there ``linear`` refuses a K at which
+K * qmax_a * qmax_w could pass 2^24; its bytes route accumulates in int32 and refuses K above ``LINEAR_K_MAX`` only."""
 from __future__ import annotations
 
 import torch
@@ -25,9 +28,10 @@ import QGTC  # the HIP extension; there is no fallback
 from . import conv, tiled
 from .tiled import _c_abi, _ptr
 
-__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes"]
+__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight"]
 
 ROUTES = ("planes", "bytes")   # how ``aggregate`` sums the codes: eight bit planes through tiledMM2Int, or one gather of byte codes
+LINEAR_K_MAX = 131071          # QGTC_LINEAR_K_MAX of include/qgtc_linear.h: K 2^14 < 2^31, the int32 accumulator of the shifted codes
 
 _identity = {}   # per device: the qparams row (1, 0, 1, 0) of an operand that is its own code; a constant, built outside captures
 
@@ -148,12 +152,36 @@ def dequant(acc: torch.Tensor, K: int, qa: torch.Tensor, row_sums, qb: torch.Ten
     return out
 
 
+def pack_weight(W: torch.Tensor, bits: int, per_column: bool = True):
+    """(codes_t, qparams, col_sums) of W [K, N] for ``linear(route="bytes")``, from one launch: ``qparams`` float32 [N, 4] (per output
+    column) or [1, 4] (per tensor), bit for bit ``affine.qparams(W, bits, per_column)``; ``codes_t`` uint8 [N, PAD16(K)], W's codes
+    transposed so that a column's K codes are contiguous, bytes K .. PAD16(K) - 1 of every line written 0; ``col_sums`` int32 [N]."""
+    bits = _check_bits(bits)
+    _check_f32(W, "W")
+    K, N = W.shape
+    if K > LINEAR_K_MAX:
+        raise ValueError(f"K = {K}: the int32 accumulator of the bytes route holds K up to {LINEAR_K_MAX}")
+    ldk = (K + 15) // 16 * 16
+    qp = torch.empty((N if per_column else 1, 4), dtype=torch.float32, device=W.device)
+    codes_t = torch.empty((N, ldk), dtype=torch.uint8, device=W.device)
+    col_sums = torch.empty((N,), dtype=torch.int32, device=W.device)
+    _c_call("affine.pack_weight", W, _c_abi().qgtc_affine_pack_weight, W.data_ptr(), K, N, bits, int(bool(per_column)), qp.data_ptr(),
+            qp.numel(), codes_t.data_ptr(), ldk, codes_t.numel(), col_sums.data_ptr(), col_sums.numel())
+    return codes_t, qp, col_sums
+
+
 def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_column: bool = True, row_scale=None, bias=None,
-           relu: bool = False) -> torch.Tensor:
+           relu: bool = False, route: str = "planes") -> torch.Tensor:
     """float32 [M, N] ~ X @ W on the bit-GEMM: X [M, K] quantised per tensor to ``a_bits`` (rows layout), W [K, N] per output column (or
     per tensor) to ``w_bits`` (cols layout, as ``GCNConv_Qnt.weight_Qnt`` packs weights), ``QGTC.bitMM2Int`` on the codes, then
     :func:`dequant` with the row sums of X's codes and the column sums of W's. Element [m][n] is within
-    (sa / 2) sum_k |W[k][n]| + (sb[n] / 2) sum_k |X[m][k]| + K sa sb[n] / 4 of the exact product (to first order)."""
+    (sa / 2) sum_k |W[k][n]| + (sb[n] / 2) sum_k |X[m][k]| + K sa sb[n] / 4 of the exact product (to first order).
+
+    ``route="bytes"`` gives the same bits from byte codes on the int8 matrix instruction (include/qgtc_linear.h):
+    :func:`qparams` of X, :func:`pack_weight` of W, then one launch that reads X, quantises it in registers, multiplies into an int32
+    accumulator and dequantises - four launches, no packed X, no intermediate. Exact for every K up to ``LINEAR_K_MAX``; the 2^24 limit
+    below belongs to the planes route."""
+    route = _check_route(route)
     a_bits, w_bits = _check_bits(a_bits, "a_bits"), _check_bits(w_bits, "w_bits")
     _check_f32(X, "X")
     _check_f32(W, "W")
@@ -161,6 +189,19 @@ def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_colum
     if W.size(0) != K or W.device != X.device:
         raise ValueError(f"W must have shape [{K}, N] on {X.device}, not {list(W.shape)} on {W.device}")
     N = W.size(1)
+    if route == "bytes":
+        if K > LINEAR_K_MAX:
+            raise ValueError(f"K = {K}: the int32 accumulator of the bytes route holds K up to {LINEAR_K_MAX}")
+        for t, name, n in ((row_scale, "row_scale", M), (bias, "bias", N)):
+            if t is not None:
+                _check_vector(t, name, torch.float32, n, X)
+        qa = qparams(X, a_bits)
+        codes_t, qb, col_sums = pack_weight(W, w_bits, per_column)
+        out = torch.empty((M, N), dtype=torch.float32, device=X.device)
+        _c_call("affine.linear", X, _c_abi().qgtc_affine_linear_u8, X.data_ptr(), M, K, qa.data_ptr(), a_bits, codes_t.data_ptr(),
+                codes_t.size(1), codes_t.numel(), N, qb.data_ptr(), qb.size(0), col_sums.data_ptr(), _ptr(row_scale), _ptr(bias),
+                int(bool(relu)), out.data_ptr(), out.numel())
+        return out
     if K * (2 ** a_bits - 1) * (2 ** w_bits - 1) >= 2 ** 24:
         raise ValueError(f"K = {K} at a_bits = {a_bits}, w_bits = {w_bits}: the float32 accumulator of bitMM2Int is exact below 2^24 only")
     qa = qparams(X, a_bits)
@@ -306,13 +347,14 @@ class GCNConv_Affine(torch.nn.Module):
     quantised, and ``A.sym_scale()`` on the aggregate). ``A`` is a QGTC.TiledAdjacency view; X moves to its numbering and the result
     back. ``nodes`` (bool [n] in X's numbering) runs the pair on the induced subgraph: one bitmap as both masks, with the masked degrees
     and scales; rows outside come back +0. ``route`` ("planes" or "bytes") is the route of both aggregates (:func:`aggregate`; the same
-    bits either way); ``linear`` stays on the bit-GEMM. Inference only: forward runs without grad."""
+    bits either way), ``linear_route`` that of both linear layers (:func:`linear`; likewise). Inference only: forward runs without grad."""
 
-    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None, route="planes"):
+    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None, route="planes", linear_route="planes"):
         super().__init__()
         self.w_bit, self.act_bit = _check_bits(w_bit, "w_bit"), _check_bits(act_bit, "act_bit")
         self.norm = norm
         self.route = route
+        self.linear_route = linear_route
         self._check_config()
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
@@ -323,9 +365,12 @@ class GCNConv_Affine(torch.nn.Module):
         _check_bits(self.w_bit, "w_bit")
         _check_bits(self.act_bit, "act_bit")
         _check_route(self.route)
+        if self.linear_route not in ROUTES:
+            raise ValueError(f'linear_route must be "planes" or "bytes", not {self.linear_route!r}')
 
     @classmethod
-    def from_float(cls, layer: "conv.GCNConv", w_bit: int = 4, act_bit: int = 8, route: str = "planes") -> "GCNConv_Affine":
+    def from_float(cls, layer: "conv.GCNConv", w_bit: int = 4, act_bit: int = 8, route: str = "planes",
+                   linear_route: str = "planes") -> "GCNConv_Affine":
         """The quantised twin of a (trained) float ``conv.GCNConv``: its two weights (copied) and its norm."""
         if not isinstance(layer, conv.GCNConv):
             raise TypeError(f"layer must be a conv.GCNConv, not {type(layer).__name__}")
@@ -333,7 +378,7 @@ class GCNConv_Affine(torch.nn.Module):
             raise ValueError(f'aggr="{layer.aggr}" has no quantised twin: only aggr="sum" is built')
         if layer.edge_drop > 0.0:
             raise ValueError(f"edge_drop={layer.edge_drop} has no quantised twin: the layer is inference only")
-        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm, route)
+        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm, route, linear_route)
         with torch.no_grad():
             new.W_in.copy_(layer.W_in)
             new.W_out.copy_(layer.W_out)
@@ -357,6 +402,8 @@ class GCNConv_Affine(torch.nn.Module):
         elif self.norm == "sym":
             row, src = A.sym_scale(**mask), A.T.sym_scale(**mask)
         W_in, W_out = self.W_in.detach().contiguous(), self.W_out.detach().contiguous()
-        h = aggregate(A, linear(A.to_new(X).contiguous(), W_in, self.act_bit, self.w_bit, True, src), self.act_bit, row, route=self.route,
-                      **mask)
-        return A.to_old(aggregate(A, linear(h, W_out, self.act_bit, self.w_bit, True, src), self.act_bit, row, route=self.route, **mask))
+        lin = {"route": self.linear_route}
+        h = aggregate(A, linear(A.to_new(X).contiguous(), W_in, self.act_bit, self.w_bit, True, src, **lin), self.act_bit, row,
+                      route=self.route, **mask)
+        return A.to_old(aggregate(A, linear(h, W_out, self.act_bit, self.w_bit, True, src, **lin), self.act_bit, row, route=self.route,
+                                  **mask))

@@ -121,7 +121,11 @@ adj.T: ``affine.codes`` beside ``val2bit_affine`` (cols, 8 bits), ``tiledMMCodes
 same alternating rounds beside ``tiledMMFloat``, and the layer on both routes beside ``conv.GCNConv``. A cell passes (4 and 8 bits only)
 when the bytes route's 90th percentile lies under the planes route's 10th.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes]
+`--leg linear` measures the byte-code route of the linear layer (include/qgtc_linear.h) at the graphs' row counts,
+(K, N) = (128, 64), (64, 40), (602, 64), (w, a) = (4, 8) and (8, 8): ``affine.linear`` on both routes and ``torch.matmul`` in the same
+alternating rounds, ``pack_weight`` alone, the traffic floor, and the layer with its linear layers on either route beside ``conv.GCNConv``.
+
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear]
 """
 from __future__ import annotations
 
@@ -899,6 +903,76 @@ def codes_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def linear_leg(torch, QGTC, graphs, reps):
+    """The byte-code route of the affine linear layer (include/qgtc_linear.h) at the graphs' row counts, Gaussian float32
+    X [n, K] and W [K, N] for (K, N) in (128, 64), (64, 40), (602, 64), bit pairs (w, a) = (4, 8) and (8, 8): linear on both routes and
+    torch.matmul in the same alternating rounds, pack_weight alone, the bytes route's time over its traffic floor
+    (4 M K + 4 M N bytes at HBM_BPS), and the layer at 128 / 64 / 40 dims with norm "mean", aggregates on the bytes route, with the linear
+    layers on either route beside conv.GCNConv. Pass mark: the bytes route's 90th percentile lies under the planes route's 10th (the planes
+    route refuses K = 602 at 8 x 8 bits: that cell has no mark)."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    dims = (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        rec = {"graph": name, "n": n, "dims": list(dims), "linear": []}
+        xr = np.random.default_rng(1)
+        for K, N in ((128, 64), (64, 40), (602, 64)):
+            X = torch.from_numpy(xr.normal(size=(n, K)).astype(np.float32)).cuda()
+            W = torch.from_numpy((xr.normal(size=(K, N)) * K ** -0.5).astype(np.float32)).cuda()
+            floor_ms = (4.0 * n * K + 4.0 * n * N) / HBM_BPS * 1e3
+            for w_bit, a_bit in ((4, 8), (8, 8)):
+                planes_ok = K * (2 ** a_bit - 1) * (2 ** w_bit - 1) < 2 ** 24
+                fns = [lambda: affine.linear(X, W, a_bit, w_bit, route="bytes"), lambda: torch.matmul(X, W), lambda: affine.pack_weight(W, w_bit)]
+                if planes_ok:
+                    assert torch.equal(fns[0]().view(torch.int32), affine.linear(X, W, a_bit, w_bit).view(torch.int32))
+                    fns.append(lambda: affine.linear(X, W, a_bit, w_bit, route="planes"))
+                by, mm, pw, *rest = timed_alternating(torch, fns, reps)
+                out = {"K": K, "N": N, "w": w_bit, "a": a_bit, "bytes_ms": by, "matmul_ms": mm, "pack_weight_ms": pw, "floor_ms": round(floor_ms, 4),
+                       "floor_over_bytes": round(floor_ms / by[0], 3), "bytes_over_matmul": round(by[0] / mm[0], 3)}
+                if rest:
+                    out.update(planes_ms=rest[0], bytes_over_planes=round(by[0] / rest[0][0], 3))
+                    out["pass"] = _separated(by, rest[0])
+                rec["linear"].append(out)
+                pl = f"planes {rest[0][0]:.4f} [{rest[0][1]:.4f}, {rest[0][2]:.4f}] ms" if rest else "planes refused (2^24)"
+                print(f"{name:9s} K={K} N={N} w{w_bit} a{a_bit}: bytes {by[0]:.4f} [{by[1]:.4f}, {by[2]:.4f}] ms  {pl}  matmul {mm[0]:.4f} [{mm[1]:.4f}, {mm[2]:.4f}] ms  "
+                      f"pack_weight {pw[0]:.4f} ms  floor {floor_ms:.4f} ms ({floor_ms / by[0]:.3f} of it)  pass {out.get('pass', '-')}", flush=True)
+            del X, W
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T, adj.mean_scale()
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, norm="mean").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(xr.normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        layer = {}
+        for w_bit, act_bit in ((4, 8), (8, 8)):
+            qb = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit, route="bytes", linear_route="bytes")
+            qpl = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit, route="bytes", linear_route="planes")
+            assert torch.equal(qb(adj, F).view(torch.int32), qpl(adj, F).view(torch.int32))
+
+            def float_forward():
+                with torch.no_grad():
+                    return ref(adj, F)
+
+            tb, tp, tf = timed_alternating(torch, [lambda: qb(adj, F), lambda: qpl(adj, F), float_forward], reps)
+            layer[f"w{w_bit}a{act_bit}"] = {"linear_bytes_ms": tb, "linear_planes_ms": tp, "float_ms": tf, "bytes_over_planes": round(tb[0] / tp[0], 3),
+                                            "bytes_over_float": round(tb[0] / tf[0], 3)}
+            print(f"{name:9s} layer {dims} w{w_bit} a{act_bit}: linear_route bytes {tb[0]:.4f} [{tb[1]:.4f}, {tb[2]:.4f}] ms  planes {tp[0]:.4f} [{tp[1]:.4f}, {tp[2]:.4f}] ms  "
+                  f"conv.GCNConv {tf[0]:.4f} [{tf[1]:.4f}, {tf[2]:.4f}] ms", flush=True)
+        rec["layer"] = layer
+        rows.append(rec)
+        del adj, dsrc, ddst, F
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1420,7 +1494,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear"))
     args = ap.parse_args()
 
     import torch
@@ -1428,9 +1502,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
