@@ -13,8 +13,11 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     q = affine.codes(x, bits, qp)                         # uint8 [H, W], one byte a code, rows PAD4(W) bytes apart
     acc = affine.tiledMMCodes(adj, q)                     # int32 [n, N]: the exact neighbour sum of the codes
     layer = affine.GCNConv_Affine.from_float(trained_gcnconv, 4, 8)
+    q = affine.linear(X, W, 8, 4, route="bytes", x_qparams=qx, out=(8, qy))   # static: fixed rows, uint8 codes out (or in: uint8 X)
+    q = affine.aggregate(adj, q, 8, route="bytes", t_qparams=qy, out=(8, qz)) # codes in, codes out: include/qgtc_chain.h
+    rows = layer.calibrate(A, X);  y = layer(A, X, act_qparams=rows)          # the layer as a chain of six launches
 
-The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h) are reached through ctypes on torch's current stream (the
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h) are reached through ctypes on torch's current stream (the
 extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
 requires grad. The accumulators of the planes route are float32 holding integers: there ``linear`` refuses a K at which
@@ -171,7 +174,7 @@ def pack_weight(W: torch.Tensor, bits: int, per_column: bool = True):
 
 
 def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_column: bool = True, row_scale=None, bias=None,
-           relu: bool = False, route: str = "planes") -> torch.Tensor:
+           relu: bool = False, route: str = "planes", x_qparams=None, out=None) -> torch.Tensor:
     """float32 [M, N] ~ X @ W on the bit-GEMM: X [M, K] quantised per tensor to ``a_bits`` (rows layout), W [K, N] per output column (or
     per tensor) to ``w_bits`` (cols layout, as ``GCNConv_Qnt.weight_Qnt`` packs weights), ``QGTC.bitMM2Int`` on the codes, then
     :func:`dequant` with the row sums of X's codes and the column sums of W's. Element [m][n] is within
@@ -180,10 +183,23 @@ def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_colum
     ``route="bytes"`` gives the same bits from byte codes on the int8 matrix instruction (include/qgtc_linear.h):
     :func:`qparams` of X, :func:`pack_weight` of W, then one launch that reads X, quantises it in registers, multiplies into an int32
     accumulator and dequantises - four launches, no packed X, no intermediate. Exact for every K up to ``LINEAR_K_MAX``; the 2^24 limit
-    below belongs to the planes route."""
+    below belongs to the planes route.
+
+    Static quantisation, on the bytes route only (include/qgtc_chain.h). ``x_qparams`` (float32 [1, 4]) fixes
+    X's row: no range launches are made. X may then be uint8 [M, K] (unit column stride), codes under that row, taken as they are.
+    ``out=(bits, row)`` returns the result's codes under the fixed per-tensor ``row`` instead of float32: uint8 [M, N], a view of a
+    buffer with rows PAD16(N) bytes apart - bit for bit ``codes(linear(...), bits, row)``, from the product's own epilogue."""
     route = _check_route(route)
     a_bits, w_bits = _check_bits(a_bits, "a_bits"), _check_bits(w_bits, "w_bits")
-    _check_f32(X, "X")
+    coded = isinstance(X, torch.Tensor) and X.dtype == torch.uint8
+    if route != "bytes" and (coded or x_qparams is not None or out is not None):
+        raise ValueError('uint8 X, x_qparams= and out= need route="bytes"')
+    if coded:
+        X = _check_u8(X, "X")
+        if x_qparams is None:
+            raise ValueError("uint8 X needs x_qparams, the row its codes were made under")
+    else:
+        _check_f32(X, "X")
     _check_f32(W, "W")
     M, K = X.shape
     if W.size(0) != K or W.device != X.device:
@@ -195,13 +211,27 @@ def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_colum
         for t, name, n in ((row_scale, "row_scale", M), (bias, "bias", N)):
             if t is not None:
                 _check_vector(t, name, torch.float32, n, X)
-        qa = qparams(X, a_bits)
+        if x_qparams is not None:
+            _check_qparams(x_qparams, "x_qparams", (1,), X)
+        out_bits, out_qp = _check_out(out, X)
+        qa = qparams(X, a_bits) if x_qparams is None else x_qparams
         codes_t, qb, col_sums = pack_weight(W, w_bits, per_column)
-        out = torch.empty((M, N), dtype=torch.float32, device=X.device)
-        _c_call("affine.linear", X, _c_abi().qgtc_affine_linear_u8, X.data_ptr(), M, K, qa.data_ptr(), a_bits, codes_t.data_ptr(),
-                codes_t.size(1), codes_t.numel(), N, qb.data_ptr(), qb.size(0), col_sums.data_ptr(), _ptr(row_scale), _ptr(bias),
-                int(bool(relu)), out.data_ptr(), out.numel())
-        return out
+        L = _c_abi()
+        right = (codes_t.data_ptr(), codes_t.size(1), codes_t.numel(), N, qb.data_ptr(), qb.size(0), col_sums.data_ptr(), _ptr(row_scale),
+                 _ptr(bias), int(bool(relu)))
+        if not coded and out is None:
+            res = torch.empty((M, N), dtype=torch.float32, device=X.device)
+            _c_call("affine.linear", X, L.qgtc_affine_linear_u8, X.data_ptr(), M, K, qa.data_ptr(), a_bits, *right, res.data_ptr(), res.numel())
+            return res
+        left = (None, X.data_ptr(), _codes_ld(X), _codes_bytes(X)) if coded else (X.data_ptr(), None, 0, 0)
+        if out is None:
+            res = torch.empty((M, N), dtype=torch.float32, device=X.device)
+            dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
+        else:
+            buf, res = _codes_out(M, N, X.device)
+            dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
+        _c_call("affine.linear", X, L.qgtc_affine_linear_chain, *left, M, K, qa.data_ptr(), a_bits, *right, *dest)
+        return res
     if K * (2 ** a_bits - 1) * (2 ** w_bits - 1) >= 2 ** 24:
         raise ValueError(f"K = {K} at a_bits = {a_bits}, w_bits = {w_bits}: the float32 accumulator of bitMM2Int is exact below 2^24 only")
     qa = qparams(X, a_bits)
@@ -210,6 +240,24 @@ def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_colum
     bit_W, col_sums = val2bit_affine(W, w_bits, qb, True, True)
     acc = QGTC.bitMM2Int(bit_X, bit_W, M, K, N, a_bits, w_bits, True)   # pad_128: W's planes are PAD128(N) lines apart
     return dequant(acc, K, qa, row_sums, qb, col_sums, row_scale, bias, relu, out=acc)
+
+
+def _check_out(out, like: torch.Tensor):
+    """``out=(bits, row)`` of the static calls as (bits, row), the row checked as a per-tensor qparams row; (0, None) without."""
+    if out is None:
+        return 0, None
+    if not isinstance(out, tuple) or len(out) != 2:
+        raise TypeError(f"out must be a tuple (bits, qparams row), not {out!r}")
+    bits = _check_bits(out[0], "out bits")
+    _check_qparams(out[1], "out qparams", (1,), like)
+    return bits, out[1]
+
+
+def _codes_out(M: int, N: int, device):
+    """(buffer, view): uint8 [M, PAD16(N)] and its columns :N, the code matrix a static call writes - rows 16-byte aligned, so that the
+    next product loads them 16 bytes at a time."""
+    buf = torch.empty((M, (N + 15) // 16 * 16), dtype=torch.uint8, device=device)
+    return buf, buf[:, :N]
 
 
 def _identity_qparams(device: torch.device) -> torch.Tensor:
@@ -247,23 +295,28 @@ def codes(x: torch.Tensor, bits: int, qp: torch.Tensor) -> torch.Tensor:
     return buf[:, :W]
 
 
-def _check_codes(adj_view, Q) -> torch.Tensor:
+def _check_codes(adj_view, Q, name: str = "Q") -> torch.Tensor:
     """Q as the C entries take it: any 2-D uint8 with unit column stride; a row stride or a base address off the 4-byte rule of a code
     matrix (include/qgtc_codes.h) gets a padded copy."""
+    if isinstance(Q, torch.Tensor) and Q.dtype == torch.uint8 and Q.is_cuda and Q.dim() == 2 and Q.numel() and (
+            Q.size(0) != adj_view.n or Q.device != adj_view.device):
+        raise ValueError(f"{name} must have shape [{adj_view.n}, N] on {adj_view.device}, not {list(Q.shape)} on {Q.device}")
+    return _check_u8(Q, name)
+
+
+def _check_u8(Q, name: str) -> torch.Tensor:
     if not isinstance(Q, torch.Tensor):
-        raise TypeError(f"Q must be a torch.Tensor, not {type(Q).__name__}")
+        raise TypeError(f"{name} must be a torch.Tensor, not {type(Q).__name__}")
     if Q.dtype != torch.uint8:
-        raise TypeError(f"Q must be uint8, not {Q.dtype}")
+        raise TypeError(f"{name} must be uint8, not {Q.dtype}")
     if not Q.is_cuda:
-        raise ValueError(f"Q must be on a GPU, not on {Q.device}")
+        raise ValueError(f"{name} must be on a GPU, not on {Q.device}")
     if Q.dim() != 2:
-        raise ValueError(f"Q must have 2 dimensions, not shape {list(Q.shape)}")
+        raise ValueError(f"{name} must have 2 dimensions, not shape {list(Q.shape)}")
     if Q.numel() == 0:
-        raise ValueError(f"Q must not be empty (shape {list(Q.shape)})")
-    if Q.size(0) != adj_view.n or Q.device != adj_view.device:
-        raise ValueError(f"Q must have shape [{adj_view.n}, N] on {adj_view.device}, not {list(Q.shape)} on {Q.device}")
+        raise ValueError(f"{name} must not be empty (shape {list(Q.shape)})")
     if Q.stride(1) != 1 and Q.size(1) > 1:
-        raise ValueError(f"Q must have unit column stride, not strides {list(Q.stride())}")
+        raise ValueError(f"{name} must have unit column stride, not strides {list(Q.stride())}")
     n, N = Q.shape
     ld = _codes_ld(Q)
     if ld < N or ld % 4 or Q.data_ptr() % 4 or Q.stride(1) != 1 or _codes_bytes(Q) < (n - 1) * ld + _pad4(N):
@@ -308,7 +361,7 @@ def tiledMMCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, row_mask=Non
 
 
 def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_scale=None, row_mask=None, nbr_mask=None,
-              route: str = "planes") -> torch.Tensor:
+              route: str = "planes", t_qparams=None, out=None) -> torch.Tensor:
     """float32 [n, N] ~ A . T on the view ``adj_view`` (``adj`` or ``adj.T``; T in the adjacency's numbering): T quantised per tensor to
     ``bits`` into the cols layout, ``QGTC.tiledMM2Int`` on the codes (the exact neighbour sum), then :func:`dequant` with the view's
     degrees under the masks as the row sums of A, and ``row_scale`` (float32 [n], say ``adj_view.mean_scale()``) applied there. Row i is
@@ -316,22 +369,45 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
 
     ``route="bytes"`` gives the same bits from byte codes (include/qgtc_codes.h): :func:`qparams`, :func:`codes`,
     then one launch that gathers the neighbours' codes, counts the terms of every row and dequantises in its epilogue - four launches, no
-    degree launch and no integer intermediate."""
+    degree launch and no integer intermediate.
+
+    Static quantisation, on the bytes route only (include/qgtc_chain.h). ``t_qparams`` (float32 [1, 4]) fixes
+    T's row: no range launches. T may then be uint8 [n, N], codes under that row: the walk is the only launch. ``out=(bits, row)``
+    returns the result's codes under the fixed ``row`` (uint8 [n, N], rows PAD16(N) apart), bit for bit ``codes(aggregate(...), bits,
+    row)``; a row without live neighbours, or outside ``row_mask``, is float +0 and so the row's zero point."""
     tiled._check(adj_view)
     route = _check_route(route)
     bits = _check_bits(bits)
-    _check_f32(T, "T")
+    coded = isinstance(T, torch.Tensor) and T.dtype == torch.uint8
+    if route != "bytes" and (coded or t_qparams is not None or out is not None):
+        raise ValueError('uint8 T, t_qparams= and out= need route="bytes"')
+    if coded:
+        T = _check_codes(adj_view, T, "T")
+        if t_qparams is None:
+            raise ValueError("uint8 T needs t_qparams, the row its codes were made under")
+    else:
+        _check_f32(T, "T")
     n, N = T.shape
     if n != adj_view.n or T.device != adj_view.device:
         raise ValueError(f"T must have shape [{adj_view.n}, N] on {adj_view.device}, not {list(T.shape)} on {T.device}")
     if row_scale is not None:
         tiled._check_scale(adj_view, row_scale)
-    qt = qparams(T, bits)
+    if t_qparams is not None:
+        _check_qparams(t_qparams, "t_qparams", (1,), T)
+    out_bits, out_qp = _check_out(out, T)
+    qt = qparams(T, bits) if t_qparams is None else t_qparams
     if route == "bytes":
         _check_masks(adj_view, row_mask, nbr_mask)
-        out = torch.empty((n, N), dtype=torch.float32, device=T.device)
-        return _u8_call("affine.aggregate", "qgtc_tiledmm_u8", adj_view, codes(T, bits, qt), out, row_mask, nbr_mask, qt.data_ptr(),
-                        _ptr(row_scale))
+        Q = T if coded else codes(T, bits, qt)
+        if out is None:
+            res = torch.empty((n, N), dtype=torch.float32, device=T.device)
+            return _u8_call("affine.aggregate", "qgtc_tiledmm_u8", adj_view, Q, res, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale))
+        buf, res = _codes_out(n, N, T.device)
+        fn = getattr(_c_abi(), "qgtc_tiledmm_u8" + ("_t" if adj_view.transposed else "") + "_requant")
+        _c_call("affine.aggregate", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), N, qt.data_ptr(),
+                _ptr(row_scale), out_qp.data_ptr(), out_bits, buf.data_ptr(), buf.size(1), buf.numel(), _ptr(row_mask), _ptr(nbr_mask),
+                adj_view.mask_words)
+        return res
     bit_T, _ = val2bit_affine(T, bits, qt, True, False)
     acc = QGTC.tiledMM2Int(adj_view, bit_T, N, bits, None, row_mask=row_mask, nbr_mask=nbr_mask)
     deg = adj_view.degrees(row_mask=row_mask, nbr_mask=nbr_mask)
@@ -384,8 +460,8 @@ class GCNConv_Affine(torch.nn.Module):
             new.W_out.copy_(layer.W_out)
         return new.to(layer.W_in.device)
 
-    @torch.no_grad()
-    def forward(self, A, X, nodes=None):
+    def _operands(self, A, X, nodes):
+        """(X in A's numbering, the mask keywords, the aggregate's row scale, the linear's) of one forward"""
         self._check_config()
         if not isinstance(A, QGTC.TiledAdjacency):
             raise NotImplementedError("GCNConv_Affine needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense A")
@@ -401,9 +477,47 @@ class GCNConv_Affine(torch.nn.Module):
             row = A.mean_scale(**mask)
         elif self.norm == "sym":
             row, src = A.sym_scale(**mask), A.T.sym_scale(**mask)
+        return A.to_new(X).contiguous(), mask, row, src
+
+    def _check_static(self):
+        if self.route != "bytes" or self.linear_route != "bytes":
+            raise ValueError(f'the static chain needs route="bytes" and linear_route="bytes", not {self.route!r} and {self.linear_route!r}')
+
+    @torch.no_grad()
+    def calibrate(self, A, X, nodes=None) -> torch.Tensor:
+        """float32 [4, 4]: the qparams rows of the four activations of ``forward(A, X, nodes)`` - X in the adjacency's numbering and the
+        outputs of the first linear, the first aggregate and the second linear -, exactly the rows the dynamic forward computes on the
+        bytes routes: ``layer(A, X, act_qparams=layer.calibrate(A, X))`` is ``layer(A, X)`` bit for bit. Nothing is kept on the module."""
+        self._check_static()
+        Xn, mask, row, src = self._operands(A, X, nodes)
         W_in, W_out = self.W_in.detach().contiguous(), self.W_out.detach().contiguous()
+        b = self.act_bit
+        rows = [qparams(Xn, b)]
+        t = linear(Xn, W_in, b, self.w_bit, True, src, route="bytes", x_qparams=rows[0])
+        rows.append(qparams(t, b))
+        h = aggregate(A, t, b, row, route="bytes", t_qparams=rows[1], **mask)
+        rows.append(qparams(h, b))
+        rows.append(qparams(linear(h, W_out, b, self.w_bit, True, src, route="bytes", x_qparams=rows[2]), b))
+        return torch.cat(rows)
+
+    @torch.no_grad()
+    def forward(self, A, X, nodes=None, act_qparams=None):
+        """``act_qparams`` (float32 [4, 4] on the device, as :meth:`calibrate` returns it) runs the static chain on the bytes routes
+        (include/qgtc_chain.h): product float -> codes, walk codes -> codes, product codes -> codes, walk codes -> float32, each stage's
+        output re-quantised in its producer's epilogue under the fixed rows; two ``pack_weight`` launches beside them, as now."""
+        Xn, mask, row, src = self._operands(A, X, nodes)
+        W_in, W_out = self.W_in.detach().contiguous(), self.W_out.detach().contiguous()
+        b = self.act_bit
+        if act_qparams is not None:
+            self._check_static()
+            _check_f32(act_qparams, "act_qparams")
+            if tuple(act_qparams.shape) != (4, 4) or act_qparams.device != X.device:
+                raise ValueError(f"act_qparams must have shape [4, 4] on {X.device}, not {list(act_qparams.shape)} on {act_qparams.device}")
+            q0, q1, q2, q3 = (act_qparams[i:i + 1] for i in range(4))   # rows of a contiguous [4, 4]: 16-byte aligned views
+            t = linear(Xn, W_in, b, self.w_bit, True, src, route="bytes", x_qparams=q0, out=(b, q1))
+            h = aggregate(A, t, b, row, route="bytes", t_qparams=q1, out=(b, q2), **mask)
+            t = linear(h, W_out, b, self.w_bit, True, src, route="bytes", x_qparams=q2, out=(b, q3))
+            return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **mask))
         lin = {"route": self.linear_route}
-        h = aggregate(A, linear(A.to_new(X).contiguous(), W_in, self.act_bit, self.w_bit, True, src, **lin), self.act_bit, row,
-                      route=self.route, **mask)
-        return A.to_old(aggregate(A, linear(h, W_out, self.act_bit, self.w_bit, True, src, **lin), self.act_bit, row, route=self.route,
-                                  **mask))
+        h = aggregate(A, linear(Xn, W_in, b, self.w_bit, True, src, **lin), b, row, route=self.route, **mask)
+        return A.to_old(aggregate(A, linear(h, W_out, b, self.w_bit, True, src, **lin), b, row, route=self.route, **mask))

@@ -135,10 +135,42 @@ __device__ __forceinline__ float tiled_u8_dequant(int acc, int terms, long long 
     return y;
 }
 
-template <bool AFFINE>
+// what a walk stores (the AFFINE switch of everything below): the int32 sums, their dequantised float, or that float re-quantised to one
+// byte a code under the caller's fixed output row (include/qgtc_chain.h)
+constexpr int TILED_U8_SUMS = 0, TILED_U8_FLOAT = 1, TILED_U8_CODES = 2;
+
+// the output of a walk as a kernel argument: a plain pointer for sums and floats, the code matrix and its row for codes
+struct TiledU8Codes {
+    uint8_t *q;         // code matrix [n, N], rows ld bytes apart
+    size_t ld;
+    const float4 *qp;   // its qparams row (scale, zero point, inverse scale, 0), per tensor
+    float qmax;
+};
+template <int AFFINE>
+struct TiledU8Out {
+    using type = void *__restrict__;
+};
+template <>
+struct TiledU8Out<TILED_U8_CODES> {
+    using type = TiledU8Codes;
+};
+
+template <int AFFINE>
 __device__ __forceinline__ void tiled_u8_store(const int (&s)[4], int terms, int row, int cb, int N, const float4 *__restrict__ qp,
-                                               const float *__restrict__ row_scale, void *__restrict__ out) {
-    if constexpr (AFFINE) {
+                                               const float *__restrict__ row_scale, typename TiledU8Out<AFFINE>::type out) {
+    if constexpr (AFFINE == TILED_U8_CODES) {
+        // the lane's four adjacent columns are one aligned dword of the row: four quantisers, one store; a column past N is the byte 0
+        const float4 g = qp[0], og = out.qp[0];
+        const long long z = static_cast<long long>(g.y);
+        const float rs = row_scale ? row_scale[row] : 1.0f;
+        uint32_t word = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t c = codes_quant(tiled_u8_dequant(s[k], terms, z, g.x, row_scale != nullptr, rs), og.z, og.y, out.qmax);
+            word |= (cb + k < N ? c : 0u) << (8 * k);
+        }
+        if (cb < N) *reinterpret_cast<uint32_t *>(out.q + static_cast<uint64_t>(row) * out.ld + cb) = word;
+    } else if constexpr (AFFINE == TILED_U8_FLOAT) {
         const float4 g = qp[0];
         const long long z = static_cast<long long>(g.y);
         const float rs = row_scale ? row_scale[row] : 1.0f;
@@ -167,11 +199,11 @@ __device__ __forceinline__ uint32_t tiled_u8_bcast(uint32_t v, int src) {
 // are broadcast, ANDed with the neighbour bitmap's words of the tile's k-quad (loaded one tile ahead) and decoded into that row's own
 // queue. A workgroup whose word of the row bitmap is zero takes an empty tile range without reading row_ptr; a masked-out row of a live
 // block does not load its tile rows. Every row of the block is stored once, through the epilogue.
-template <int LPR, bool AFFINE>
+template <int LPR, int AFFINE>
 __global__ __launch_bounds__(256) void k_tiled_mm_u8(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                      const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
                                                      const uint8_t *__restrict__ Q, size_t ld, int N, const float4 *__restrict__ qp,
-                                                     const float *__restrict__ row_scale, void *__restrict__ out, TiledNodes nodes) {
+                                                     const float *__restrict__ row_scale, typename TiledU8Out<AFFINE>::type out, TiledNodes nodes) {
     constexpr int G = 256 / LPR, RPG = 32 / G;   // row groups per workgroup, rows per group
     TiledNodesWalk<true> nd;
     __shared__ int lists[G][RPG][TILED_U8_CAP];
@@ -241,12 +273,12 @@ __global__ __launch_bounds__(256) void k_tiled_mm_u8(const int64_t *__restrict__
 // 128 x W outputs (int32, one int4 a lane) and the 128 counters beside them live in LDS between rounds; each word is read and written
 // by the lanes of one row group only, and every lane of the group writes the counter (the same value to the same address). A k-quad whose
 // four row-bitmap words are zero walks nothing and stores its rows through the epilogue with acc = cnt = 0.
-template <int LPR, bool AFFINE>
+template <int LPR, int AFFINE>
 __global__ __launch_bounds__(256) void k_tiled_mm_u8_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                        const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
                                                        uint64_t n_tiles, int n, const uint8_t *__restrict__ Q, size_t ld, int N,
                                                        const float4 *__restrict__ qp, const float *__restrict__ row_scale,
-                                                       void *__restrict__ out, TiledNodes nodes) {
+                                                       typename TiledU8Out<AFFINE>::type out, TiledNodes nodes) {
     constexpr int G = 256 / LPR, TS = TILED_T_TS;
     static_assert(TS == 8, "an output row reads its 8 masks of a round as two uint4");
     __shared__ __attribute__((aligned(16))) uint32_t mk[128 * TS];   // [tile column][staged tile]
@@ -357,9 +389,9 @@ void tiled_u8_width_switch(int N, int widest, F &&launch) {
     }
 }
 
-template <bool AFFINE>
+template <int AFFINE>
 int tiled_u8_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, int N,
-                    const float *qparams, const float *row_scale, void *out, const TiledNodes &nodes, hipStream_t st) {
+                    const float *qparams, const float *row_scale, typename TiledU8Out<AFFINE>::type out, const TiledNodes &nodes, hipStream_t st) {
     tiled_u8_width_switch(N, 64, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value;
         hipLaunchKernelGGL((k_tiled_mm_u8<LPR, AFFINE>), dim3((n + 31) / 32, (N + LPR * 4 - 1) / (LPR * 4)), dim3(256), 0, st, ix.row_ptr,
@@ -370,9 +402,9 @@ int tiled_u8_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_ti
     return QGTC_OK;
 }
 
-template <bool AFFINE>
+template <int AFFINE>
 int tiled_u8_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, int N,
-                    const float *qparams, const float *row_scale, void *out, const TiledNodes &nodes, hipStream_t st) {
+                    const float *qparams, const float *row_scale, typename TiledU8Out<AFFINE>::type out, const TiledNodes &nodes, hipStream_t st) {
     tiled_u8_width_switch(N, 32, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value;
         if constexpr (LPR <= 32)
@@ -394,7 +426,7 @@ inline bool codes_matrix_misaligned(const void *p, size_t ld, int W) {
 inline size_t codes_matrix_bytes(int H, int W, size_t ld) { return static_cast<size_t>(H - 1) * ld + codes_pad4(W); }
 
 // either view; AFFINE wants qparams (16-byte aligned) and takes an optional row_scale
-template <bool AFFINE, class Index>
+template <int AFFINE, class Index>
 int tiled_u8_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, size_t q_bytes, int N,
                    const float *qparams, const float *row_scale, void *out, size_t out_elems, const uint32_t *row_mask,
                    const uint32_t *nbr_mask, size_t mask_words, void *stream) {
@@ -406,6 +438,23 @@ int tiled_u8_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int 
     if ((row_mask || nbr_mask) && mask_words < static_cast<size_t>(step128(n)) * 4) return QGTC_ESIZE;
     return tiled_u8_launch<AFFINE>(ix, tiles, n_tiles, n, Q, ld, N, qparams, row_scale, out, TiledNodes{row_mask, nbr_mask},
                                    static_cast<hipStream_t>(stream));
+}
+
+// either view with the code output of include/qgtc_chain.h: outq a code matrix [n, N] under (out_qp, out_bits)
+template <class Index>
+int tiled_u8_requant_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, size_t q_bytes, int N,
+                           const float *qparams, const float *row_scale, const float *out_qp, int out_bits, uint8_t *outq, size_t ldo,
+                           size_t outq_bytes, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
+    if (!Q || !outq || !qparams || !out_qp || N < 1 || out_bits < 1 || out_bits > 8 || tiled_adj_malformed(ix.ok(), tiles, n_tiles, n))
+        return QGTC_EINVAL;
+    if (tiled_adj_misaligned(tiles) || codes_matrix_misaligned(Q, ld, N) || codes_matrix_misaligned(outq, ldo, N) || !aligned16(qparams) ||
+        !aligned16(out_qp) || !codes_aligned4(row_scale) || !aligned16(row_mask) || !aligned16(nbr_mask))
+        return QGTC_EALIGN;
+    if (q_bytes < codes_matrix_bytes(n, N, ld) || outq_bytes < codes_matrix_bytes(n, N, ldo)) return QGTC_ESIZE;
+    if ((row_mask || nbr_mask) && mask_words < static_cast<size_t>(step128(n)) * 4) return QGTC_ESIZE;
+    const TiledU8Codes out{outq, ldo, reinterpret_cast<const float4 *>(out_qp), static_cast<float>((1 << out_bits) - 1)};
+    return tiled_u8_launch<TILED_U8_CODES>(ix, tiles, n_tiles, n, Q, ld, N, qparams, row_scale, out, TiledNodes{row_mask, nbr_mask},
+                                           static_cast<hipStream_t>(stream));
 }
 
 }  // namespace

@@ -124,8 +124,10 @@ when the bytes route's 90th percentile lies under the planes route's 10th.
 `--leg linear` measures the byte-code route of the linear layer (include/qgtc_linear.h) at the graphs' row counts,
 (K, N) = (128, 64), (64, 40), (602, 64), (w, a) = (4, 8) and (8, 8): ``affine.linear`` on both routes and ``torch.matmul`` in the same
 alternating rounds, ``pack_weight`` alone, the traffic floor, and the layer with its linear layers on either route beside ``conv.GCNConv``.
+`--leg chain` measures the static affine chain (include/qgtc_chain.h): the layer at 128 / 64 / 40 on calibrated rows beside
+the dynamic layer on the bytes routes and ``conv.GCNConv`` in the same alternating rounds, and each new launch beside its float twin.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear]
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain]
 """
 from __future__ import annotations
 
@@ -973,6 +975,68 @@ def linear_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def chain_leg(torch, QGTC, graphs, reps):
+    """The static affine chain (include/qgtc_chain.h): the layer at 128 / 64 / 40 dims with norm "mean", (w, a) = (4, 8) and
+    (8, 8), on calibrated rows (``forward(act_qparams=)``) beside the dynamic layer on the bytes routes and conv.GCNConv in the same
+    alternating rounds, and each new launch beside its float-producing twin at the layer's shapes. Pass mark: the static layer's 90th
+    percentile lies under the dynamic layer's 10th. The ratio to conv.GCNConv carries no mark."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    dims = (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T, adj.mean_scale()
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, norm="mean").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(np.random.default_rng(1).normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        rec = {"graph": name, "n": n, "dims": list(dims), "layer": {}, "launches": {}}
+        for w_bit, act_bit in ((4, 8), (8, 8)):
+            q = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit, route="bytes", linear_route="bytes")
+            qp = q.calibrate(adj, F)
+            assert torch.equal(q(adj, F, act_qparams=qp).view(torch.int32), q(adj, F).view(torch.int32))
+
+            def float_forward():
+                with torch.no_grad():
+                    return ref(adj, F)
+
+            ts, td, tf = timed_alternating(torch, [lambda: q(adj, F, act_qparams=qp), lambda: q(adj, F), float_forward], reps)
+            rec["layer"][f"w{w_bit}a{act_bit}"] = {"static_ms": ts, "dynamic_ms": td, "float_ms": tf, "static_over_dynamic": round(ts[0] / td[0], 3),
+                                                   "static_over_float": round(ts[0] / tf[0], 3), "pass": _separated(ts, td)}
+            print(f"{name:9s} layer {dims} w{w_bit} a{act_bit}: static {ts[0]:.4f} [{ts[1]:.4f}, {ts[2]:.4f}] ms  dynamic {td[0]:.4f} [{td[1]:.4f}, {td[2]:.4f}] ms  "
+                  f"conv.GCNConv {tf[0]:.4f} [{tf[1]:.4f}, {tf[2]:.4f}] ms  pass {_separated(ts, td)}", flush=True)
+        # each new launch beside its float-producing twin, at the first stage's shapes (weights prepared outside: pack_weight is in both)
+        q0, q1, q2 = (qp[i:i + 1] for i in range(3))
+        W = ref.W_in.detach().contiguous()
+        Xn = adj.to_new(F).contiguous()
+        Xq = affine.codes(Xn, 8, q0)
+        kw = {"route": "bytes", "x_qparams": q0}
+        t_float = affine.linear(Xn, W, 8, 4, **kw)
+        t_codes = affine.linear(Xn, W, 8, 4, out=(8, q1), **kw)
+        cells = {"linear float->float": lambda: affine.linear(Xn, W, 8, 4, **kw), "linear float->codes": lambda: affine.linear(Xn, W, 8, 4, out=(8, q1), **kw),
+                 "linear codes->float": lambda: affine.linear(Xq, W, 8, 4, **kw), "linear codes->codes": lambda: affine.linear(Xq, W, 8, 4, out=(8, q1), **kw)}
+        for tag, a in (("adj", adj), ("adjT", adj.T)):
+            a.mean_scale()
+            cells[f"walk {tag} float->float"] = lambda a=a: affine.aggregate(a, t_float, 8, a.mean_scale(), route="bytes", t_qparams=q1)
+            cells[f"walk {tag} codes->float"] = lambda a=a: affine.aggregate(a, t_codes, 8, a.mean_scale(), route="bytes", t_qparams=q1)
+            cells[f"walk {tag} codes->codes"] = lambda a=a: affine.aggregate(a, t_codes, 8, a.mean_scale(), route="bytes", t_qparams=q1, out=(8, q2))
+        for tag, t in zip(cells, timed_alternating(torch, list(cells.values()), reps)):
+            rec["launches"][tag] = t
+            print(f"{name:9s} {tag:24s} {t[0]:.4f} [{t[1]:.4f}, {t[2]:.4f}] ms", flush=True)
+        rows.append(rec)
+        del adj, dsrc, ddst, F
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1494,7 +1558,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain"))
     args = ap.parse_args()
 
     import torch
@@ -1502,9 +1566,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
