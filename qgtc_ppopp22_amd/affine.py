@@ -16,8 +16,10 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     q = affine.linear(X, W, 8, 4, route="bytes", x_qparams=qx, out=(8, qy))   # static: fixed rows, uint8 codes out (or in: uint8 X)
     q = affine.aggregate(adj, q, 8, route="bytes", t_qparams=qy, out=(8, qz)) # codes in, codes out: include/qgtc_chain.h
     rows = layer.calibrate(A, X);  y = layer(A, X, act_qparams=rows)          # the layer as a chain of six launches
+    q = affine.aggregate_linear(adj, q, qy, (8, qz), W, 4, out=(8, qo))       # the middle walk and the product behind it, one launch
+    y = layer(A, X, act_qparams=rows, fuse=True)                              # five launches, the same bits: include/qgtc_fused.h
 
-The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h) are reached through ctypes on torch's current stream (the
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h, one of include/qgtc_fused.h) are reached through ctypes on torch's current stream (the
 extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
 requires grad. The accumulators of the planes route are float32 holding integers: there ``linear`` refuses a K at which
@@ -31,9 +33,10 @@ import QGTC  # the HIP extension; there is no fallback
 from . import conv, tiled
 from .tiled import _c_abi, _ptr
 
-__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight"]
+__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight", "aggregate_linear"]
 
 ROUTES = ("planes", "bytes")   # how ``aggregate`` sums the codes: eight bit planes through tiledMM2Int, or one gather of byte codes
+FUSED_MAX = 256                # QGTC_FUSED_K_MAX and QGTC_FUSED_N_MAX of include/qgtc_fused.h: the widths one workgroup holds
 LINEAR_K_MAX = 131071          # QGTC_LINEAR_K_MAX of include/qgtc_linear.h: K 2^14 < 2^31, the int32 accumulator of the shifted codes
 
 _identity = {}   # per device: the qparams row (1, 0, 1, 0) of an operand that is its own code; a constant, built outside captures
@@ -414,6 +417,55 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     return dequant(acc, n, _identity_qparams(T.device), deg, qt, None, row_scale, out=acc)
 
 
+def aggregate_linear(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, t_qparams: torch.Tensor, h, W: torch.Tensor, w_bits: int,
+                     per_column: bool = True, agg_row_scale=None, lin_row_scale=None, bias=None, relu: bool = False, row_mask=None,
+                     nbr_mask=None, out=None) -> torch.Tensor:
+    """The middle of the static chain in one launch (include/qgtc_fused.h): bit for bit
+    ``linear(aggregate(adj_view, T, hb, agg_row_scale, row_mask, nbr_mask, route="bytes", t_qparams=t_qparams, out=h), W, hb, w_bits,
+    per_column, lin_row_scale, bias, relu, route="bytes", x_qparams=h[1], out=out)`` with ``h = (hb, row)``, the intermediate never
+    stored. T is uint8 [n, K], codes under ``t_qparams``; ``h`` the intermediate's fixed per-tensor row and its bits; W float32 [K, N2].
+    ``out=(bits, row)`` gives uint8 codes [n, N2] (rows PAD16(N2) apart), otherwise float32 [n, N2]. :func:`pack_weight`, then the launch.
+    The row view only, K and N2 up to ``FUSED_MAX``: anything else raises and names the two calls above, which serve it."""
+    tiled._check(adj_view)
+    two_calls = "; call aggregate(..., out=h) and then linear(..., x_qparams=h[1]) instead"
+    if adj_view.transposed:
+        raise ValueError("aggregate_linear has no fused kernel for the transposed view (adj.T)" + two_calls)
+    T = _check_codes(adj_view, T, "T")
+    n, K = T.shape
+    if n != adj_view.n or T.device != adj_view.device:
+        raise ValueError(f"T must have shape [{adj_view.n}, K] on {adj_view.device}, not {list(T.shape)} on {T.device}")
+    _check_qparams(t_qparams, "t_qparams", (1,), T)
+    h_bits, h_qp = _check_out(h, T)
+    if h_qp is None:
+        raise TypeError("h must be a tuple (bits, qparams row): the fixed row of the intermediate")
+    w_bits = _check_bits(w_bits, "w_bits")
+    _check_f32(W, "W")
+    if W.size(0) != K or W.device != T.device:
+        raise ValueError(f"W must have shape [{K}, N2] on {T.device}, not {list(W.shape)} on {W.device}")
+    N2 = W.size(1)
+    if K > FUSED_MAX or N2 > FUSED_MAX:
+        raise ValueError(f"K = {K}, N2 = {N2}: the fused kernel holds widths up to {FUSED_MAX} in one workgroup" + two_calls)
+    if agg_row_scale is not None:
+        tiled._check_scale(adj_view, agg_row_scale)
+    for t, name, m in ((lin_row_scale, "lin_row_scale", n), (bias, "bias", N2)):
+        if t is not None:
+            _check_vector(t, name, torch.float32, m, T)
+    _check_masks(adj_view, row_mask, nbr_mask)
+    out_bits, out_qp = _check_out(out, T)
+    codes_t, qb, col_sums = pack_weight(W, w_bits, per_column)
+    if out is None:
+        res = torch.empty((n, N2), dtype=torch.float32, device=T.device)
+        dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
+    else:
+        buf, res = _codes_out(n, N2, T.device)
+        dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
+    _c_call("affine.aggregate_linear", T, _c_abi().qgtc_tiledmm_u8_linear, *tiled._view_args(adj_view), T.data_ptr(), _codes_ld(T),
+            _codes_bytes(T), K, t_qparams.data_ptr(), _ptr(agg_row_scale), h_qp.data_ptr(), h_bits, codes_t.data_ptr(), codes_t.size(1),
+            codes_t.numel(), N2, qb.data_ptr(), qb.size(0), col_sums.data_ptr(), _ptr(lin_row_scale), _ptr(bias), int(bool(relu)), *dest,
+            _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+    return res
+
+
 class GCNConv_Affine(torch.nn.Module):
     """The layer pair of ``conv.GCNConv`` on the bit-GEMM engine with affine quantisation:
     out = agg(linear(agg(linear(X, W_in)), W_out)), weights quantised per output column to ``w_bit`` bits, activations per tensor to
@@ -501,13 +553,17 @@ class GCNConv_Affine(torch.nn.Module):
         return torch.cat(rows)
 
     @torch.no_grad()
-    def forward(self, A, X, nodes=None, act_qparams=None):
+    def forward(self, A, X, nodes=None, act_qparams=None, fuse=False):
         """``act_qparams`` (float32 [4, 4] on the device, as :meth:`calibrate` returns it) runs the static chain on the bytes routes
         (include/qgtc_chain.h): product float -> codes, walk codes -> codes, product codes -> codes, walk codes -> float32, each stage's
-        output re-quantised in its producer's epilogue under the fixed rows; two ``pack_weight`` launches beside them, as now."""
+        output re-quantised in its producer's epilogue under the fixed rows; two ``pack_weight`` launches beside them, as now. ``fuse=True`` (with
+        ``act_qparams`` only) runs the first walk and the second product as one launch (:func:`aggregate_linear`): five launches, the
+        same bits."""
         Xn, mask, row, src = self._operands(A, X, nodes)
         W_in, W_out = self.W_in.detach().contiguous(), self.W_out.detach().contiguous()
         b = self.act_bit
+        if fuse and act_qparams is None:
+            raise ValueError("fuse=True needs act_qparams: only the static chain has a fused launch")
         if act_qparams is not None:
             self._check_static()
             _check_f32(act_qparams, "act_qparams")
@@ -515,6 +571,9 @@ class GCNConv_Affine(torch.nn.Module):
                 raise ValueError(f"act_qparams must have shape [4, 4] on {X.device}, not {list(act_qparams.shape)} on {act_qparams.device}")
             q0, q1, q2, q3 = (act_qparams[i:i + 1] for i in range(4))   # rows of a contiguous [4, 4]: 16-byte aligned views
             t = linear(Xn, W_in, b, self.w_bit, True, src, route="bytes", x_qparams=q0, out=(b, q1))
+            if fuse:
+                t = aggregate_linear(A, t, q1, (b, q2), W_out, self.w_bit, True, row, src, out=(b, q3), **mask)
+                return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **mask))
             h = aggregate(A, t, b, row, route="bytes", t_qparams=q1, out=(b, q2), **mask)
             t = linear(h, W_out, b, self.w_bit, True, src, route="bytes", x_qparams=q2, out=(b, q3))
             return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **mask))

@@ -126,8 +126,10 @@ when the bytes route's 90th percentile lies under the planes route's 10th.
 alternating rounds, ``pack_weight`` alone, the traffic floor, and the layer with its linear layers on either route beside ``conv.GCNConv``.
 `--leg chain` measures the static affine chain (include/qgtc_chain.h): the layer at 128 / 64 / 40 on calibrated rows beside
 the dynamic layer on the bytes routes and ``conv.GCNConv`` in the same alternating rounds, and each new launch beside its float twin.
+`--leg fused` measures the fused middle of that chain (include/qgtc_fused.h): the static layer with ``fuse=True`` beside
+``fuse=False``, and ``affine.aggregate_linear`` beside the walk and the product it replaces, also once at K = N2 = 256 on arxiv.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain]
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain|fused]
 """
 from __future__ import annotations
 
@@ -1037,6 +1039,63 @@ def chain_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def fused_leg(torch, QGTC, graphs, reps):
+    """The fused middle of the static chain (include/qgtc_fused.h): (a) the static layer at 128 / 64 / 40 dims with norm
+    "mean", (w, a) = (4, 8) and (8, 8), with ``fuse=True`` beside ``fuse=False``; (b) ``affine.aggregate_linear`` alone beside the two
+    launches it replaces (the re-quantising walk, then the codes -> codes product; ``pack_weight`` is in both), at the layer's K = 64,
+    N2 = 40 and, on the arxiv-sized graph, once at K = N2 = 256. Alternating rounds. Pass mark: the fused 90th percentile lies under the
+    unfused 10th."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    dims = (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        scale = adj.mean_scale()
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, norm="mean").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(np.random.default_rng(1).normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        rec = {"graph": name, "n": n, "dims": list(dims), "layer": {}, "launches": {}}
+        for w_bit, act_bit in ((4, 8), (8, 8)):
+            q = affine.GCNConv_Affine.from_float(ref, w_bit, act_bit, route="bytes", linear_route="bytes")
+            qp = q.calibrate(adj, F)
+            assert torch.equal(q(adj, F, act_qparams=qp, fuse=True).view(torch.int32), q(adj, F, act_qparams=qp).view(torch.int32))
+            tf, tu = timed_alternating(torch, [lambda: q(adj, F, act_qparams=qp, fuse=True), lambda: q(adj, F, act_qparams=qp)], reps)
+            rec["layer"][f"w{w_bit}a{act_bit}"] = {"fused_ms": tf, "unfused_ms": tu, "fused_over_unfused": round(tf[0] / tu[0], 3), "pass": _separated(tf, tu)}
+            print(f"{name:9s} layer {dims} w{w_bit} a{act_bit}: fuse=True {tf[0]:.4f} [{tf[1]:.4f}, {tf[2]:.4f}] ms  fuse=False {tu[0]:.4f} [{tu[1]:.4f}, {tu[2]:.4f}] ms  "
+                  f"pass {_separated(tf, tu)}", flush=True)
+        q1, q2, q3 = (qp[i:i + 1] for i in range(1, 4))
+        for K, N2 in ((dims[1], dims[2]),) + (((256, 256),) if name == "arxiv" else ()):
+            T = torch.randint(0, 256, (n, K), dtype=torch.uint8, device="cuda", generator=torch.Generator("cuda").manual_seed(2))
+            W = torch.randn((K, N2), device="cuda") * K ** -0.5
+
+            def two_launches():
+                h = affine.aggregate(adj, T, 8, scale, route="bytes", t_qparams=q1, out=(8, q2))
+                return affine.linear(h, W, 8, 4, route="bytes", x_qparams=q2, out=(8, q3))
+
+            def one_launch():
+                return affine.aggregate_linear(adj, T, q1, (8, q2), W, 4, agg_row_scale=scale, out=(8, q3))
+
+            assert torch.equal(one_launch(), two_launches())
+            tf, tu = timed_alternating(torch, [one_launch, two_launches], reps)
+            rec["launches"][f"K{K} N{N2}"] = {"fused_ms": tf, "two_launches_ms": tu, "fused_over_two": round(tf[0] / tu[0], 3), "pass": _separated(tf, tu)}
+            print(f"{name:9s} K={K} N2={N2}: aggregate_linear {tf[0]:.4f} [{tf[1]:.4f}, {tf[2]:.4f}] ms  walk + product {tu[0]:.4f} [{tu[1]:.4f}, {tu[2]:.4f}] ms  "
+                  f"pass {_separated(tf, tu)}", flush=True)
+            del T, W
+        rows.append(rec)
+        del adj, dsrc, ddst, F
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1558,7 +1617,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused"))
     args = ap.parse_args()
 
     import torch
@@ -1566,9 +1625,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg, "fused": fused_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
