@@ -18,8 +18,11 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     rows = layer.calibrate(A, X);  y = layer(A, X, act_qparams=rows)          # the layer as a chain of six launches
     q = affine.aggregate_linear(adj, q, qy, (8, qz), W, 4, out=(8, qo))       # the middle walk and the product behind it, one launch
     y = layer(A, X, act_qparams=rows, fuse=True)                              # five launches, the same bits: include/qgtc_fused.h
+    m = affine.tiledMaxCodes(adj, q, reduce="max")        # uint8 [n, N]: the extremum of the neighbours' codes, itself a code under q's row
+    y = affine.aggregate(adj, T, 8, route="bytes", reduce="max")              # ~ max over the neighbours' rows of T: include/qgtc_codes_max.h
+    layer = affine.GCNConv_Affine.from_float(gcnconv_with_aggr_max, 4, 8, route="bytes", linear_route="bytes")
 
-The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h, one of include/qgtc_fused.h) are reached through ctypes on torch's current stream (the
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h, one of include/qgtc_fused.h, four of include/qgtc_codes_max.h) are reached through ctypes on torch's current stream (the
 extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
 requires grad. The accumulators of the planes route are float32 holding integers: there ``linear`` refuses a K at which
@@ -33,9 +36,10 @@ import QGTC  # the HIP extension; there is no fallback
 from . import conv, tiled
 from .tiled import _c_abi, _ptr
 
-__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight", "aggregate_linear"]
+__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight", "aggregate_linear", "tiledMaxCodes"]
 
 ROUTES = ("planes", "bytes")   # how ``aggregate`` sums the codes: eight bit planes through tiledMM2Int, or one gather of byte codes
+REDUCES = ("sum", "max", "min")   # the reducer of ``aggregate`` and of the layer's ``aggr``; an extremum is served on route="bytes" only
 FUSED_MAX = 256                # QGTC_FUSED_K_MAX and QGTC_FUSED_N_MAX of include/qgtc_fused.h: the widths one workgroup holds
 LINEAR_K_MAX = 131071          # QGTC_LINEAR_K_MAX of include/qgtc_linear.h: K 2^14 < 2^31, the int32 accumulator of the shifted codes
 
@@ -275,6 +279,12 @@ def _identity_qparams(device: torch.device) -> torch.Tensor:
     return t
 
 
+def _check_reduce(reduce, name: str = "reduce") -> str:
+    if reduce not in REDUCES:
+        raise ValueError(f'{name} must be "sum", "max" or "min", not {reduce!r}')
+    return reduce
+
+
 def _check_route(route) -> str:
     if route not in ROUTES:
         raise ValueError(f'route must be "planes" or "bytes", not {route!r}')
@@ -363,8 +373,31 @@ def tiledMMCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, row_mask=Non
     return _u8_call("affine.tiledMMCodes", "qgtc_tiledmm_u8", adj_view, Q, out, row_mask, nbr_mask)
 
 
+def tiledMaxCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, reduce: str = "max", empty: int = 0, row_mask=None,
+                  nbr_mask=None) -> torch.Tensor:
+    """uint8 [n, N]: the element-wise maximum (``reduce="max"``) or minimum ("min") of the code rows Q[k] (uint8 [n, N], in the
+    adjacency's numbering) over the neighbours k of every row of the view ``adj_view`` (``adj`` or ``adj.T``), under the node masks of
+    :func:`tiledMMCodes` (include/qgtc_codes_max.h). The quantiser is monotone, so the result is the code of the
+    extremum under Q's own qparams row, with no error of its own. A row without a live neighbour, or outside ``row_mask``, holds
+    ``empty`` (0 .. 255). A view of a buffer with rows PAD16(N) bytes apart, bytes N .. PAD4(N) - 1 written 0. One launch."""
+    tiled._check(adj_view)
+    Q = _check_codes(adj_view, Q)
+    if _check_reduce(reduce) == "sum":
+        raise ValueError('reduce must be "max" or "min" here: tiledMMCodes is the sum')
+    if isinstance(empty, bool) or not isinstance(empty, int):
+        raise TypeError(f"empty must be an int in 0 .. 255, not {empty!r}")
+    if not 0 <= empty <= 255:
+        raise ValueError(f"empty must lie in 0 .. 255, not {empty}")
+    _check_masks(adj_view, row_mask, nbr_mask)
+    buf, res = _codes_out(adj_view.n, Q.size(1), Q.device)
+    fn = getattr(_c_abi(), "qgtc_tiledmax_u8" + ("_t" if adj_view.transposed else ""))
+    _c_call("affine.tiledMaxCodes", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), Q.size(1),
+            int(reduce == "min"), empty, buf.data_ptr(), buf.size(1), buf.numel(), _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+    return res
+
+
 def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_scale=None, row_mask=None, nbr_mask=None,
-              route: str = "planes", t_qparams=None, out=None) -> torch.Tensor:
+              route: str = "planes", t_qparams=None, out=None, reduce: str = "sum") -> torch.Tensor:
     """float32 [n, N] ~ A . T on the view ``adj_view`` (``adj`` or ``adj.T``; T in the adjacency's numbering): T quantised per tensor to
     ``bits`` into the cols layout, ``QGTC.tiledMM2Int`` on the codes (the exact neighbour sum), then :func:`dequant` with the view's
     degrees under the masks as the row sums of A, and ``row_scale`` (float32 [n], say ``adj_view.mean_scale()``) applied there. Row i is
@@ -377,10 +410,20 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     Static quantisation, on the bytes route only (include/qgtc_chain.h). ``t_qparams`` (float32 [1, 4]) fixes
     T's row: no range launches. T may then be uint8 [n, N], codes under that row: the walk is the only launch. ``out=(bits, row)``
     returns the result's codes under the fixed ``row`` (uint8 [n, N], rows PAD16(N) apart), bit for bit ``codes(aggregate(...), bits,
-    row)``; a row without live neighbours, or outside ``row_mask``, is float +0 and so the row's zero point."""
+    row)``; a row without live neighbours, or outside ``row_mask``, is float +0 and so the row's zero point.
+
+    ``reduce="max"`` / ``"min"``, on the bytes route only (include/qgtc_codes_max.h), replace the sum by the
+    element-wise extremum over the neighbours: scale * (m - zero_point) with m the extremum of the neighbours' codes, which is the
+    quantised value of the extremum itself - the aggregate adds no error to T's quantisation. Float T, uint8 T with ``t_qparams`` and
+    ``out=(bits, row)`` work as for the sum; ``row_scale`` is a ValueError (an extremum is not scaled); a row without a term is +0."""
     tiled._check(adj_view)
     route = _check_route(route)
     bits = _check_bits(bits)
+    if _check_reduce(reduce) != "sum":
+        if route != "bytes":
+            raise ValueError(f'reduce="{reduce}" needs route="bytes": the planes route sums')
+        if row_scale is not None:
+            raise ValueError(f'row_scale cannot be combined with reduce="{reduce}"')
     coded = isinstance(T, torch.Tensor) and T.dtype == torch.uint8
     if route != "bytes" and (coded or t_qparams is not None or out is not None):
         raise ValueError('uint8 T, t_qparams= and out= need route="bytes"')
@@ -402,6 +445,17 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     if route == "bytes":
         _check_masks(adj_view, row_mask, nbr_mask)
         Q = T if coded else codes(T, bits, qt)
+        if reduce != "sum":
+            if out is None:
+                res = torch.empty((n, N), dtype=torch.float32, device=T.device)
+                dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
+            else:
+                buf, res = _codes_out(n, N, T.device)
+                dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
+            fn = getattr(_c_abi(), "qgtc_tiledmax_u8" + ("_t" if adj_view.transposed else "") + "_affine")
+            _c_call("affine.aggregate", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), N, qt.data_ptr(),
+                    int(reduce == "min"), *dest, _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+            return res
         if out is None:
             res = torch.empty((n, N), dtype=torch.float32, device=T.device)
             return _u8_call("affine.aggregate", "qgtc_tiledmm_u8", adj_view, Q, res, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale))
@@ -475,14 +529,18 @@ class GCNConv_Affine(torch.nn.Module):
     quantised, and ``A.sym_scale()`` on the aggregate). ``A`` is a QGTC.TiledAdjacency view; X moves to its numbering and the result
     back. ``nodes`` (bool [n] in X's numbering) runs the pair on the induced subgraph: one bitmap as both masks, with the masked degrees
     and scales; rows outside come back +0. ``route`` ("planes" or "bytes") is the route of both aggregates (:func:`aggregate`; the same
-    bits either way), ``linear_route`` that of both linear layers (:func:`linear`; likewise). Inference only: forward runs without grad."""
+    bits either way), ``linear_route`` that of both linear layers (:func:`linear`; likewise). ``aggr`` is the reducer of both aggregates,
+    read at every forward like ``norm``: "sum", or "max" / "min", the twin of ``conv.GCNConv(aggr=...)`` on the extremum walks of
+    include/qgtc_codes_max.h - with ``norm=None`` and ``route="bytes"`` only, anything else a ValueError. Inference only: forward runs
+    without grad."""
 
-    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None, route="planes", linear_route="planes"):
+    def __init__(self, input_dim, hidden_dim, output_dim, w_bit=4, act_bit=8, norm=None, route="planes", linear_route="planes", aggr="sum"):
         super().__init__()
         self.w_bit, self.act_bit = _check_bits(w_bit, "w_bit"), _check_bits(act_bit, "act_bit")
         self.norm = norm
         self.route = route
         self.linear_route = linear_route
+        self.aggr = aggr
         self._check_config()
         self.W_in = torch.nn.Parameter(torch.randn(input_dim, hidden_dim))
         self.W_out = torch.nn.Parameter(torch.randn(hidden_dim, output_dim))
@@ -495,18 +553,22 @@ class GCNConv_Affine(torch.nn.Module):
         _check_route(self.route)
         if self.linear_route not in ROUTES:
             raise ValueError(f'linear_route must be "planes" or "bytes", not {self.linear_route!r}')
+        if _check_reduce(self.aggr, "aggr") != "sum":
+            if self.norm is not None:
+                raise ValueError(f'aggr="{self.aggr}" takes no norm (norm={self.norm!r}): an extremum is not scaled')
+            if self.route != "bytes":
+                raise ValueError(f'aggr="{self.aggr}" needs route="bytes", not {self.route!r}: the planes route sums')
 
     @classmethod
     def from_float(cls, layer: "conv.GCNConv", w_bit: int = 4, act_bit: int = 8, route: str = "planes",
                    linear_route: str = "planes") -> "GCNConv_Affine":
-        """The quantised twin of a (trained) float ``conv.GCNConv``: its two weights (copied) and its norm."""
+        """The quantised twin of a (trained) float ``conv.GCNConv``: its two weights (copied), its norm and its aggr."""
         if not isinstance(layer, conv.GCNConv):
             raise TypeError(f"layer must be a conv.GCNConv, not {type(layer).__name__}")
-        if layer.aggr != "sum":
-            raise ValueError(f'aggr="{layer.aggr}" has no quantised twin: only aggr="sum" is built')
         if layer.edge_drop > 0.0:
             raise ValueError(f"edge_drop={layer.edge_drop} has no quantised twin: the layer is inference only")
-        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm, route, linear_route)
+        new = cls(layer.W_in.size(0), layer.W_in.size(1), layer.W_out.size(1), w_bit, act_bit, layer.norm, route, linear_route,
+                  layer.aggr)
         with torch.no_grad():
             new.W_in.copy_(layer.W_in)
             new.W_out.copy_(layer.W_out)
@@ -547,7 +609,7 @@ class GCNConv_Affine(torch.nn.Module):
         rows = [qparams(Xn, b)]
         t = linear(Xn, W_in, b, self.w_bit, True, src, route="bytes", x_qparams=rows[0])
         rows.append(qparams(t, b))
-        h = aggregate(A, t, b, row, route="bytes", t_qparams=rows[1], **mask)
+        h = aggregate(A, t, b, row, route="bytes", t_qparams=rows[1], reduce=self.aggr, **mask)
         rows.append(qparams(h, b))
         rows.append(qparams(linear(h, W_out, b, self.w_bit, True, src, route="bytes", x_qparams=rows[2]), b))
         return torch.cat(rows)
@@ -564,6 +626,9 @@ class GCNConv_Affine(torch.nn.Module):
         b = self.act_bit
         if fuse and act_qparams is None:
             raise ValueError("fuse=True needs act_qparams: only the static chain has a fused launch")
+        if fuse and self.aggr != "sum":
+            raise ValueError(f'fuse=True cannot be combined with aggr="{self.aggr}": the fused kernel sums; use fuse=False')
+        red = {"reduce": self.aggr}
         if act_qparams is not None:
             self._check_static()
             _check_f32(act_qparams, "act_qparams")
@@ -574,9 +639,9 @@ class GCNConv_Affine(torch.nn.Module):
             if fuse:
                 t = aggregate_linear(A, t, q1, (b, q2), W_out, self.w_bit, True, row, src, out=(b, q3), **mask)
                 return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **mask))
-            h = aggregate(A, t, b, row, route="bytes", t_qparams=q1, out=(b, q2), **mask)
+            h = aggregate(A, t, b, row, route="bytes", t_qparams=q1, out=(b, q2), **red, **mask)
             t = linear(h, W_out, b, self.w_bit, True, src, route="bytes", x_qparams=q2, out=(b, q3))
-            return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **mask))
+            return A.to_old(aggregate(A, t, b, row, route="bytes", t_qparams=q3, **red, **mask))
         lin = {"route": self.linear_route}
-        h = aggregate(A, linear(Xn, W_in, b, self.w_bit, True, src, **lin), b, row, route=self.route, **mask)
-        return A.to_old(aggregate(A, linear(h, W_out, b, self.w_bit, True, src, **lin), b, row, route=self.route, **mask))
+        h = aggregate(A, linear(Xn, W_in, b, self.w_bit, True, src, **lin), b, row, route=self.route, **red, **mask)
+        return A.to_old(aggregate(A, linear(h, W_out, b, self.w_bit, True, src, **lin), b, row, route=self.route, **red, **mask))

@@ -1,0 +1,32 @@
+// qgtc_tiled_codes_max.hip — translation unit of libqgtc_hip.so (compiled in parallel with the others): the row-view entries of max and
+// min aggregation on byte codes (include/qgtc_codes_max.h), over the kernels of tiled_codes_max_kernels.hip.h.
+// Every entry checks, makes one launch on the caller's stream and returns: no atomics, no host read, no allocation.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "qgtc_codes_max.h"
+
+#include "common.hip.h"
+#include "bitmm_popcount.hip.h"   // requant, for tiled_t_kernels.hip.h (templates only: nothing is instantiated here)
+#include "tiled_codes_max_kernels.hip.h"
+
+int qgtc_tiledmax_u8(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld,
+                     size_t q_bytes, int N, int is_min, int empty_code, uint8_t *out, size_t ldo, size_t out_bytes, const uint32_t *row_mask,
+                     const uint32_t *nbr_mask, size_t mask_words, void *stream) {
+    const TiledRowIndex ix{row_ptr, kquad};
+    return tiled_max_raw_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, is_min, empty_code, out, ldo, out_bytes, row_mask, nbr_mask,
+                               mask_words, stream);
+}
+
+int qgtc_tiledmax_u8_affine(const int64_t *row_ptr, const int32_t *kquad, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q,
+                            size_t ld, size_t q_bytes, int N, const float *qparams, int is_min, float *out, size_t out_elems, uint8_t *outq,
+                            size_t ldo, size_t outq_bytes, const float *out_qp, int out_bits, const uint32_t *row_mask,
+                            const uint32_t *nbr_mask, size_t mask_words, void *stream) {
+    const TiledRowIndex ix{row_ptr, kquad};
+    return tiled_max_affine_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, qparams, is_min, out, out_elems, outq, ldo, outq_bytes, out_qp,
+                                  out_bits, row_mask, nbr_mask, mask_words, stream);
+}

@@ -126,10 +126,12 @@ when the bytes route's 90th percentile lies under the planes route's 10th.
 alternating rounds, ``pack_weight`` alone, the traffic floor, and the layer with its linear layers on either route beside ``conv.GCNConv``.
 `--leg chain` measures the static affine chain (include/qgtc_chain.h): the layer at 128 / 64 / 40 on calibrated rows beside
 the dynamic layer on the bytes routes and ``conv.GCNConv`` in the same alternating rounds, and each new launch beside its float twin.
+`--leg codesmax` measures max aggregation on byte codes (include/qgtc_codes_max.h): the extremum walk codes -> codes and
+codes -> float at N = 64 and 256 on adj and adj.T beside tiledMMFloat(reduce="max") and the sum walk, and the static layer with aggr="max".
 `--leg fused` measures the fused middle of that chain (include/qgtc_fused.h): the static layer with ``fuse=True`` beside
 ``fuse=False``, and ``affine.aggregate_linear`` beside the walk and the product it replaces, also once at K = N2 = 256 on arxiv.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain|fused]
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain|fused|codesmax]
 """
 from __future__ import annotations
 
@@ -1096,6 +1098,72 @@ def fused_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def codesmax_leg(torch, QGTC, graphs, reps):
+    """Max aggregation on byte codes (include/qgtc_codes_max.h) on the reordered graphs, 8-bit codes of Gaussian float32
+    [n, 64] and [n, 256], adj and adj.T, in the same alternating rounds: the extremum walk codes -> codes (tiledMaxCodes) and
+    codes -> float (aggregate(reduce="max") on uint8), QGTC.tiledMMFloat(reduce="max") on the dequantised matrix, and the sum walk
+    codes -> float (aggregate on uint8). Then the static layer at 128 / 64 / 40 dims with aggr="max", (w, a) = (4, 8), beside the
+    dynamic layer and conv.GCNConv(aggr="max"). ``beats_float``: the walk's 90th percentile lies under the float max launch's 10th."""
+    from qgtc_ppopp22_amd import affine, conv
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    dims = (128, 64, 40)
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        adj.T
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "tiles": adj.n_tiles, "dims": list(dims), "agg": []}
+        xr = np.random.default_rng(1)
+        for N in (64, 256):
+            X = torch.from_numpy(xr.normal(size=(n, N)).astype(np.float32)).cuda()
+            qp = affine.qparams(X, 8)
+            Q = affine.codes(X, 8, qp)
+            for view, a in (("adj", adj), ("adjT", adj.T)):
+                deq = (Q.to(torch.float32) - qp[0, 1]) * qp[0, 0]
+                got = affine.aggregate(a, Q, 8, route="bytes", t_qparams=qp, reduce="max")
+                assert torch.equal(got.view(torch.int32), QGTC.tiledMMFloat(a, deq, reduce="max").view(torch.int32))
+                cc, cf, fm, sm = timed_alternating(torch, [lambda: affine.tiledMaxCodes(a, Q, "max"),
+                                                           lambda: affine.aggregate(a, Q, 8, route="bytes", t_qparams=qp, reduce="max"),
+                                                           lambda: QGTC.tiledMMFloat(a, deq, reduce="max"),
+                                                           lambda: affine.aggregate(a, Q, 8, route="bytes", t_qparams=qp)], reps)
+                out = {"N": N, "view": view, "max_codes_to_codes_ms": cc, "max_codes_to_float_ms": cf, "tiledMMFloat_max_ms": fm,
+                       "sum_codes_to_float_ms": sm, "codes_over_float_max": round(cc[0] / fm[0], 3),
+                       "float_over_float_max": round(cf[0] / fm[0], 3), "max_over_sum": round(cf[0] / sm[0], 3),
+                       "beats_float": {"codes": _separated(cc, fm), "float": _separated(cf, fm)}}
+                rec["agg"].append(out)
+                print(f"{name:9s} N={N} {view:4s}: max codes->codes {cc[0]:.4f} [{cc[1]:.4f}, {cc[2]:.4f}] ms  max codes->float {cf[0]:.4f} [{cf[1]:.4f}, {cf[2]:.4f}] ms  "
+                      f"tiledMMFloat max {fm[0]:.4f} [{fm[1]:.4f}, {fm[2]:.4f}] ms  sum codes->float {sm[0]:.4f} [{sm[1]:.4f}, {sm[2]:.4f}] ms  "
+                      f"beats float: {out['beats_float']}", flush=True)
+            del X, Q, deq
+        torch.manual_seed(0)
+        ref = conv.GCNConv(*dims, aggr="max").cuda()
+        with torch.no_grad():
+            ref.W_in.mul_(dims[0] ** -0.5)
+            ref.W_out.mul_(dims[1] ** -0.5)
+        F = torch.from_numpy(xr.normal(size=(n, dims[0])).astype(np.float32)).cuda()
+        q = affine.GCNConv_Affine.from_float(ref, 4, 8, route="bytes", linear_route="bytes")
+        rows_qp = q.calibrate(adj, F)
+        assert torch.equal(q(adj, F, act_qparams=rows_qp).view(torch.int32), q(adj, F).view(torch.int32))
+
+        def float_forward():
+            with torch.no_grad():
+                return ref(adj, F)
+
+        ts, td, tf = timed_alternating(torch, [lambda: q(adj, F, act_qparams=rows_qp), lambda: q(adj, F), float_forward], reps)
+        rec["layer"] = {"static_ms": ts, "dynamic_ms": td, "float_ms": tf, "static_over_float": round(ts[0] / tf[0], 3),
+                        "beats_float": _separated(ts, tf)}
+        print(f"{name:9s} layer {dims} aggr=max w4 a8: static {ts[0]:.4f} [{ts[1]:.4f}, {ts[2]:.4f}] ms  dynamic {td[0]:.4f} [{td[1]:.4f}, {td[2]:.4f}] ms  "
+              f"conv.GCNConv {tf[0]:.4f} [{tf[1]:.4f}, {tf[2]:.4f}] ms  beats float {_separated(ts, tf)}", flush=True)
+        rows.append(rec)
+        del adj, dsrc, ddst, F
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1617,7 +1685,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax"))
     args = ap.parse_args()
 
     import torch
@@ -1625,9 +1693,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg, "fused": fused_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg, "fused": fused_leg, "codesmax": codesmax_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
