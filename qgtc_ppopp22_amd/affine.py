@@ -231,13 +231,8 @@ def linear(X: torch.Tensor, W: torch.Tensor, a_bits: int, w_bits: int, per_colum
             _c_call("affine.linear", X, L.qgtc_affine_linear_u8, X.data_ptr(), M, K, qa.data_ptr(), a_bits, *right, res.data_ptr(), res.numel())
             return res
         left = (None, X.data_ptr(), _codes_ld(X), _codes_bytes(X)) if coded else (X.data_ptr(), None, 0, 0)
-        if out is None:
-            res = torch.empty((M, N), dtype=torch.float32, device=X.device)
-            dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
-        else:
-            buf, res = _codes_out(M, N, X.device)
-            dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
-        _c_call("affine.linear", X, L.qgtc_affine_linear_chain, *left, M, K, qa.data_ptr(), a_bits, *right, *dest)
+        res, flt, mat, row = _dest(out, out_bits, out_qp, M, N, X.device)
+        _c_call("affine.linear", X, L.qgtc_affine_linear_chain, *left, M, K, qa.data_ptr(), a_bits, *right, *flt, *mat, *row)
         return res
     if K * (2 ** a_bits - 1) * (2 ** w_bits - 1) >= 2 ** 24:
         raise ValueError(f"K = {K} at a_bits = {a_bits}, w_bits = {w_bits}: the float32 accumulator of bitMM2Int is exact below 2^24 only")
@@ -258,6 +253,17 @@ def _check_out(out, like: torch.Tensor):
     bits = _check_bits(out[0], "out bits")
     _check_qparams(out[1], "out qparams", (1,), like)
     return bits, out[1]
+
+
+def _dest(out, out_bits: int, out_qp, rows: int, cols: int, device):
+    """(res, flt, mat, row): the result of a static call and its destination arguments in three named parts - ``flt`` (out, out_elems),
+    ``mat`` (outq, ldo, outq_bytes) and ``row`` (out_qp, out_bits); the C entries take ``*flt, *mat, *row``, the requant walks
+    ``*row, *mat``. float32 [rows, cols] without ``out=``, the code matrix of :func:`_codes_out` with."""
+    if out is None:
+        res = torch.empty((rows, cols), dtype=torch.float32, device=device)
+        return res, (res.data_ptr(), res.numel()), (None, 0, 0), (None, 0)
+    buf, res = _codes_out(rows, cols, device)
+    return res, (None, 0), (buf.data_ptr(), buf.size(1), buf.numel()), (out_qp.data_ptr(), out_bits)
 
 
 def _codes_out(M: int, N: int, device):
@@ -355,11 +361,15 @@ def _check_masks(adj_view, row_mask, nbr_mask) -> None:
             tiled._check_mask(adj_view, m, name)
 
 
-def _u8_call(what: str, stem: str, adj_view, Q: torch.Tensor, out: torch.Tensor, row_mask, nbr_mask, *extra) -> torch.Tensor:
-    fn = getattr(_c_abi(), stem + ("_t" if adj_view.transposed else "") + ("_affine" if extra else ""))
-    _c_call(what, Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), Q.size(1), *extra, out.data_ptr(),
-            out.numel(), _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
-    return out
+def _codes_args(Q: torch.Tensor) -> tuple:
+    """A code matrix as the C entries take it: (pointer, row stride, bytes from the first on, columns)."""
+    return Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), Q.size(1)
+
+
+def _u8_call(what: str, stem: str, suffix: str, adj_view, Q: torch.Tensor, row_mask, nbr_mask, *args) -> None:
+    """The walk entry ``stem`` [``_t`` on the transposed view] ``suffix`` on the view's index arrays, Q, ``args`` and the masks."""
+    fn = getattr(_c_abi(), stem + ("_t" if adj_view.transposed else "") + suffix)
+    _c_call(what, Q, fn, *tiled._view_args(adj_view), *_codes_args(Q), *args, _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
 
 
 def tiledMMCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, row_mask=None, nbr_mask=None) -> torch.Tensor:
@@ -370,7 +380,8 @@ def tiledMMCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, row_mask=Non
     Q = _check_codes(adj_view, Q)
     _check_masks(adj_view, row_mask, nbr_mask)
     out = torch.empty((adj_view.n, Q.size(1)), dtype=torch.int32, device=Q.device)
-    return _u8_call("affine.tiledMMCodes", "qgtc_tiledmm_u8", adj_view, Q, out, row_mask, nbr_mask)
+    _u8_call("affine.tiledMMCodes", "qgtc_tiledmm_u8", "", adj_view, Q, row_mask, nbr_mask, out.data_ptr(), out.numel())
+    return out
 
 
 def tiledMaxCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, reduce: str = "max", empty: int = 0, row_mask=None,
@@ -390,9 +401,8 @@ def tiledMaxCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, reduce: str
         raise ValueError(f"empty must lie in 0 .. 255, not {empty}")
     _check_masks(adj_view, row_mask, nbr_mask)
     buf, res = _codes_out(adj_view.n, Q.size(1), Q.device)
-    fn = getattr(_c_abi(), "qgtc_tiledmax_u8" + ("_t" if adj_view.transposed else ""))
-    _c_call("affine.tiledMaxCodes", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), Q.size(1),
-            int(reduce == "min"), empty, buf.data_ptr(), buf.size(1), buf.numel(), _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+    _u8_call("affine.tiledMaxCodes", "qgtc_tiledmax_u8", "", adj_view, Q, row_mask, nbr_mask, int(reduce == "min"), empty, buf.data_ptr(),
+             buf.size(1), buf.numel())
     return res
 
 
@@ -445,25 +455,15 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     if route == "bytes":
         _check_masks(adj_view, row_mask, nbr_mask)
         Q = T if coded else codes(T, bits, qt)
+        res, flt, mat, row = _dest(out, out_bits, out_qp, n, N, T.device)
         if reduce != "sum":
-            if out is None:
-                res = torch.empty((n, N), dtype=torch.float32, device=T.device)
-                dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
-            else:
-                buf, res = _codes_out(n, N, T.device)
-                dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
-            fn = getattr(_c_abi(), "qgtc_tiledmax_u8" + ("_t" if adj_view.transposed else "") + "_affine")
-            _c_call("affine.aggregate", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), N, qt.data_ptr(),
-                    int(reduce == "min"), *dest, _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
-            return res
-        if out is None:
-            res = torch.empty((n, N), dtype=torch.float32, device=T.device)
-            return _u8_call("affine.aggregate", "qgtc_tiledmm_u8", adj_view, Q, res, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale))
-        buf, res = _codes_out(n, N, T.device)
-        fn = getattr(_c_abi(), "qgtc_tiledmm_u8" + ("_t" if adj_view.transposed else "") + "_requant")
-        _c_call("affine.aggregate", Q, fn, *tiled._view_args(adj_view), Q.data_ptr(), _codes_ld(Q), _codes_bytes(Q), N, qt.data_ptr(),
-                _ptr(row_scale), out_qp.data_ptr(), out_bits, buf.data_ptr(), buf.size(1), buf.numel(), _ptr(row_mask), _ptr(nbr_mask),
-                adj_view.mask_words)
+            _u8_call("affine.aggregate", "qgtc_tiledmax_u8", "_affine", adj_view, Q, row_mask, nbr_mask, qt.data_ptr(), int(reduce == "min"),
+                     *flt, *mat, *row)
+        elif out is None:
+            _u8_call("affine.aggregate", "qgtc_tiledmm_u8", "_affine", adj_view, Q, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale), *flt)
+        else:
+            _u8_call("affine.aggregate", "qgtc_tiledmm_u8", "_requant", adj_view, Q, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale),
+                     *row, *mat)
         return res
     bit_T, _ = val2bit_affine(T, bits, qt, True, False)
     acc = QGTC.tiledMM2Int(adj_view, bit_T, N, bits, None, row_mask=row_mask, nbr_mask=nbr_mask)
@@ -507,16 +507,10 @@ def aggregate_linear(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, t_qparam
     _check_masks(adj_view, row_mask, nbr_mask)
     out_bits, out_qp = _check_out(out, T)
     codes_t, qb, col_sums = pack_weight(W, w_bits, per_column)
-    if out is None:
-        res = torch.empty((n, N2), dtype=torch.float32, device=T.device)
-        dest = (res.data_ptr(), res.numel(), None, 0, 0, None, 0)
-    else:
-        buf, res = _codes_out(n, N2, T.device)
-        dest = (None, 0, buf.data_ptr(), buf.size(1), buf.numel(), out_qp.data_ptr(), out_bits)
-    _c_call("affine.aggregate_linear", T, _c_abi().qgtc_tiledmm_u8_linear, *tiled._view_args(adj_view), T.data_ptr(), _codes_ld(T),
-            _codes_bytes(T), K, t_qparams.data_ptr(), _ptr(agg_row_scale), h_qp.data_ptr(), h_bits, codes_t.data_ptr(), codes_t.size(1),
-            codes_t.numel(), N2, qb.data_ptr(), qb.size(0), col_sums.data_ptr(), _ptr(lin_row_scale), _ptr(bias), int(bool(relu)), *dest,
-            _ptr(row_mask), _ptr(nbr_mask), adj_view.mask_words)
+    res, flt, mat, row = _dest(out, out_bits, out_qp, n, N2, T.device)
+    _u8_call("affine.aggregate_linear", "qgtc_tiledmm_u8", "_linear", adj_view, T, row_mask, nbr_mask, t_qparams.data_ptr(),
+             _ptr(agg_row_scale), h_qp.data_ptr(), h_bits, codes_t.data_ptr(), codes_t.size(1), codes_t.numel(), N2, qb.data_ptr(), qb.size(0),
+             col_sums.data_ptr(), _ptr(lin_row_scale), _ptr(bias), int(bool(relu)), *flt, *mat, *row)
     return res
 
 

@@ -65,21 +65,19 @@ int qgtc_affine_linear_chain(const float *x, const uint8_t *xq, size_t ldx, size
                              const uint8_t *codes_t, size_t ldk, size_t codes_bytes, int N, const float *qb, int groups_b,
                              const int32_t *col_sums, const float *row_scale, const float *bias, int relu, float *out, size_t out_elems,
                              uint8_t *outq, size_t ldo, size_t outq_bytes, const float *out_qp, int out_bits, void *stream) {
+    const CodesDest d{out, out_elems, outq, ldo, outq_bytes, out_qp, out_bits};
     if (!qa || !codes_t || !qb || !col_sums || M <= 0 || K <= 0 || N <= 0 || a_bits < 1 || a_bits > 8 || (groups_b != 1 && groups_b != N) ||
-        K > QGTC_LINEAR_K_MAX || (x != nullptr) == (xq != nullptr) || (out != nullptr) == (outq != nullptr) || (x && out) ||
-        (outq && (!out_qp || out_bits < 1 || out_bits > 8)))
+        K > QGTC_LINEAR_K_MAX || (x != nullptr) == (xq != nullptr) || (x && out) || codes_dest_invalid(d))
         return QGTC_EINVAL;
     const bool w_off = !aligned16(codes_t) || ldk < static_cast<size_t>(K) || (ldk & 15u) != 0;
     if (!aligned16(qa) || !aligned16(qb) || w_off || !codes_aligned4(x) || !codes_aligned4(col_sums) || !codes_aligned4(row_scale) ||
-        !codes_aligned4(bias) || !codes_aligned4(out) || (xq && codes_matrix_misaligned(xq, ldx, K)) ||
-        (outq && (codes_matrix_misaligned(outq, ldo, N) || !aligned16(out_qp))))
+        !codes_aligned4(bias) || (xq && codes_matrix_misaligned(xq, ldx, K)) || codes_dest_misaligned(d, N))
         return QGTC_EALIGN;
-    if (codes_bytes < static_cast<size_t>(N) * ldk || (xq && xq_bytes < codes_matrix_bytes(M, K, ldx)) ||
-        (out && out_elems < static_cast<size_t>(M) * static_cast<size_t>(N)) || (outq && outq_bytes < codes_matrix_bytes(M, N, ldo)))
+    if (codes_bytes < static_cast<size_t>(N) * ldk || (xq && xq_bytes < codes_matrix_bytes(M, K, ldx)) || codes_dest_short(d, M, N))
         return QGTC_ESIZE;
     const ChainLeft l{x, xq, ldx, M, K, reinterpret_cast<const float4 *>(qa), static_cast<float>((1 << a_bits) - 1)};
     const AlinRight w{codes_t, ldk, N, reinterpret_cast<const float4 *>(qb), groups_b == N && N > 1 ? 1 : 0, col_sums, row_scale, bias, relu ? 1 : 0};
-    const AlinOut o{out, outq, ldo, reinterpret_cast<const float4 *>(out_qp), outq ? static_cast<float>((1 << out_bits) - 1) : 0.0f};
+    const AlinOut o{out, outq, ldo, d.qp(), d.qmax()};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (x) return (K & 3) == 0 && aligned16(x) ? chain_pick<1, true>(l, w, o, st) : chain_pick<0, true>(l, w, o, st);
     const bool v16 = (ldx & 15u) == 0 && aligned16(xq);
@@ -92,8 +90,8 @@ int qgtc_tiledmm_u8_requant(const int64_t *row_ptr, const int32_t *kquad, const 
                             int out_bits, uint8_t *outq, size_t ldo, size_t outq_bytes, const uint32_t *row_mask, const uint32_t *nbr_mask,
                             size_t mask_words, void *stream) {
     const TiledRowIndex ix{row_ptr, kquad};
-    return tiled_u8_requant_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, qparams, row_scale, out_qp, out_bits, outq, ldo, outq_bytes,
-                                  row_mask, nbr_mask, mask_words, stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_u8_requant_entry(ix, in, qparams, row_scale, {nullptr, 0, outq, ldo, outq_bytes, out_qp, out_bits}, stream);
 }
 
 int qgtc_tiledmm_u8_t_requant(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
@@ -101,6 +99,6 @@ int qgtc_tiledmm_u8_t_requant(const int64_t *col_ptr, const int64_t *col_tile, c
                               const float *out_qp, int out_bits, uint8_t *outq, size_t ldo, size_t outq_bytes, const uint32_t *row_mask,
                               const uint32_t *nbr_mask, size_t mask_words, void *stream) {
     const TiledColIndex ix{col_ptr, col_tile, col_rb};
-    return tiled_u8_requant_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, qparams, row_scale, out_qp, out_bits, outq, ldo, outq_bytes,
-                                  row_mask, nbr_mask, mask_words, stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_u8_requant_entry(ix, in, qparams, row_scale, {nullptr, 0, outq, ldo, outq_bytes, out_qp, out_bits}, stream);
 }

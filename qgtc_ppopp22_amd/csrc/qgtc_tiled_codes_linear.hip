@@ -21,18 +21,10 @@
 
 namespace {
 
-struct TclAdj {
-    TiledRowIndex ix;
-    const uint32_t *tiles;
-    int64_t n_tiles;
-    int n;
-    TiledNodes nodes;
-};
-
 template <int LPR, int NT, bool OUTQ>
-int tcl_launch(const TclAdj &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
-    hipLaunchKernelGGL((k_tiled_mm_u8_lin<LPR, NT, OUTQ>), dim3((a.n + 31) / 32), dim3(256), tcl_lds(K, NT), st, a.ix.row_ptr, a.ix.kquad,
-                       a.tiles, static_cast<uint64_t>(a.n_tiles), a.n, K, h, w, o, a.nodes);
+int tcl_launch(const TiledRowIndex &ix, const TiledU8In &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
+    hipLaunchKernelGGL((k_tiled_mm_u8_lin<LPR, NT, OUTQ>), dim3((a.n + 31) / 32), dim3(256), tcl_lds(K, NT), st, ix.row_ptr, ix.kquad,
+                       a.tiles, static_cast<uint64_t>(a.n_tiles), a.n, K, h, w, o, TiledNodes{a.row_mask, a.nbr_mask});
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
@@ -40,25 +32,25 @@ int tcl_launch(const TclAdj &a, int K, const TclWalk &h, const AlinRight &w, con
 // NT: the accumulators a wave needs for all of W's column tiles (half of them, the waves split them odd and even), halved until s_h and
 // the 2 NT tiles of a pass fit the budget - then the tiles go in passes
 template <int LPR, bool OUTQ>
-int tcl_pick(const TclAdj &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
+int tcl_pick(const TiledRowIndex &ix, const TiledU8In &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
     const int per_wave = ((w.N + 15) / 16 + 1) / 2;
     int nt = per_wave <= 1 ? 1 : per_wave <= 2 ? 2 : per_wave <= 4 ? 4 : 8;
     while (nt > 1 && tcl_lds(K, nt) > static_cast<size_t>(TCL_LDS_BUDGET)) nt >>= 1;
     switch (nt) {
-        case 1: return tcl_launch<LPR, 1, OUTQ>(a, K, h, w, o, st);
-        case 2: return tcl_launch<LPR, 2, OUTQ>(a, K, h, w, o, st);
-        case 4: return tcl_launch<LPR, 4, OUTQ>(a, K, h, w, o, st);
+        case 1: return tcl_launch<LPR, 1, OUTQ>(ix, a, K, h, w, o, st);
+        case 2: return tcl_launch<LPR, 2, OUTQ>(ix, a, K, h, w, o, st);
+        case 4: return tcl_launch<LPR, 4, OUTQ>(ix, a, K, h, w, o, st);
         default:
-            if constexpr (LPR < 64) return tcl_launch<LPR, 8, OUTQ>(a, K, h, w, o, st);   // (K > 128: 8 never fits beside s_h)
+            if constexpr (LPR < 64) return tcl_launch<LPR, 8, OUTQ>(ix, a, K, h, w, o, st);   // (K > 128: 8 never fits beside s_h)
             return QGTC_EINVAL;
     }
 }
 
 template <bool OUTQ>
-int tcl_width(const TclAdj &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
-    if (K <= 64) return tcl_pick<16, OUTQ>(a, K, h, w, o, st);
-    if (K <= 128) return tcl_pick<32, OUTQ>(a, K, h, w, o, st);
-    return tcl_pick<64, OUTQ>(a, K, h, w, o, st);
+int tcl_width(const TiledRowIndex &ix, const TiledU8In &a, int K, const TclWalk &h, const AlinRight &w, const AlinOut &o, hipStream_t st) {
+    if (K <= 64) return tcl_pick<16, OUTQ>(ix, a, K, h, w, o, st);
+    if (K <= 128) return tcl_pick<32, OUTQ>(ix, a, K, h, w, o, st);
+    return tcl_pick<64, OUTQ>(ix, a, K, h, w, o, st);
 }
 
 }  // namespace
@@ -70,26 +62,22 @@ int qgtc_tiledmm_u8_linear(const int64_t *row_ptr, const int32_t *kquad, const u
                            uint8_t *outq, size_t ldo, size_t outq_bytes, const float *out_qp, int out_bits, const uint32_t *row_mask,
                            const uint32_t *nbr_mask, size_t mask_words, void *stream) {
     const TiledRowIndex ix{row_ptr, kquad};
-    if (!Q || !t_qparams || !h_qp || !codes_t || !qb || !col_sums || K < 1 || K > QGTC_FUSED_K_MAX || N2 < 1 || N2 > QGTC_FUSED_N_MAX ||
-        h_bits < 1 || h_bits > 8 || (groups_b != 1 && groups_b != N2) || (out != nullptr) == (outq != nullptr) || (outq && (!out_qp || out_bits < 1 || out_bits > 8)) ||
-        tiled_adj_malformed(ix.ok(), tiles, n_tiles, n))
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, K, row_mask, nbr_mask, mask_words};
+    const CodesDest d{out, out_elems, outq, ldo, outq_bytes, out_qp, out_bits};
+    if (tiled_u8_invalid(ix, in) || codes_dest_invalid(d) || !t_qparams || !h_qp || !codes_t || !qb || !col_sums || K > QGTC_FUSED_K_MAX ||
+        N2 < 1 || N2 > QGTC_FUSED_N_MAX || h_bits < 1 || h_bits > 8 || (groups_b != 1 && groups_b != N2))
         return QGTC_EINVAL;
     const bool w_off = !aligned16(codes_t) || ldk < static_cast<size_t>(K) || (ldk & 15u) != 0;
-    if (tiled_adj_misaligned(tiles) || codes_matrix_misaligned(Q, ld, K) || !aligned16(t_qparams) || !aligned16(h_qp) ||
+    if (tiled_u8_misaligned(in) || codes_dest_misaligned(d, N2) || !aligned16(t_qparams) || !aligned16(h_qp) ||
         !codes_aligned4(agg_row_scale) || w_off || !aligned16(qb) || !codes_aligned4(col_sums) || !codes_aligned4(lin_row_scale) ||
-        !codes_aligned4(bias) || !codes_aligned4(out) || (outq && (codes_matrix_misaligned(outq, ldo, N2) || !aligned16(out_qp))) ||
-        !aligned16(row_mask) || !aligned16(nbr_mask))
+        !codes_aligned4(bias))
         return QGTC_EALIGN;
-    if (q_bytes < codes_matrix_bytes(n, K, ld) || codes_bytes < static_cast<size_t>(N2) * ldk ||
-        (out && out_elems < static_cast<size_t>(n) * static_cast<size_t>(N2)) || (outq && outq_bytes < codes_matrix_bytes(n, N2, ldo)))
-        return QGTC_ESIZE;
-    if ((row_mask || nbr_mask) && mask_words < static_cast<size_t>(step128(n)) * 4) return QGTC_ESIZE;
-    const TclAdj a{ix, tiles, n_tiles, n, TiledNodes{row_mask, nbr_mask}};
+    if (tiled_u8_short(in) || codes_dest_short(d, n, N2) || codes_bytes < static_cast<size_t>(N2) * ldk) return QGTC_ESIZE;
     const TclWalk h{Q, ld, reinterpret_cast<const float4 *>(t_qparams), agg_row_scale, reinterpret_cast<const float4 *>(h_qp),
                     static_cast<float>((1 << h_bits) - 1)};
     const AlinRight w{codes_t, ldk, N2, reinterpret_cast<const float4 *>(qb), groups_b == N2 && N2 > 1 ? 1 : 0, col_sums, lin_row_scale, bias,
                       relu ? 1 : 0};
-    const AlinOut o{out, outq, ldo, reinterpret_cast<const float4 *>(out_qp), outq ? static_cast<float>((1 << out_bits) - 1) : 0.0f};
+    const AlinOut o{out, outq, ldo, d.qp(), d.qmax()};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return outq ? tcl_width<true>(a, K, h, w, o, st) : tcl_width<false>(a, K, h, w, o, st);
+    return outq ? tcl_width<true>(ix, in, K, h, w, o, st) : tcl_width<false>(ix, in, K, h, w, o, st);
 }

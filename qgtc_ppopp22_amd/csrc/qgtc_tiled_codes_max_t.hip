@@ -18,8 +18,8 @@ int qgtc_tiledmax_u8_t(const int64_t *col_ptr, const int64_t *col_tile, const in
                        const uint8_t *Q, size_t ld, size_t q_bytes, int N, int is_min, int empty_code, uint8_t *out, size_t ldo,
                        size_t out_bytes, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
     const TiledColIndex ix{col_ptr, col_tile, col_rb};
-    return tiled_max_raw_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, is_min, empty_code, out, ldo, out_bytes, row_mask, nbr_mask,
-                               mask_words, stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_max_raw_entry(ix, in, is_min, empty_code, out, ldo, out_bytes, stream);
 }
 
 int qgtc_tiledmax_u8_t_affine(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
@@ -27,6 +27,6 @@ int qgtc_tiledmax_u8_t_affine(const int64_t *col_ptr, const int64_t *col_tile, c
                               size_t out_elems, uint8_t *outq, size_t ldo, size_t outq_bytes, const float *out_qp, int out_bits,
                               const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
     const TiledColIndex ix{col_ptr, col_tile, col_rb};
-    return tiled_max_affine_entry(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, qparams, is_min, out, out_elems, outq, ldo, outq_bytes, out_qp,
-                                  out_bits, row_mask, nbr_mask, mask_words, stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_max_affine_entry(ix, in, qparams, is_min, {out, out_elems, outq, ldo, outq_bytes, out_qp, out_bits}, stream);
 }

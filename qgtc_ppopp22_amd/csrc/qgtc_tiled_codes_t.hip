@@ -19,8 +19,8 @@ int qgtc_tiledmm_u8_t(const int64_t *col_ptr, const int64_t *col_tile, const int
                       const uint8_t *Q, size_t ld, size_t q_bytes, int N, int32_t *out, size_t out_elems, const uint32_t *row_mask,
                       const uint32_t *nbr_mask, size_t mask_words, void *stream) {
     const TiledColIndex ix{col_ptr, col_tile, col_rb};
-    return tiled_u8_entry<false>(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, nullptr, nullptr, out, out_elems, row_mask, nbr_mask, mask_words,
-                                 stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_u8_entry<false>(ix, in, nullptr, nullptr, out, out_elems, stream);
 }
 
 int qgtc_tiledmm_u8_t_affine(const int64_t *col_ptr, const int64_t *col_tile, const int32_t *col_rb, const uint32_t *tiles, int64_t n_tiles,
@@ -28,6 +28,6 @@ int qgtc_tiledmm_u8_t_affine(const int64_t *col_ptr, const int64_t *col_tile, co
                              float *out, size_t out_elems, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words,
                              void *stream) {
     const TiledColIndex ix{col_ptr, col_tile, col_rb};
-    return tiled_u8_entry<true>(ix, tiles, n_tiles, n, Q, ld, q_bytes, N, qparams, row_scale, out, out_elems, row_mask, nbr_mask, mask_words,
-                                stream);
+    const TiledU8In in{tiles, n_tiles, n, Q, ld, q_bytes, N, row_mask, nbr_mask, mask_words};
+    return tiled_u8_entry<true>(ix, in, qparams, row_scale, out, out_elems, stream);
 }

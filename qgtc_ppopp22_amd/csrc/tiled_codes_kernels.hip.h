@@ -2,29 +2,15 @@
 // bitmm_popcount.hip.h): the byte-code route of affine quantisation (include/qgtc_codes.h) - the quantiser to
 // one byte a code, and the neighbour sum of a uint8 code matrix on the tile-compressed adjacency, on both views, under node masks, with
 // the dequantising epilogue of qgtc_affine_dequant in the same launch.
-//
-// The walks are those of k_tiled_mm_f32 (tiled_float_kernels.hip.h) and k_tiled_mm_f32_t (tiled_float_t_kernels.hip.h): a tile is a
-// compressed neighbour list, its set bits are decoded MSB first into an LDS queue of TILED_U8_CAP ids, and the addressed rows of the
-// operand are loaded TILED_U8_AHEAD at a time. What differs:
-//   - a lane owns FOUR ADJACENT columns and loads one dword per neighbour row (hence ld % 4 == 0 in the contract); a lane whose columns
-//     all lie past N loads nothing, a dword that straddles N is loaded and its surplus sums are not stored;
-//   - the sums are int32, one register per column, and each byte is added to its own: the compiler selects the bytes in the add itself
-//     (v_add_u32_sdwa with a BYTE_k source on gfx950; DESIGN.md section 6.15p has the ISA that was read), so a dword costs four VALU
-//     instructions and nothing has to be widened at a flush;
-//   - integer sums are exact in any order: there is no add-order contract and the adds of a column are not one dependent chain per
-//     neighbour beyond the accumulator itself; only the loads need run ahead;
-//   - the decoder counts the ids it queues per output row: cnt[o], the degree under the masks, which the affine epilogue needs.
-// The node masks are always compiled in (either pointer may be null: all nodes), through TiledNodesWalk<true> / tiled_nodes_quad.
+// The family's shared tile walks are tiled_codes_walk.hip.h's; the walk is described there. k_tiled_mm_u8 and k_tiled_mm_u8_t below
+// keep their own copy of it, with their own adder and decoder: on the shared walk the 16-lane float-output sum ran 2 to 4 % longer
+// (profiles/codes_walk/README.md). Here besides: the quantiser, the sum's three output forms, and what the
+// whole byte-code family shares on the host - the width rule, the one launcher per view and the argument predicates.
 #pragma once
 
-#include "tiled_args.hip.h"
-#include "tiled_nodes.hip.h"
-#include "tiled_t_kernels.hip.h"   // the in-register bit transpose of the column view
+#include "tiled_codes_walk.hip.h"
 
 namespace {
-
-constexpr int TILED_U8_CAP = 32;    // decoded neighbour ids a row group queues in LDS before it adds their rows
-constexpr int TILED_U8_AHEAD = 4;   // rows of Q whose loads are in flight before the first of them is added
 
 // ---- the quantiser to bytes -----------------------------------------------------------------------------------------------------------
 // aquant of affine_kernels.hip.h, to the letter: one multiply, one v_rndne, one add, a clamp, and the select that sends a NaN to the zero
@@ -81,33 +67,7 @@ __global__ __launch_bounds__(256) void k_affine_codes(const float *__restrict__ 
     }
 }
 
-// ---- the adder and the decoder both views share ---------------------------------------------------------------------------------------
-// s[k] += Q[list[j]][cb + k], k < 4, for j = 0 .. cnt - 1. The loads of TILED_U8_AHEAD neighbours are issued together (past the end of the
-// list the last entry is loaded again and not added). `mine`: the lane's first column lies inside N, otherwise it loads nothing. `list`
-// lives in LDS and every lane of the row group wrote every entry itself, so no lane reads a word another lane produced.
-__device__ __forceinline__ void tiled_u8_add_rows(int (&s)[4], const int *list, int cnt, const uint8_t *__restrict__ Q, size_t ld, int cb,
-                                                  bool mine) {
-#pragma nounroll
-    for (int j = 0; j < cnt; j += TILED_U8_AHEAD) {
-        uint32_t w[TILED_U8_AHEAD];
-#pragma unroll
-        for (int u = 0; u < TILED_U8_AHEAD; ++u) {
-            const int v = list[j + u < cnt ? j + u : cnt - 1];
-            w[u] = mine ? *reinterpret_cast<const uint32_t *>(Q + static_cast<size_t>(v) * ld + cb) : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < TILED_U8_AHEAD; ++u)
-            if (j + u < cnt) {
-                s[0] += static_cast<int>(w[u] & 0xffu);
-                s[1] += static_cast<int>((w[u] >> 8) & 0xffu);
-                s[2] += static_cast<int>((w[u] >> 16) & 0xffu);
-                s[3] += static_cast<int>(w[u] >> 24);
-            }
-    }
-}
-
-// the set bits of `m`, MSB first, as neighbour ids base + (leading zeros), queued in `list` and counted in `terms`; ids from n up are
-// dropped (the format keeps such cells zero; a foreign tile must not make the kernel read past Q). A full queue is added at once.
+// tiled_u8_decode of tiled_codes_walk.hip.h on the two sum kernels' own state: ids counted in `terms`, a full queue added at once
 __device__ __forceinline__ void tiled_u8_decode(uint32_t m, int base, int n, int (&s)[4], int *list, int &cnt, int &terms,
                                                 const uint8_t *__restrict__ Q, size_t ld, int cb, bool mine) {
     while (m) {
@@ -186,19 +146,9 @@ __device__ __forceinline__ void tiled_u8_store(const int (&s)[4], int terms, int
     }
 }
 
-template <int LPR>
-__device__ __forceinline__ uint32_t tiled_u8_bcast(uint32_t v, int src) {
-    if constexpr (LPR == 64) return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), src));
-    else return static_cast<uint32_t>(__shfl(static_cast<int>(v), src, LPR));
-}
-
 // ---- the row view: out = A_tiled . Q --------------------------------------------------------------------------------------------------
-// One workgroup (256 threads) per 32-row block and chunk of 4 LPR output columns. A ROW GROUP of LPR lanes (16, 32 or a whole wave) owns
-// RPG = 32 / (256 / LPR) output rows of the block, lane l on the columns chunk + 4 l .. 4 l + 3. The group walks the block's tiles once:
-// lanes 0 .. RPG - 1 load the 16-byte tile rows of the group's rows (the next tile's while this one is decoded), every row's four words
-// are broadcast, ANDed with the neighbour bitmap's words of the tile's k-quad (loaded one tile ahead) and decoded into that row's own
-// queue. A workgroup whose word of the row bitmap is zero takes an empty tile range without reading row_ptr; a masked-out row of a live
-// block does not load its tile rows. Every row of the block is stored once, through the epilogue.
+// The row walk of tiled_codes_walk.hip.h (tiled_u8_row_walk describes it), written out here for the sum, per chunk of 4 LPR output
+// columns (grid.y). Every row of the block is stored once, through the epilogue.
 template <int LPR, int AFFINE>
 __global__ __launch_bounds__(256) void k_tiled_mm_u8(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ kquad,
                                                      const uint32_t *__restrict__ tiles, uint64_t n_tiles, int n,
@@ -265,14 +215,9 @@ __global__ __launch_bounds__(256) void k_tiled_mm_u8(const int64_t *__restrict__
 }
 
 // ---- the column view: out = A_tiled^T . Q ---------------------------------------------------------------------------------------------
-// One workgroup (256 threads) per k-quad q (output rows 128 q .. 128 q + 127) and chunk of W = 4 LPR output columns. The k-quad's column
-// list is walked TS = 8 tiles a round, as in k_tiled_mm_f32_t: each half-wave loads one tile (its list entry two rounds, its words one
-// round ahead), ANDs both bitmaps into the words and runs the 32 x 32 bit transpose; the column masks go to LDS as [tile column][staged
-// tile]. A row group of LPR lanes owns the output rows j = g, g + G, ..; a row with a mask in this round takes its four sums and its term
-// counter from LDS, decodes the staged tiles, adds the addressed rows of Q and puts sums and counter back: the running sums of the
-// 128 x W outputs (int32, one int4 a lane) and the 128 counters beside them live in LDS between rounds; each word is read and written
-// by the lanes of one row group only, and every lane of the group writes the counter (the same value to the same address). A k-quad whose
-// four row-bitmap words are zero walks nothing and stores its rows through the epilogue with acc = cnt = 0.
+// The column walk of tiled_codes_walk.hip.h (tiled_u8_col_walk describes it), written out here for the sum: the running sums of the
+// 128 x 4 LPR outputs (int32, one int4 a lane) and the 128 term counters beside them live in LDS between rounds. A k-quad whose four
+// row-bitmap words are zero walks nothing and stores its rows through the epilogue with acc = cnt = 0.
 template <int LPR, int AFFINE>
 __global__ __launch_bounds__(256) void k_tiled_mm_u8_t(const int64_t *__restrict__ col_ptr, const int64_t *__restrict__ col_tile,
                                                        const int32_t *__restrict__ col_rb, const uint32_t *__restrict__ tiles,
@@ -376,9 +321,8 @@ __global__ __launch_bounds__(256) void k_tiled_mm_u8_t(const int64_t *__restrict
     }
 }
 
-// ---- the host side: lanes per output row by N, on both views -------------------------------------------------------------------------
-// N up to 64: 16 lanes; up to 128: 32 lanes; beyond: a whole wave and chunks of 256 columns (grid.y). The column view keeps 128 x 4 LPR
-// int32 sums in LDS, 128 KiB at 64 lanes, which leaves one workgroup a CU: it stops at 32 lanes (64 KiB) and takes chunks of 128.
+// ---- the host side of the family: lanes per output row by N, one launcher per view -------------------------------------------------------
+// N up to 64: 16 lanes; up to 128: 32 lanes; beyond: a whole wave and chunks of 256 columns (grid.y), if the view has that class
 template <class F>
 void tiled_u8_width_switch(int N, int widest, F &&launch) {
     const int lanes = N <= 64 ? 16 : (N <= 128 || widest == 32 ? 32 : 64);
@@ -389,34 +333,58 @@ void tiled_u8_width_switch(int N, int widest, F &&launch) {
     }
 }
 
+// what every entry of the family is given: the adjacency's tiles, the code matrix Q [n, N] and the node masks
+struct TiledU8In {
+    const uint32_t *tiles;
+    int64_t n_tiles;
+    int n;
+    const uint8_t *Q;
+    size_t ld, q_bytes;
+    int N;
+    const uint32_t *row_mask, *nbr_mask;
+    size_t mask_words;
+};
+
+// A kernel family as the launchers take it: its kernels and the column view's widest class (the sum's LDS is 128 KiB at 64 lanes: 32).
 template <int AFFINE>
-int tiled_u8_launch(const TiledRowIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, int N,
-                    const float *qparams, const float *row_scale, typename TiledU8Out<AFFINE>::type out, const TiledNodes &nodes, hipStream_t st) {
-    tiled_u8_width_switch(N, 64, [&](auto lpr) {
+struct TiledU8SumKernels {
+    static constexpr int COL_WIDEST = 32;
+    template <int LPR> static auto row() { return k_tiled_mm_u8<LPR, AFFINE>; }
+    template <int LPR> static auto col() { return k_tiled_mm_u8_t<LPR, AFFINE>; }
+};
+
+// `tail`: the family's kernel arguments between N and the node masks, in the kernels' order and types - for TiledU8SumKernels
+// (const float4 *qp, const float *row_scale, TiledU8Out<AFFINE>::type out). A unit instantiates the kernels it passes and no others.
+template <class F, class... Tail>
+int tiled_u8_launch(const TiledRowIndex &ix, const TiledU8In &a, void *stream, Tail... tail) {
+    const TiledNodes nodes{a.row_mask, a.nbr_mask};
+    tiled_u8_width_switch(a.N, 64, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value;
-        hipLaunchKernelGGL((k_tiled_mm_u8<LPR, AFFINE>), dim3((n + 31) / 32, (N + LPR * 4 - 1) / (LPR * 4)), dim3(256), 0, st, ix.row_ptr,
-                           ix.kquad, tiles, static_cast<uint64_t>(n_tiles), n, Q, ld, N, reinterpret_cast<const float4 *>(qparams), row_scale,
-                           out, nodes);
+        hipLaunchKernelGGL((F::template row<LPR>()), dim3((a.n + 31) / 32, (a.N + LPR * 4 - 1) / (LPR * 4)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), ix.row_ptr, ix.kquad, a.tiles, static_cast<uint64_t>(a.n_tiles), a.n, a.Q, a.ld,
+                           a.N, tail..., nodes);
     });
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
 
-template <int AFFINE>
-int tiled_u8_launch(const TiledColIndex &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, int N,
-                    const float *qparams, const float *row_scale, typename TiledU8Out<AFFINE>::type out, const TiledNodes &nodes, hipStream_t st) {
-    tiled_u8_width_switch(N, 32, [&](auto lpr) {
+template <class F, class... Tail>
+int tiled_u8_launch(const TiledColIndex &ix, const TiledU8In &a, void *stream, Tail... tail) {
+    const TiledNodes nodes{a.row_mask, a.nbr_mask};
+    tiled_u8_width_switch(a.N, F::COL_WIDEST, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value;
-        if constexpr (LPR <= 32)
-            hipLaunchKernelGGL((k_tiled_mm_u8_t<LPR, AFFINE>), dim3(step128(n), (N + LPR * 4 - 1) / (LPR * 4)), dim3(256), 0, st, ix.col_ptr,
-                               ix.col_tile, ix.col_rb, tiles, static_cast<uint64_t>(n_tiles), n, Q, ld, N,
-                               reinterpret_cast<const float4 *>(qparams), row_scale, out, nodes);
+        if constexpr (LPR <= F::COL_WIDEST)
+            hipLaunchKernelGGL((F::template col<LPR>()), dim3(step128(a.n), (a.N + LPR * 4 - 1) / (LPR * 4)), dim3(256), 0,
+                               static_cast<hipStream_t>(stream), ix.col_ptr, ix.col_tile, ix.col_rb, a.tiles, static_cast<uint64_t>(a.n_tiles),
+                               a.n, a.Q, a.ld, a.N, tail..., nodes);
     });
     HIP_TRY(hipGetLastError());
     return QGTC_OK;
 }
 
 // ---- the argument checks, made before any device work: invalid, then misaligned, then short ------------------------------------------
+// One predicate per error class and part of the argument list, so that an entry ORs its own clauses with them class by class and still
+// reports every invalid argument before any misaligned one and every misaligned one before any short one.
 inline bool codes_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline size_t codes_pad4(int W) { return (static_cast<size_t>(W) + 3u) & ~static_cast<size_t>(3); }
 // the three rules of a code matrix [H, W]
@@ -425,36 +393,58 @@ inline bool codes_matrix_misaligned(const void *p, size_t ld, int W) {
 }
 inline size_t codes_matrix_bytes(int H, int W, size_t ld) { return static_cast<size_t>(H - 1) * ld + codes_pad4(W); }
 
-// either view; AFFINE wants qparams (16-byte aligned) and takes an optional row_scale
-template <int AFFINE, class Index>
-int tiled_u8_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, size_t q_bytes, int N,
-                   const float *qparams, const float *row_scale, void *out, size_t out_elems, const uint32_t *row_mask,
-                   const uint32_t *nbr_mask, size_t mask_words, void *stream) {
-    if (!Q || !out || N < 1 || (AFFINE && !qparams) || tiled_adj_malformed(ix.ok(), tiles, n_tiles, n)) return QGTC_EINVAL;
-    if (tiled_adj_misaligned(tiles) || codes_matrix_misaligned(Q, ld, N) || !codes_aligned4(out) || !aligned16(qparams) ||
-        !codes_aligned4(row_scale) || !aligned16(row_mask) || !aligned16(nbr_mask))
-        return QGTC_EALIGN;
-    if (q_bytes < codes_matrix_bytes(n, N, ld) || out_elems < static_cast<size_t>(n) * static_cast<size_t>(N)) return QGTC_ESIZE;
-    if ((row_mask || nbr_mask) && mask_words < static_cast<size_t>(step128(n)) * 4) return QGTC_ESIZE;
-    return tiled_u8_launch<AFFINE>(ix, tiles, n_tiles, n, Q, ld, N, qparams, row_scale, out, TiledNodes{row_mask, nbr_mask},
-                                   static_cast<hipStream_t>(stream));
+// what every entry shares: the graph, the code matrix, the masks
+template <class Index>
+bool tiled_u8_invalid(const Index &ix, const TiledU8In &a) {
+    return !a.Q || a.N < 1 || tiled_adj_malformed(ix.ok(), a.tiles, a.n_tiles, a.n);
+}
+inline bool tiled_u8_misaligned(const TiledU8In &a) {
+    return tiled_adj_misaligned(a.tiles) || codes_matrix_misaligned(a.Q, a.ld, a.N) || !aligned16(a.row_mask) || !aligned16(a.nbr_mask);
+}
+inline bool tiled_u8_short(const TiledU8In &a) {
+    return a.q_bytes < codes_matrix_bytes(a.n, a.N, a.ld) || ((a.row_mask || a.nbr_mask) && a.mask_words < static_cast<size_t>(step128(a.n)) * 4);
 }
 
-// either view with the code output of include/qgtc_chain.h: outq a code matrix [n, N] under (out_qp, out_bits)
+// the destination of the static chain's entries: float32 [H, W] at `out` or codes [H, W] at `outq` under the row (out_qp, out_bits), not both
+struct CodesDest {
+    float *out;
+    size_t out_elems;
+    uint8_t *outq;
+    size_t ldo, outq_bytes;
+    const float *out_qp;
+    int out_bits;
+    const float4 *qp() const { return reinterpret_cast<const float4 *>(out_qp); }
+    float qmax() const { return outq ? static_cast<float>((1 << out_bits) - 1) : 0.0f; }
+};
+inline bool codes_dest_invalid(const CodesDest &d) {
+    return (d.out != nullptr) == (d.outq != nullptr) || (d.outq && (!d.out_qp || d.out_bits < 1 || d.out_bits > 8));
+}
+inline bool codes_dest_misaligned(const CodesDest &d, int W) {
+    return !codes_aligned4(d.out) || (d.outq && (codes_matrix_misaligned(d.outq, d.ldo, W) || !aligned16(d.out_qp)));
+}
+inline bool codes_dest_short(const CodesDest &d, int H, int W) {
+    return (d.out && d.out_elems < static_cast<size_t>(H) * static_cast<size_t>(W)) || (d.outq && d.outq_bytes < codes_matrix_bytes(H, W, d.ldo));
+}
+
+// either view; AFFINE wants qparams (16-byte aligned) and takes an optional row_scale
+template <int AFFINE, class Index>
+int tiled_u8_entry(const Index &ix, const TiledU8In &a, const float *qparams, const float *row_scale, void *out, size_t out_elems,
+                   void *stream) {
+    if (tiled_u8_invalid(ix, a) || !out || (AFFINE && !qparams)) return QGTC_EINVAL;
+    if (tiled_u8_misaligned(a) || !codes_aligned4(out) || !aligned16(qparams) || !codes_aligned4(row_scale)) return QGTC_EALIGN;
+    if (tiled_u8_short(a) || out_elems < static_cast<size_t>(a.n) * static_cast<size_t>(a.N)) return QGTC_ESIZE;
+    return tiled_u8_launch<TiledU8SumKernels<AFFINE>>(ix, a, stream, reinterpret_cast<const float4 *>(qparams), row_scale, out);
+}
+
+// either view with the code output of include/qgtc_chain.h: d.outq a code matrix [n, N] under (d.out_qp, d.out_bits), d.out null
 template <class Index>
-int tiled_u8_requant_entry(const Index &ix, const uint32_t *tiles, int64_t n_tiles, int n, const uint8_t *Q, size_t ld, size_t q_bytes, int N,
-                           const float *qparams, const float *row_scale, const float *out_qp, int out_bits, uint8_t *outq, size_t ldo,
-                           size_t outq_bytes, const uint32_t *row_mask, const uint32_t *nbr_mask, size_t mask_words, void *stream) {
-    if (!Q || !outq || !qparams || !out_qp || N < 1 || out_bits < 1 || out_bits > 8 || tiled_adj_malformed(ix.ok(), tiles, n_tiles, n))
-        return QGTC_EINVAL;
-    if (tiled_adj_misaligned(tiles) || codes_matrix_misaligned(Q, ld, N) || codes_matrix_misaligned(outq, ldo, N) || !aligned16(qparams) ||
-        !aligned16(out_qp) || !codes_aligned4(row_scale) || !aligned16(row_mask) || !aligned16(nbr_mask))
-        return QGTC_EALIGN;
-    if (q_bytes < codes_matrix_bytes(n, N, ld) || outq_bytes < codes_matrix_bytes(n, N, ldo)) return QGTC_ESIZE;
-    if ((row_mask || nbr_mask) && mask_words < static_cast<size_t>(step128(n)) * 4) return QGTC_ESIZE;
-    const TiledU8Codes out{outq, ldo, reinterpret_cast<const float4 *>(out_qp), static_cast<float>((1 << out_bits) - 1)};
-    return tiled_u8_launch<TILED_U8_CODES>(ix, tiles, n_tiles, n, Q, ld, N, qparams, row_scale, out, TiledNodes{row_mask, nbr_mask},
-                                           static_cast<hipStream_t>(stream));
+int tiled_u8_requant_entry(const Index &ix, const TiledU8In &a, const float *qparams, const float *row_scale, const CodesDest &d,
+                           void *stream) {
+    if (tiled_u8_invalid(ix, a) || codes_dest_invalid(d) || !qparams) return QGTC_EINVAL;
+    if (tiled_u8_misaligned(a) || codes_dest_misaligned(d, a.N) || !aligned16(qparams) || !codes_aligned4(row_scale)) return QGTC_EALIGN;
+    if (tiled_u8_short(a) || codes_dest_short(d, a.n, a.N)) return QGTC_ESIZE;
+    return tiled_u8_launch<TiledU8SumKernels<TILED_U8_CODES>>(ix, a, stream, reinterpret_cast<const float4 *>(qparams), row_scale,
+                                                              TiledU8Codes{d.outq, d.ldo, d.qp(), d.qmax()});
 }
 
 }  // namespace

@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 8
     constexpr int G = 256 / LPR, RPG = 32 / G;   // row groups per workgroup, rows per group
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];   // s_h [32][stride], then s_w [32 NT][stride]
     __shared__ int lists[G][RPG][TILED_U8_CAP];
-    TiledNodesWalk<true> nd;
     const int rb = blockIdx.x, tid = threadIdx.x;
     const int stride = tcl_pad64(K) + ALIN_PAD;
     uint8_t *s_h = s_dyn, *s_w = s_dyn + 32 * stride;
@@ -58,76 +57,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 8
     // W's first pass, ahead of the walk: nothing of the walk touches s_w, and the hand-over's barrier publishes it
     alin_stage<false>(s_w, stride, w.wt, w.ldk, w.N, 0, min(2 * NT, tiles_n), 0, stride - ALIN_PAD, tid);
 
-    // ---- the walk of k_tiled_mm_u8<LPR, TILED_U8_CODES>, chunk 0 --------------------------------------------------------------------
+    // ---- the walk of k_tiled_mm_u8<LPR, TILED_U8_CODES>, chunk 0, and the hand-over: the dword mode 2 would store, as signed bytes,
+    // into s_h ---------------------------------------------------------------------------------------------------------------------------
     const int g = LPR == 64 ? __builtin_amdgcn_readfirstlane(tid / LPR) : tid / LPR;
     const int l = tid % LPR, cb = l * 4;
     const bool mine_cols = cb < K;
-    const int nq = step128(n);
-    nd.start(nodes, rb, g * RPG + l);
-
-    uint64_t t0 = 0, t1 = 0;   // an adjacency without tiles may come without row_ptr
-    if (n_tiles != 0 && nd.block_live()) {
-        t0 = static_cast<uint64_t>(row_ptr[rb]);
-        t1 = static_cast<uint64_t>(row_ptr[rb + 1]);
-        t1 = t1 < n_tiles ? t1 : n_tiles;
-    }
-    int s[RPG][4], cnt[RPG], terms[RPG];
-#pragma unroll
-    for (int ri = 0; ri < RPG; ++ri) {
-        cnt[ri] = terms[ri] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[ri][k] = 0;
-    }
-    const uint32_t *mine = tiles + (g * RPG + (l < RPG ? l : 0)) * 4;   // lane l < RPG: row g * RPG + l of every tile
-    uint4 a = make_uint4(0, 0, 0, 0);
-    int q = -1;
-    if (t0 < t1) {
-        q = kquad[t0];
-        if (l < RPG && nd.row_live()) a = *reinterpret_cast<const uint4 *>(mine + t0 * 128);
-        nd.load(nd.nb, q, nq);
-    }
-    for (uint64_t t = t0; t < t1; ++t) {
-        uint4 an = make_uint4(0, 0, 0, 0);
-        int qn = -1;
-        if (t + 1 < t1) {
-            qn = kquad[t + 1];
-            if (l < RPG && nd.row_live()) an = *reinterpret_cast<const uint4 *>(mine + (t + 1) * 128);
-            nd.load(nd.nbn, qn, nq);
-        }
-        if (static_cast<unsigned>(q) < static_cast<unsigned>(nq) && nd.tile_live()) {
-            const uint32_t wd[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int ri = 0; ri < RPG; ++ri)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    tiled_u8_decode(tiled_u8_bcast<LPR>(wd[k], ri) & nd.word(k), q * 128 + k * 32, n, s[ri], lists[g][ri], cnt[ri], terms[ri], Q,
-                                    ld, cb, mine_cols);
-        }
-        a = an;
-        q = qn;
-        nd.nb = nd.nbn;
-    }
-
-    // ---- the hand-over: the dword mode 2 would store, as signed bytes, into s_h -----------------------------------------------------
-    {
+    TiledU8Sum red[RPG];
+    tiled_u8_row_walk<LPR>(row_ptr, kquad, tiles, n_tiles, n, Q, ld, cb, mine_cols, lists[g], nodes, rb, g, l, red, [&](int ri) {
         const float4 gq = h.qp[0], og = h.hq[0];
         const long long z = static_cast<long long>(gq.y);
         const uint32_t zero = codes_quant(0.0f, og.z, og.y, h.hmax);   // a row past n: float +0
+        const int r = g * RPG + ri, row = rb * 32 + r;
+        const float rs = h.row_scale && row < n ? h.row_scale[row] : 1.0f;
+        uint32_t word = 0;
 #pragma unroll
-        for (int ri = 0; ri < RPG; ++ri) {
-            tiled_u8_add_rows(s[ri], lists[g][ri], cnt[ri], Q, ld, cb, mine_cols);
-            const int r = g * RPG + ri, row = rb * 32 + r;
-            const float rs = h.row_scale && row < n ? h.row_scale[row] : 1.0f;
-            uint32_t word = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t c = zero;
-                if (row < n) c = codes_quant(tiled_u8_dequant(s[ri][k], terms[ri], z, gq.x, h.row_scale != nullptr, rs), og.z, og.y, h.hmax);
-                word |= (cb + k < K ? c ^ 0x80u : 0u) << (8 * k);
-            }
-            if (cb < stride - ALIN_PAD) *reinterpret_cast<uint32_t *>(s_h + r * stride + cb) = word;
+        for (int k = 0; k < 4; ++k) {
+            uint32_t c = zero;
+            if (row < n) c = codes_quant(tiled_u8_dequant(red[ri].s[k], red[ri].terms, z, gq.x, h.row_scale != nullptr, rs), og.z, og.y, h.hmax);
+            word |= (cb + k < K ? c ^ 0x80u : 0u) << (8 * k);
         }
-    }
+        if (cb < stride - ALIN_PAD) *reinterpret_cast<uint32_t *>(s_h + r * stride + cb) = word;
+    });
     __syncthreads();
 
     // ---- the product and its epilogue, 2 NT column tiles a pass ----------------------------------------------------------------------
