@@ -18,16 +18,20 @@ and come back in real units. tests/affine_model.py states every bit of it in Num
     rows = layer.calibrate(A, X);  y = layer(A, X, act_qparams=rows)          # the layer as a chain of six launches
     q = affine.aggregate_linear(adj, q, qy, (8, qz), W, 4, out=(8, qo))       # the middle walk and the product behind it, one launch
     y = layer(A, X, act_qparams=rows, fuse=True)                              # five launches, the same bits: include/qgtc_fused.h
+    y = affine.aggregate(adj, T, 8, route="bytes", edge_weight=alpha)         # ~ sum_k alpha[slot] T[k]: include/qgtc_codes_edge.h
+    layer = affine.TransformerConv_Affine.from_float(trained_transformerconv, 4, 8)   # likewise GATv2Conv_Affine
     m = affine.tiledMaxCodes(adj, q, reduce="max")        # uint8 [n, N]: the extremum of the neighbours' codes, itself a code under q's row
     y = affine.aggregate(adj, T, 8, route="bytes", reduce="max")              # ~ max over the neighbours' rows of T: include/qgtc_codes_max.h
     layer = affine.GCNConv_Affine.from_float(gcnconv_with_aggr_max, 4, 8, route="bytes", linear_route="bytes")
 
-The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h, one of include/qgtc_fused.h, four of include/qgtc_codes_max.h) are reached through ctypes on torch's current stream (the
+The C entries (four of include/qgtc_affine.h, five of include/qgtc_codes.h, two of include/qgtc_linear.h, three of include/qgtc_chain.h, one of include/qgtc_fused.h, four of include/qgtc_codes_max.h, two of include/qgtc_codes_edge.h) are reached through ctypes on torch's current stream (the
 extension binds no name for them): every call enqueues, reads nothing back and can be captured into a graph; the quantisation parameters stay on the device, so a replay follows the data's
 range. The outputs and the scratch of the range launch are allocated here. Inference only: nothing here is differentiable, and no output
 requires grad. The accumulators of the planes route are float32 holding integers: there ``linear`` refuses a K at which
 K * qmax_a * qmax_w could pass 2^24; its bytes route accumulates in int32 and refuses K above ``LINEAR_K_MAX`` only."""
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -36,7 +40,8 @@ import QGTC  # the HIP extension; there is no fallback
 from . import conv, tiled
 from .tiled import _c_abi, _ptr
 
-__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight", "aggregate_linear", "tiledMaxCodes"]
+__all__ = ["qparams", "val2bit_affine", "dequant", "linear", "aggregate", "GCNConv_Affine", "codes", "tiledMMCodes", "pack_weight", "aggregate_linear", "tiledMaxCodes",
+           "TransformerConv_Affine", "GATv2Conv_Affine"]
 
 ROUTES = ("planes", "bytes")   # how ``aggregate`` sums the codes: eight bit planes through tiledMM2Int, or one gather of byte codes
 REDUCES = ("sum", "max", "min")   # the reducer of ``aggregate`` and of the layer's ``aggr``; an extremum is served on route="bytes" only
@@ -407,7 +412,7 @@ def tiledMaxCodes(adj_view: "tiled.TiledAdjacency", Q: torch.Tensor, reduce: str
 
 
 def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_scale=None, row_mask=None, nbr_mask=None,
-              route: str = "planes", t_qparams=None, out=None, reduce: str = "sum") -> torch.Tensor:
+              route: str = "planes", t_qparams=None, out=None, reduce: str = "sum", edge_weight=None) -> torch.Tensor:
     """float32 [n, N] ~ A . T on the view ``adj_view`` (``adj`` or ``adj.T``; T in the adjacency's numbering): T quantised per tensor to
     ``bits`` into the cols layout, ``QGTC.tiledMM2Int`` on the codes (the exact neighbour sum), then :func:`dequant` with the view's
     degrees under the masks as the row sums of A, and ``row_scale`` (float32 [n], say ``adj_view.mean_scale()``) applied there. Row i is
@@ -425,10 +430,21 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     ``reduce="max"`` / ``"min"``, on the bytes route only (include/qgtc_codes_max.h), replace the sum by the
     element-wise extremum over the neighbours: scale * (m - zero_point) with m the extremum of the neighbours' codes, which is the
     quantised value of the extremum itself - the aggregate adds no error to T's quantisation. Float T, uint8 T with ``t_qparams`` and
-    ``out=(bits, row)`` work as for the sum; ``row_scale`` is a ValueError (an extremum is not scaled); a row without a term is +0."""
+    ``out=(bits, row)`` work as for the sum; ``row_scale`` is a ValueError (an extremum is not scaled); a row without a term is +0.
+
+    ``edge_weight`` (float32 [nnz], or [nnz, H] for H heads, in slot order: ``tiled.edge_values``, ``tiled.tiledEdgeSoftmax``), on the
+    bytes route and the sum only (include/qgtc_codes_edge.h), weighs every term:
+    ``scale * sum_k w[slot(o, k), c // (N / H)] * (q[k][c] - zero_point)`` - the sum every attention layer ends in, gathered one byte an
+    element. Float T, uint8 T with ``t_qparams``, ``out=(bits, row)``, ``row_scale`` and both masks work as for the plain sum; a
+    masked-out cell keeps its slot, so the masks only drop terms. The sum is float32 with fused multiply-adds and no fixed order: within
+    (terms + 4) 2^-23 scale |row_scale| (255 + zero_point) sum|w| of the exact value. With H > 1 a head's N / H columns must be a
+    multiple of 4; other shapes are served by ``tiled.tiledAggregate(adj, dequantised T, edge_weight=)``. The first call on an
+    adjacency builds its value index, which reads nnz back once: warm up before a capture."""
     tiled._check(adj_view)
     route = _check_route(route)
     bits = _check_bits(bits)
+    if edge_weight is not None and (route != "bytes" or _check_reduce(reduce) != "sum"):
+        raise ValueError(f'edge_weight needs route="bytes" and reduce="sum", not route={route!r}, reduce={reduce!r}')
     if _check_reduce(reduce) != "sum":
         if route != "bytes":
             raise ValueError(f'reduce="{reduce}" needs route="bytes": the planes route sums')
@@ -451,12 +467,23 @@ def aggregate(adj_view: "tiled.TiledAdjacency", T: torch.Tensor, bits: int, row_
     if t_qparams is not None:
         _check_qparams(t_qparams, "t_qparams", (1,), T)
     out_bits, out_qp = _check_out(out, T)
+    if edge_weight is not None:
+        tiled._check_edge_vector(adj_view, edge_weight, "edge_weight", T)
+        heads = edge_weight.size(1) if edge_weight.dim() == 2 else 1
+        if heads > 1 and (N // heads) % 4:
+            raise ValueError(f"edge_weight has {heads} heads of {N // heads} columns: the byte-code walk needs a multiple of 4 columns a head; "
+                             "tiled.tiledAggregate(adj, T, edge_weight=) on the dequantised T serves this shape")
     qt = qparams(T, bits) if t_qparams is None else t_qparams
     if route == "bytes":
         _check_masks(adj_view, row_mask, nbr_mask)
         Q = T if coded else codes(T, bits, qt)
         res, flt, mat, row = _dest(out, out_bits, out_qp, n, N, T.device)
-        if reduce != "sum":
+        if edge_weight is not None:
+            val_ptr, val_row, nnz = tiled._value_index(adj_view)
+            index = (val_ptr.data_ptr(), val_row.data_ptr()) if adj_view.n_tiles else (None, None)
+            _u8_call("affine.aggregate", "qgtc_tiledmm_u8", "_edge", adj_view, Q, row_mask, nbr_mask, qt.data_ptr(), _ptr(row_scale), *index,
+                     edge_weight.data_ptr() if nnz else None, nnz, heads, *flt, *mat, *row)
+        elif reduce != "sum":
             _u8_call("affine.aggregate", "qgtc_tiledmax_u8", "_affine", adj_view, Q, row_mask, nbr_mask, qt.data_ptr(), int(reduce == "min"),
                      *flt, *mat, *row)
         elif out is None:
@@ -639,3 +666,102 @@ class GCNConv_Affine(torch.nn.Module):
         lin = {"route": self.linear_route}
         h = aggregate(A, linear(Xn, W_in, b, self.w_bit, True, src, **lin), b, row, route=self.route, **red, **mask)
         return A.to_old(aggregate(A, linear(h, W_out, b, self.w_bit, True, src, **lin), b, row, route=self.route, **red, **mask))
+
+
+class _AttentionConv_Affine(torch.nn.Module):
+    """What the two quantised attention layers share. The projections run through ``linear(..., route="bytes")`` (weights per output
+    column to ``w_bit`` bits, X per tensor to ``act_bit``), the scores and the edge softmax are the float launches of ``tiled`` on the
+    projected features, and the value sum is ``aggregate(A, V, act_bit, route="bytes", edge_weight=alpha)``: V is gathered one byte an
+    element. The head mean and ``to_new`` / ``to_old`` are the float layers'. ``nodes`` (bool [n] in X's numbering) is one bitmap as
+    both masks of the value aggregate: rows outside come back +0 and neighbours outside add nothing. The softmax still normalises over
+    ALL stored neighbours, so the masked layer is the aggregate restricted to the node set, not a softmax over the induced subgraph.
+    Inference only: forward runs without grad. A subclass gives ``_project`` and ``_scores``."""
+
+    def _init_common(self, input_dim, output_dim, heads, concat, w_bit, act_bit):
+        if int(heads) < 1:
+            raise ValueError(f"heads must be at least 1, not {heads!r}")
+        self.input_dim, self.output_dim, self.heads, self.concat = int(input_dim), int(output_dim), int(heads), bool(concat)
+        self.w_bit, self.act_bit = _check_bits(w_bit, "w_bit"), _check_bits(act_bit, "act_bit")
+
+    def _weight(self):
+        return torch.nn.Parameter(torch.randn(self.input_dim, self.heads * self.output_dim) / self.input_dim ** 0.5)
+
+    def _linear(self, Xn, W):
+        return linear(Xn, W.detach().contiguous(), self.act_bit, self.w_bit, route="bytes")
+
+    @torch.no_grad()
+    def forward(self, A, X, nodes=None):
+        if not isinstance(A, QGTC.TiledAdjacency):
+            raise NotImplementedError(f"{type(self).__name__} needs a QGTC.TiledAdjacency (QGTC.pack_edges_tiled), not a dense or edge-list A")
+        _check_f32(X, "X")
+        if X.size(0) != A.n:
+            raise ValueError(f"X must have one row per node ({A.n}), not shape {list(X.shape)}")
+        mask = {}
+        if nodes is not None:
+            bm = conv._node_mask(A, nodes)
+            mask = {"row_mask": bm, "nbr_mask": bm}
+        V, logits = self._scores(A, A.to_new(X).contiguous())
+        out = aggregate(A, V, self.act_bit, route="bytes", edge_weight=tiled.tiledEdgeSoftmax(A, logits), **mask)
+        if self.heads > 1 and not self.concat:   # the mean over the heads, in the layout and order of torch.stack(heads).mean(dim=0)
+            out = out.view(A.n, self.heads, self.output_dim).transpose(0, 1).contiguous().mean(dim=0)
+        return A.to_old(out)
+
+
+class TransformerConv_Affine(_AttentionConv_Affine):
+    """The quantised inference twin of ``conv.TransformerConv``: q, k, v = linear(X, W_q / W_k / W_v), the scores
+    ``tiled.tiledEdgeScores(A, q, k, heads) / sqrt(output_dim)``, then the shared softmax and byte-code value sum."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, w_bit=4, act_bit=8):
+        super().__init__()
+        self._init_common(input_dim, output_dim, heads, concat, w_bit, act_bit)
+        for name in ("W_q", "W_k", "W_v"):
+            setattr(self, name, self._weight())
+
+    @classmethod
+    def from_float(cls, layer: "conv.TransformerConv", w_bit: int = 4, act_bit: int = 8) -> "TransformerConv_Affine":
+        """The twin of a (trained) float layer: its three weights (copied), its heads and concat."""
+        if not isinstance(layer, conv.TransformerConv):
+            raise TypeError(f"layer must be a conv.TransformerConv, not {type(layer).__name__}")
+        new = cls(layer.input_dim, layer.output_dim, layer.heads, layer.concat, w_bit, act_bit)
+        with torch.no_grad():
+            for name in ("W_q", "W_k", "W_v"):
+                getattr(new, name).copy_(getattr(layer, name))
+        return new.to(layer.W_q.device)
+
+    def _scores(self, A, Xn):
+        q, k, v = (self._linear(Xn, W) for W in (self.W_q, self.W_k, self.W_v))
+        return v, tiled.tiledEdgeScores(A, q, k, self.heads) * (1.0 / math.sqrt(self.output_dim))
+
+
+class GATv2Conv_Affine(_AttentionConv_Affine):
+    """The quantised inference twin of ``conv.GATv2Conv``: hl = linear(X, W_l), hr = linear(X, W_r) (hl itself with ``share_weights``),
+    the scores ``tiled.tiledEdgeAdditiveScores(A, hr, hl, att, negative_slope, heads)``, then the shared softmax and byte-code value sum
+    of hl. ``att`` stays float32."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, share_weights=False, w_bit=4, act_bit=8):
+        super().__init__()
+        self._init_common(input_dim, output_dim, heads, concat, w_bit, act_bit)
+        slope = float(negative_slope)
+        if not 0.0 <= slope <= 1.0:
+            raise ValueError(f"negative_slope must lie in [0, 1], not {negative_slope!r}")
+        self.negative_slope, self.share_weights = slope, bool(share_weights)
+        self.W_l = self._weight()
+        if not self.share_weights:
+            self.W_r = self._weight()
+        self.att = torch.nn.Parameter(torch.randn(self.heads, self.output_dim) / self.output_dim ** 0.5)
+
+    @classmethod
+    def from_float(cls, layer: "conv.GATv2Conv", w_bit: int = 4, act_bit: int = 8) -> "GATv2Conv_Affine":
+        """The twin of a (trained) float layer: its weights and ``att`` (copied), its heads, slope, concat and share_weights."""
+        if not isinstance(layer, conv.GATv2Conv):
+            raise TypeError(f"layer must be a conv.GATv2Conv, not {type(layer).__name__}")
+        new = cls(layer.input_dim, layer.output_dim, layer.heads, layer.negative_slope, layer.concat, layer.share_weights, w_bit, act_bit)
+        with torch.no_grad():
+            for name in ("W_l", "att") + (() if layer.share_weights else ("W_r",)):
+                getattr(new, name).copy_(getattr(layer, name))
+        return new.to(layer.W_l.device)
+
+    def _scores(self, A, Xn):
+        hl = self._linear(Xn, self.W_l)
+        hr = hl if self.share_weights else self._linear(Xn, self.W_r)
+        return hl, tiled.tiledEdgeAdditiveScores(A, hr, hl, self.att.detach(), self.negative_slope, self.heads)

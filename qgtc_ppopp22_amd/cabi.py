@@ -23,6 +23,7 @@ LINEAR_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_linear.h")   # the b
 CHAIN_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_chain.h")   # the static affine chain: the product and the walks with uint8 codes in and out, likewise
 FUSED_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_fused.h")   # the chain's middle walk fused with the product behind it, likewise
 CODES_MAX_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_codes_max.h")   # max and min aggregation on byte codes, on both views, likewise
+CODES_EDGE_HEADER = os.path.join(os.path.dirname(HEADER), "qgtc_codes_edge.h")   # the edge-weighted sum on byte codes, on both views, likewise
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
             "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
@@ -60,7 +61,7 @@ def signatures(text: str | None = None) -> dict:
 
 def load():
     """The library, opened once per process, with ``restype`` and ``argtypes`` set on every declared entry - those of include/qgtc.h
-    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h, include/qgtc_addscore.h, include/qgtc_fanout.h, include/qgtc_blocks.h, include/qgtc_bitnodes.h, include/qgtc_affine.h, include/qgtc_codes.h, include/qgtc_linear.h, include/qgtc_chain.h, include/qgtc_fused.h and include/qgtc_codes_max.h. A declared entry the library does not
+    and, through the same parser, those of include/qgtc_heads.h, include/qgtc_attn_heads.h, include/qgtc_addscore.h, include/qgtc_fanout.h, include/qgtc_blocks.h, include/qgtc_bitnodes.h, include/qgtc_affine.h, include/qgtc_codes.h, include/qgtc_linear.h, include/qgtc_chain.h, include/qgtc_fused.h, include/qgtc_codes_max.h and include/qgtc_codes_edge.h. A declared entry the library does not
     export is an error naming it."""
     global _lib
     if _lib is None:
@@ -89,11 +90,13 @@ def load():
             fused = signatures(f.read())
         with open(CODES_MAX_HEADER) as f:
             codes_max = signatures(f.read())
+        with open(CODES_EDGE_HEADER) as f:
+            codes_edge = signatures(f.read())
         for header, table in (("qgtc.h", signatures()), ("qgtc_heads.h", heads), ("qgtc_attn_heads.h", attn_heads),
                               ("qgtc_addscore.h", addscore), ("qgtc_fanout.h", fanout), ("qgtc_blocks.h", blocks),
                               ("qgtc_bitnodes.h", bitnodes), ("qgtc_affine.h", affine), ("qgtc_codes.h", codes),
                               ("qgtc_linear.h", linear), ("qgtc_chain.h", chain), ("qgtc_fused.h", fused),
-                              ("qgtc_codes_max.h", codes_max)):
+                              ("qgtc_codes_max.h", codes_max), ("qgtc_codes_edge.h", codes_edge)):
             for name, (restype, argtypes) in table.items():
                 try:
                     fn = getattr(lib, name)

@@ -128,10 +128,13 @@ alternating rounds, ``pack_weight`` alone, the traffic floor, and the layer with
 the dynamic layer on the bytes routes and ``conv.GCNConv`` in the same alternating rounds, and each new launch beside its float twin.
 `--leg codesmax` measures max aggregation on byte codes (include/qgtc_codes_max.h): the extremum walk codes -> codes and
 codes -> float at N = 64 and 256 on adj and adj.T beside tiledMMFloat(reduce="max") and the sum walk, and the static layer with aggr="max".
+`--leg codesedge` measures the edge-weighted sum on byte codes (include/qgtc_codes_edge.h): the new launch at five (H, d)
+on adj and adj.T beside ``tiledMMFloat(edge_weight=)`` on the dequantised matrix and the plain ``tiledMMCodes`` walk, and the two quantised
+attention layers' error against their float twins.
 `--leg fused` measures the fused middle of that chain (include/qgtc_fused.h): the static layer with ``fuse=True`` beside
 ``fuse=False``, and ``affine.aggregate_linear`` beside the walk and the product it replaces, also once at K = N2 = 256 on arxiv.
 
-    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain|fused|codesmax]
+    python tools/tiled_bench.py [--graphs arxiv,reddit,products] [--reps 10] [--json OUT] [--leg orders|transposed|scaled|float|sym|max|attn|drop|nodes|edge|esoftmax|heads|gatheads|gatv2|fanout|blocks|bitnodes|affine|codes|linear|chain|fused|codesmax|codesedge]
 """
 from __future__ import annotations
 
@@ -1164,6 +1167,68 @@ def codesmax_leg(torch, QGTC, graphs, reps):
     return rows
 
 
+def codesedge_leg(torch, QGTC, graphs, reps):
+    """The edge-weighted sum on byte codes (include/qgtc_codes_edge.h) on the reordered graphs, 8-bit codes of Gaussian
+    float32 [n, H d], softmax weights [nnz, H], adj and adj.T, in the same alternating rounds: the new launch on the codes,
+    ``tiledMMFloat(adj, dequantised V, edge_weight=)`` - the only route before it - and the plain ``tiledMMCodes`` walk of the same shape,
+    which shows what the weights cost. ``beats_float``: the walk's 90th percentile lies under the float launch's 10th. Then each new
+    layer's relative error against its float twin at (heads, d) = (4, 8) and (8, 8) on the arxiv-sized graph (recorded, not asserted)."""
+    from qgtc_ppopp22_amd import affine, conv, tiled
+    from qgtc_ppopp22_amd.graph import make_sbm_graph
+
+    rows = []
+    for name in graphs:
+        n, deg = GRAPHS[name]
+        g = make_sbm_graph(name, n, max(1, n // 128), deg, 1, seed=3)
+        perm = np.random.default_rng(7).permutation(n)
+        dsrc, ddst = torch.from_numpy(perm[g.src]).cuda(), torch.from_numpy(perm[g.dst]).cuda()
+        adj = QGTC.pack_edges_tiled(dsrc, ddst, n, reorder=True)
+        nnz = tiled._value_index(adj)[2]
+        rec = {"graph": name, "order": "reordered", "n": n, "edges": int(g.src.size), "set_cells": nnz, "tiles": adj.n_tiles, "agg": []}
+        xr = np.random.default_rng(1)
+        for H, d in ((1, 64), (8, 8), (4, 16), (8, 32), (4, 64)):
+            N = H * d
+            X = torch.from_numpy(xr.normal(size=(n, N)).astype(np.float32)).cuda()
+            qp = affine.qparams(X, 8)
+            Q = affine.codes(X, 8, qp)
+            deq = (Q.to(torch.float32) - qp[0, 1]) * qp[0, 0]
+            logits = torch.from_numpy(xr.standard_normal((nnz, H) if H > 1 else nnz).astype(np.float32)).cuda()
+            for view, a in (("adj", adj), ("adjT", adj.T)):
+                w = tiled.tiledEdgeSoftmax(a, logits)
+                got, ref = affine.aggregate(a, Q, 8, route="bytes", t_qparams=qp, edge_weight=w), QGTC.tiledMMFloat(a, deq, edge_weight=w)
+                err = float((got - ref).abs().max() / ref.abs().max())
+                assert err < 1e-5, err
+                ce, fe, cp = timed_alternating(torch, [lambda: affine.aggregate(a, Q, 8, route="bytes", t_qparams=qp, edge_weight=w),
+                                                       lambda: QGTC.tiledMMFloat(a, deq, edge_weight=w),
+                                                       lambda: affine.tiledMMCodes(a, Q)], reps)
+                out = {"H": H, "d": d, "view": view, "codes_edge_ms": ce, "tiledMMFloat_edge_ms": fe, "tiledMMCodes_ms": cp,
+                       "codes_over_float": round(ce[0] / fe[0], 3), "weighted_over_plain": round(ce[0] / cp[0], 3),
+                       "beats_float": _separated(ce, fe), "max_diff_over_max": err}
+                rec["agg"].append(out)
+                print(f"{name:9s} H={H} d={d:<2d} {view:4s}: codes edge {ce[0]:.4f} [{ce[1]:.4f}, {ce[2]:.4f}] ms  tiledMMFloat edge {fe[0]:.4f} "
+                      f"[{fe[1]:.4f}, {fe[2]:.4f}] ms  tiledMMCodes {cp[0]:.4f} [{cp[1]:.4f}, {cp[2]:.4f}] ms  codes / float "
+                      f"{out['codes_over_float']}  weighted / plain {out['weighted_over_plain']}  beats float: {out['beats_float']}", flush=True)
+            del X, Q, deq, logits
+        if name == "arxiv":
+            rec["layers"] = []
+            F = torch.from_numpy(xr.normal(size=(n, 128)).astype(np.float32)).cuda()
+            for H, d in ((4, 8), (8, 8)):
+                torch.manual_seed(H)
+                for fl, cls in ((conv.TransformerConv(128, d, H).cuda(), affine.TransformerConv_Affine),
+                                (conv.GATv2Conv(128, d, H).cuda(), affine.GATv2Conv_Affine)):
+                    with torch.no_grad():
+                        want = fl(adj, F)
+                    got = cls.from_float(fl, 4, 8)(adj, F)
+                    rel = float((got - want).norm() / want.norm())
+                    rec["layers"].append({"layer": cls.__name__, "H": H, "d": d, "w_bit": 4, "act_bit": 8, "rel_error": round(rel, 4)})
+                    print(f"{name:9s} {cls.__name__} H={H} d={d} w4 a8: relative error against the float layer {rel:.4f}", flush=True)
+            del F
+        rows.append(rec)
+        del adj, dsrc, ddst
+        torch.cuda.empty_cache()
+    return rows
+
+
 def edge_leg(torch, QGTC, graphs, reps):
     from qgtc_ppopp22_amd import tiled
     from qgtc_ppopp22_amd.graph import make_sbm_graph
@@ -1685,7 +1750,7 @@ def main() -> None:
     ap.add_argument("--graphs", default="arxiv,reddit,products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax"))
+    ap.add_argument("--leg", default="orders", choices=("orders", "transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax", "codesedge"))
     args = ap.parse_args()
 
     import torch
@@ -1693,9 +1758,9 @@ def main() -> None:
     import QGTC
     from qgtc_ppopp22_amd.graph import make_sbm_graph
 
-    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax"):
+    if args.leg in ("transposed", "scaled", "float", "sym", "max", "attn", "drop", "nodes", "edge", "esoftmax", "heads", "gatheads", "gatv2", "fanout", "blocks", "bitnodes", "affine", "codes", "linear", "chain", "fused", "codesmax", "codesedge"):
         leg = {"transposed": transposed_leg, "scaled": scaled_leg, "float": float_leg, "sym": sym_leg, "max": max_leg, "attn": attn_leg,
-               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg, "fused": fused_leg, "codesmax": codesmax_leg}[args.leg]
+               "drop": drop_leg, "nodes": nodes_leg, "edge": edge_leg, "esoftmax": esoftmax_leg, "heads": heads_leg, "gatheads": gatheads_leg, "gatv2": gatv2_leg, "fanout": fanout_leg, "blocks": blocks_leg, "bitnodes": bitnodes_leg, "affine": affine_leg, "codes": codes_leg, "linear": linear_leg, "chain": chain_leg, "fused": fused_leg, "codesmax": codesmax_leg, "codesedge": codesedge_leg}[args.leg]
         rows = leg(torch, QGTC, args.graphs.split(","), args.reps)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
